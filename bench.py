@@ -13,8 +13,14 @@ as the extra field `device_resident`.
 
 `--gpus N` without a torchrun environment starts its own N ranks (one process per GPU, RCCL over xGMI).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel class, hipEvent-timed on the engine's own stream inside
-the timed region) and `cpu_baseline` (the oracle pipeline -- C restatement + torch-CPU network -- on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`); every other figure is behind `--full`: `roofline` (dominant kernel class, hipEvent-timed on the engine's own
+stream inside the timed region, after an untimed discovery pass), the device-resident, pipelined, lighter-graph and two-stream
+timings, the committed counter summaries (`conv_mfma_util`) and `cpu_baseline` (the oracle pipeline -- C restatement + torch-CPU
+network -- on a bounded sample).  Those fields are null (the untimed kernel breakdown empty) in a plain run.
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's gathered pages when N > 1) as DIR/<name>.npy
+(see dump_outputs); the pages and graphs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -74,6 +80,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-real-size", action="store_true", help="skip the extra timing of the real-size detector (config 1, one GPU)")
     ap.add_argument("--stub-engine", action="store_true", help=argparse.SUPPRESS)   # tests/test_bench_cpu.py: control flow without a GPU
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py starts its own ranks (0 = pick a free one)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline (profiler discovery pass + sampled launches), device-resident, "
+                    "pipelined, lighter-graph and two-stream timings, committed counter summaries and the CPU baseline (the --no-* / --cpu-pages options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write the last timed step's results as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args(argv)
     if args.steps <= 0:
         args.steps = 100 if args.config == 1 and not args.stub_engine else 10
@@ -134,6 +143,20 @@ def pin_rank_to_its_cores(local_rank: int, local_world: int) -> int:
         except OSError:
             pass
     return per if quota is None else max(1, min(per, int(quota // max(local_world, 1))))
+
+
+def dump_outputs(out_dir, packed):
+    """What a caller of the timed path receives (api.PackedPages) as float32 / float64 .npy files: page i owns regions
+    [region_offsets[i], region_offsets[i + 1]); region k has box points[k] (4 x 2), scores[k] and the UTF-8 bytes
+    text_utf8[text_offsets[k]:text_offsets[k + 1]].  Offsets and bytes are integers, exact in float64 / float32."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"region_offsets": np.asarray(packed.region_offsets, np.float64), "points": np.asarray(packed.points, np.float32),
+              "scores": np.asarray(packed.scores, np.float32), "text_utf8": np.frombuffer(packed.utf8, np.uint8).astype(np.float32),
+              "text_offsets": np.asarray(packed.text_offsets, np.float64)}
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 class StubEngine:
@@ -281,13 +304,14 @@ def main():
         if rank == 0:
             merged = api.PackedPages.merge(blobs)   # oar_packed_merge: block partition => concatenation in rank order restores page order
             gathered.update(pages=len(merged.region_offsets) - 1, regions=len(merged.scores), bytes=len(merged.utf8))
+            return merged
         return packed
 
     # -- untimed: discover the kernel classes with every class instrumented.  `dominant` = the class with the largest share (it is `roofline`);
     # the four largest are all sampled inside the timed region (`roofline.by_family`): one profiler class per kernel FAMILY,
     # e.g. dsblock_rs (row-streaming separable blocks, HBM-bound) and dsblock_cs (chunk-streamed ones, bound by their own instruction streams).
     dominant, dominant_launches, breakdown, families = None, 0, {}, []
-    if not args.no_prof and not stub:
+    if args.full and not args.no_prof and not stub:
         step()
         api.prof_enable(True)
         api.prof_filter("")
@@ -318,7 +342,7 @@ def main():
     for i in range(args.steps):
         if dominant:
             api.prof_sampling(S, i % S if i < balanced else -1)
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     cpu1 = os.times()
@@ -326,6 +350,8 @@ def main():
     host_cpu_ms = ((cpu1.user - cpu0.user) + (cpu1.system - cpu0.system)) / max(args.steps, 1) * 1e3
     if not stub:
         api.prof_sampling(1, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     roof = None
     cfg_sfx = "" if args.config in (1, 3) else f"_c{args.config}"   # committed counter summaries are per workload: profiles/r*/pmc_traffic[_c2].json, mfma_util[_c2].json
     from oar_ocr_amd.build import csrc_fingerprint
@@ -385,7 +411,7 @@ def main():
     # committed rocprofv3 --pmc pass over this same command (tools/profile_round.sh pass 3 -> profiles/r*/mfma_util.json; the
     # counters cannot be collected inside the timed region).  Only reported for the workload the pass was made on (config 1).
     mfma_util = None
-    if rank == 0 and args.config in (1, 2):
+    if rank == 0 and args.full and args.config in (1, 2):
         for mf in sorted(ROOT.glob(f"profiles/r*/mfma_util{cfg_sfx}.json"), reverse=True):
             try:
                 m = json.loads(mf.read_text())
@@ -424,7 +450,7 @@ def main():
 
     # -- second figure: pages already resident in HBM, no decode (round 1's headline), same step count
     dev_res = None
-    if not stub and not args.no_device_resident and world == 1:
+    if args.full and not stub and not args.no_device_resident and world == 1:
         dev_pages = [api.DeviceBuffer(p, dev) for p in host_pages]
         ptrs = [int(b.ptr.value) for b in dev_pages]
         ws = hs = [size] * n_pages
@@ -444,7 +470,7 @@ def main():
     # -- third figure: two calls in flight on one handle (oar_ocr_predict_async, oar_ocr_cfg.lanes = 2): call k + 1 uploads and detects
     # while call k recognises.  Same pages, same per-call results (tests/test_gpu_async.py); reported next to the synchronous headline.
     pipelined = None
-    if not stub and not args.no_pipelined and world == 1:
+    if args.full and not stub and not args.no_pipelined and world == 1:
         eng.close()
         ocr2 = builder.lanes(2).build()
         for _ in range(max(2, args.warmup)):
@@ -466,7 +492,7 @@ def main():
     # -- fourth figure (config 1, one GPU): the same step on the lighter graphs rounds 1-5 quoted their headline on (the file sizes
     # pin 0.445 M / 1.116 M parameters; since round 6 the headline runs graphs of that size and the lighter ones are the side figure)
     real_size = None
-    if not stub and world == 1 and args.config == 1 and det_name == "tiny_full" and not args.no_real_size:
+    if args.full and not stub and world == 1 and args.config == 1 and det_name == "tiny_full" and not args.no_real_size:
         det_cls, det_cls_info = models.build_det("tiny", seed=0)
         rec_cls, rec_cls_info = models.build_rec("tiny", vocab=vocab, seed=1)
         ocr3 = (api.OAROCRBuilder(det_cls, rec_cls, chars).text_detection_config(cfg).image_batch_size(image_batch).region_batch_size(args.region_batch).device(dev)).build()
@@ -488,7 +514,7 @@ def main():
     # headline keeps one stream: with two, kernels of different batches share the GPU and a launch's duration stops being the kernel's own
     # (the roofline accounting above would be measuring the overlap), so this stays an opt-in with its own line.
     rec_two = None
-    if not stub and world == 1 and args.config == 1 and not args.no_real_size:
+    if args.full and not stub and world == 1 and args.config == 1 and not args.no_real_size:
         os.environ["OAR_REC_LANES"] = "2"
         try:
             ocr4 = builder.lanes(1).build()
@@ -509,7 +535,7 @@ def main():
     if rank == 0:
         value = total_pages * args.steps / tmax
         cpu = None
-        if args.cpu_pages > 0 and world == 1 and not stub:   # the CPU baseline is timed on rank 0 of the single-GPU run only
+        if args.full and args.cpu_pages > 0 and world == 1 and not stub:   # the CPU baseline is timed on rank 0 of the single-GPU run only
             from oracle import pipeline_ref
             torch.set_num_threads(min(os.cpu_count() or 1, 64))
             # SURVEY 8d "ORT-CPU stand-in": only possible when onnxruntime AND operator-supplied weights exist on this box -- say which oracle ran

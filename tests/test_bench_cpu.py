@@ -50,6 +50,19 @@ def test_bench_single_rank_needs_no_launcher():
     assert out["n_gpus"] == 1 and out["config"]["pages_gathered_per_step"] == 4 and out["per_rank"] is None
 
 
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0's gathered result of the last timed step, as float .npy files a second build can be compared against"""
+    out = _run("--gpus", "2", "--pages", "2", "--dump-outputs", str(tmp_path))
+    assert out["steps"] == 3
+    d = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sorted(d) == ["points", "region_offsets", "scores", "text_offsets", "text_utf8"]
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert d["region_offsets"].tolist() == [0, 3, 6, 9, 12] and d["points"].shape == (12, 4, 2) and d["scores"].shape == (12,)
+    assert np.array_equal(d["points"][6:] - d["points"][:6], np.ones((6, 4, 2), np.float32))   # rank 1's boxes follow rank 0's
+    utf8, to = d["text_utf8"].astype(np.uint8).tobytes(), d["text_offsets"].astype(np.int64)
+    assert [utf8[to[k]:to[k + 1]].decode() for k in (0, 5, 6, 11)] == ["r0p0k0", "r0p1k2", "r1p0k0", "r1p1k2"]
+
+
 def test_packed_pages_roundtrip():
     from oar_ocr_amd import api
     p = api.PackedPages(np.array([0, 2, 2, 3], np.uint32), np.arange(24, dtype=np.float32).reshape(3, 4, 2), np.array([.5, .25, 1], np.float32),

@@ -1,6 +1,6 @@
 # where the caller's threads run: floating / taskset from outside / affinity set in-process BEFORE anything touches the HIP runtime
 mkdir -p gpurun_out/s4
-ARGS="--cpu-pages 0 --no-pipelined --steps 20"
+ARGS="--full --cpu-pages 0 --no-pipelined --steps 20"
 show() { python - <<P
 import json
 d=json.load(open("gpurun_out/s4/ab_$1.json"))

@@ -10,7 +10,7 @@ TAG=${1:-r2a}
 CFG=${2:-1}          # bench.py --config of the session; != 1: raw passes go to gpurun_out/pmc_*_c<CFG>
 SFX=""; if [ "$CFG" != "1" ]; then SFX="_c$CFG"; fi
 R=$PWD; cd /tmp; export TMPDIR=/tmp
-BENCH="python $R/bench.py --config $CFG --cpu-pages 0 --no-device-resident --no-pipelined --no-real-size"
+BENCH="python $R/bench.py --full --config $CFG --cpu-pages 0 --no-device-resident --no-pipelined --no-real-size"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$TAG -o $TAG -- $BENCH --steps 5 --warmup 2 > $R/gpurun_out/prof_$TAG.log 2>&1 < /dev/null
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $R/gpurun_out/pmc_$c$SFX
