@@ -814,20 +814,33 @@ struct Planner {
         temps.push_back({(size_t)l.off, bytes});
         return l;
     }
+    // root -> the values whose bytes lie in it (kept for check_release: only the aliases of the roots being freed are looked at).  Stale entries (a value since
+    // re-planned or re-rooted) are skipped by comparing the value's current root.
+    std::map<std::string, std::vector<std::string>> root_aliases;
     TInfo& new_out(const std::string& name, const std::vector<int64_t>& dims, Layout lay) {
         TInfo t;
         t.dims = dims; t.layout = lay; t.root = name;
         t.loc = alloc_arena(t.bytes(), name);
+        root_aliases[name].push_back(name);
         return vals[name] = t;
     }
     // A node planned as several operators leaves its result as a VIEW of a temporary (e.g. pool -> "out::kept" -> Squeeze -> "out"): the arena bytes are then booked
     // under the temporary's name, which compute_last_use() knows nothing about -- release_dead() would free them right after the node although "out" is read later.
     // The node's output takes the booking over (round 6; tools/op_fuzz.py found a reduce whose result was overwritten by the next node's output).
+    // Every other value in those bytes moves to the new root with it.
     void adopt_root(const std::string& out, const std::string& tmp) {
         auto it = vals.find(out);
-        if (it == vals.end() || tmp == out || it->second.root != tmp) return;
+        if (it == vals.end() || tmp.empty() || tmp == out || it->second.root != tmp) return;
         auto rb = root_bytes.find(tmp);
         if (rb != root_bytes.end()) { root_bytes[out] = rb->second; root_off[out] = root_off[tmp]; root_bytes.erase(tmp); root_off.erase(tmp); }
+        std::vector<std::string> moved;
+        moved.swap(root_aliases[tmp]);
+        root_aliases.erase(tmp);
+        std::vector<std::string>& dst = root_aliases[out];
+        for (auto& a : moved) {
+            auto va = vals.find(a);
+            if (va != vals.end() && va->second.root == tmp) { va->second.root = out; dst.push_back(a); }
+        }
         it->second.root = out;
     }
     TInfo& alias_out(const std::string& name, const TInfo& src, const std::vector<int64_t>& dims, Layout lay, int64_t byte_off = 0) {
@@ -835,6 +848,7 @@ struct Planner {
         t.dims = dims; t.layout = lay; t.root = src.root; t.loc = src.loc; t.ht = nullptr;
         if (t.loc.kind == Loc::CONST) t.loc.cptr = (const float*)((const char*)t.loc.cptr + byte_off);
         else t.loc.off += byte_off;
+        if (!t.root.empty()) root_aliases[t.root].push_back(name);
         return vals[name] = t;
     }
     void step(std::function<void(const RunCtx&)> f, double flops = 0, double bytes = 0) {
@@ -3121,6 +3135,7 @@ struct Planner {
             GNode t2; t2.op = "Transpose"; t2.in = {sm.out[0]}; t2.out = {n.out[0]};
             Attr p2; p2.kind = Attr::IS; p2.is = inv; t2.attrs["perm"] = p2;
             op_transpose(t2);
+            adopt_root(n.out[0], sm.out[0]);   // (axis 1 at rank 3..5: the result is a channels-last view of "::sm")
             return;
         }
         if (E_opset13()) {
@@ -3257,6 +3272,38 @@ struct Planner {
         last_use = lu;
     }
 
+    // Liveness invariant, checked at plan time (plans are cached per shape): bytes handed back to the arena hold no value that a later node (or the caller, for
+    // a graph output) still reads, and every arena value produced since the last release that is read later sits in a root that stays booked -- not in a
+    // per-node temp and not in the bytes of an internal temporary whose name compute_last_use() does not know (the "out::sm" / "out::kept" class of defect).
+    int read_after(const std::string& v) const { auto it = last_use.find(v); return it == last_use.end() ? -1 : it->second; }
+    std::string node_desc(int i) const {
+        const GNode& g = E.nodes_[(size_t)i];
+        return "node " + std::to_string(i) + " (" + g.op + " -> " + (g.out.empty() ? std::string("?") : g.out[0]) + ")";
+    }
+    int checked_upto = -1;   // nodes whose outputs check_release has seen
+    void check_release(const std::vector<std::string>& dead, int i) {
+        for (auto& d : dead) {
+            auto al = root_aliases.find(d);
+            if (al == root_aliases.end()) continue;
+            for (auto& v : al->second) {
+                auto vi = vals.find(v);
+                if (vi == vals.end() || vi->second.root != d || vi->second.loc.kind != Loc::ARENA) continue;
+                const int r = read_after(v);
+                OAR_CHECK(r <= i, OAR_INTERNAL, "plan liveness: " + node_desc(i) + " frees root '" + d + "' but '" + v + "' lives in it and is read " +
+                          (r >= (1 << 30) ? std::string("as a graph output") : "at node " + std::to_string(r)));
+            }
+        }
+        for (int j = checked_upto + 1; j <= i; ++j) {
+            for (auto& o : E.nodes_[(size_t)j].out) {
+                auto vi = vals.find(o);
+                if (vi == vals.end() || vi->second.loc.kind != Loc::ARENA || read_after(o) <= i) continue;
+                const std::string& rt = vi->second.root;
+                OAR_CHECK(!rt.empty() && root_bytes.count(rt), OAR_INTERNAL, "plan liveness: '" + o + "' of " + node_desc(j) + " is read after " + node_desc(i) +
+                          (rt.empty() ? std::string(" but lives in a per-node temp") : " but its root '" + rt + "' is not booked"));
+            }
+        }
+        checked_upto = i;
+    }
     void release_dead(int i) {
         for (auto& t : temps) arena.release(t.first, t.second);
         temps.clear();
@@ -3267,6 +3314,8 @@ struct Planner {
             if (lu <= i) dead.push_back(rb.first);
         }
         for (auto& d : dead) { arena.release(root_off[d], root_bytes[d]); root_bytes.erase(d); root_off.erase(d); }
+        check_release(dead, i);
+        for (auto& d : dead) root_aliases.erase(d);
     }
 
     bool skip_final_softmax = false;
@@ -3301,6 +3350,7 @@ struct Planner {
                 if (axis < 0) axis += r;
                 if (E_opset13() && axis == r - 1 && x.layout == Layout::NATIVE) {
                     alias_out(n.out[0], x, x.dims, Layout::NATIVE);
+                    adopt_root(n.out[0], x.root);   // the output is a view of the logits: it takes their booking over, they live until the caller reads it
                     P.skipped_softmax = true;
                     release_dead(i);
                     continue;
@@ -3327,6 +3377,9 @@ struct Planner {
                 continue;
             }
             po.dtype = (t.is_int || declared == 7 || declared == 6) ? 7 : 1;
+            // (the layout conversions below allocate arena bytes: an output whose root was released could be overwritten by the next output's)
+            OAR_CHECK(t.loc.kind != Loc::ARENA || (!t.root.empty() && root_bytes.count(t.root)), OAR_INTERNAL,
+                      "plan liveness: graph output '" + on + "' lives in " + (t.root.empty() ? std::string("a per-node temp") : "root '" + t.root + "', which was released"));
             if (t.layout == Layout::CLAST) { po.has_clast = true; po.loc_clast = t.loc; }
             Loc nat = to_native_loc(t);
             if (nat.kind == Loc::ARENA && nat.off != t.loc.off) {

@@ -10,6 +10,8 @@ coordinate modes, count_include_pad, axis conventions, ...) shows up there inste
 It shares onnx_ref's protobuf reader (parse_model) and nothing else."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 from .onnx_ref import parse_model
@@ -170,6 +172,9 @@ def _grid_sample(x, grid, a):
     return out
 
 
+_erf = np.vectorize(math.erf, otypes=[F64])
+
+
 def run(model, feeds: dict):
     """model: parse_model() dict (or raw bytes).  feeds: name -> np.ndarray.  Returns the graph outputs as float32 / integer arrays."""
     if isinstance(model, (bytes, bytearray)):
@@ -277,9 +282,20 @@ def run(model, feeds: dict):
             y = (z - mu) / np.sqrt(var + a.get("epsilon", 1e-5)) * x[1]
             if len(x) > 2 and x[2] is not None:
                 y = y + x[2]
-        elif op == "ReduceMax":
+        elif op in ("ReduceMax", "ReduceMin", "ReduceMean", "ReduceSum"):
             axes = a.get("axes") or ([int(v) for v in x[1]] if len(x) > 1 and x[1] is not None else list(range(x[0].ndim)))
-            y = x[0].max(axis=tuple(axes), keepdims=bool(a.get("keepdims", 1)))
+            f = {"ReduceMax": np.max, "ReduceMin": np.min, "ReduceMean": np.mean, "ReduceSum": np.sum}[op]
+            y = f(x[0].astype(F64), axis=tuple(int(v) for v in axes), keepdims=bool(a.get("keepdims", 1)))
+        elif op == "Gather":
+            y = np.take(x[0], np.asarray(x[1]).astype(np.int64), axis=a.get("axis", 0))
+        elif op == "Erf":
+            y = _erf(x[0].astype(F64))
+        elif op == "Gelu":
+            z = x[0].astype(F64)
+            if a.get("approximate", "none") == "tanh":
+                y = 0.5 * z * (1.0 + np.tanh(np.sqrt(2.0 / np.pi) * (z + 0.044715 * z ** 3)))
+            else:
+                y = 0.5 * z * (1.0 + _erf(z / np.sqrt(2.0)))
         elif op == "ArgMax":
             ax = a.get("axis", 0)
             if a.get("select_last_index", 0):

@@ -388,6 +388,7 @@ def run(model, feeds: dict, want=None):
             elif op == "Gather":
                 ax = a.get("axis", 0)
                 idx = x[1].long()
+                idx = torch.where(idx < 0, idx + x[0].shape[ax], idx)   # (negative indices count from the end)
                 y = torch.index_select(x[0], ax, idx.reshape(-1)).reshape(
                     list(x[0].shape[:ax]) + list(idx.shape) + list(x[0].shape[ax + 1:]))
             elif op == "Shape":

@@ -43,6 +43,16 @@ def test_random_graphs_match_oracle():
     assert "92/92 cases within" in r.stdout, r.stdout[-1500:]
 
 
+def test_random_late_reader_graphs_match_oracle():
+    """tools/op_fuzz.py kind "late": a node the planner decomposes (or a view) mid-graph, allocations after it, then a late reader of its result -- with the
+    engine's plan-time liveness check on, each graph on two input shapes through one engine."""
+    import os
+    root = Path(__file__).resolve().parents[1]
+    r = subprocess.run([sys.executable, str(root / "tools" / "op_fuzz.py"), "48", "3", "late"], cwd=root, capture_output=True, text=True, timeout=900, env=dict(os.environ, OP_FUZZ_RESHAPE="1"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "48/48 cases within" in r.stdout, r.stdout[-1500:]
+
+
 def test_degenerate_and_extreme_pages_match_oracle():
     """tools/edge_pages.py: no pages (both refuse, ocr.rs:525), a 1 x 1 page, slivers, black / white / noise pages, a page beyond max_side_limit, a dense page, mixed sizes in one
     call -- under three batch policies each."""

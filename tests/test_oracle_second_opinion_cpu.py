@@ -103,3 +103,26 @@ def test_operator_attribute_corners(case):
         g.add_output(tr, ["N", 10, "T"])
         g.add_output(am, ["N", "T"])
         _agree(g.model(), {"x": rng.standard_normal((3, 7, 24)).astype(np.float32)})
+
+
+def test_reductions_gather_erf_gelu():
+    """the operators onnx_np gained for the planner-liveness graphs: ReduceMean / Sum / Min / Max over leading, inner and trailing axis sets with and
+    without keepdims, Gather of one index (scalar and [1]-shaped) and of several, Erf, and Gelu in both forms"""
+    rng = np.random.default_rng(12)
+    g = GraphBuilder("ops")
+    g.add_input("x", ["N", 6, "H", "W"])
+    outs = []
+    for op, axes, kd in (("ReduceMean", [2, 3], 0), ("ReduceMean", [1], 1), ("ReduceSum", [0, 2], 0), ("ReduceSum", [3], 1), ("ReduceMin", [1, 3], 0),
+                         ("ReduceMin", [0], 1), ("ReduceMax", [2], 0), ("ReduceMean", [-1], 0)):
+        outs.append(g.op(op, ["x"], axes=axes, keepdims=kd))
+    outs.append(g.op("ReduceSum", ["x", g.init(np.array([1, 2], np.int64), "axes")], keepdims=1))   # axes as an input (opset 13+)
+    for axis, idx in ((0, np.array(1, np.int64)), (1, np.array([4], np.int64)), (3, np.array(-1, np.int64)), (2, np.array([[0, 2], [1, 1]], np.int64))):
+        outs.append(g.op("Gather", ["x", g.init(idx, "i")], axis=axis))
+    outs.append(g.op("Erf", [g.op("Mul", ["x", g.init(np.array(1.7, np.float32), "c")])]))
+    outs.append(g.op("Gelu", ["x"]))
+    outs.append(g.op("Gelu", ["x"], approximate="tanh"))
+    for o in outs:
+        g.add_output(o, ["A", "B", "C", "D"])
+    got = _agree(g.model(), {"x": (2.5 * rng.standard_normal((3, 6, 5, 7))).astype(np.float32)})
+    assert [a.shape for a in got[:4]] == [(3, 6), (3, 1, 5, 7), (6, 7), (3, 6, 5, 1)]
+    assert [a.shape for a in got[9:13]] == [(6, 5, 7), (3, 1, 5, 7), (3, 6, 5), (3, 6, 2, 2, 7)]

@@ -2,7 +2,7 @@
 eligibility boundary of the bf16x6 kernels (weight-stationary one- and two-fragment tiles, output-stationary, row-streaming 3x3, LDS-tiled large kernel,
 grouped, multi-source concat reads, streaming attention), random epilogues (bias, ReLU / hard-swish / GELU / none, residual).  Reports, per case, the kernel
 classes that ran and the largest |difference| relative to the output scale; the tolerance is the engine tests' 2e-4.
-usage: python tools/op_fuzz.py [n_cases] [seed] [kind]      kind: p2o | neck | net | convmisc | convt | gemm | gridsample | eltwise | reduce | resize | shape | svtr_block | dbhead | fpn | pool | dsblock | dschain | conv1x1 | conv3x3 | convk | grouped | concat | attention | all"""
+usage: python tools/op_fuzz.py [n_cases] [seed] [kind]      kind: p2o | neck | net | convmisc | convt | gemm | gridsample | eltwise | reduce | resize | shape | svtr_block | dbhead | fpn | pool | dsblock | dschain | conv1x1 | conv3x3 | convk | grouped | concat | attention | all | late (named only)"""
 import sys, time
 sys.path.insert(0, ".")
 import numpy as np
@@ -18,7 +18,7 @@ TOL = 2e-4
 import os
 DRY = os.environ.get("OP_FUZZ_DRY") == "1"
 RESHAPE = os.environ.get("OP_FUZZ_RESHAPE") == "1"   # run every case on two input shapes through ONE engine (A, B, A again)
-RESHAPE_KINDS = {"conv1x1", "conv3x3", "convk", "grouped", "concat", "dsblock", "dschain", "net", "attention", "svtr_block", "neck", "convmisc", "eltwise", "dbhead"}
+RESHAPE_KINDS = {"conv1x1", "conv3x3", "convk", "grouped", "concat", "dsblock", "dschain", "net", "attention", "svtr_block", "neck", "convmisc", "eltwise", "dbhead", "late"}
 
 
 def act(g, y, kind):
@@ -718,7 +718,92 @@ def case_p2o():
     return f"p2o {which} c{c} {n}x{h}x{w}", g.model(), (n, 8, h, w)
 
 
+def case_late():
+    """a node the planner decomposes into several operators (inner-axis Softmax, Reduce* off the trailing axes, Gather of one index, the Conv / DSBlock
+    fallbacks) or a graph-level view, placed mid-graph: fresh instances of the same node on new producers of the input and random element-wise ops
+    allocate after it, then a late reader takes its result -- bytes released too early are overwritten by then"""
+    c = int(rng.choice([8, 12, 16, 24]))
+    n, h, w = int(rng.integers(1, 4)), int(rng.integers(2, 20)), 2 * int(rng.integers(1, 16))
+    dim, T = int(rng.choice([8, 24, 33])), int(rng.integers(3, 30))
+    site = str(rng.choice(["softmax_ax1", "softmax_ax2", "softmax_ax1_native", "softmax_ax1_rank5", "softmax_seq_ax1", "softmax_seq_ax0", "reduce_hw", "reduce_spatial",
+                           "reduce_channels", "reduce_seq", "gather_view", "gather_copy", "conv_bcast_res", "conv_se", "dsblock", "view_to_last", "view_from_last",
+                           "view_reshape", "view_squeeze", "view_slice", "view_split"]))
+    seq = site in ("softmax_seq_ax1", "softmax_seq_ax0", "reduce_seq", "gather_view", "gather_copy", "view_slice", "view_split")
+    g = GraphBuilder("f")
+    i64 = lambda v: g.init(np.array(v, np.int64), "i")
+    if seq:
+        g.add_input("x", ["N", "T", dim])
+        prod = lambda: _linear(g, "x", dim, dim)
+    elif site in ("softmax_ax1_native", "view_from_last"):
+        g.add_input("x", ["N", 8, "H", "W"])
+        prod = lambda: g.op("Mul", ["x", g.init(np.array(1.0 + rng.random(), np.float32), "c")])
+    else:
+        g.add_input("x", ["N", 8, "H", "W"])
+        prod = lambda: stem(g, c)
+    cc = 8 if site in ("softmax_ax1_native", "view_from_last") else c
+    kd = int(rng.random() < 0.5)
+
+    def node(t):
+        if site in ("softmax_ax1", "softmax_ax1_native", "softmax_seq_ax1"):
+            return g.op("Softmax", [t], axis=1)
+        if site == "softmax_ax2":
+            return g.op("Softmax", [t], axis=2)
+        if site == "softmax_seq_ax0":
+            return g.op("Softmax", [t], axis=0)
+        if site == "softmax_ax1_rank5":
+            return g.op("Softmax", [g.op("Reshape", [t, i64([0, 0, 0, 2, -1])])], axis=1)
+        if site == "reduce_hw":
+            return g.op("ReduceMean", [t], axes=[2, 3], keepdims=0)
+        if site == "reduce_spatial":
+            return g.op("ReduceMean" if ax_op == 0 else "ReduceMax", [t], axes=[ax_sp], keepdims=kd)
+        if site == "reduce_channels":
+            return g.op(red_op, [t], axes=[1], keepdims=kd)
+        if site == "reduce_seq":
+            return g.op(red_op, [t], axes=[0, 1] if kd else [1], keepdims=kd)
+        if site == "gather_view":
+            return g.op("Gather", [t, g.init(np.array(0, np.int64), "i")], axis=0)
+        if site == "gather_copy":
+            return g.op("Gather", [t, g.init(np.array(part, np.int64), "i")], axis=1)
+        if site == "conv_bcast_res":
+            return g.op("Add", [conv(g, t, c, c, 1), g.op("GlobalAveragePool", [t])])
+        if site == "conv_se":
+            gate = g.op("HardSigmoid", [conv(g, g.op("Relu", [conv(g, g.op("GlobalAveragePool", [t]), c, 4, 1)]), 4, c, 1)], alpha=1.0 / 6.0, beta=0.5)
+            return conv(g, g.op("Mul", [t, gate]), c, 16, 1)
+        if site == "dsblock":
+            return conv(g, g.op("Relu", [conv(g, t, c, c, 3, groups=c)]), c, 16, 1)
+        if site == "view_to_last":
+            return g.op("Transpose", [t], perm=[0, 2, 3, 1])
+        if site == "view_from_last":
+            return g.op("Transpose", [t], perm=[0, 3, 1, 2])
+        if site == "view_reshape":
+            return g.op("Reshape", [t, i64([0, 0, -1])])
+        if site == "view_squeeze":
+            return g.op("Squeeze", [g.op("MaxPool", [t], kernel_shape=[h, 1], strides=[h, 1]), i64([2])])
+        if site == "view_slice":
+            return g.op("Slice", [t, i64([0]), i64([1]), i64([0])])
+        return g.op("Split", [g.op("Transpose", [t], perm=[2, 0, 1]), i64([dim // 2, dim - dim // 2])], n_out=2, axis=0)[part]
+
+    ax_op, ax_sp, part = int(rng.integers(0, 2)), int(rng.choice([2, 3])), int(rng.integers(0, 2))
+    red_op = str(rng.choice(["ReduceMean", "ReduceSum", "ReduceMax", "ReduceMin"]))
+    y = node(prod())
+    z = None
+    for _ in range(int(rng.integers(2, 4))):   # live allocations after y's node: each as large as y
+        t = node(prod())
+        t = g.op(str(rng.choice(["Relu", "Sigmoid", "Neg", "Identity"])), [t]) if rng.random() < 0.5 else t
+        z = t if z is None else g.op("Add", [z, t])
+    out = g.op(str(rng.choice(["Sub", "Mul", "Max"])), [y, z])
+    rank = {"reduce_hw": 2, "gather_view": 2, "gather_copy": 2, "softmax_ax1_rank5": 5, "view_reshape": 3, "view_squeeze": 3}.get(site, 3 if seq else 4)
+    if site == "reduce_spatial" or site == "reduce_channels":
+        rank = 4 if kd else 3
+    if site == "reduce_seq":
+        rank = 3 if kd else 2
+    g.add_output(out, [f"d{i}" for i in range(rank)])
+    return f"late {site}{' kd' if kd else ''} c{cc} {n}x{h}x{w} dim{dim} T{T}", g.model(), ((n, T, dim) if seq else (n, 8, h, w))
+
+
 KINDS = {"p2o": case_p2o, "neck": case_neck, "net": case_net, "convmisc": case_convmisc, "convt": case_convt, "gemm": case_gemm, "gridsample": case_gridsample, "eltwise": case_eltwise, "reduce": case_reduce, "resize": case_resize, "shape": case_shape, "svtr_block": case_svtr_block, "dbhead": case_dbhead, "fpn": case_fpn, "pool": case_pool, "dsblock": case_dsblock, "dschain": case_dschain, "conv1x1": case_conv1x1, "conv3x3": case_conv3x3, "convk": case_convk, "grouped": case_grouped, "concat": case_concat, "attention": case_attention}
+# kinds that run only when named: adding one to the "all" rotation would change every draw of the seeded slices
+KINDS_BY_NAME = {"late": case_late}
 names = list(KINDS) if only == "all" else [only]
 bad = 0
 worst = {}
@@ -726,7 +811,7 @@ seen = {}
 t0 = time.time()
 for i in range(n_cases):
     kind = names[i % len(names)]
-    label, model, shape = KINDS[kind]()
+    label, model, shape = {**KINDS, **KINDS_BY_NAME}[kind]()
     x = rng.standard_normal(shape).astype(np.float32)
     if DRY:   # (no GPU: the graphs only -- build, parse, evaluate on the CPU)
         r = onnx_ref.run(model, {"x": x})
