@@ -135,6 +135,64 @@ void Profiler::drop_events() {
     pool.clear();
     (void)hipGetLastError();   // (results deliberately ignored above: do not leave their error state behind)
 }
+void Profiler::add_lanes(const void* owner, const std::vector<hipStream_t>& streams) {
+    if (streams.size() < 2) return;
+    std::unique_ptr<LaneGroup> g(new LaneGroup());
+    g->owner = owner;
+    for (hipStream_t st : streams) {
+        hipEvent_t e;
+        OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        g->streams.push_back(st);
+        g->marks.push_back(e);
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    lane_groups.push_back(std::move(g));
+}
+void Profiler::remove_lanes(const void* owner) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto it = lane_groups.begin(); it != lane_groups.end(); ++it) {
+        if ((*it)->owner != owner) continue;
+        for (hipEvent_t e : (*it)->marks) (void)hipEventDestroy(e);
+        lane_groups.erase(it);
+        (void)hipGetLastError();
+        return;
+    }
+}
+// A wait captures the event's state at the time of the call, so one mark per lane stream is re-recorded by every fence.  A stream
+// that is in several groups (identical groups: a recognizer on its detector's lane streams) is fenced once.
+bool Profiler::fence_before(hipStream_t s) {
+    std::lock_guard<std::mutex> lk(mu);
+    bool found = false;
+    std::vector<hipStream_t> done;
+    for (auto& g : lane_groups) {
+        bool in = false;
+        for (hipStream_t st : g->streams) in = in || st == s;
+        if (!in) continue;
+        found = true;
+        for (size_t i = 0; i < g->streams.size(); ++i) {
+            if (g->streams[i] == s || std::find(done.begin(), done.end(), g->streams[i]) != done.end()) continue;
+            done.push_back(g->streams[i]);
+            OAR_HIP(hipEventRecord(g->marks[i], g->streams[i]));
+            OAR_HIP(hipStreamWaitEvent(s, g->marks[i], 0));
+        }
+    }
+    return found;
+}
+void Profiler::fence_after(hipStream_t s) {
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<hipStream_t> done;
+    for (auto& g : lane_groups) {
+        size_t self = g->streams.size();
+        for (size_t i = 0; i < g->streams.size(); ++i) if (g->streams[i] == s) self = i;
+        if (self == g->streams.size()) continue;
+        (void)hipEventRecord(g->marks[self], s);
+        for (size_t i = 0; i < g->streams.size(); ++i) {
+            if (i == self || std::find(done.begin(), done.end(), g->streams[i]) != done.end()) continue;
+            done.push_back(g->streams[i]);
+            (void)hipStreamWaitEvent(g->streams[i], g->marks[self], 0);
+        }
+    }
+}
 void Profiler::reset() {
     flush();
     std::lock_guard<std::mutex> lk(mu);

@@ -165,12 +165,25 @@ struct Profiler {
     // hipErrorStreamCaptureUnsupported from whatever call came next: seen as a 1-in-8 flake of the profiler-using engine tests).
     void drop_events();
     void reset();
+
+    // Lanes: streams of engine instances whose work overlaps (the detector's and the recognizer's lanes).  A SAMPLED launch on
+    // one of them is fenced against the others -- its stream first waits for everything already enqueued on the other lanes,
+    // and they wait for it before their next work -- so its hipEvent interval holds that kernel alone while unsampled launches
+    // keep overlapping.  A stream may be in several groups (a detector lane and the recognizer lane of the same index share
+    // one); it is fenced against the union.  Unfenced (and nothing extra enqueued) while the profiler is off or not sampling.
+    struct LaneGroup { const void* owner; std::vector<hipStream_t> streams; std::vector<hipEvent_t> marks; };   // marks[i]: the fence event of streams[i]
+    std::vector<std::unique_ptr<LaneGroup>> lane_groups;
+    void add_lanes(const void* owner, const std::vector<hipStream_t>& streams);   // no-op for fewer than two streams
+    void remove_lanes(const void* owner);                                         // before any of the owner's streams is destroyed
+    bool fence_before(hipStream_t s);   // false: s is in no lane group (no fence_after needed)
+    void fence_after(hipStream_t s);
 };
 
 struct ProfScope {
     hipStream_t s;
     bool on;
     bool ext = false;
+    bool fenced = false;   // the launch is fenced against the other lanes (Profiler::fence_before)
     hipEvent_t a = nullptr, b = nullptr;
     size_t handle = 0;
     // single_launch: the scope covers exactly one kernel and the launch site passes start() / stop() to
@@ -185,11 +198,13 @@ struct ProfScope {
         }
         if (!on) return;
         const int c = p.cls(name);
+        if (!Profiler::capturing) fenced = p.fence_before(s);   // (a capture may not wait on other streams)
         if (single_launch && p.begin_ext(c, bytes, flops, a, b)) ext = true;
         else handle = p.begin(s, c, bytes, flops);
     }
     ~ProfScope() {
         if (on && !ext) Profiler::get().end(s, handle);
+        if (fenced) Profiler::get().fence_after(s);
     }
     hipEvent_t start() const { return ext ? a : nullptr; }
     hipEvent_t stop() const { return ext ? b : nullptr; }

@@ -227,6 +227,18 @@ Detector::Detector(const uint8_t* onnx, size_t len, const oar_det_cfg& cfg) : cf
     OAR_CHECK(cfg_.box_type == 0 || cfg_.box_type == 1, OAR_INVALID_INPUT, "box_type must be 0 (Quad) or 1 (Poly)");
     OAR_CHECK(cfg_.score_mode == 0 || cfg_.score_mode == 1, OAR_INVALID_INPUT, "score_mode must be 0 (fast) or 1 (slow)");
     eng_.reset(new Engine(onnx, len, cfg_.device_id));
+    // OAR_DET_LANES (default 2, 1 = one engine on one stream): read per handle.  The lane streams are created right after the first
+    // engine's, before the auxiliary streams, so that they land on different hardware queues (HIP hands queues out in stream order).
+    const int n_lanes = [] { const char* e = getenv("OAR_DET_LANES"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > 4 ? 4 : v; }();
+    for (int i = 1; i < n_lanes; ++i) {
+        lanes_.emplace_back(new Engine(onnx, len, cfg_.device_id));
+        lane_in_.emplace_back(new DevBuf());
+    }
+    if (n_lanes > 1) {
+        std::vector<hipStream_t> ls;
+        for (int i = 0; i < n_lanes; ++i) ls.push_back(lane_stream(i));
+        Profiler::get().add_lanes(this, ls);
+    }
     pool_.reset(new ThreadPool(cfg_.host_threads));
     OAR_HIP(hipSetDevice(eng_->device()));
     // OAR_CONTOUR_CUS=n (experiment): the streams that carry the border follower / unclip / box scores are confined to n CUs spread over
@@ -245,9 +257,13 @@ Detector::Detector(const uint8_t* onnx, size_t len, const oar_det_cfg& cfg) : cf
     OAR_HIP(hipStreamCreateWithFlags(&upload_stream_, hipStreamNonBlocking));
     OAR_HIP(hipStreamCreateWithFlags(&upload_stream2_, hipStreamNonBlocking));
     OAR_HIP(hipEventCreateWithFlags(&stage_free_, hipEventDisableTiming));
+    OAR_HIP(hipEventCreateWithFlags(&lanes_start_, hipEventDisableTiming));
 }
 Detector::~Detector() {
+    if (!lanes_.empty()) Profiler::get().remove_lanes(this);
     Profiler::get().drop_events();   // (see Profiler::drop_events: pooled events must not outlive the streams they were recorded on)
+    for (auto& l : lanes_) (void)hipStreamSynchronize(l->stream());
+    if (lanes_start_) (void)hipEventDestroy(lanes_start_);
     if (copy_stream_) { (void)hipStreamSynchronize(copy_stream_); (void)hipStreamDestroy(copy_stream_); }
     if (score_stream_) { (void)hipStreamSynchronize(score_stream_); (void)hipStreamDestroy(score_stream_); }
     if (upload_stream_) { (void)hipStreamSynchronize(upload_stream_); (void)hipStreamDestroy(upload_stream_); }
@@ -258,6 +274,10 @@ Detector::~Detector() {
     for (hipEvent_t e : sub_events_) (void)hipEventDestroy(e);
     for (hipEvent_t e : mask_ready_) (void)hipEventDestroy(e);
     for (hipEvent_t e : score_done_) (void)hipEventDestroy(e);
+}
+
+void Detector::sync_lanes() {
+    for (auto& l : lanes_) OAR_HIP(hipStreamSynchronize(l->stream()));
 }
 
 namespace {
@@ -605,7 +625,7 @@ void Detector::run(const std::vector<PageRef>& pages, float thresh, float box_th
         OAR_CHECK(p.w > 0 && p.h > 0 && (p.host || p.dev), OAR_INVALID_INPUT, "detector: empty page");
         if (!p.dev) total += ((size_t)p.w * p.h * 3 + 255) & ~(size_t)255;
     }
-    if (total > pages_dev_.cap) { OAR_HIP(hipStreamSynchronize(s)); OAR_HIP(hipStreamSynchronize(upload_stream_)); OAR_HIP(hipStreamSynchronize(upload_stream2_)); pages_dev_.reserve(total); }
+    if (total > pages_dev_.cap) { OAR_HIP(hipStreamSynchronize(s)); sync_lanes(); OAR_HIP(hipStreamSynchronize(upload_stream_)); OAR_HIP(hipStreamSynchronize(upload_stream2_)); pages_dev_.reserve(total); }
     // whatever still reads the staging area on the engine stream (the previous call's crop kernels) must be done before
     // this call's uploads overwrite it
     OAR_HIP(hipEventRecord(stage_free_, s));
@@ -631,7 +651,7 @@ void Detector::run(const std::vector<PageRef>& pages, float thresh, float box_th
     size_t pad_total = 0;
     for (int i = 0; i < n; ++i)
         if (pages[i].h + pages[i].w < 64) pad_total += ((size_t)std::max(pages[i].w, 32u) * std::max(pages[i].h, 32u) * 3 + 255) & ~(size_t)255;
-    if (pad_total > padded_dev_.cap) { OAR_HIP(hipStreamSynchronize(s)); padded_dev_.reserve(pad_total); }
+    if (pad_total > padded_dev_.cap) { OAR_HIP(hipStreamSynchronize(s)); sync_lanes(); padded_dev_.reserve(pad_total); }
     size_t pad_off = 0;
     for (int i = 0; i < n; ++i) {
         det_src_[i] = page_ptrs_[i]; det_w_[i] = pages[i].w; det_h_[i] = pages[i].h;
@@ -719,21 +739,37 @@ void Detector::run_group(const std::vector<int>& idx, const std::vector<PageRef>
     size_t need_in = (size_t)SB * plane * 3 * sizeof(float);
     size_t need_rs = 0;
     for (int b = 0; b < B; ++b) if (det_w_[idx[b]] != rw || det_h_[idx[b]] != rh) need_rs += (plane * 3 + 255) & ~(size_t)255;
-    if (need_in > input_f32_.cap || need_rs > resized_dev_.cap || (size_t)B * hw > mask_dev_.cap || (size_t)B * hw * 4 > probs_keep_.cap ||
+    bool lane_in_short = false;
+    for (auto& li : lane_in_) lane_in_short = lane_in_short || need_in > li->cap;
+    if (need_in > input_f32_.cap || lane_in_short || need_rs > resized_dev_.cap || (size_t)B * hw > mask_dev_.cap || (size_t)B * hw * 4 > probs_keep_.cap ||
         (cfg_.use_dilation && (size_t)B * hw > mask_dil_.cap)) {
-        OAR_HIP(hipStreamSynchronize(s));
+        OAR_HIP(hipStreamSynchronize(s)); sync_lanes();
         input_f32_.reserve(need_in); resized_dev_.reserve(need_rs); mask_dev_.reserve((size_t)B * hw); probs_keep_.reserve((size_t)B * hw * 4);
+        for (auto& li : lane_in_) li->reserve(need_in);
         if (cfg_.use_dilation) mask_dil_.reserve((size_t)B * hw);
     }
     mask_host_.reserve((size_t)B * hw);
     const size_t hbits = (size_t)H * ((W + 7) / 8);   // bytes of one mask as a bit plane (what the host border follower reads back)
-    if ((size_t)B * hbits > mask_bits_.cap) { OAR_HIP(hipStreamSynchronize(s)); OAR_HIP(hipStreamSynchronize(copy_stream_)); mask_bits_.reserve((size_t)B * hbits); }
+    if ((size_t)B * hbits > mask_bits_.cap) { OAR_HIP(hipStreamSynchronize(s)); sync_lanes(); OAR_HIP(hipStreamSynchronize(copy_stream_)); mask_bits_.reserve((size_t)B * hbits); }
     // a8 on the host pool (default) or on the GPU: oar_det_cfg.gpu_contours, overridden by OAR_GPU_CONTOURS=0|1
     static const int gpu_contours_env = [] { const char* e = getenv("OAR_GPU_CONTOURS"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1; }();
     const bool gpu_contours = gpu_contours_env >= 0 ? gpu_contours_env == 1 : cfg_.gpu_contours != 0;
     if (gpu_contours) {
-        if (!trace_.fits(B, SB, H, W, nsub)) { OAR_HIP(hipStreamSynchronize(s)); OAR_HIP(hipStreamSynchronize(copy_stream_)); }
+        if (!trace_.fits(B, SB, H, W, nsub)) { OAR_HIP(hipStreamSynchronize(s)); sync_lanes(); OAR_HIP(hipStreamSynchronize(copy_stream_)); }
         trace_.reserve(B, SB, H, W, nsub);
+    }
+    // OAR_GPU_CONTOURS_INLINE=1 (experiment, round 5; default 0): the border follower ON the detector's stream, between this sub-batch's network and the
+    // next one's.  Measured (profiles/r5/gpu_follower_inline.txt): 35.6 ms per step against 31.3 on its own stream and 14-25 with the host tracer -- the
+    // follower's launch time is not queueing behind the network but its own serial work: one wave per mask segment, ~0.5 us per border pixel, so a launch
+    // lasts as long as its longest segment (a 900-pixel text line: ~1.5 ms), alone on the GPU as well.
+    static const bool trace_inline = [] { const char* e = getenv("OAR_GPU_CONTOURS_INLINE"); return e && atoi(e) != 0; }();
+    // sub-batch sb runs on lane sb % L.  Every buffer a sub-batch's kernels write is per page (resized copies, kept probabilities, masks, bit
+    // planes) or per lane (engine arena, unfused input tensor); the tracer's shared work space stays in order on the copy stream, so the
+    // inline tracer (which would run it on the lane streams) keeps one lane.
+    const int L = (gpu_contours && trace_inline) ? 1 : std::min(lanes(), nsub);
+    if (L > 1) {   // what run() put on lane 0 before the sub-batches (padded pages, their uploads) precedes every lane
+        OAR_HIP(hipEventRecord(lanes_start_, s));
+        for (int l = 1; l < L; ++l) OAR_HIP(hipStreamWaitEvent(lane_stream(l), lanes_start_, 0));
     }
     while ((int)sub_events_.size() < nsub) { hipEvent_t e; OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); sub_events_.push_back(e); }
     while ((int)mask_ready_.size() < nsub) { hipEvent_t e; OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); mask_ready_.push_back(e); }
@@ -789,6 +825,10 @@ void Detector::run_group(const std::vector<int>& idx, const std::vector<PageRef>
     // GPU work of one sub-batch: (wait for its pages) -> normalize -> network -> threshold -> mask D2H on the copy stream
     auto enqueue = [&](int sb) {
         const int b0 = sb_off[sb], nb = sb_off[sb + 1] - b0;
+        const int lane = sb % L;
+        Engine& le = lane_engine(lane);
+        const hipStream_t s = le.stream();
+        float* const in_f32 = lane == 0 ? input_f32_.as<float>() : lane_in_[lane - 1]->as<float>();
         const uint8_t* srcs[32];
         if (any_upload) {
             for (int t = 0; t < n_up; ++t)
@@ -807,16 +847,16 @@ void Detector::run_group(const std::vector<int>& idx, const std::vector<PageRef>
                 rs_off += (plane * 3 + 255) & ~(size_t)255;
             }
             if (nb <= 32) srcs[k] = src;
-            else pp::normalize(s, src, input_f32_.as<float>() + (size_t)k * plane * 3, 1, (int64_t)plane, kDbSrc, alpha, beta, 1);
+            else pp::normalize(s, src, in_f32 + (size_t)k * plane * 3, 1, (int64_t)plane, kDbSrc, alpha, beta, 1);
         }
         k::StemU8 st{};
         if (stem) {
             for (int k = 0; k < nb; ++k) st.pages[k] = srcs[k];
             for (int c = 0; c < 3; ++c) { st.src[c] = kDbSrc[c]; st.alpha[c] = alpha[c]; st.beta[c] = beta[c]; }
         } else if (nb <= 32) {
-            pp::normalize_pages(s, srcs, nb, input_f32_.as<float>(), (int64_t)plane, kDbSrc, alpha, beta, 1);   // one launch per sub-batch
+            pp::normalize_pages(s, srcs, nb, in_f32, (int64_t)plane, kDbSrc, alpha, beta, 1);   // one launch per sub-batch
         }
-        const Plan& plan = stem ? eng_->run_stem(st, {nb, 3, (int64_t)rh, (int64_t)rw}) : eng_->run(input_f32_.as<float>(), {nb, 3, (int64_t)rh, (int64_t)rw}, true);
+        const Plan& plan = stem ? le.run_stem(st, {nb, 3, (int64_t)rh, (int64_t)rw}) : le.run(in_f32, {nb, 3, (int64_t)rh, (int64_t)rw}, true);
         const PlanOutput& po = plan.outputs[0];
         OAR_CHECK(po.dims.size() == 4 && po.dims[0] == nb && po.dims[1] == C && po.dims[2] == H && po.dims[3] == W, OAR_SHAPE_MISMATCH,
                   "DB: inconsistent output shape across sub-batches");
@@ -826,9 +866,9 @@ void Detector::run_group(const std::vector<int>& idx, const std::vector<PageRef>
         const bool fused_finish = fused_finish_env && !gpu_contours && !cfg_.use_dilation;   // nothing else reads the byte mask then
         const uint8_t* traced = mask_dev_.as<uint8_t>() + (size_t)b0 * hw;
         if (fused_finish) {
-            pp::db_keep_and_pack(s, eng_->out_ptr(po.loc), (int64_t)(hw * C), probs + (size_t)b0 * hw, mask_bits_.as<uint8_t>() + (size_t)b0 * hbits, nb, H, W, thresh);
+            pp::db_keep_and_pack(s, le.out_ptr(po.loc), (int64_t)(hw * C), probs + (size_t)b0 * hw, mask_bits_.as<uint8_t>() + (size_t)b0 * hbits, nb, H, W, thresh);
         } else {
-            k::copy2d(s, eng_->out_ptr(po.loc), probs + (size_t)b0 * hw, nb, (int)hw, (int)(hw * C), (int)hw);
+            k::copy2d(s, le.out_ptr(po.loc), probs + (size_t)b0 * hw, nb, (int)hw, (int)(hw * C), (int)hw);
             pp::threshold(s, probs + (size_t)b0 * hw, mask_dev_.as<uint8_t>() + (size_t)b0 * hw, (int64_t)nb * hw, thresh);
         }
         if (cfg_.use_dilation) {   // db_postprocess.rs:163-168: the contours are traced on the dilated mask, the scores still read pred
@@ -836,11 +876,6 @@ void Detector::run_group(const std::vector<int>& idx, const std::vector<PageRef>
             traced = mask_dil_.as<uint8_t>() + (size_t)b0 * hw;
         }
         OAR_HIP(hipEventRecord(mask_ready_[sb], s));
-        // OAR_GPU_CONTOURS_INLINE=1 (experiment, round 5; default 0): the border follower ON the detector's stream, between this sub-batch's network and the
-        // next one's.  Measured (profiles/r5/gpu_follower_inline.txt): 35.6 ms per step against 31.3 on its own stream and 14-25 with the host tracer -- the
-        // follower's launch time is not queueing behind the network but its own serial work: one wave per mask segment, ~0.5 us per border pixel, so a launch
-        // lasts as long as its longest segment (a 900-pixel text line: ~1.5 ms), alone on the GPU as well.
-        static const bool trace_inline = [] { const char* e = getenv("OAR_GPU_CONTOURS_INLINE"); return e && atoi(e) != 0; }();
         hipStream_t ts = (gpu_contours && trace_inline) ? s : copy_stream_;
         if (ts != s) OAR_HIP(hipStreamWaitEvent(copy_stream_, mask_ready_[sb], 0));
         if (gpu_contours) {
@@ -1136,21 +1171,31 @@ void Detector::postprocess_host(const float* pred, int H, int W, uint32_t src_w,
 }
 
 // ================================================================================================= recognizer
-Recognizer::Recognizer(const uint8_t* onnx, size_t len, const oar_rec_cfg& cfg) : cfg_(cfg) {
+Recognizer::Recognizer(const uint8_t* onnx, size_t len, const oar_rec_cfg& cfg, const std::vector<hipStream_t>& lane_streams) : cfg_(cfg) {
     if (cfg_.rec_image_shape[0] == 0) { cfg_.rec_image_shape[0] = 3; cfg_.rec_image_shape[1] = 48; cfg_.rec_image_shape[2] = 320; }
     if (cfg_.max_img_w == 0) cfg_.max_img_w = 3200;
-    eng_.reset(new Engine(onnx, len, cfg_.device_id));
-    // OAR_REC_LANES (default 1): with 2 lanes bench.py gains 4-5 % (1447-1500 vs 1393-1421 images/s), but the kernels of
-    // the two streams then share the GPU and their individual durations (the roofline accounting, the rocprof averages)
-    // stop being comparable with the isolated numbers -- opt-in until the profiler separates lanes
-    const int n_lanes = [] { const char* e = getenv("OAR_REC_LANES"); int v = e ? atoi(e) : 1; return v < 1 ? 1 : v > 4 ? 4 : v; }();   // read per handle: bench.py times both
+    eng_.reset(new Engine(onnx, len, cfg_.device_id, lane_streams.empty() ? nullptr : lane_streams[0]));
+    // OAR_REC_LANES (default 2; 1 = one engine on one stream): bench.py gained 3-5 % with 2 lanes in every round it was timed (r6: 2309 -> 2379
+    // images/s).  The kernels of the two streams share the GPU; a launch the profiler samples is fenced against the other lanes
+    // (Profiler::add_lanes), so its timed duration is still the kernel's own.
+    const int n_lanes = [] { const char* e = getenv("OAR_REC_LANES"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > 4 ? 4 : v; }();   // read per handle: bench.py times both
     for (int i = 1; i < n_lanes; ++i) {
-        lanes_.emplace_back(new Engine(onnx, len, cfg_.device_id));
+        lanes_.emplace_back(new Engine(onnx, len, cfg_.device_id, i < (int)lane_streams.size() ? lane_streams[i] : nullptr));
         lane_in_.emplace_back(new DevBuf());
         hipEvent_t ev;
         OAR_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         lane_done_.push_back(ev);
     }
+    if (n_lanes > 1) {
+        std::vector<hipStream_t> ls{eng_->stream()};
+        for (auto& l : lanes_) ls.push_back(l->stream());
+        Profiler::get().add_lanes(this, ls);
+    }
+}
+Recognizer::~Recognizer() {
+    if (!lanes_.empty()) Profiler::get().remove_lanes(this);
+    for (auto& l : lanes_) (void)hipStreamSynchronize(l->stream());
+    for (hipEvent_t e : lane_done_) (void)hipEventDestroy(e);
 }
 
 const float* Recognizer::pack(const std::vector<Crop>& crops, int& Wt, bool nchw, size_t desc_slot, size_t stage_slot, int lane) {
@@ -1615,7 +1660,13 @@ Ocr::Ocr(const uint8_t* det, size_t det_len, const uint8_t* rec, size_t rec_len,
     OAR_CHECK(cfg_.image_batch_size <= 4096 && cfg_.region_batch_size <= 4096, OAR_INVALID_INPUT,
               "batch sizes must be in 1..=4096");                  // src/oarocr/ocr.rs:250-255,419-430
     det_.reset(new Detector(det, det_len, cfg_.det));
-    rec_.reset(new Recognizer(rec, rec_len, cfg_.rec));
+    // the recognizer's lane i runs on the detector's lane-i stream: the two phases of a call take turns on it.  Lanes then add one stream,
+    // not two, and the recognizer's lanes sit on the hardware queues of the detector's, which are distinct (a recognizer stream of its own
+    // was handed the queue of detector lane 1 -- the two recognizer lanes then ran one after the other: rocprofv3 --kernel-trace Queue_Id)
+    // (OAR_DET_LANES=1 keeps the recognizer's streams its own, as before lanes)
+    std::vector<hipStream_t> lane_streams;
+    for (int i = 0; det_->lanes() > 1 && i < det_->lanes(); ++i) lane_streams.push_back(det_->lane_stream(i));
+    rec_.reset(new Recognizer(rec, rec_len, cfg_.rec, lane_streams));
 }
 
 // DocumentPreprocessor::preprocess (src/oarocr/preprocess.rs:59-97) for every page: optional orientation class ->

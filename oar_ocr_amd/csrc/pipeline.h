@@ -90,6 +90,9 @@ class Detector {
     void run(const std::vector<PageRef>& pages, float thresh, float box_thresh, float unclip, std::vector<DetBoxes>& out,
              std::vector<const uint8_t*>* dev_pages_out = nullptr, const ReadyFn& on_ready = nullptr);
     Engine& engine() { return *eng_; }
+    // detector lanes (OAR_DET_LANES): lane 0 is engine(); the streams of lanes >= 1 are lent to the recognizer's lanes of the same index
+    int lanes() const { return 1 + (int)lanes_.size(); }
+    hipStream_t lane_stream(int lane) const { return lane == 0 ? eng_->stream() : lanes_[lane - 1]->stream(); }
     static void postprocess_host(const float* pred, int H, int W, uint32_t src_w, uint32_t src_h, float thresh, float box_thresh,
                                  float unclip, uint32_t max_candidates, DetBoxes& out, int score_mode = 0, int use_dilation = 0, int box_type = 0);
     ThreadPool& pool() { return *pool_; }
@@ -100,6 +103,13 @@ class Detector {
     void run_group(const std::vector<int>& idx, const std::vector<PageRef>& pages, uint32_t rh, uint32_t rw, float thresh,
                    float box_thresh, float unclip, std::vector<DetBoxes>& out, const ReadyFn& on_ready);
     std::unique_ptr<Engine> eng_;
+    // Sub-batches are independent page sets: sub-batch sb runs on lane sb % lanes() -- its own engine (same weights, own arena)
+    // on its own stream -- so one sub-batch's low-resolution tail of short launches overlaps the next one's network.
+    std::vector<std::unique_ptr<Engine>> lanes_;
+    std::vector<std::unique_ptr<DevBuf>> lane_in_;   // input_f32_ of lanes >= 1 (unfused-stem path)
+    hipEvent_t lanes_start_ = nullptr;               // lanes >= 1 wait for what run() enqueued on lane 0 before the sub-batches (padded pages)
+    Engine& lane_engine(int lane) { return lane == 0 ? *eng_ : *lanes_[lane - 1]; }
+    void sync_lanes();                               // every lane stream idle (before a shared buffer is reallocated)
     std::unique_ptr<ThreadPool> pool_;
     oar_det_cfg cfg_;
     DevBuf pages_dev_, resized_dev_, input_f32_, mask_dev_, probs_keep_;
@@ -144,7 +154,10 @@ struct RecOut {
 // TextRecognitionAdapter + CRNNModel (domain/adapters/text_recognition_adapter.rs:35-111, models/recognition/crnn.rs:247-293)
 class Recognizer {
    public:
-    Recognizer(const uint8_t* onnx, size_t len, const oar_rec_cfg& cfg);
+    // lane_streams (optional): the stream of lane i (Detector::lane_stream: a detector lane and the recognizer lane of the same index
+    // share one stream); lanes beyond it get their own
+    Recognizer(const uint8_t* onnx, size_t len, const oar_rec_cfg& cfg, const std::vector<hipStream_t>& lane_streams = {});
+    ~Recognizer();
     struct Crop { const uint8_t* host = nullptr; const uint8_t* dev = nullptr; uint32_t w = 0, h = 0; bool flip = false; };   // flip: recognise rotate180 of the crop
     void run(const std::vector<Crop>& crops, RecOut& out);
     // Several recognition batches back to back on the engine stream with ONE synchronisation at the end
