@@ -1901,3 +1901,135 @@ def host_rotate_back_points(pts: np.ndarray, angle: float, rotated_w: int, rotat
     p = np.ascontiguousarray(pts, np.float32).copy()
     _check(lib().oar_host_rotate_back_points(_p(p), p.size // 2, C.c_float(angle), rotated_w, rotated_h))
     return p
+
+
+# ---------------------------------------------------------------------------------------------- table cell detection / classification
+@dataclass
+class TableCellModelConfig:
+    """domain/adapters/table_cell_detection_adapter.rs:18-59"""
+    model_name: str
+    num_classes: int
+    class_labels: dict
+    model_type: str = "rtdetr"
+    input_size: Optional[tuple] = (640, 640)
+
+    @staticmethod
+    def rtdetr_l_wired_table_cell_det():
+        return TableCellModelConfig("rt-detr-l_wired_table_cell_det", 1, {0: "cell"}, "rtdetr", (640, 640))
+
+    @staticmethod
+    def rtdetr_l_wireless_table_cell_det():
+        return TableCellModelConfig("rt-detr-l_wireless_table_cell_det", 1, {0: "cell"}, "rtdetr", (640, 640))
+
+
+@dataclass
+class TableCellDetectionConfig:
+    """domain/tasks/table_cell_detection.rs:15-34"""
+    score_threshold: float = 0.3
+    max_cells: int = 300
+
+    def validate(self):
+        if not (0.0 <= self.score_threshold <= 1.0):       # (also refuses NaN)
+            raise OCRError(OAR_INVALID_INPUT, "score_threshold must be in [0.0, 1.0]")
+        if self.max_cells < 1:
+            raise OCRError(OAR_INVALID_INPUT, "max_cells must be >= 1")
+
+
+@dataclass
+class TableCellDetection:
+    bbox: np.ndarray          # [4, 2]: x1 y1, x2 y1, x2 y2, x1 y2 in the pixels of the image given to predict
+    score: float
+    label: str
+
+
+class TableCellDetectionPredictor:
+    """TableCellDetectionAdapter (domain/adapters/table_cell_detection_adapter.rs:61-178, 227-288) over RTDetrModel: DetResizeForTest to the fixed
+    image_shape with its default Triangle filter, BGR, scale 1/255 without mean / std shift (models/detection/rtdetr.rs:38-50, 86-112), the graph
+    with its query selection on the device, and LayoutPostProcess (model_type "rtdetr", NMS 0.5, max_detections = max_cells) -- one C call into the
+    layout adapter's HBM-resident kernels; then the adapter's own per-call filter (score < threshold dropped, stop at max_cells)."""
+
+    def __init__(self, onnx_bytes: bytes, model_config: Optional[TableCellModelConfig] = None, config: Optional[TableCellDetectionConfig] = None, device_id: int = 0):
+        self.model_config = model_config or TableCellModelConfig.rtdetr_l_wired_table_cell_det()
+        self.config = config or TableCellDetectionConfig()
+        self.config.validate()
+        if self.model_config.model_type != "rtdetr":
+            raise OCRError(OAR_INVALID_INPUT, f"Unsupported model type '{self.model_config.model_type}' for table cell detection. Supported type: rtdetr")
+        c = LayoutCfg()
+        c.device_id = device_id
+        c.input_h, c.input_w = self.model_config.input_size or (640, 640)
+        c.resize_filter, c.color_bgr, c.scale = LAYOUT_FILTERS["triangle"], 1, 1.0 / 255.0
+        c.mean, c.std = (C.c_float * 3)(0.0, 0.0, 0.0), (C.c_float * 3)(1.0, 1.0, 1.0)
+        c.num_classes, c.model_type = self.model_config.num_classes, LAYOUT_MODEL_TYPES["rtdetr"]
+        c.score_threshold, c.nms_threshold, c.max_detections = self.config.score_threshold, 0.5, self.config.max_cells
+        buf = (C.c_char * len(onnx_bytes)).from_buffer_copy(onnx_bytes)
+        self._h = C.c_void_p()
+        _check(lib().oar_layout_create(C.cast(buf, C.c_void_p), len(onnx_bytes), C.byref(c), C.byref(self._h)))
+        self.input_hw = (int(c.input_h), int(c.input_w))
+
+    @staticmethod
+    def recommended_batch_size() -> int:
+        return 4
+
+    def preprocess(self, image: np.ndarray) -> np.ndarray:
+        img = np.ascontiguousarray(image, np.uint8)
+        out = np.empty((3, self.input_hw[0], self.input_hw[1]), np.float32)
+        _check(lib().oar_layout_preprocess(self._h, _p(img), img.shape[1], img.shape[0], _p(out)))
+        return out
+
+    def detect_raw(self, images: Sequence[np.ndarray]):
+        """LayoutPostProcess::apply's output: per image (boxes [k, 4], classes [k], scores [k])"""
+        imgs, ptrs, ws, hs = _img_arrays(images)
+        res = LayoutResult()
+        _check(lib().oar_layout_run(self._h, ptrs, ws, hs, len(imgs), C.byref(res)))
+        try:
+            return _unpack_layout(res)
+        finally:
+            lib().oar_layout_result_free(C.byref(res))
+
+    def predict(self, images: Sequence[np.ndarray], config: Optional[TableCellDetectionConfig] = None) -> List[List[TableCellDetection]]:
+        cfg = config or self.config
+        cfg.validate()
+        out = []
+        for i0 in range(0, len(images), self.recommended_batch_size()):
+            for boxes, classes, scores in self.detect_raw(images[i0:i0 + self.recommended_batch_size()]):
+                cells = []
+                for b, c, s in zip(boxes, classes, scores):
+                    if s < np.float32(cfg.score_threshold):
+                        continue
+                    cells.append(TableCellDetection(np.array([[b[0], b[1]], [b[2], b[1]], [b[2], b[3]], [b[0], b[3]]], np.float32), float(s),
+                                                    self.model_config.class_labels.get(int(c), "cell")))
+                    if len(cells) >= cfg.max_cells:
+                        break
+                out.append(cells)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.oar_layout_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@dataclass
+class LabelledClassification:
+    class_id: int
+    score: float
+    label: str
+
+
+class TableClassifier(ImageClassifier):
+    """TableClassificationAdapter (domain/adapters/table_classification_adapter.rs): PP-LCNet with pp_lcnet_preprocess(input_shape) -- the
+    PP-LCNet defaults, resize-short 256 then the centre crop (domain/adapters/preprocessing.rs:19-24) -- and the labels wired_table / wireless_table."""
+    LABELS = ["wired_table", "wireless_table"]
+
+    def __init__(self, model: bytes, input_hw=(224, 224), topk: int = 1, device_id: int = 0):
+        super().__init__(model, input_hw=input_hw, resize_short=256, topk=topk, device_id=device_id)
+
+    def predict(self, images: Sequence[np.ndarray]) -> List[List[LabelledClassification]]:
+        return [[LabelledClassification(c.class_id, c.score, self.LABELS[c.class_id] if 0 <= c.class_id < len(self.LABELS) else "unknown") for c in per]
+                for per in super().predict(images)]

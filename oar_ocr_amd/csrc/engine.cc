@@ -846,6 +846,7 @@ struct Planner {
     TInfo& alias_out(const std::string& name, const TInfo& src, const std::vector<int64_t>& dims, Layout lay, int64_t byte_off = 0) {
         TInfo t;
         t.dims = dims; t.layout = lay; t.root = src.root; t.loc = src.loc; t.ht = nullptr;
+        t.is_int = src.is_int;   // a view of a device index tensor (Reshape / Squeeze / Unsqueeze / Slice of one) is still one
         if (t.loc.kind == Loc::CONST) t.loc.cptr = (const float*)((const char*)t.loc.cptr + byte_off);
         else t.loc.off += byte_off;
         if (!t.root.empty()) root_aliases[t.root].push_back(name);
@@ -2064,6 +2065,7 @@ struct Planner {
             }
         }
         TInfo a = get(n.in[0]), b = get(n.in[1]);
+        const bool ints_in = (a.host_int ? !a.host_f : a.is_int) && (b.host_int ? !b.host_f : b.is_int);
         // a plan-time value meeting a device tensor (e.g. a scale computed from Shape): materialise it as an f32 constant
         if (a.host_int) { a.loc = host_to_device(n.in[0], a); a.host_int = false; a.layout = Layout::NATIVE; }
         if (b.host_int) { b.loc = host_to_device(n.in[1], b); b.host_int = false; b.layout = Layout::NATIVE; }
@@ -2106,6 +2108,7 @@ struct Planner {
         bool commut = op == 0 || op == 2 || op == 6 || op == 7 || op == 8 || op == 11 || op == 12;
         if (commut && numel(pad) < numel(pbd)) { std::swap(al, bl); std::swap(sa, sb); }
         TInfo& y = new_out(n.out[0], od, clast ? Layout::CLAST : Layout::NATIVE);
+        y.is_int = ints_in && (op == 0 || op == 1 || op == 2 || op == 6 || op == 7) && n.act.kind == k::ACT_NONE;   // index arithmetic (idx + offset, idx - dim) stays an index tensor
         Loc yl = y.loc;
         Act post = n.act;
         int64_t cnt = numel(od);
@@ -2209,7 +2212,7 @@ struct Planner {
     // ------------------------------------------------------------------ broadcast copies (Expand / Tile)
     // y (contiguous, dims od) = x read through `in_strides` (0 = broadcast); dims of size 1 are dropped and neighbours that
     // are contiguous in x are merged so that real-world ranks fit the 6-d permute kernel
-    void strided_copy(const std::string& out, Loc xin, std::vector<int64_t> od_full, std::vector<int64_t> vd, std::vector<int64_t> vs) {
+    void strided_copy(const std::string& out, Loc xin, std::vector<int64_t> od_full, std::vector<int64_t> vd, std::vector<int64_t> vs, bool is_int = false) {
         std::vector<int64_t> d, st;
         for (size_t i = 0; i < vd.size(); ++i) {
             if (vd[i] == 1) continue;
@@ -2220,6 +2223,7 @@ struct Planner {
         if (d.empty()) { d.push_back(1); st.push_back(0); }
         OAR_CHECK(d.size() <= 6, OAR_UNSUPPORTED_OP, "Expand / Tile: more than 6 effective dimensions at " + out);
         TInfo& y = new_out(out, od_full, Layout::NATIVE);
+        y.is_int = is_int;
         Loc yl = y.loc;
         const int r = (int)d.size();
         step([=](const RunCtx& c) { k::permute(c.s, c.at(xin), c.mut(yl), r, d.data(), st.data()); }, 0, 8.0 * numel(od_full));
@@ -2239,7 +2243,7 @@ struct Planner {
         Loc xin = to_native_loc(x);
         std::vector<int64_t> st = contig_strides(xd);
         for (int i = 0; i < r; ++i) if (xd[i] == 1) st[i] = 0;
-        strided_copy(n.out[0], xin, od, od, st);
+        strided_copy(n.out[0], xin, od, od, st, x.is_int);
     }
     void op_tile(const GNode& n) {
         TInfo x = get(n.in[0]);
@@ -2253,7 +2257,7 @@ struct Planner {
             vd.push_back(rp.hv[i]); vs.push_back(0);          // [repeat][extent] with stride [0][s]
             vd.push_back(x.dims[i]); vs.push_back(xs[i]);
         }
-        strided_copy(n.out[0], xin, od, vd, vs);
+        strided_copy(n.out[0], xin, od, vd, vs, x.is_int);
     }
     void op_constant_of_shape(const GNode& n) {
         const TInfo& sh = get(n.in[0]);
@@ -2772,7 +2776,10 @@ struct Planner {
         for (int i = (int)axis + 1; i < r; ++i) inner *= od[i];
         std::vector<Loc> ins;
         for (auto& t : xs) ins.push_back(to_native_loc(t));
+        bool all_int = true;   // index tensors concatenated stay an index tensor
+        for (auto& t : xs) all_int = all_int && t.is_int;
         TInfo& y = new_out(n.out[0], od, Layout::NATIVE);
+        y.is_int = all_int;
         Loc yl = y.loc;
         int64_t coff = 0, total = od[axis] * inner;
         for (size_t i = 0; i < xs.size(); ++i) {
@@ -2893,6 +2900,7 @@ struct Planner {
         std::vector<int64_t> ns = contig_strides(x.dims), is(r);
         for (int i = 0; i < r; ++i) is[i] = ns[perm[i]];
         TInfo& y = new_out(n.out[0], od, Layout::NATIVE);
+        y.is_int = x.is_int;
         Loc yl = y.loc;
         step([=](const RunCtx& c) { k::permute(c.s, c.at(xin), c.mut(yl), r, od.data(), is.data()); }, 0, 8.0 * numel(od));
     }
@@ -2910,6 +2918,7 @@ struct Planner {
             if (!tmp.root.empty() || xin.kind == Loc::CONST) { alias_out(out, tmp, od, Layout::NATIVE, start * ns[axis] * 4); return; }
         }
         TInfo& y = new_out(out, od, Layout::NATIVE);
+        y.is_int = x.is_int;
         Loc yl = y.loc;
         int r = (int)od.size();
         int64_t off = start * ns[axis];
@@ -2955,8 +2964,8 @@ struct Planner {
     void op_gather(const GNode& n) {
         TInfo x = get(n.in[0]);
         const TInfo& idx = get(n.in[1]);
-        OAR_CHECK(idx.host_int, OAR_UNSUPPORTED_OP, "Gather: indices must be host ints");
         int64_t axis = n.ai("axis", 0);
+        if (!idx.host_int || (!x.host_int && idx.hv.size() != 1)) return op_gather_device(n);   // device indices, or several host ints
         if (x.host_int) {
             OAR_CHECK(x.dims.size() <= 1, OAR_UNSUPPORTED_OP, "Gather: host data rank > 1");
             std::vector<double> xv = host_values(x), ov;
@@ -2980,6 +2989,140 @@ struct Planner {
         for (int d = 0; d < r; ++d) if (d != axis || !idx.dims.empty()) od.push_back(d == axis ? 1 : x.dims[d]);
         alias_out(n.out[0], s, od, Layout::NATIVE);
         adopt_root(n.out[0], tmpn);   // (when the slice was a copy: the bytes are this node's output)
+    }
+
+    // ------------------------------------------------------------------ device-side selection (index_ops.hip)
+    // An index operand: a device index tensor (is_int) or host ints, range-checked here and uploaded once as f32.
+    // dim_of(i): the extent the i-th index addresses.
+    template <typename F>
+    Loc index_operand(const GNode& n, size_t in_idx, const TInfo& idx, F dim_of) {
+        if (idx.host_int) {
+            OAR_CHECK(!idx.host_f, OAR_UNSUPPORTED_OP, n.op + ": indices must be integers at " + n.out[0]);
+            for (size_t i = 0; i < idx.hv.size(); ++i) {
+                const int64_t d = dim_of(i), v = idx.hv[i] < 0 ? idx.hv[i] + d : idx.hv[i];
+                OAR_CHECK(v >= 0 && v < d, OAR_SHAPE_MISMATCH, n.op + ": index out of range at " + n.out[0]);
+            }
+            return host_to_device(n.in[in_idx], idx);
+        }
+        OAR_CHECK(idx.is_int && idx.loc.kind != Loc::NONE, OAR_UNSUPPORTED_OP, n.op + ": indices must be an integer tensor at " + n.out[0]);
+        return to_native_loc(idx);
+    }
+    // data operand of a gather: device tensor, or a plan-time value materialised as one
+    Loc gather_data(const GNode& n, const TInfo& x, bool& is_int) {
+        for (auto d : x.dims) OAR_CHECK(d < (1 << 24), OAR_UNSUPPORTED_OP, n.op + ": a dimension of 2^24 or more cannot be addressed by f32-coded indices");
+        is_int = x.host_int ? !x.host_f : x.is_int;
+        return x.host_int ? host_to_device(n.in[0], x) : to_native_loc(x);
+    }
+
+    // TopK over the last axis, K known at plan time
+    void op_topk(const GNode& n) {
+        TInfo x = get(n.in[0]);
+        OAR_CHECK(n.in.size() >= 2 && !n.in[1].empty(), OAR_UNSUPPORTED_OP, "TopK: K must be input 1 (opset >= 10)");
+        const TInfo& kt = get(n.in[1]);
+        OAR_CHECK(kt.host_int && kt.hv.size() == 1, OAR_UNSUPPORTED_OP, "TopK: K must be known on the host");
+        OAR_CHECK(!x.host_int && !x.dims.empty(), OAR_UNSUPPORTED_OP, "TopK: input must be a device tensor of rank >= 1");
+        const int r = (int)x.dims.size();
+        int64_t axis = n.ai("axis", -1);
+        if (axis < 0) axis += r;
+        OAR_CHECK(axis == r - 1, OAR_UNSUPPORTED_OP, "TopK: only the last axis is supported");
+        const int64_t C = x.dims[axis], K = kt.hv[0], rows = numel(x.dims) / std::max<int64_t>(C, 1);
+        OAR_CHECK(C >= 1 && C <= k::kTopKMaxC, OAR_UNSUPPORTED_OP, "TopK: row length " + std::to_string(C) + " is outside [1, " + std::to_string(k::kTopKMaxC) + "]");
+        OAR_CHECK(K >= 1 && K <= C, OAR_SHAPE_MISMATCH, "TopK: K = " + std::to_string(K) + " is outside [1, " + std::to_string(C) + "] at " + n.out[0]);
+        const bool largest = n.ai("largest", 1) != 0;   // (sorted = 0 leaves the order free: sorted results are a valid answer)
+        Loc xin = to_native_loc(x);
+        std::vector<int64_t> od = x.dims;
+        od[axis] = K;
+        auto out = [&](size_t i, bool is_int) -> Loc {
+            if (i >= n.out.size() || n.out[i].empty()) return alloc_temp((size_t)std::max<int64_t>(numel(od), 1) * 4);
+            TInfo& y = new_out(n.out[i], od, Layout::NATIVE);
+            y.is_int = is_int;
+            return y.loc;
+        };
+        Loc vl = out(0, x.is_int), il = out(1, true);
+        step([=](const RunCtx& c) { k::topk_lastdim(c.s, c.at(xin), c.mut(vl), c.mut(il), rows, (int)C, (int)K, largest); }, 0, 4.0 * rows * (C + 2.0 * K));
+    }
+
+    // Gather with a tensor of indices: y = x[..., idx, ...] along `axis`
+    void op_gather_device(const GNode& n) {
+        TInfo x = get(n.in[0]), idx = get(n.in[1]);
+        const int r = (int)x.dims.size();
+        int64_t axis = n.ai("axis", 0);
+        if (axis < 0) axis += r;
+        OAR_CHECK(r >= 1 && axis >= 0 && axis < r, OAR_SHAPE_MISMATCH, "Gather: axis out of range at " + n.out[0]);
+        bool is_int = false;
+        Loc xin = gather_data(n, x, is_int);
+        const int64_t D = x.dims[axis];
+        Loc iin = index_operand(n, 1, idx, [&](size_t) { return D; });
+        k::GatherRowsP p{};
+        int64_t outer = 1, inner = 1;
+        for (int i = 0; i < axis; ++i) outer *= x.dims[i];
+        for (int i = (int)axis + 1; i < r; ++i) inner *= x.dims[i];
+        const int64_t J = numel(idx.dims);
+        p.slices = outer * J; p.inner = inner; p.group = std::max<int64_t>(J, 1); p.group_stride = D * inner; p.idx_mod = J; p.m = 1;
+        p.dims[0] = D; p.strides[0] = inner;
+        std::vector<int64_t> od(x.dims.begin(), x.dims.begin() + axis);
+        od.insert(od.end(), idx.dims.begin(), idx.dims.end());
+        od.insert(od.end(), x.dims.begin() + axis + 1, x.dims.end());
+        TInfo& y = new_out(n.out[0], od, Layout::NATIVE);
+        y.is_int = is_int;
+        Loc yl = y.loc;
+        step([=](const RunCtx& c) { k::gather_rows(c.s, c.at(xin), c.at(iin), c.mut(yl), p); }, 0, 8.0 * numel(od) + 4.0 * J);
+    }
+
+    // GatherND: the last axis of `indices` holds tuples of m leading coordinates (after batch_dims shared ones)
+    void op_gather_nd(const GNode& n) {
+        TInfo x = get(n.in[0]), idx = get(n.in[1]);
+        const int64_t b = n.ai("batch_dims", 0);
+        OAR_CHECK(b == 0 || b == 1, OAR_UNSUPPORTED_OP, "GatherND: batch_dims > 1 is not supported");
+        const int r = (int)x.dims.size(), q = (int)idx.dims.size();
+        OAR_CHECK(r >= 1 && q >= 1 && b < r && b < q, OAR_SHAPE_MISMATCH, "GatherND: rank of data / indices at " + n.out[0]);
+        const int64_t m = idx.dims[q - 1];
+        OAR_CHECK(m >= 1 && m <= r - b && m <= 6, OAR_SHAPE_MISMATCH, "GatherND: index tuples of length " + std::to_string(m) + " for data of rank " + std::to_string(r) + " at " + n.out[0]);
+        for (int i = 0; i < b; ++i) OAR_CHECK(x.dims[i] == idx.dims[i], OAR_SHAPE_MISMATCH, "GatherND: batch dimensions of data and indices differ at " + n.out[0]);
+        bool is_int = false;
+        Loc xin = gather_data(n, x, is_int);
+        Loc iin = index_operand(n, 1, idx, [&](size_t i) { return x.dims[(size_t)b + i % (size_t)m]; });
+        const std::vector<int64_t> xs = contig_strides(x.dims);
+        k::GatherRowsP p{};
+        int64_t batch = 1;
+        for (int i = 0; i < b; ++i) batch *= x.dims[i];
+        std::vector<int64_t> od(idx.dims.begin(), idx.dims.end() - 1);
+        p.slices = numel(od);
+        od.insert(od.end(), x.dims.begin() + b + m, x.dims.end());
+        p.inner = 1;
+        for (int i = (int)(b + m); i < r; ++i) p.inner *= x.dims[i];
+        p.group = std::max<int64_t>(p.slices / std::max<int64_t>(batch, 1), 1);
+        p.group_stride = b > 0 ? xs[(size_t)b - 1] : 0;
+        p.idx_mod = 0; p.m = (int)m;
+        for (int i = 0; i < m; ++i) { p.dims[i] = x.dims[(size_t)(b + i)]; p.strides[i] = xs[(size_t)(b + i)]; }
+        TInfo& y = new_out(n.out[0], od, Layout::NATIVE);
+        y.is_int = is_int;
+        Loc yl = y.loc;
+        step([=](const RunCtx& c) { k::gather_rows(c.s, c.at(xin), c.at(iin), c.mut(yl), p); }, 0, 8.0 * numel(od) + 4.0 * numel(idx.dims));
+    }
+
+    // GatherElements: y[i...] = x[i... with coordinate `axis` replaced by idx[i...]]; y has the shape of idx
+    void op_gather_elements(const GNode& n) {
+        TInfo x = get(n.in[0]), idx = get(n.in[1]);
+        const int r = (int)x.dims.size();
+        OAR_CHECK(r >= 1 && r <= 6, OAR_UNSUPPORTED_OP, "GatherElements: rank must be in [1, 6]");
+        OAR_CHECK((int)idx.dims.size() == r, OAR_SHAPE_MISMATCH, "GatherElements: data and indices differ in rank at " + n.out[0]);
+        int64_t axis = n.ai("axis", 0);
+        if (axis < 0) axis += r;
+        OAR_CHECK(axis >= 0 && axis < r, OAR_SHAPE_MISMATCH, "GatherElements: axis out of range at " + n.out[0]);
+        for (int i = 0; i < r; ++i) OAR_CHECK(i == axis || idx.dims[i] <= x.dims[i], OAR_SHAPE_MISMATCH, "GatherElements: indices exceed the data's shape at " + n.out[0]);
+        bool is_int = false;
+        Loc xin = gather_data(n, x, is_int);
+        const int64_t D = x.dims[axis];
+        Loc iin = index_operand(n, 1, idx, [&](size_t) { return D; });
+        const std::vector<int64_t> xs = contig_strides(x.dims);
+        k::GatherElemP p{};
+        p.total = numel(idx.dims); p.axis_dim = D; p.rank = r; p.axis = (int)axis;
+        for (int i = 0; i < r; ++i) { p.dims[i] = idx.dims[i]; p.xstrides[i] = xs[(size_t)i]; }
+        TInfo& y = new_out(n.out[0], idx.dims, Layout::NATIVE);
+        y.is_int = is_int;
+        Loc yl = y.loc;
+        step([=](const RunCtx& c) { k::gather_elements(c.s, c.at(xin), c.at(iin), c.mut(yl), p); }, 0, 12.0 * (double)p.total);
     }
 
     // true when `name` is consumed by nothing but the Softmax that produces graph output 0
@@ -3459,6 +3602,9 @@ struct Planner {
         if (op == "Split") return op_split(n);
         if (op == "Slice") return op_slice(n);
         if (op == "Gather") return op_gather(n);
+        if (op == "GatherND") return op_gather_nd(n);
+        if (op == "GatherElements") return op_gather_elements(n);
+        if (op == "TopK") return op_topk(n);
         if (op == "Linear") return op_linear(n, false);
         if (op == "Gemm") return op_linear(n, true);
         if (op == "MatMul") return op_matmul(n);
@@ -3472,7 +3618,8 @@ struct Planner {
             const TInfo& x = get(n.in[0]);
             const int64_t to = n.ai("to", 1);
             OAR_CHECK(to == 1 || to == 9 || to == 10 || to == 11 || x.is_int, OAR_UNSUPPORTED_OP, "Cast of a device tensor to an integer type");
-            TInfo xx = x; alias_out(n.out[0], xx, xx.dims, xx.layout).is_int = x.is_int; return;
+            TInfo xx = x; alias_out(n.out[0], xx, xx.dims, xx.layout).is_int = x.is_int && !(to == 1 || to == 10 || to == 11);   // (a float Cast of an index tensor is a float tensor: views keep the mark now)
+            return;
         }
         fail(OAR_UNSUPPORTED_OP, "operator '" + op + "' is not implemented (node output " + (n.out.empty() ? "?" : n.out[0]) + ")");
     }
@@ -3527,7 +3674,8 @@ const std::set<std::string>& Engine::supported_ops() {
         "LeakyRelu", "Tanh", "Erf", "Sqrt", "Exp", "Abs", "Neg", "Reciprocal", "Log", "Gelu", "Softplus", "Clip", "Add", "Sub", "Mul", "Div", "Pow", "PRelu",
         "ReduceMean", "GridSample", "Pad", "GlobalAveragePool", "AveragePool", "MaxPool", "Resize", "Concat", "Reshape", "Flatten", "Squeeze", "Unsqueeze",
         "Transpose", "Split", "Slice", "Gather", "Gemm", "MatMul", "Softmax", "LayerNormalization", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Not",
-        "Floor", "Ceil", "Round", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "Expand", "Tile", "Where", "ConstantOfShape", "Range", "ArgMax", "ArgMin"};
+        "Floor", "Ceil", "Round", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "Expand", "Tile", "Where", "ConstantOfShape", "Range", "ArgMax", "ArgMin",
+        "TopK", "GatherND", "GatherElements"};
     return ops;
 }
 

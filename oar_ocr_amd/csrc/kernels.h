@@ -162,6 +162,19 @@ void pad_nd(hipStream_t s, const float* x, float* y, int rank, const int64_t* in
 // reduction over the last axis: x [rows][C] -> y [rows]; mode 0 mean, 1 sum, 2 max, 3 min, 4 prod
 void reduce_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C, int mode);
 void argreduce_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C, bool is_min, bool select_last);
+// index_ops.hip: TopK over the last axis, x [rows][C] -> values / indices [rows][K], sorted (largest: descending), ties to the lower column
+// (np.argsort(kind="stable")); indices are f32-coded.  1 <= K <= C <= kTopKMaxC.  One workgroup per row, the row resident in LDS.
+constexpr int kTopKMaxC = 16384;
+size_t topk_lds_bytes(int C, int K);
+void topk_lastdim(hipStream_t s, const float* x, float* values, float* indices, int64_t rows, int C, int K, bool largest);
+// y[s][0 .. inner) = x[row(s)][0 .. inner) for s in [0, slices): the index tuple of slice s is idx[(idx_mod > 0 ? s % idx_mod : s) * m + q], q < m, f32-coded;
+// row(s) = (s / group) * group_stride + sum_q wrap(tuple[q], dims[q]) * strides[q] (elements).  Gather: m = 1, idx_mod = number of indices, group = the same,
+// group_stride = dims[0] * inner; GatherND: idx_mod = 0, group = slices per batch.  A negative index wraps once; one still out of range zero-fills the slice.
+struct GatherRowsP { long slices, inner, group, group_stride, idx_mod; int m; long dims[6], strides[6]; };
+void gather_rows(hipStream_t s, const float* x, const float* idx, float* y, const GatherRowsP& p);
+// GatherElements: y[w] = x[coords of w with coordinate `axis` replaced by idx[w]]; dims = the index / output dims, xstrides = the data's strides (elements)
+struct GatherElemP { long total, axis_dim; int rank, axis; long dims[6], xstrides[6]; };
+void gather_elements(hipStream_t s, const float* x, const float* idx, float* y, const GatherElemP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

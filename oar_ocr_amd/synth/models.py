@@ -786,3 +786,95 @@ def build_layout(kind="picodet", n_classes=5, seed=11, image_shape=(800, 608), f
     g.nodes.append(node("Reshape", [allr, g.init(np.array([-1, feat], np.int64), "shape")], ["boxes"]))
     g.add_output("boxes", ["M", feat])
     return g.model(), {"params": g.n_params, "kind": kind, "classes": n_classes, "anchors": (H // 16) * (W // 16) + (H // 32) * (W // 32), "feat": feat}
+
+
+# ---------------------------------------------------------------------------------------------- table cell detector: a graph that SELECTS
+def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classes=1, seed=21):
+    """An RT-DETR-shaped table cell detector with synthetic weights whose query selection really runs in the graph (build_layout's "rtdetr" is
+    a CNN head with RT-DETR's column order).  Inputs, bound by name as RTDetrModel::infer binds them (models/detection/rtdetr.rs:160-180):
+    "image" [N,3,H,W] (declared first: the engine's primary input), "scale_factor" [N,2] = (ratio_h, ratio_w), "im_shape" [N,2] = resized (h, w).
+      backbone  ds_block stages to strides 8 / 16 / 32, a 1x1 projection to D = 64 each, flattened and concatenated: memory [N, A, D]
+      select    encoder score head -> ReduceMax over classes -> enc_scores [N, A] -> TopK(queries) -> topk_idx [N, Q]
+      gather    memory through GatherND(batch_dims = 1); the constant anchor logits through GatherElements with the index Expanded to [N, Q, 4]
+      decode    two-layer MLP; box = sigmoid(anchor logit + delta) as (cx, cy, w, h) -> x1 y1 x2 y2, * im_shape, / scale_factor; class scores
+      order     TopK(keep) over the per-query best score; a tensor-indexed Gather over the batch-flattened rows assembles
+                output 0 "boxes" [N * keep, 6] = (class, score, x1, y1, x2, y2), sorted by score like the real export's
+    Every TopK has its input and its index output declared as further graph outputs (info["topk"]), so a test can check each selection exactly
+    and evaluate the float segments between the selections on their own.  The class bias keeps most queries above the default threshold 0.3."""
+    H, W = image_shape
+    n = _Net("synth_table_cell_det", seed, decomposed_hswish=False)
+    g = n.g
+    g.add_input("image", ["N", 3, H, W])
+    g.add_input("scale_factor", ["N", 2])
+    g.add_input("im_shape", ["N", 2])
+    D = 64
+    c1, c2, c3, c4, c5 = 16, 24, 48, 96, 128
+    x = n.conv("image", 3, c1, 3, 2, act="hswish")
+    x = n.ds_block(x, c1, c2, 3, 2)
+    f8 = n.ds_block(x, c2, c3, 3, 2)
+    f8 = n.ds_block(f8, c3, c3, 3, 1)
+    f16 = n.ds_block(f8, c3, c4, 3, 2)
+    f16 = n.ds_block(f16, c4, c4, 5, 1)
+    f32_ = n.ds_block(f16, c4, c5, 5, 2, use_se=True)
+
+    def i64(v, prefix="shape"):
+        return g.init(np.asarray(v, np.int64), prefix)
+
+    def linear(t, cin, cout, gain=2.0, bias=None):
+        w = n._w((cin, cout), cin, gain)
+        b = n._b(cout) if bias is None else np.asarray(bias, np.float32)
+        return g.op("Add", [g.op("MatMul", [t, g.init(w)]), g.init(b, "b")])
+
+    tokens, anchors = [], []
+    for lvl, (ft, cin, stride) in enumerate(((f8, c3, 8), (f16, c4, 16), (f32_, c5, 32))):
+        h, w = H // stride, W // stride
+        p = n.conv(ft, cin, D, 1, act="hswish")
+        tokens.append(g.op("Transpose", [g.op("Reshape", [p, i64([0, D, h * w])])], perm=[0, 2, 1]))                    # [N, h * w, D]
+        ys, xs = np.mgrid[0:h, 0:w]
+        size = 0.12 * 2.0 ** lvl                                                                                        # RT-DETR's anchors: grid centres, a size per level
+        anchors.append(np.stack([(xs + 0.5) / w, (ys + 0.5) / h, np.full_like(xs, size, float), np.full_like(xs, size * 0.6, float)], -1).reshape(-1, 4))
+    A = sum(a.shape[0] for a in anchors)
+    assert 1 <= queries <= A and 1 <= keep <= queries
+    memory = g.op("Concat", tokens, axis=1)                                                                             # [N, A, D]
+    enc_logits = linear(memory, D, n_classes, gain=8.0)
+    enc_scores = g.op("ReduceMax", [enc_logits], axes=[2], keepdims=0)                                                  # [N, A]
+    _, topk_idx = g.op("TopK", [enc_scores, i64([queries], "k")], n_out=2, axis=-1, largest=1, sorted=1)               # [N, Q]
+    idx3 = g.op("Unsqueeze", [topk_idx, i64([2], "axes")])                                                              # [N, Q, 1]
+    tgt = g.op("GatherND", [memory, idx3], batch_dims=1)                                                                # [N, Q, D]
+    a = np.clip(np.concatenate(anchors, 0), 1e-4, 1.0 - 1e-4)
+    anchor_logit = np.log(a / (1.0 - a)).astype(np.float32).reshape(1, A, 4)
+    zero = g.op("Mul", [g.op("Unsqueeze", [enc_scores, i64([2], "axes")]), g.init(np.zeros((1, 1, 4), np.float32), "zero")])
+    anchors_n = g.op("Add", [zero, g.init(anchor_logit, "anchors")])                                                    # the constant, once per image: [N, A, 4]
+    ref = g.op("GatherElements", [anchors_n, g.op("Expand", [idx3, i64([1, 1, 4])])], axis=1)                           # [N, Q, 4]
+    hdn = g.op("Relu", [linear(tgt, D, D)])
+    hdn = g.op("Relu", [linear(hdn, D, D)])
+    delta = linear(hdn, D, 4, gain=0.5)
+    box = g.op("Sigmoid", [g.op("Add", [ref, delta])])                                                                  # cx cy w h in [0, 1]
+    cxcy, wh = g.op("Split", [box, i64([2, 2], "split")], n_out=2, axis=2)
+    half = g.op("Mul", [wh, g.init(np.array(0.5, np.float32), "c")])
+    xyxy = g.op("Concat", [g.op("Sub", [cxcy, half]), g.op("Add", [cxcy, half])], axis=2)                               # [N, Q, 4]
+
+    def pair(name):   # [N, 2] = (h, w) -> [N, 1, 4] = (w, h, w, h)
+        ax1 = i64([1], "axes")
+        a0 = g.op("Slice", [name, i64([0], "starts"), i64([1], "ends"), ax1])
+        a1 = g.op("Slice", [name, i64([1], "starts"), i64([2], "ends"), ax1])
+        return g.op("Unsqueeze", [g.op("Concat", [a1, a0, a1, a0], axis=1), i64([1], "axes")])
+
+    xyxy = g.op("Div", [g.op("Mul", [xyxy, pair("im_shape")]), pair("scale_factor")])                                   # original-image pixels
+    cls_bias = np.full(n_classes, -0.2, np.float32) + n._b(n_classes)
+    prob = g.op("Sigmoid", [linear(hdn, D, n_classes, gain=24.0, bias=cls_bias)])                                        # [N, Q, C]
+    best = g.op("ReduceMax", [prob], axes=[2], keepdims=0)                                                              # [N, Q]
+    cid = g.op("Cast", [g.op("ArgMax", [prob], axis=2, keepdims=1)], to=1)                                              # [N, Q, 1]
+    rows = g.op("Concat", [cid, g.op("Unsqueeze", [best, i64([2], "axes")]), xyxy], axis=2)                             # [N, Q, 6]
+    _, keep_idx = g.op("TopK", [best, i64([keep], "k")], n_out=2, axis=-1, largest=1, sorted=1)                         # [N, keep]
+    # rows of image b start at b * Q in the batch-flattened table: (arange(N) * Q)[:, None] + keep_idx
+    nb = g.op("Gather", [g.op("Shape", ["image"]), g.init(np.array(0, np.int64), "zero")], axis=0)
+    base = g.op("Mul", [g.op("Range", [g.init(np.array(0, np.int64), "zero"), nb, g.init(np.array(1, np.int64), "one")]), g.init(np.array(queries, np.int64), "q")])
+    flat_idx = g.op("Reshape", [g.op("Add", [keep_idx, g.op("Unsqueeze", [base, i64([1], "axes")])]), i64([-1])])       # [N * keep]
+    g.nodes.append(node("Gather", [g.op("Reshape", [rows, i64([-1, 6])]), flat_idx], ["boxes"], axis=0))
+    g.add_output("boxes", ["M", 6])
+    topk = [{"input": enc_scores, "index": topk_idx, "k": queries}, {"input": best, "index": keep_idx, "k": keep}]
+    for t, cols in zip(topk, ("A", "Q")):
+        g.add_output(t["input"], ["N", A if cols == "A" else queries])
+        g.add_output(t["index"], ["N", t["k"]], elem_type=7)
+    return g.model(), {"params": g.n_params, "kind": "rtdetr", "classes": n_classes, "anchors": A, "queries": queries, "keep": keep, "feat": 6, "topk": topk}

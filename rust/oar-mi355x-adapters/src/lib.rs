@@ -15,6 +15,7 @@
 //! | `text_line_orientation_adapter.rs`                           | [`Mi355xTextLineOrientationAdapter`]| `oar_cls_*`               |
 //! | `document_rectification_adapter.rs` `UVDocRectifierAdapter`  | [`Mi355xRectifierAdapter`]          | `oar_rect_*`              |
 //! | `layout_detection_adapter.rs` `LayoutDetectionAdapter` (PicoDet / RT-DETR) | [`Mi355xLayoutDetectionAdapter`]   | `oar_layout_*`            |
+//! | `table_cell_detection_adapter.rs` `TableCellDetectionAdapter` (RT-DETR) | [`Mi355xTableCellDetectionAdapter`] | `oar_layout_*` (model_type 1) |
 //! | `core/inference/ort_infer_execution.rs` `OrtInfer` (Seam A)  | [`Mi355xInfer`]                     | `oar_engine_*`            |
 //! | `src/oarocr/ocr.rs` `OAROCR::predict`                        | [`Mi355xOcr`]                       | `oar_ocr_*`               |
 //! | (no counterpart: one process per GPU)             | [`shard`]                           | `oar_shard_range`, `oar_ocr_pack`, `oar_packed_merge` |
@@ -31,6 +32,7 @@ pub mod pipeline;
 pub mod rectification;
 pub mod seal_text_detection;
 pub mod shard;
+pub mod table_cell_detection;
 pub mod text_detection;
 pub mod text_recognition;
 
@@ -45,6 +47,7 @@ pub use pipeline::{Mi355xOcr, Mi355xOcrBuilder, Mi355xOcrPage, Mi355xOcrRegion};
 pub use rectification::{Mi355xRectifierAdapter, Mi355xRectifierAdapterBuilder};
 pub use seal_text_detection::{Mi355xSealTextDetectionAdapter, Mi355xSealTextDetectionAdapterBuilder};
 pub use shard::{PackedPages, merge_packed, shard_range};
+pub use table_cell_detection::{Mi355xTableCellDetectionAdapter, Mi355xTableCellDetectionAdapterBuilder};
 pub use text_detection::{Mi355xTextDetectionAdapter, Mi355xTextDetectionAdapterBuilder};
 pub use text_recognition::{Mi355xTextRecognitionAdapter, Mi355xTextRecognitionAdapterBuilder};
 
