@@ -2033,3 +2033,192 @@ class TableClassifier(ImageClassifier):
     def predict(self, images: Sequence[np.ndarray]) -> List[List[LabelledClassification]]:
         return [[LabelledClassification(c.class_id, c.score, self.LABELS[c.class_id] if 0 <= c.class_id < len(self.LABELS) else "unknown") for c in per]
                 for per in super().predict(images)]
+
+
+# ---------------------------------------------------------------------------------------------- table structure recognition (SLANet family)
+@dataclass
+class TableStructureRecognitionConfig:
+    """domain/tasks/table_structure_recognition.rs: below-threshold results are kept (the adapter only logs them)"""
+    score_threshold: float = 0.5
+    max_structure_length: int = 500
+
+
+@dataclass
+class TableStructureRecognitionOutput:
+    structures: List[List[str]]               # per image: structure tokens, without the html / body / table wrapping
+    bboxes: List[List[np.ndarray]]            # per image: one [8] f32 box (four corner points, input-image pixels) per cell token
+    structure_scores: List[float]
+
+
+class TableStructureDecode:
+    """TableStructureDecode (processors/table_structure_decode.rs:405-741): the Paddle table dictionary with merge_no_span_structure
+    (`<td></td>` appended when missing, `<td>` removed), "sos" at index 0 and "eos" last; greedy decode of [B, T, V] scores and [B, T, >= 8] boxes."""
+
+    def __init__(self, dict_text: str):
+        d = [ln.rstrip() for ln in dict_text.splitlines()]            # trailing whitespace only: ` colspan="2"` keeps its leading space
+        d = [ln for ln in d if ln]
+        if "<td></td>" not in d:
+            d.append("<td></td>")
+        if "<td>" in d:
+            d.remove("<td>")                                          # the first occurrence, like Vec::remove(position)
+        self.character_dict = ["sos"] + d + ["eos"]
+        self.end_idx = len(self.character_dict) - 1
+        self.ignored_tokens = [0, self.end_idx]
+        self.td_token_indices = [self.character_dict.index(t) for t in ("<td>", "<td", "<td></td>") if t in self.character_dict]
+
+    @classmethod
+    def from_dict_path(cls, path) -> "TableStructureDecode":
+        try:
+            with open(path, encoding="utf-8") as f:
+                return cls(f.read())
+        except OSError as ex:
+            raise OCRError(OAR_INVALID_INPUT, f"configuration: Failed to open dictionary file '{path}': {ex}")
+
+    @staticmethod
+    def argmax_at(row: np.ndarray):
+        """:664-684: the first maximum by strict `>` from -inf (a NaN never wins)"""
+        row = np.asarray(row, np.float32)
+        if row.size and not np.isnan(row).any():
+            i = int(np.argmax(row))
+            return i, np.float32(row[i])
+        idx, val = 0, np.float32(-np.inf)
+        for k, v in enumerate(row):
+            if v > val:
+                idx, val = k, v
+        return idx, val
+
+    @staticmethod
+    def extract_bbox(bbox_preds: np.ndarray, batch_idx: int, seq_idx: int, shape_info) -> np.ndarray:
+        """:693-740: [0, 1] coordinates of the padded square x the longest side of the original (target_size / scale), clamped to the original"""
+        if bbox_preds.shape[2] < 8:
+            raise OCRError(OAR_INVALID_INPUT, f"invalid input: bbox predictions carry {bbox_preds.shape[2]} coordinates per step, 8 are needed")
+        bbox = np.asarray(bbox_preds[batch_idx, seq_idx, :8], np.float32).copy()
+        if batch_idx < len(shape_info):
+            orig_h, orig_w, scale, _pad_h, _pad_w, target_size = (np.float32(v) for v in shape_info[batch_idx])
+            if scale <= 0.0 or target_size <= 0.0:
+                raise OCRError(OAR_INVALID_INPUT, f"invalid input: Invalid shape info for batch {batch_idx}: scale={scale} target_size={target_size}")
+            longest_side = np.float32(target_size / scale)
+            for i in range(8):
+                c = np.float32(bbox[i] * longest_side)
+                bbox[i] = min(max(c, np.float32(0.0)), orig_w if i % 2 == 0 else orig_h)
+        return bbox
+
+    def decode_single(self, structure_logits: np.ndarray, bbox_preds: np.ndarray, batch_idx: int, shape_info):
+        """:569-661 -> (tokens, boxes, mean of the maxima of the kept steps)"""
+        tokens, bboxes, scores = [], [], []
+        for seq_idx in range(structure_logits.shape[1]):
+            token_idx, token_prob = self.argmax_at(structure_logits[batch_idx, seq_idx])
+            if seq_idx > 0 and token_idx == self.end_idx:
+                break
+            if token_idx in self.ignored_tokens:
+                continue
+            tokens.append(self.character_dict[token_idx] if token_idx < len(self.character_dict) else f"UNK_{token_idx}")
+            scores.append(token_prob)
+            if token_idx in self.td_token_indices:
+                bboxes.append(self.extract_bbox(bbox_preds, batch_idx, seq_idx, shape_info))
+        mean = np.float32(0.0)
+        if scores:
+            s = np.float32(0.0)
+            for v in scores:
+                s = np.float32(s + v)
+            mean = np.float32(s / np.float32(len(scores)))
+        return tokens, bboxes, mean
+
+    def decode(self, structure_logits: np.ndarray, bbox_preds: np.ndarray, shape_info):
+        structure_logits, bbox_preds = np.asarray(structure_logits, np.float32), np.asarray(bbox_preds, np.float32)
+        out = [self.decode_single(structure_logits, bbox_preds, b, shape_info) for b in range(structure_logits.shape[0])]
+        return [o[0] for o in out], [o[1] for o in out], [o[2] for o in out]
+
+
+class TableStructureRecognitionPredictor:
+    """TableStructureRecognitionAdapter (domain/adapters/table_structure_recognition_adapter.rs:62-195) over SLANetModel (models/recognition/slanet.rs:72-245):
+    ResizeByLong to the model's input size (Triangle filter), BGR with the ImageNet statistics applied in that output order, zero padding in normalised
+    space to the square when the model's spatial dims are fixed; the graph through the engine, whose Loop rewrite runs the whole SLA decode as one launch;
+    outputs [0] = boxes [B, T, 8], [1] = structure scores [B, T, V]; TableStructureDecode on the host."""
+    DEFAULT_INPUT_SHAPE = (512, 512)             # SLANeXt_wired
+    DEFAULT_WIRELESS_INPUT_SHAPE = (488, 488)    # SLANet_plus
+
+    def __init__(self, onnx_bytes: bytes, dict_text: str, config: Optional[TableStructureRecognitionConfig] = None, input_shape: Optional[tuple] = None,
+                 device_id: int = 0):
+        self.config = config or TableStructureRecognitionConfig()
+        self.decoder = dict_text if isinstance(dict_text, TableStructureDecode) else TableStructureDecode(dict_text)
+        self._eng = OrtInfer(onnx_bytes, device_id=device_id)
+        if input_shape is not None:                                   # SLANetModelBuilder::input_size: dynamic batch, fixed spatial dims
+            dims = [-1, 3, int(input_shape[0]), int(input_shape[1])]
+        else:
+            dims = self._eng.primary_input_shape()
+            if dims is None or len(dims) != 4:
+                dims = [-1, 3, 512, 512]
+        self.input_dims = dims
+        self.needs_padding = dims[2] > 0 and dims[3] > 0              # InputShape::has_fixed_spatial
+        th, tw = (dims[2], dims[3]) if self.needs_padding else (488, 488)
+        self.target_size = np.float32(max(th, tw))
+        scale = np.float32(1.0) / np.float32(255.0)
+        mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)   # in OUTPUT (B, G, R) order, as the reference applies them
+        self.alpha, self.beta = (scale / std).astype(np.float32), (-mean / std).astype(np.float32)
+
+    @staticmethod
+    def recommended_batch_size() -> int:
+        return 8
+
+    def preprocess(self, images: Sequence[np.ndarray]):
+        """slanet.rs:72-170 -> (tensor [n, 3, h, w], shape_info [n][6] = orig_h, orig_w, scale, pad_h, pad_w, target_size)"""
+        tensors, info = [], []
+        T = self.target_size
+        for img in images:
+            img = np.ascontiguousarray(img, np.uint8)
+            orig_h, orig_w = np.float32(img.shape[0]), np.float32(img.shape[1])
+            scale = np.float32(T / max(orig_h, orig_w))
+            rh, rw = int(np.floor(np.float64(np.float32(orig_h * scale)) + 0.5)), int(np.floor(np.float64(np.float32(orig_w * scale)) + 0.5))   # f32::round
+            if rh < 1 or rw < 1:
+                raise OCRError(OAR_INVALID_INPUT, f"invalid input: image of {img.shape[1]}x{img.shape[0]} resizes to an empty image")
+            t = k_normalize(k_resize_triangle(img, rw, rh), self.alpha, self.beta, src=(2, 1, 0), layout="chw")
+            pad_h = pad_w = np.float32(0.0)
+            if self.needs_padding:
+                Ti = int(T)
+                if rh > Ti or rw > Ti:
+                    raise OCRError(OAR_INVALID_INPUT, "invalid input: resized image exceeds the padded input")
+                padded = np.zeros((3, Ti, Ti), np.float32)
+                padded[:, :rh, :rw] = t
+                t, pad_h, pad_w = padded, np.float32(T - np.float32(rh)), np.float32(T - np.float32(rw))
+            tensors.append(t)
+            info.append(np.array([orig_h, orig_w, scale, pad_h, pad_w, T], np.float32))
+        if any(t.shape != tensors[0].shape for t in tensors):
+            raise OCRError(OAR_INVALID_INPUT, "invalid input: SLANet preprocess produced tensors with inconsistent shapes")
+        return (np.stack(tensors) if tensors else np.zeros((0, 0, 0, 0), np.float32)), info
+
+    def infer(self, batch: np.ndarray):
+        """-> (bbox_preds [n, T, 8], structure scores [n, T, V]): the graph's outputs 0 and 1 (slanet.rs:175-224)"""
+        outs = self._eng.infer(batch)
+        if len(outs) < 2:
+            raise OCRError(OAR_INVALID_INPUT, f"invalid input: SLANet: expected at least 2 outputs, got {len(outs)}")
+        bbox, logits = outs[0][1], outs[1][1]
+        if bbox.ndim != 3 or logits.ndim != 3 or bbox.dtype != np.float32 or logits.dtype != np.float32:
+            raise OCRError(OAR_INVALID_INPUT, "invalid input: SLANet: outputs 0 and 1 must be f32 tensors of rank 3")
+        return bbox, logits
+
+    def predict(self, images: Sequence[np.ndarray], config: Optional[TableStructureRecognitionConfig] = None) -> TableStructureRecognitionOutput:
+        cfg = config or self.config
+        if len(images) == 0:
+            raise OCRError(OAR_INVALID_INPUT, "invalid input: No images provided")
+        out = TableStructureRecognitionOutput([], [], [])
+        for i0 in range(0, len(images), self.recommended_batch_size()):
+            batch, shape_info = self.preprocess(images[i0:i0 + self.recommended_batch_size()])
+            bbox, logits = self.infer(batch)
+            for tokens, boxes, score in zip(*self.decoder.decode(logits, bbox, shape_info)):
+                trimmed = tokens[:cfg.max_structure_length]           # (a score below cfg.score_threshold keeps its result: :127-135)
+                out.structures.append(trimmed)
+                out.bboxes.append(boxes[:len(trimmed)])
+                out.structure_scores.append(float(score))
+        return out
+
+    def close(self):
+        if getattr(self, "_eng", None) is not None:
+            self._eng.close()
+            self._eng = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -390,6 +390,23 @@ oar_status oar_onnx_inspect(const uint8_t* onnx, size_t onnx_len, char* summary,
         }
         text = "opset=" + std::to_string(m.opset) + " input=" + m.inputs[0] + " outputs=" + std::to_string(m.outputs.size()) + " initializers=" +
                std::to_string(m.initializers.size()) + " nodes=" + std::to_string(m.nodes.size()) + " | " + text;
+        // graph-valued attributes (Loop bodies), depth first: " | <op>.<attr>{inputs=a,b outputs=c initializers=n nodes=n: Op:count ...}"
+        std::function<void(const OnnxModel&)> nested = [&](const OnnxModel& g) {
+            for (auto& n : g.nodes)
+                for (auto& kv : n.attrs) {
+                    if (kv.second.kind != Attr::G || !kv.second.g) continue;
+                    const OnnxModel& b = *kv.second.g;
+                    auto join = [](const std::vector<std::string>& v) { std::string o; for (auto& x : v) o += (o.empty() ? "" : ",") + x; return o; };
+                    std::map<std::string, int> h;
+                    for (auto& bn : b.nodes) h[bn.op]++;
+                    text += " | " + n.op + "." + kv.first + "{inputs=" + join(b.inputs) + " outputs=" + join(b.outputs) + " initializers=" + std::to_string(b.initializers.size()) +
+                            " nodes=" + std::to_string(b.nodes.size()) + ":";
+                    for (auto& hk : h) text += " " + hk.first + ":" + std::to_string(hk.second);
+                    text += "}";
+                    nested(b);
+                }
+        };
+        nested(m);
         if (summary && cap) snprintf(summary, cap, "%s", text.c_str());
         OAR_CHECK(missing.empty(), OAR_UNSUPPORTED_OP, "operators not implemented: " + missing);
     });

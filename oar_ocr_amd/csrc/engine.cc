@@ -112,6 +112,269 @@ static Act act_of(const GNode& n) {
     return a;
 }
 
+// -------------------------------------------------------------------------------------------------
+// Loop -> SLADecode.  The body contract, with h [B,H], pre [B] the loop-carried state and fea [B,HW,C] from the outer scope:
+//   hp = Gemm(h, W_h2h, b_h2h, transB=1)        e = MatMul(Tanh(Add(MatMul(fea, W_i2h^T), Unsqueeze(hp, [1]))), w_score^T)
+//   ctx = Squeeze(MatMul(Transpose(Softmax(e, axis=1), [0,2,1]), fea), [1])      x = Concat(ctx, OneHot(pre, V, [0,1]), axis=1)
+//   xr,xz,xc = Split(Gemm(x, W_ih, b_ih, transB=1))   hr,hz,hc = Split(Gemm(h, W_hh, b_hh, transB=1))
+//   r = Sigmoid(xr+hr)  z = Sigmoid(xz+hz)  c = Tanh(xc + r*hc)  h_new = (h - c)*z + c
+//   logits = Gemm(Gemm(h_new, W_s1, b_s1), W_s2, b_s2)   loc = Sigmoid(Gemm(Gemm(h_new, W_l1, b_l1), W_l2, b_l2))   pre_new = ArgMax(logits, axis=1, keepdims=0)
+// Tolerated: MatMul(x, W^T) + Add(bias) for a Gemm, Cast around OneHot / ArgMax, weights as body or outer initializers (or Constant
+// nodes), axes as attribute or input, cond_out as Identity(cond_in) or a constant true.
+void Engine::match_sla_loop(const GNode& loop, GNode& lin_out, GNode& dec_out) {
+    const std::string where = "Loop (" + (loop.out.empty() ? std::string("?") : loop.out[0]) + ")";
+    auto refuse = [&](const std::string& why) { fail(OAR_UNSUPPORTED_OP, where + ": only the SLA decode step is supported as a Loop body: " + why); };
+    auto bit = loop.attrs.find("body");
+    if (bit == loop.attrs.end() || bit->second.kind != Attr::G || !bit->second.g) refuse("the node has no body graph");
+    const OnnxModel& body = *bit->second.g;
+    // constants: body initializers, body Constant nodes, then the outer scope
+    std::map<std::string, HostTensor> local;
+    std::map<std::string, int> producer;
+    std::vector<bool> used(body.nodes.size(), false);
+    for (int i = 0; i < (int)body.nodes.size(); ++i) {
+        const OnnxNode& bn = body.nodes[i];
+        if (bn.op == "Constant") {
+            auto it = bn.attrs.find("value");
+            if (it != bn.attrs.end() && it->second.kind == Attr::T && !bn.outputs.empty()) { local[bn.outputs[0]] = it->second.t; used[i] = true; continue; }
+        }
+        for (auto& o : bn.outputs) producer[o] = i;
+    }
+    auto cst = [&](const std::string& s) -> const HostTensor* {
+        auto a = body.initializers.find(s);
+        if (a != body.initializers.end()) return &a->second;
+        auto b = local.find(s);
+        if (b != local.end()) return &b->second;
+        if (producer.count(s)) return nullptr;
+        auto c = inits_.find(s);
+        return c == inits_.end() ? nullptr : &c->second;
+    };
+    auto node_desc = [&](int i) { const OnnxNode& bn = body.nodes[i]; return "body node '" + (bn.name.empty() ? (bn.outputs.empty() ? std::string("?") : bn.outputs[0]) : bn.name) + "' (" + bn.op + ")"; };
+    // the node that produces `v`, which must be a `op`; marks it
+    auto expect = [&](const std::string& v, const char* op, const char* role) -> const OnnxNode& {
+        auto it = producer.find(v);
+        if (it == producer.end()) refuse(std::string("the ") + role + " '" + v + "' is not computed by a " + op + " in the body");
+        const OnnxNode& bn = body.nodes[it->second];
+        if (bn.op != op) refuse(node_desc(it->second) + " does not fit: the " + role + " must be a " + op);
+        used[it->second] = true;
+        return bn;
+    };
+    auto bad = [&](const OnnxNode& bn, const std::string& why) { refuse(node_desc((int)(&bn - body.nodes.data())) + " does not fit: " + why); };
+    auto is_op = [&](const std::string& v, const char* op) { auto it = producer.find(v); return it != producer.end() && body.nodes[it->second].op == op; };
+    auto strip_casts = [&](std::string v) {
+        while (is_op(v, "Cast")) { const int i = producer[v]; used[i] = true; v = body.nodes[i].inputs[0]; }
+        return v;
+    };
+    auto ints_arg = [&](const OnnxNode& bn, const char* attr, size_t input) -> std::vector<int64_t> {
+        if (bn.has(attr)) { auto& a = bn.attrs.at(attr); return a.kind == Attr::I ? std::vector<int64_t>{a.i} : a.is; }
+        if (input < bn.inputs.size() && !bn.inputs[input].empty())
+            if (const HostTensor* t = cst(bn.inputs[input])) return t->i;
+        return {};
+    };
+    auto f32c = [&](const OnnxNode& bn, const std::string& s, size_t rank) -> const HostTensor& {
+        const HostTensor* t = cst(s);
+        if (!t || t->dtype != DType::F32 || t->dims.size() != rank || (int64_t)t->f.size() != t->numel() || t->numel() == 0) bad(bn, "'" + s + "' must be a constant f32 tensor of rank " + std::to_string(rank));
+        return *t;
+    };
+    // y = x W^T + b as Gemm(x, W, b, transB) or [Add(] MatMul(x, W^T) [, b)]: W comes back as [N][K] row-major
+    struct Lin { std::string x; std::vector<float> w, b; int64_t N = 0, K = 0; };
+    auto lin = [&](const std::string& v, const char* role, bool want_bias) -> Lin {
+        Lin r;
+        auto it = producer.find(v);
+        if (it == producer.end()) refuse(std::string("the ") + role + " '" + v + "' is not computed in the body");
+        const OnnxNode* bn = &body.nodes[it->second];
+        used[it->second] = true;
+        if (bn->op == "Gemm") {
+            if (bn->inputs.size() < 2 || bn->af("alpha", 1.0f) != 1.0f || bn->af("beta", 1.0f) != 1.0f || bn->ai("transA", 0) != 0) bad(*bn, "Gemm with alpha / beta / transA");
+            const HostTensor& W = f32c(*bn, bn->inputs[1], 2);
+            const bool tb = bn->ai("transB", 0) != 0;
+            r.N = tb ? W.dims[0] : W.dims[1]; r.K = tb ? W.dims[1] : W.dims[0];
+            r.w.resize((size_t)(r.N * r.K));
+            for (int64_t a = 0; a < r.N; ++a) for (int64_t k = 0; k < r.K; ++k) r.w[(size_t)(a * r.K + k)] = tb ? W.f[(size_t)(a * r.K + k)] : W.f[(size_t)(k * r.N + a)];
+            if (bn->inputs.size() > 2 && !bn->inputs[2].empty()) { const HostTensor& b = f32c(*bn, bn->inputs[2], 1); if (b.numel() != r.N) bad(*bn, "bias length"); r.b = b.f; }
+            r.x = bn->inputs[0];
+        } else {
+            const OnnxNode* mm = bn;
+            if (bn->op == "Add") {
+                if (bn->inputs.size() != 2) bad(*bn, "Add needs two inputs");
+                const int mi = is_op(bn->inputs[0], "MatMul") ? 0 : is_op(bn->inputs[1], "MatMul") ? 1 : -1;
+                if (mi < 0) bad(*bn, std::string("the ") + role + " must be a Gemm or MatMul + Add");
+                const HostTensor& b = f32c(*bn, bn->inputs[1 - mi], 1);
+                r.b = b.f;
+                used[producer[bn->inputs[mi]]] = true;
+                mm = &body.nodes[producer[bn->inputs[mi]]];
+            } else if (bn->op != "MatMul") {
+                bad(*bn, std::string("the ") + role + " must be a Gemm or MatMul [+ Add]");
+            }
+            if (mm->inputs.size() != 2) bad(*mm, "MatMul needs two inputs");
+            const HostTensor& W = f32c(*mm, mm->inputs[1], 2);
+            r.K = W.dims[0]; r.N = W.dims[1];
+            r.w.resize((size_t)(r.N * r.K));
+            for (int64_t a = 0; a < r.N; ++a) for (int64_t k = 0; k < r.K; ++k) r.w[(size_t)(a * r.K + k)] = W.f[(size_t)(k * r.N + a)];
+            if (!r.b.empty() && (int64_t)r.b.size() != r.N) bad(*bn, "bias length");
+            r.x = mm->inputs[0];
+        }
+        if (want_bias && r.b.empty()) bad(*bn, std::string("the ") + role + " needs a bias");
+        if (!want_bias && !r.b.empty()) bad(*bn, std::string("the ") + role + " has no bias in the SLA step");
+        return r;
+    };
+    auto two = [&](const OnnxNode& bn) { if (bn.inputs.size() != 2) bad(bn, "needs two inputs"); };
+
+    if (body.inputs.size() != 4 || body.outputs.size() != 5) refuse("the body must have the inputs (i, cond, h, pre) and the outputs (cond, h, pre, logits, loc)");
+    if (loop.in.size() != 4 || loop.out.size() != 4) refuse("the node must carry (M, cond, h0, pre0) and yield (h, pre, logits scan, loc scan)");
+    if (opset_ < 13) refuse("Softmax / Split / Squeeze semantics below opset 13");
+    const std::string &cond_in = body.inputs[1], &h = body.inputs[2], &pre = body.inputs[3];
+    const std::string &cond_out = body.outputs[0], &h_new = body.outputs[1], &pre_new = body.outputs[2], &logits = body.outputs[3], &loc = body.outputs[4];
+    // trip count and condition
+    const HostTensor* mt = loop.in[0].empty() ? nullptr : [&]() -> const HostTensor* { auto it = inits_.find(loop.in[0]); return it == inits_.end() ? nullptr : &it->second; }();
+    if (!mt || mt->dtype == DType::F32 || mt->i.size() != 1) refuse("the trip count M must be a constant integer scalar");
+    const int64_t M = mt->i[0];
+    if (!loop.in[1].empty()) {
+        auto it = inits_.find(loop.in[1]);
+        if (it == inits_.end() || it->second.i.size() != 1 || it->second.i[0] == 0) refuse("the loop condition must be absent or a constant true");
+    }
+    if (const HostTensor* ct = cst(cond_out)) {
+        if (ct->i.size() != 1 || ct->i[0] == 0) refuse("cond_out must be Identity(cond_in) or a constant true");
+    } else {
+        const OnnxNode& id = expect(cond_out, "Identity", "loop condition");
+        if (id.inputs.size() != 1 || id.inputs[0] != cond_in) bad(id, "cond_out must be Identity(cond_in)");
+    }
+    // greedy token
+    {
+        const OnnxNode& am = expect(strip_casts(pre_new), "ArgMax", "next token");
+        if (am.inputs.size() != 1 || am.inputs[0] != logits) bad(am, "ArgMax must read the logits output");
+        const int64_t ax = am.ai("axis", 0);
+        if ((ax != 1 && ax != -1) || am.ai("keepdims", 1) != 0 || am.ai("select_last_index", 0) != 0) bad(am, "ArgMax must be axis=1, keepdims=0, first index");
+    }
+    // heads
+    Lin s2 = lin(logits, "structure head", true), s1 = lin(s2.x, "structure head hidden layer", true);
+    const OnnxNode& lsig = expect(loc, "Sigmoid", "location output");
+    Lin l2 = lin(lsig.inputs[0], "location head", true), l1 = lin(l2.x, "location head hidden layer", true);
+    if (s1.x != h_new || l1.x != h_new) refuse("both heads must read the new hidden state '" + h_new + "'");
+    // GRU cell: h_new = Add(Mul(Sub(h, c), z), c)
+    const OnnxNode& hadd = expect(h_new, "Add", "new hidden state");
+    two(hadd);
+    const int mi = is_op(hadd.inputs[0], "Mul") ? 0 : 1;
+    const std::string cval = hadd.inputs[1 - mi];
+    const OnnxNode& hmul = expect(hadd.inputs[mi], "Mul", "(h - c) * z");
+    two(hmul);
+    const int si = is_op(hmul.inputs[0], "Sub") ? 0 : 1;
+    const OnnxNode& hsub = expect(hmul.inputs[si], "Sub", "h - c");
+    two(hsub);
+    if (hsub.inputs[0] != h || hsub.inputs[1] != cval) bad(hsub, "must be Sub(h, c)");
+    const std::string zval = hmul.inputs[1 - si];
+    const OnnxNode& ctanh = expect(cval, "Tanh", "candidate state c");
+    const OnnxNode& cadd = expect(ctanh.inputs[0], "Add", "xc + r * hc");
+    two(cadd);
+    const int cm = is_op(cadd.inputs[0], "Mul") ? 0 : 1;
+    const OnnxNode& rmul = expect(cadd.inputs[cm], "Mul", "r * hc");
+    two(rmul);
+    const std::string xc_or = cadd.inputs[1 - cm];
+    const int ri = is_op(rmul.inputs[0], "Sigmoid") ? 0 : 1;
+    const OnnxNode& rsig = expect(rmul.inputs[ri], "Sigmoid", "reset gate r");
+    const std::string hc_v = rmul.inputs[1 - ri];
+    const OnnxNode& radd = expect(rsig.inputs[0], "Add", "xr + hr");
+    two(radd);
+    const OnnxNode& zsig = expect(zval, "Sigmoid", "update gate z");
+    const OnnxNode& zadd = expect(zsig.inputs[0], "Add", "xz + hz");
+    two(zadd);
+    const OnnxNode& hsplit = expect(hc_v, "Split", "hidden-side gate split");
+    const OnnxNode& xsplit = expect(xc_or, "Split", "input-side gate split");
+    for (const OnnxNode* sp : {&hsplit, &xsplit}) {
+        const int64_t ax = sp->ai("axis", 0);
+        if (sp->outputs.size() != 3 || sp->inputs.empty() || (ax != 1 && ax != -1)) bad(*sp, "Split must cut axis 1 into three");
+        std::vector<int64_t> parts = ints_arg(*sp, "split", 1);
+        if (!parts.empty() && (parts.size() != 3 || parts[0] != parts[1] || parts[1] != parts[2])) bad(*sp, "Split must cut three equal parts");
+    }
+    auto pair_is = [&](const OnnxNode& a, const std::string& u, const std::string& v) { return (a.inputs[0] == u && a.inputs[1] == v) || (a.inputs[0] == v && a.inputs[1] == u); };
+    if (&hsplit == &xsplit || hc_v != hsplit.outputs[2] || xc_or != xsplit.outputs[2]) bad(cadd, "the candidate must combine the third parts of the two splits");
+    if (!pair_is(radd, xsplit.outputs[0], hsplit.outputs[0])) bad(radd, "must be xr + hr");
+    if (!pair_is(zadd, xsplit.outputs[1], hsplit.outputs[1])) bad(zadd, "must be xz + hz");
+    Lin hh = lin(hsplit.inputs[0], "hidden-side gates", true), ih = lin(xsplit.inputs[0], "input-side gates", true);
+    if (hh.x != h) refuse("the hidden-side gates must read the loop state '" + h + "'");
+    // x = Concat(ctx, OneHot(pre))
+    const OnnxNode& cat = expect(ih.x, "Concat", "GRU input");
+    if (cat.inputs.size() != 2 || (cat.ai("axis", 0) != 1 && cat.ai("axis", 0) != -1)) bad(cat, "must be Concat(ctx, one-hot, axis=1)");
+    const OnnxNode& oh = expect(strip_casts(cat.inputs[1]), "OneHot", "previous-token encoding");
+    if (oh.inputs.size() != 3 || strip_casts(oh.inputs[0]) != pre || oh.ai("axis", -1) != -1) bad(oh, "must be OneHot(pre, V, [0, 1]) on the last axis");
+    const HostTensor *dep = cst(oh.inputs[1]), *ohv = cst(oh.inputs[2]);
+    auto cval_of = [](const HostTensor* t, size_t i) { return t->dtype == DType::F32 ? (double)t->f[i] : (double)t->i[i]; };
+    if (!dep || dep->numel() != 1 || !ohv || ohv->numel() != 2 || cval_of(ohv, 0) != 0.0 || cval_of(ohv, 1) != 1.0) bad(oh, "depth must be a constant and values [0, 1]");
+    const int64_t V = (int64_t)cval_of(dep, 0);
+    // ctx = Squeeze(MatMul(Transpose(Softmax(e, 1), [0,2,1]), fea), [1])
+    const OnnxNode& sq = expect(cat.inputs[0], "Squeeze", "context vector");
+    if (ints_arg(sq, "axes", 1) != std::vector<int64_t>{1}) bad(sq, "must squeeze axis 1");
+    const OnnxNode& cmm = expect(sq.inputs[0], "MatMul", "attention-weighted sum");
+    two(cmm);
+    const std::string fea = cmm.inputs[1];
+    if (producer.count(fea) || cst(fea) || fea == h || fea == pre) bad(cmm, "the features must come from the outer scope");
+    const OnnxNode& tr = expect(cmm.inputs[0], "Transpose", "attention weights");
+    if (tr.ais("perm") != std::vector<int64_t>{0, 2, 1}) bad(tr, "must be perm [0, 2, 1]");
+    const OnnxNode& sm = expect(tr.inputs[0], "Softmax", "attention weights");
+    if (sm.ai("axis", -1) != 1) bad(sm, "must be Softmax over axis 1");
+    Lin sc = lin(sm.inputs[0], "attention score", false);
+    const OnnxNode& ttanh = expect(sc.x, "Tanh", "attention activation");
+    const OnnxNode& tadd = expect(ttanh.inputs[0], "Add", "projected features + projected state");
+    two(tadd);
+    const int ui = is_op(tadd.inputs[0], "Unsqueeze") ? 0 : 1;
+    const OnnxNode& un = expect(tadd.inputs[ui], "Unsqueeze", "projected state");
+    if (ints_arg(un, "axes", 1) != std::vector<int64_t>{1}) bad(un, "must unsqueeze axis 1");
+    Lin h2h = lin(un.inputs[0], "state projection", true);
+    if (h2h.x != h) refuse("the state projection must read the loop state '" + h + "'");
+    Lin i2h = lin(tadd.inputs[1 - ui], "feature projection", false);
+    if (i2h.x != fea) refuse("the feature projection and the weighted sum must read the same features");
+    for (int i = 0; i < (int)body.nodes.size(); ++i)
+        if (!used[i]) refuse(node_desc(i) + " does not fit: it is not part of the SLA decode step");
+    // dimensions
+    const int64_t H = h2h.N, C = i2h.K, L = l2.N;
+    auto shape_ok = h2h.K == H && i2h.N == H && sc.N == 1 && sc.K == H && hh.N == 3 * H && hh.K == H && ih.N == 3 * H && ih.K == C + V && s1.N == H && s1.K == H &&
+                    s2.N == V && s2.K == H && l1.N == H && l1.K == H && l2.K == H;
+    if (!shape_ok) refuse("the weights do not have the shapes of an SLA step with H = " + std::to_string(H) + ", C = " + std::to_string(C) + ", V = " + std::to_string(V));
+    if (!k::sla_decode_supported(1, (int)std::min<int64_t>(C, 1 << 20), (int)std::min<int64_t>(H, 1 << 20), (int)std::min<int64_t>(V, 1 << 20), (int)std::min<int64_t>(L, 1 << 20),
+                                 (int)std::min<int64_t>(std::max<int64_t>(M, 0), 1 << 20)))
+        refuse("H = " + std::to_string(H) + ", C = " + std::to_string(C) + ", V = " + std::to_string(V) + ", L = " + std::to_string(L) + ", M = " + std::to_string(M) + " is outside H <= " +
+               std::to_string(k::kSlaMaxH) + ", C <= " + std::to_string(k::kSlaMaxC) + ", V <= " + std::to_string(k::kSlaMaxV) + ", 1 <= L <= " + std::to_string(k::kSlaMaxL) + ", 1 <= M <= " +
+               std::to_string(k::kSlaMaxM));
+    // constants in the kernel's layout (kernels.h: SlaDecodeP): rows padded to a multiple of four floats
+    const std::string pfx = "sla::" + loop.out[2] + "::";
+    auto put = [&](const char* nm, std::vector<int64_t> dims, std::vector<float> v) {
+        HostTensor t; t.name = pfx + nm; t.dtype = DType::F32; t.dims = std::move(dims); t.f = std::move(v);
+        const std::string key = t.name;
+        inits_[key] = std::move(t);
+        return key;
+    };
+    auto padded = [](const std::vector<const std::vector<float>*>& mats, int64_t col0, int64_t cols, int64_t ld) {   // rows of several [.][ld] matrices, columns [col0, col0 + cols) -> [rows][pad4(cols)]
+        const int64_t Kp = (cols + 3) / 4 * 4;
+        std::vector<float> o;
+        for (auto* m : mats) {
+            const int64_t rows = (int64_t)m->size() / ld;
+            for (int64_t r = 0; r < rows; ++r) {
+                for (int64_t c = 0; c < Kp; ++c) o.push_back(c < cols ? (*m)[(size_t)(r * ld + col0 + c)] : 0.0f);
+            }
+        }
+        return o;
+    };
+    auto cat2 = [](const std::vector<float>& a, const std::vector<float>& b) { std::vector<float> o(a); o.insert(o.end(), b.begin(), b.end()); return o; };
+    const int64_t Hp = (H + 3) / 4 * 4, Cp = (C + 3) / 4 * 4;
+    std::vector<float> wi2h((size_t)(C * H));   // [C][H]: the Linear node's B
+    for (int64_t c = 0; c < C; ++c) for (int64_t a = 0; a < H; ++a) wi2h[(size_t)(c * H + a)] = i2h.w[(size_t)(a * C + c)];
+    std::vector<float> ihv((size_t)(V * 3 * H));   // [V][3H] = W_ih[:, C:]^T
+    for (int64_t v = 0; v < V; ++v) for (int64_t r = 0; r < 3 * H; ++r) ihv[(size_t)(v * 3 * H + r)] = ih.w[(size_t)(r * (C + V) + C + v)];
+    lin_out = GNode();
+    lin_out.op = "Linear";
+    lin_out.in = {fea, put("w_i2h", {C, H}, wi2h)};
+    lin_out.out = {pfx + "proj"};
+    dec_out = GNode();
+    dec_out.op = "SLADecode";
+    dec_out.in = {fea, lin_out.out[0], loop.in[2], loop.in[3],
+                  put("w_h4", {4 * H, Hp}, padded({&h2h.w, &hh.w}, 0, H, H)), put("b_h4", {4 * H}, cat2(h2h.b, hh.b)), put("w_score", {Hp}, padded({&sc.w}, 0, H, H)),
+                  put("w_ihc", {3 * H, Cp}, padded({&ih.w}, 0, C, C + V)), put("w_ihv", {V, 3 * H}, ihv), put("b_ih", {3 * H}, ih.b),
+                  put("w_sl1", {2 * H, Hp}, padded({&s1.w, &l1.w}, 0, H, H)), put("b_sl1", {2 * H}, cat2(s1.b, l1.b)),
+                  put("w_s2", {V, Hp}, padded({&s2.w}, 0, H, H)), put("b_s2", {V}, s2.b), put("w_l2", {L, Hp}, padded({&l2.w}, 0, H, H)), put("b_l2", {L}, l2.b)};
+    dec_out.out = loop.out;
+    auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; dec_out.attrs[k] = a; };
+    iattr("steps", M); iattr("hidden", H); iattr("channels", C); iattr("vocab", V); iattr("loc", L);
+}
+
 void Engine::rewrite_graph(OnnxModel& m) {
     inits_ = std::move(m.initializers);
     std::vector<GNode> nodes;
@@ -138,6 +401,22 @@ void Engine::rewrite_graph(OnnxModel& m) {
         return c;
     };
     auto is_init = [&](const std::string& s) { return inits_.count(s) != 0; };
+
+    // ---- pass 0: Loop whose body is the SLANet structure head's step (PaddleOCR SLAHead._decode: AttentionGRUCell + GRUCell + both
+    // output heads, greedy feedback of the arg max)  ->  Linear (the loop-invariant projection of the features) + ONE SLADecode node.
+    // No other Loop is executed: there is no generic sub-graph executor, and anything that is not this body, in one of the spellings
+    // match_sla_loop tolerates, is refused with the name of the first body node that did not fit.
+    {
+        std::vector<GNode> out;
+        for (auto& n : nodes) {
+            if (n.op != "Loop") { out.push_back(std::move(n)); continue; }
+            GNode lin, dec;
+            match_sla_loop(n, lin, dec);
+            out.push_back(std::move(lin));
+            out.push_back(std::move(dec));
+        }
+        nodes.swap(out);
+    }
 
     // ---- pass 1: fold BatchNormalization into the producing Conv / ConvTranspose
     {
@@ -3042,6 +3321,45 @@ struct Planner {
         step([=](const RunCtx& c) { k::topk_lastdim(c.s, c.at(xin), c.mut(vl), c.mut(il), rows, (int)C, (int)K, largest); }, 0, 4.0 * rows * (C + 2.0 * K));
     }
 
+    // The SLANet structure head (rewrite pass 0): every step of the greedy decode in one launch (sla_decode.hip).  Nothing is allocated or read back at
+    // run time, so the plan stays capturable; all `steps` steps run (exact Loop semantics), the host decoder stops at eos.
+    void op_sla_decode(const GNode& n) {
+        TInfo fea = get(n.in[0]), proj = get(n.in[1]), h0 = get(n.in[2]), pre0 = get(n.in[3]);
+        const int64_t M = n.ai("steps", 0), H = n.ai("hidden", 0), C = n.ai("channels", 0), V = n.ai("vocab", 0), L = n.ai("loc", 0);
+        OAR_CHECK(!fea.host_int && fea.dims.size() == 3 && fea.dims[2] == C, OAR_SHAPE_MISMATCH, "SLADecode: the features must be [B, HW, " + std::to_string(C) + "] at " + n.out[2]);
+        const int64_t B = fea.dims[0], HW = fea.dims[1];
+        OAR_CHECK(B >= 1 && B < (1 << 20), OAR_SHAPE_MISMATCH, "SLADecode: batch out of range at " + n.out[2]);
+        OAR_CHECK(k::sla_decode_supported((int)std::min<int64_t>(HW, 1 << 20), (int)C, (int)H, (int)V, (int)L, (int)M), OAR_UNSUPPORTED_OP,
+                  "Loop (" + n.out[2] + "): HW = " + std::to_string(HW) + " is outside 1 <= HW <= " + std::to_string(k::kSlaMaxHW));
+        OAR_CHECK(proj.dims == (std::vector<int64_t>{B, HW, H}), OAR_INTERNAL, "SLADecode: projection shape");
+        OAR_CHECK(numel(h0.dims) == B * H && numel(pre0.dims) == B, OAR_SHAPE_MISMATCH, "SLADecode: the initial state must be h0 [B, H] and pre0 [B] at " + n.out[2]);
+        OAR_CHECK(pre0.host_int ? !pre0.host_f : pre0.is_int, OAR_UNSUPPORTED_OP, "SLADecode: pre0 must be an integer tensor at " + n.out[2]);
+        auto dev = [&](const std::string& nm, const TInfo& t) -> Loc { return t.host_int ? host_to_device(nm, t) : to_native_loc(t); };
+        Loc fl = to_native_loc(fea), pl = to_native_loc(proj), hl = dev(n.in[2], h0), p0 = dev(n.in[3], pre0);
+        k::SlaDecodeP p{};
+        p.B = (int)B; p.HW = (int)HW; p.C = (int)C; p.H = (int)H; p.V = (int)V; p.L = (int)L; p.M = (int)M;
+        const float** w[12] = {&p.w_h4, &p.b_h4, &p.w_score, &p.w_ihc, &p.w_ihv, &p.b_ih, &p.w_sl1, &p.b_sl1, &p.w_s2, &p.b_s2, &p.w_l2, &p.b_l2};
+        for (int i = 0; i < 12; ++i) {
+            const TInfo& t = get(n.in[(size_t)(4 + i)]);
+            OAR_CHECK(t.ht && t.loc.kind == Loc::CONST, OAR_INTERNAL, "SLADecode: weight is not a constant");
+            *w[i] = t.loc.cptr;
+        }
+        auto out = [&](size_t i, std::vector<int64_t> od, bool is_int) -> Loc {
+            if (i >= n.out.size() || n.out[i].empty()) return alloc_temp((size_t)numel(od) * 4);
+            TInfo& y = new_out(n.out[i], od, Layout::NATIVE);
+            y.is_int = is_int;
+            return y.loc;
+        };
+        Loc ho = out(0, {B, H}, false), po = out(1, {B}, true), lo = out(2, {M, B, V}, false), bo = out(3, {M, B, L}, false);
+        const double macs = 4.0 * H * H + (double)HW * H + (double)HW * C + 3.0 * H * C + 2.0 * H * H + ((double)V + L) * H;   // per step and image
+        step([=](const RunCtx& c) {
+            k::SlaDecodeP q = p;
+            q.fea = c.at(fl); q.proj = c.at(pl); q.h0 = c.at(hl); q.pre0 = c.at(p0);
+            q.h_out = c.mut(ho); q.pre_out = c.mut(po); q.logits = c.mut(lo); q.loc = c.mut(bo);
+            k::sla_decode(c.s, q);
+        }, 2.0 * macs * M * B, 4.0 * (macs + 3.0 * H + V + L) * M * B);
+    }
+
     // Gather with a tensor of indices: y = x[..., idx, ...] along `axis`
     void op_gather_device(const GNode& n) {
         TInfo x = get(n.in[0]), idx = get(n.in[1]);
@@ -3610,6 +3928,7 @@ struct Planner {
         if (op == "MatMul") return op_matmul(n);
         if (op == "Softmax") return op_softmax(n);
         if (op == "Attention") return op_attention(n);
+        if (op == "SLADecode") return op_sla_decode(n);
         if (op == "SEGate") return op_se_gate(n);
         if (op == "DSBlock") return op_dsblock(n);
         if (op == "LayerNormalization") return op_layernorm(n);
@@ -3675,7 +3994,7 @@ const std::set<std::string>& Engine::supported_ops() {
         "ReduceMean", "GridSample", "Pad", "GlobalAveragePool", "AveragePool", "MaxPool", "Resize", "Concat", "Reshape", "Flatten", "Squeeze", "Unsqueeze",
         "Transpose", "Split", "Slice", "Gather", "Gemm", "MatMul", "Softmax", "LayerNormalization", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Not",
         "Floor", "Ceil", "Round", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "Expand", "Tile", "Where", "ConstantOfShape", "Range", "ArgMax", "ArgMin",
-        "TopK", "GatherND", "GatherElements"};
+        "TopK", "GatherND", "GatherElements", "Loop"};   // (Loop: the SLA decode step only, see match_sla_loop)
     return ops;
 }
 

@@ -130,6 +130,7 @@ class Engine {
    private:
     friend struct Planner;
     void rewrite_graph(OnnxModel& m);
+    void match_sla_loop(const GNode& loop, GNode& linear, GNode& decode);   // a Loop whose body is the SLA decode step -> Linear + SLADecode; throws OAR_UNSUPPORTED_OP otherwise
     const float* upload_const(const std::string& key, const std::vector<float>& v);
 
     int device_ = 0;

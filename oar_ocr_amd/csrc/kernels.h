@@ -175,6 +175,21 @@ void gather_rows(hipStream_t s, const float* x, const float* idx, float* y, cons
 // GatherElements: y[w] = x[coords of w with coordinate `axis` replaced by idx[w]]; dims = the index / output dims, xstrides = the data's strides (elements)
 struct GatherElemP { long total, axis_dim; int rank, axis; long dims[6], xstrides[6]; };
 void gather_elements(hipStream_t s, const float* x, const float* idx, float* y, const GatherElemP& p);
+// sla_decode.hip: the SLANet structure head, all `M` greedy steps of every image in one launch (one workgroup per image).
+//   fea [B][HW][C], proj [B][HW][H] (= fea W_i2h^T), h0 [B][H], pre0 [B] (f32-coded token)
+//   w_h4 [4H][Hp] = W_h2h ; W_hh with b_h4 [4H];  w_score [Hp];  w_ihc [3H][Cp] = W_ih[:, :C], w_ihv [V][3H] = W_ih[:, C:]^T, b_ih [3H];
+//   w_sl1 [2H][Hp] = W_s1 ; W_l1 with b_sl1 [2H];  w_s2 [V][Hp], b_s2 [V];  w_l2 [L][Hp], b_l2 [L]      (Hp / Cp: H / C rounded up to 4, zero filled)
+//   -> h_out [B][H], pre_out [B] (f32-coded), logits [M][B][V], loc [M][B][L] (after the sigmoid)
+constexpr int kSlaMaxH = 512, kSlaMaxC = 512, kSlaMaxV = 1024, kSlaMaxHW = 1024, kSlaMaxL = 16, kSlaMaxM = 4096;
+struct SlaDecodeP {
+    int B, HW, C, H, V, L, M;
+    const float *fea, *proj, *h0, *pre0;
+    const float *w_h4, *b_h4, *w_score, *w_ihc, *w_ihv, *b_ih, *w_sl1, *b_sl1, *w_s2, *b_s2, *w_l2, *b_l2;
+    float *h_out, *pre_out, *logits, *loc;
+};
+bool sla_decode_supported(int HW, int C, int H, int V, int L, int M);
+size_t sla_decode_lds_bytes(int HW, int C, int H, int V);
+void sla_decode(hipStream_t s, const SlaDecodeP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

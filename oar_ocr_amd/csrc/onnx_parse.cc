@@ -186,7 +186,11 @@ HostTensor parse_tensor(Rd r) {
     return t;
 }
 
-void parse_attr(Rd r, std::string& name, Attr& a) {
+void parse_graph(Rd r, OnnxModel& m, int depth);
+
+constexpr int kMaxGraphDepth = 8;   // nested graph attributes recurse: a crafted file must not recurse without bound
+
+void parse_attr(Rd r, std::string& name, Attr& a, int depth) {
     int type = 0;
     bool has_f = false, has_i = false, has_s = false, has_t = false;
     while (!r.done()) {
@@ -198,6 +202,14 @@ void parse_attr(Rd r, std::string& name, Attr& a) {
             case 3: a.i = (int64_t)r.varint(); has_i = true; break;
             case 4: a.s = r.str(); has_s = true; break;
             case 5: a.t = parse_tensor(r.sub()); has_t = true; break;
+            case 6: {   // g: GraphProto
+                if (wt != 2) { r.skip(wt); break; }
+                OAR_CHECK(depth < kMaxGraphDepth, OAR_MODEL_LOAD, "onnx: graph attributes nested deeper than " + std::to_string(kMaxGraphDepth));
+                auto sub = std::make_shared<OnnxModel>();
+                parse_graph(r.sub(), *sub, depth + 1);
+                a.g = std::move(sub);
+                break;
+            }
             case 7: read_floats(r, wt, a.fs); break;
             case 8: read_ints(r, wt, a.is); break;
             case 20: type = (int)r.varint(); break;
@@ -209,14 +221,15 @@ void parse_attr(Rd r, std::string& name, Attr& a) {
         case 2: a.kind = Attr::I; break;
         case 3: a.kind = Attr::S; break;
         case 4: a.kind = Attr::T; break;
+        case 5: a.kind = a.g ? Attr::G : Attr::NONE; break;
         case 6: a.kind = Attr::FS; break;
         case 7: a.kind = Attr::IS; break;
         default:
-            a.kind = has_t ? Attr::T : has_s ? Attr::S : !a.is.empty() ? Attr::IS : !a.fs.empty() ? Attr::FS : has_i ? Attr::I : has_f ? Attr::F : Attr::NONE;
+            a.kind = a.g ? Attr::G : has_t ? Attr::T : has_s ? Attr::S : !a.is.empty() ? Attr::IS : !a.fs.empty() ? Attr::FS : has_i ? Attr::I : has_f ? Attr::F : Attr::NONE;
     }
 }
 
-OnnxNode parse_node(Rd r) {
+OnnxNode parse_node(Rd r, int depth) {
     OnnxNode n;
     while (!r.done()) {
         uint32_t f, wt;
@@ -229,7 +242,7 @@ OnnxNode parse_node(Rd r) {
             case 5: {
                 std::string k;
                 Attr a;
-                parse_attr(r.sub(), k, a);
+                parse_attr(r.sub(), k, a, depth);
                 n.attrs[k] = std::move(a);
                 break;
             }
@@ -284,13 +297,13 @@ ValueInfo parse_value_info(Rd r) {
     return vi;
 }
 
-void parse_graph(Rd r, OnnxModel& m) {
+void parse_graph(Rd r, OnnxModel& m, int depth) {
     std::vector<ValueInfo> inputs;
     while (!r.done()) {
         uint32_t f, wt;
         r.key(f, wt);
         switch (f) {
-            case 1: m.nodes.push_back(parse_node(r.sub())); break;
+            case 1: m.nodes.push_back(parse_node(r.sub(), depth)); break;
             case 5: {
                 HostTensor t = parse_tensor(r.sub());
                 std::string nm = t.name;
@@ -317,7 +330,7 @@ OnnxModel parse_onnx(const uint8_t* data, size_t len) {
         uint32_t f, wt;
         r.key(f, wt);
         if (f == 7 && wt == 2) {
-            parse_graph(r.sub(), m);
+            parse_graph(r.sub(), m, 0);
             have_graph = true;
         } else if (f == 8 && wt == 2) {
             Rd s = r.sub();

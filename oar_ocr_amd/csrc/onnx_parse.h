@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -24,14 +25,17 @@ struct HostTensor {
     }
 };
 
+struct OnnxModel;
+
 struct Attr {
-    enum Kind { NONE, F, I, S, T, FS, IS } kind = NONE;
+    enum Kind { NONE, F, I, S, T, FS, IS, G } kind = NONE;
     float f = 0;
     int64_t i = 0;
     std::string s;
     HostTensor t;
     std::vector<float> fs;
     std::vector<int64_t> is;
+    std::shared_ptr<const OnnxModel> g;   // G: AttributeProto.g, a nested graph (Loop / If / Scan bodies); its own graph attributes nest the same way
 };
 
 struct OnnxNode {
@@ -67,7 +71,7 @@ struct ValueInfo {  // a graph input / output as declared (ValueInfoProto): dyna
 struct OnnxModel {
     std::vector<OnnxNode> nodes;
     std::map<std::string, HostTensor> initializers;
-    std::vector<std::string> inputs;   // non-initializer graph inputs
+    std::vector<std::string> inputs;   // non-initializer graph inputs (a nested graph: its formal parameters, in order)
     std::vector<std::string> outputs;
     std::vector<ValueInfo> input_infos, output_infos;   // same order as inputs / outputs
     int64_t opset = 0;

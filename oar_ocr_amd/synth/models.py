@@ -878,3 +878,108 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
         g.add_output(t["input"], ["N", A if cols == "A" else queries])
         g.add_output(t["index"], ["N", t["k"]], elem_type=7)
     return g.model(), {"params": g.n_params, "kind": "rtdetr", "classes": n_classes, "anchors": A, "queries": queries, "keep": keep, "feat": 6, "topk": topk}
+
+
+# ---------------------------------------------------------------------------------------------- table structure recognition: SLANet
+SLA_WEIGHT_NAMES = ("i2h", "h2h_w", "h2h_b", "score", "wih", "bih", "whh", "bhh", "s1w", "s1b", "s2w", "s2b", "l1w", "l1b", "l2w", "l2b")
+
+
+def sla_weights(C, H, V, L, seed=0):
+    """f32 weights of one SLA head, well conditioned for a 500-step free-running decode: U(-1, 1) / sqrt(fan) everywhere (fan = C for the feature
+    projection, H otherwise), then the score vector x4, W_ih's context columns x2 and its token columns x6, the heads' first layers x2, the
+    structure head's second layer x6 and the location head's x3; W_hh and W_h2h stay x1 (a higher recurrent gain makes the GRU chaotic: f32 and
+    f64 then disagree completely after a few hundred steps)."""
+    rng = np.random.default_rng(seed)
+    u = lambda *s, k: ((rng.random(s) * 2.0 - 1.0) / np.sqrt(k)).astype(np.float32)
+    w = dict(i2h=u(H, C, k=C), h2h_w=u(H, H, k=H), h2h_b=u(H, k=H), score=u(1, H, k=H) * np.float32(4.0),
+             wih=u(3 * H, C + V, k=H), bih=u(3 * H, k=H), whh=u(3 * H, H, k=H), bhh=u(3 * H, k=H),
+             s1w=u(H, H, k=H) * np.float32(2.0), s1b=u(H, k=H), s2w=u(V, H, k=H) * np.float32(6.0), s2b=u(V, k=H),
+             l1w=u(H, H, k=H) * np.float32(2.0), l1b=u(H, k=H), l2w=u(L, H, k=H) * np.float32(3.0), l2b=u(L, k=H))
+    w["wih"][:, :C] *= np.float32(2.0)
+    w["wih"][:, C:] *= np.float32(6.0)
+    return {k: np.ascontiguousarray(v, np.float32) for k, v in w.items()}
+
+
+def _sla_body(w, B, spelling="gemm", first_act="Tanh", outer=None):
+    """The Loop body of the SLA head (PaddleOCR SLAHead._decode + AttentionGRUCell + GRUCell), one greedy step: inputs (i, cond, h, pre), outputs
+    (cond, h_new, pre_new, logits, loc); `fea` is read from the outer scope.  spelling "gemm": Gemm(transB=1) with the weights as body initializers;
+    "matmul": MatMul with the transposed weight + Add, the weights as initializers of `outer` (the enclosing GraphBuilder)."""
+    from .onnx_writer import BOOL, FLOAT, INT64
+    H, V, L = w["h2h_w"].shape[0], w["s2w"].shape[0], w["l2w"].shape[0]
+    b = GraphBuilder("sla_step")
+    b.add_input("sla_i", [], INT64)
+    b.add_input("sla_cond_in", [], BOOL)
+    b.add_input("sla_h", [B, H])
+    b.add_input("sla_pre", [B], INT64)
+    store = b if spelling == "gemm" else outer
+    c = lambda arr, p="c": b.init(np.asarray(arr), "sla_" + p)
+
+    def lin(x, wn, bn=None, outputs=None):
+        if spelling == "gemm" and bn is not None:
+            return b.op("Gemm", [x, store.init(w[wn], "sla_" + wn), store.init(w[bn], "sla_" + bn)], outputs=outputs, transB=1)
+        y = b.op("MatMul", [x, store.init(np.ascontiguousarray(w[wn].T), "sla_" + wn + "_t")], outputs=None if bn is not None else outputs)
+        return y if bn is None else b.op("Add", [y, store.init(w[bn], "sla_" + bn)], outputs=outputs)
+
+    hp = lin("sla_h", "h2h_w", "h2h_b")
+    hpu = b.op("Unsqueeze", [hp, c(np.array([1], np.int64), "axes")])
+    proj = lin("fea", "i2h")
+    e = lin(b.op(first_act, [b.op("Add", [proj, hpu])]), "score")                                   # [B, HW, 1]
+    alpha = b.op("Transpose", [b.op("Softmax", [e], axis=1)], perm=[0, 2, 1])
+    ctx = b.op("Squeeze", [b.op("MatMul", [alpha, "fea"]), c(np.array([1], np.int64), "axes")])      # [B, C]
+    onehot = b.op("OneHot", ["sla_pre", c(np.array(V, np.int64), "depth"), c(np.array([0.0, 1.0], np.float32), "values")], axis=-1)
+    x = b.op("Concat", [ctx, onehot], axis=1)
+    xr, xz, xc = b.op("Split", [lin(x, "wih", "bih")], n_out=3, axis=1)
+    hr, hz, hc = b.op("Split", [lin("sla_h", "whh", "bhh")], n_out=3, axis=1)
+    r = b.op("Sigmoid", [b.op("Add", [xr, hr])])
+    z = b.op("Sigmoid", [b.op("Add", [xz, hz])])
+    cand = b.op("Tanh", [b.op("Add", [xc, b.op("Mul", [r, hc])])])
+    b.op("Add", [b.op("Mul", [b.op("Sub", ["sla_h", cand]), z]), cand], outputs=["sla_h_new"])
+    lin(lin("sla_h_new", "s1w", "s1b"), "s2w", "s2b", outputs=["sla_logits"])
+    b.op("Sigmoid", [lin(lin("sla_h_new", "l1w", "l1b"), "l2w", "l2b")], outputs=["sla_loc"])
+    b.op("ArgMax", ["sla_logits"], outputs=["sla_pre_new"], axis=1, keepdims=0)
+    b.op("Identity", ["sla_cond_in"], outputs=["sla_cond_out"])
+    b.add_output("sla_cond_out", [], BOOL)
+    b.add_output("sla_h_new", [B, H])
+    b.add_output("sla_pre_new", [B], INT64)
+    b.add_output("sla_logits", [B, V])
+    b.add_output("sla_loc", [B, L])
+    return b
+
+
+def build_slanet(C=96, H=256, V=50, L=8, M=501, image_shape=(64, 64), seed=0, head_only=False, weights=None, spelling="gemm", first_act="Tanh"):
+    """SLANet-shaped table structure recognizer: a tiny conv backbone to stride 8 -> fea [B, HW, C] -> the SLA head as an ONNX Loop of M greedy steps
+    -> bbox [B, M, L] and structure probabilities [B, M, V], in the reference's output order (models/recognition/slanet.rs).  `fea`, the last hidden
+    state and the last token are further declared outputs, so that a test can check the head apart from the backbone.  head_only: the graph input is
+    `fea` [B, HW, C] itself.  weights: the head's arrays (SLA_WEIGHT_NAMES; default sla_weights(C, H, V, L, seed)); spelling / first_act: see _sla_body
+    (first_act other than "Tanh" writes a body the engine must refuse).  Returns (onnx_bytes, info) with info["weights"] for the reference computation."""
+    from .onnx_writer import INT64
+    w = weights if weights is not None else sla_weights(C, H, V, L, seed)
+    net = _Net("slanet", seed + 100)
+    g = net.g
+    if head_only:
+        g.add_input("fea", ["B", "HW", C])
+    else:
+        g.add_input("x", ["B", 3, image_shape[0], image_shape[1]])
+        t = net.conv("x", 3, 16, 3, 2, act="hswish")
+        t = net.ds_block(t, 16, 32, 3, 2)
+        t = net.ds_block(t, 32, 64, 3, 2)
+        t = net.conv(t, 64, C, 1, 1, act=None)                                                     # [B, C, h, w]
+        t = g.op("Reshape", [t, g.init(np.array([0, C, -1], np.int64), "shape")])
+        g.nodes.append(node("Transpose", [t], ["fea"], name=g.uid("n"), perm=[0, 2, 1]))
+    shp = g.op("Shape", ["fea"])
+    bdim = g.op("Gather", [shp, g.init(np.array([0], np.int64), "idx")], axis=0)                  # [1]
+    h0 = g.op("ConstantOfShape", [g.op("Concat", [bdim, g.init(np.array([H], np.int64), "h")], axis=0)], value=np.zeros(1, np.float32))
+    pre0 = g.op("ConstantOfShape", [bdim], value=np.zeros(1, np.int64))
+    body = _sla_body(w, "B", spelling, first_act, outer=g)
+    m_name, cond = g.init(np.array(M, np.int64), "trip"), g.init(np.array(True), "cond")
+    g.op("Loop", [m_name, cond, h0, pre0], outputs=["h_last", "pre_last", "logits_scan", "loc_scan"], body=body)
+    g.nodes.append(node("Transpose", ["loc_scan"], ["bbox"], name=g.uid("n"), perm=[1, 0, 2]))
+    lt = g.op("Transpose", ["logits_scan"], perm=[1, 0, 2])
+    g.nodes.append(node("Softmax", [lt], ["structure_probs"], name=g.uid("n"), axis=2))
+    g.add_output("bbox", ["B", M, L])
+    g.add_output("structure_probs", ["B", M, V])
+    if not head_only:
+        g.add_output("fea", ["B", "HW", C])
+    g.add_output("h_last", ["B", H])
+    g.add_output("pre_last", ["B"], INT64)
+    return g.model(), {"params": g.n_params, "weights": w, "C": C, "H": H, "V": V, "L": L, "M": M}

@@ -13,7 +13,7 @@ from typing import Iterable, Sequence
 
 import numpy as np
 
-FLOAT, INT32, INT64 = 1, 6, 7
+FLOAT, INT32, INT64, BOOL = 1, 6, 7, 9
 
 
 def _varint(n: int) -> bytes:
@@ -58,6 +58,8 @@ def tensor_proto(name: str, arr: np.ndarray) -> bytes:
         dt = INT64
     elif arr.dtype == np.int32:
         dt = INT32
+    elif arr.dtype == np.bool_:
+        dt = BOOL
     else:
         raise TypeError(arr.dtype)
     out = b"".join(_f_varint(1, d) for d in arr.shape)
@@ -67,9 +69,20 @@ def tensor_proto(name: str, arr: np.ndarray) -> bytes:
     return out
 
 
+class SubGraph:
+    """GraphProto bytes as an attribute value (`GraphBuilder.graph()`): a Loop / If / Scan body."""
+
+    def __init__(self, graph_proto: bytes):
+        self.proto = graph_proto
+
+
 def attr(name: str, value) -> bytes:
     out = _f_str(1, name)
-    if isinstance(value, float):
+    if isinstance(value, GraphBuilder):
+        value = SubGraph(value.graph())
+    if isinstance(value, SubGraph):
+        out += _f_bytes(6, value.proto) + _f_varint(20, 5)      # AttributeProto.g, type GRAPH
+    elif isinstance(value, float):
         out += _f_float(2, value) + _f_varint(20, 1)
     elif isinstance(value, (int, np.integer)) and not isinstance(value, bool):
         out += _f_varint(3, int(value)) + _f_varint(20, 2)
@@ -132,24 +145,31 @@ class GraphBuilder:
     def add_output(self, name, shape, elem_type: int = FLOAT):
         self.outputs.append(value_info(name, shape, elem_type))
 
-    def init(self, arr: np.ndarray, prefix: str = "w") -> str:
-        name = self.uid(prefix)
+    def init(self, arr: np.ndarray, prefix: str = "w", name: str = None) -> str:
+        name = name or self.uid(prefix)
         self.inits.append(tensor_proto(name, arr))
         if arr.dtype == np.float32:
             self.n_params += arr.size
         return name
 
-    def op(self, op_type: str, inputs: Sequence[str], n_out: int = 1, **attrs):
-        outs = [self.uid(op_type.lower()) for _ in range(n_out)]
+    def op(self, op_type: str, inputs: Sequence[str], n_out: int = 1, outputs: Sequence[str] = None, **attrs):
+        """outputs: fixed output names (a sub-graph's outputs must be known to the graph that declares them)"""
+        outs = list(outputs) if outputs is not None else [self.uid(op_type.lower()) for _ in range(n_out)]
+        n_out = len(outs)
         self.nodes.append(node(op_type, inputs, outs, name=self.uid("n"), **attrs))
         return outs[0] if n_out == 1 else outs
 
-    def model(self) -> bytes:
+    def graph(self) -> bytes:
+        """Serialised GraphProto: what `model()` wraps, and what a graph-valued attribute (a Loop body) holds."""
         g = b"".join(_f_bytes(1, n) for n in self.nodes)
         g += _f_str(2, self.name)
         g += b"".join(_f_bytes(5, t) for t in self.inits)
         g += b"".join(_f_bytes(11, i) for i in self.inputs)
         g += b"".join(_f_bytes(12, o) for o in self.outputs)
+        return g
+
+    def model(self) -> bytes:
+        g = self.graph()
         m = _f_varint(1, 8)                      # ir_version
         m += _f_str(2, "oar_ocr_amd.synth")      # producer_name
         m += _f_bytes(7, g)

@@ -1,4 +1,4 @@
-"""Table analysis, cells -> HTML mode: the branch of `TableAnalyzer` (src/oarocr/table_analyzer.rs) that needs no structure-recognition model.
+"""Table analysis: `TableAnalyzer` (src/oarocr/table_analyzer.rs) with its cells -> HTML mode and, when a structure recognizer is given, the SLANet mode.
 
 A table becomes HTML from the table classifier and the cell detector alone (`use_wired_table_cells_trans_to_html` /
 `use_wireless_table_cells_trans_to_html`): `table_cells_to_html_structure` rebuilds rows, columns and spans from the detected cell boxes
@@ -7,7 +7,10 @@ A table becomes HTML from the table classifier and the cell detector alone (`use
 Host orchestration only: crops come from `structure.crop_bounding_box`, classification and cell detection run through the C-ABI predictors of
 `api.py` (the cell detector over all tables of a page in batches of its recommended size, not one call per table).  All coordinate arithmetic is f32
 in the reference's operation order.  Where the reference needs a structure adapter (:535-543) or ends without cells (:676-682) this module raises
-`api.OCRError` with the reference's message.  Table orientation correction and SLANet structure recognition are not part of this module."""
+`api.OCRError` with the reference's message.  With a structure recognizer (`api.TableStructureRecognitionPredictor`: the SLANet family, whose decode
+loop the engine runs as one launch) the cells come from the recognized structure tokens and boxes (:481-584), `parse_cell_grid_info` gives them their
+grid positions, and in the non-e2e mode the cell detector's boxes travel along as `detected_cell_bboxes` (:625-639).  Table orientation correction is
+not part of this module."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -206,6 +209,98 @@ def wrap_table_html(tokens: Sequence[str], cell_texts: Optional[Sequence[Optiona
     return "".join(out)
 
 
+# ------------------------------------------------------------------------------------------------ tokens -> grid positions
+def parse_span_attr(token: str, attr: str) -> Optional[int]:
+    """processors/table_structure_decode.rs:293-306: the value of `attr="<unsigned integer>"` inside a tag or attribute token"""
+    pattern = attr + '="'
+    start = token.find(pattern)
+    if start < 0:
+        return None
+    rest = token[start + len(pattern):]
+    end = rest.find('"')
+    if end < 0:
+        return None
+    v = rest[:end]
+    if v.startswith("+"):                                             # usize::from_str accepts a leading plus sign
+        v = v[1:]
+    return int(v) if v.isascii() and v.isdigit() else None
+
+
+def parse_td_tag(tokens: Sequence[str], start: int) -> Tuple[str, int, int, int]:
+    """parse_td_tag (:326-392) -> (attributes, row_span, col_span, index to continue from): `_parse_td_tag` with the spans read on the way"""
+    row_span = col_span = 1
+
+    def spans(text):
+        nonlocal row_span, col_span
+        v = parse_span_attr(text, "colspan")
+        if v is not None:
+            col_span = v
+        v = parse_span_attr(text, "rowspan")
+        if v is not None:
+            row_span = v
+
+    t0 = tokens[start]
+    if t0.startswith("<td"):
+        before_gt = t0[3:].split(">")[0]
+        if before_gt:
+            spans(before_gt)
+    idx = start + 1
+    while idx < len(tokens):
+        t = tokens[idx]
+        if t in (">", "</td>", "<tr>", "</tr>") or t.startswith("<td"):
+            break
+        spans(t)
+        idx += 1
+    attrs, nxt = _parse_td_tag(tokens, start)
+    return attrs, row_span, col_span, nxt
+
+
+def parse_cell_grid_info(tokens: Sequence[str]) -> List[CellGridInfo]:
+    """processors/table_structure_decode.rs:210-291: one CellGridInfo per `<td` token, in order; a rowspan occupies its columns in the rows below"""
+    cells, occupied = [], set()
+    row = col = idx = 0
+    while idx < len(tokens):
+        t = tokens[idx]
+        if t == "<tr>":
+            col = 0
+            while (row, col) in occupied:
+                col += 1
+            idx += 1
+        elif t == "</tr>":
+            row += 1
+            idx += 1
+        elif t == "<td></td>":
+            while (row, col) in occupied:
+                col += 1
+            cells.append(CellGridInfo(row, col, 1, 1))
+            col += 1
+            idx += 1
+        elif t.startswith("<td"):
+            _, row_span, col_span, nxt = parse_td_tag(tokens, idx)
+            while (row, col) in occupied:
+                col += 1
+            cells.append(CellGridInfo(row, col, row_span, col_span))
+            for r in range(1, row_span):
+                for c in range(col_span):
+                    occupied.add((row + r, col + c))
+            col += col_span
+            idx = nxt
+        else:
+            idx += 1
+    return cells
+
+
+def cell_bbox_from_coords(coords) -> np.ndarray:
+    """table_analyzer.rs:120-145: the axis-aligned box of a recognized cell (four corner points, or x_min y_min x_max y_max)"""
+    c = [F(v) for v in coords]
+    if len(c) >= 8:
+        xs, ys = c[0:8:2], c[1:8:2]
+        return from_coords(min(xs), min(ys), max(xs), max(ys))
+    if len(c) >= 4:
+        return from_coords(c[0], c[1], c[2], c[3])
+    return from_coords(F(0.0), F(0.0), F(0.0), F(0.0))
+
+
 # ------------------------------------------------------------------------------------------------ the analyzer
 def _translate(box: np.ndarray, dx, dy) -> np.ndarray:
     b = np.asarray(box, np.float32).reshape(-1, 2)
@@ -220,14 +315,19 @@ def _first(*adapters):
 
 
 class TableAnalyzer:
-    """TableAnalyzer (table_analyzer.rs:267-747) without structure-recognition and orientation adapters.  The predictors are anything with the
-    interface of `api.TableClassifier` (`predict(images)` -> per image a list of objects with `.label` and `.score`) and of
-    `api.TableCellDetectionPredictor` (`predict(images)` -> per image a list of objects with `.bbox` and `.score`)."""
+    """TableAnalyzer (table_analyzer.rs:267-747) without orientation adapters.  The predictors are anything with the
+    interface of `api.TableClassifier` (`predict(images)` -> per image a list of objects with `.label` and `.score`), of
+    `api.TableCellDetectionPredictor` (`predict(images)` -> per image a list of objects with `.bbox` and `.score`) and of
+    `api.TableStructureRecognitionPredictor` (`predict(images)` -> an object with `.structures`, `.bboxes`, `.structure_scores`, one entry per image)."""
 
     def __init__(self, table_classifier=None, table_cell_detector=None, wired_table_cell_detector=None, wireless_table_cell_detector=None,
                  use_e2e_wired_table_rec: bool = False, use_e2e_wireless_table_rec: bool = False,
-                 use_wired_table_cells_trans_to_html: bool = False, use_wireless_table_cells_trans_to_html: bool = False, cell_batch_size: int = 4):
+                 use_wired_table_cells_trans_to_html: bool = False, use_wireless_table_cells_trans_to_html: bool = False, cell_batch_size: int = 4,
+                 table_structure_recognizer=None, wired_table_structure_recognizer=None, wireless_table_structure_recognizer=None):
         self.table_classifier = table_classifier
+        self.table_structure_recognizer = table_structure_recognizer
+        self.wired_table_structure_recognizer = wired_table_structure_recognizer
+        self.wireless_table_structure_recognizer = wireless_table_structure_recognizer
         self.table_cell_detector = table_cell_detector
         self.wired_table_cell_detector = wired_table_cell_detector
         self.wireless_table_cell_detector = wireless_table_cell_detector
@@ -267,18 +367,43 @@ class TableAnalyzer:
         if not use_e2e or cells_to_html:                           # :440-479
             d, wd, wl = self.table_cell_detector, self.wired_table_cell_detector, self.wireless_table_cell_detector
             detector = {WIRED: _first(wd, d, wl), WIRELESS: _first(wl, d, wd), UNKNOWN: _first(d, wd, wl)}[kind]
-        # no structure adapter exists in this build (:535-543)
-        if not cells_to_html or effective_e2e:
-            raise api.OCRError(api.OAR_INVALID_INPUT, f"configuration: table_structure_recognition: table {idx} ({kind}): no structure adapter available and "
-                                                      "cells->html conversion is disabled")
-        return {"idx": idx, "element": element, "crop": crop, "off": off, "kind": kind, "cls_conf": cls_conf, "use_e2e": use_e2e, "detector": detector}
+        r, wr, wlr = self.table_structure_recognizer, self.wired_table_structure_recognizer, self.wireless_table_structure_recognizer
+        recognizer = {WIRED: _first(wr, r), WIRELESS: _first(wlr, r), UNKNOWN: _first(r, wlr, wr)}[kind]          # :424-435
+        tokens, boxes, score = None, [], None
+        if recognizer is None:                                     # :535-543
+            if not cells_to_html or effective_e2e:
+                raise api.OCRError(api.OAR_INVALID_INPUT, f"configuration: table_structure_recognition: table {idx} ({kind}): no structure adapter available and "
+                                                          "cells->html conversion is disabled")
+        else:                                                      # :485-533
+            try:
+                res = recognizer.predict([crop])
+            except api.OCRError as ex:
+                if not cells_to_html:                              # surfaced with the table's context; with cells -> HTML the detected cells stand in
+                    raise api.OCRError(ex.code, f"adapter execution failed: table_structure_recognition: table {idx} ({kind}): structure recognition failed: {ex.message}")
+            else:
+                if len(res.structures) > 0 and len(res.bboxes) > 0 and len(res.structure_scores) > 0:
+                    tokens, boxes, score = list(res.structures[0]), list(res.bboxes[0]), F(res.structure_scores[0])
+        return {"idx": idx, "element": element, "crop": crop, "off": off, "kind": kind, "cls_conf": cls_conf, "use_e2e": use_e2e, "detector": detector,
+                "cells_to_html": cells_to_html, "tokens": tokens, "boxes": boxes, "score": score}
 
     @staticmethod
     def _finish(st, detected) -> TableResult:
-        """:586-746 for the cells -> HTML mode; `detected` is the cell detector's output for this table's crop (None: no detector, or it failed)"""
+        """:553-746; `detected` is the cell detector's output for this table's crop (None: no detector, or it failed)"""
         idx, kind, (dx, dy) = st["idx"], st["kind"], st["off"]
-        cells = [TableCell(_translate(c.bbox, dx, dy), float(c.score)) for c in (detected or [])]
-        tokens = None
+        cells_to_html, tokens, score = st["cells_to_html"], st["tokens"], st["score"]
+        cells = []
+        if tokens is not None:                                     # :553-584: the recognized cells, with the grid position their token implies
+            grid = parse_cell_grid_info(tokens)
+            for ci, coords in enumerate(st["boxes"]):
+                cell = TableCell(_translate(cell_bbox_from_coords(coords), dx, dy), 1.0)
+                if ci < len(grid):
+                    cell.row, cell.col, cell.row_span, cell.col_span = grid[ci].row, grid[ci].col, grid[ci].row_span, grid[ci].col_span
+                cells.append(cell)
+        found = list(detected or [])
+        if cells_to_html and found:                                # :610-623: detected cells override the recognized ones; the tokens are regenerated below
+            cells = [TableCell(_translate(c.bbox, dx, dy), float(c.score)) for c in found]
+            tokens = None
+        detected_page = [_translate(c.bbox, dx, dy) for c in found] if (not st["use_e2e"] and not cells_to_html and found) else None   # :625-639
 
         def regenerate(cells, tokens):
             crop_boxes = []
@@ -296,17 +421,19 @@ class TableAnalyzer:
                     re.append(TableCell(c.bbox, c.confidence, gi.row, gi.col, gi.row_span, gi.col_span, c.text))
             return (re, new_tokens, True) if re else (cells, tokens, False)
 
-        if cells:                                                  # :641-674
+        if cells and tokens is None:                               # :641-674
             cells, tokens, _ = regenerate(cells, tokens)
         if not cells:
             raise api.OCRError(api.OAR_INVALID_INPUT, f"invalid input: table {idx} ({kind}): structure recognition produced no cells")
-        cells, tokens, ok = regenerate(cells, tokens)              # :684-717 (use_cells_trans_to_html holds in this branch)
-        score = 1.0 if ok else None
+        if cells_to_html:                                          # :684-717
+            cells, tokens, ok = regenerate(cells, tokens)
+            if ok and score is None:
+                score = 1.0
         if tokens is None:
             raise api.OCRError(api.OAR_INVALID_INPUT, f"invalid input: table {idx} ({kind}): structure recognition produced no structure tokens")
         return TableResult(bbox=np.asarray(st["element"].bbox, np.float32), table_type=kind, cells=cells, html_structure=wrap_table_html(tokens),
-                           structure_tokens=tokens, is_e2e=bool(st["use_e2e"]), structure_confidence=score,
-                           classification_confidence=None if st["cls_conf"] is None else float(st["cls_conf"]))
+                           structure_tokens=tokens, is_e2e=bool(st["use_e2e"]), structure_confidence=None if score is None else float(score),
+                           classification_confidence=None if st["cls_conf"] is None else float(st["cls_conf"]), detected_cell_bboxes=detected_page)
 
     def analyze_tables(self, page_image: np.ndarray, layout_elements: Sequence) -> List[TableResult]:
         """analyze_tables (:285-301): one TableResult per element of type "table", in order; the first table that cannot become a real result raises."""
