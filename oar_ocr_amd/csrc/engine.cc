@@ -923,6 +923,7 @@ struct TInfo {
     std::vector<double> hd;
     const HostTensor* ht = nullptr;  // f32 initializer
     bool is_int = false;             // device tensor whose f32 values are integers by construction (ArgMax, integer Cast of one)
+    bool is01 = false;               // device tensor whose values are 0.0f / 1.0f by construction (comparison, logic op, Not, bool Cast): a Cast to bool of it is an alias
     bool u8_stem = false;            // the graph input of a run_stem plan: u8 pages read by the fused stem, no f32 tensor behind it
     std::string root;                // storage root (for liveness)
     int gap_tiles = 0, gap_hw = 0;   // [n, tiles * C, 1, 1]: per-tile channel sums of a pooling depthwise conv, still to be reduced and divided by gap_hw (SEGate does)
@@ -1126,10 +1127,15 @@ struct Planner {
         TInfo t;
         t.dims = dims; t.layout = lay; t.root = src.root; t.loc = src.loc; t.ht = nullptr;
         t.is_int = src.is_int;   // a view of a device index tensor (Reshape / Squeeze / Unsqueeze / Slice of one) is still one
+        t.is01 = src.is01;       // ... and a view of a 0/1 mask still a mask
         if (t.loc.kind == Loc::CONST) t.loc.cptr = (const float*)((const char*)t.loc.cptr + byte_off);
         else t.loc.off += byte_off;
         if (!t.root.empty()) root_aliases[t.root].push_back(name);
         return vals[name] = t;
+    }
+    std::string node_label() const {
+        const GNode* g = cur >= 0 && cur < (int)E.nodes_.size() ? &E.nodes_[(size_t)cur] : nullptr;
+        return g ? g->op + " -> " + (g->out.empty() ? std::string("?") : g->out[0]) : std::string("?");
     }
     void step(std::function<void(const RunCtx&)> f, double flops = 0, double bytes = 0) {
         P.steps.push_back(std::move(f));
@@ -1465,6 +1471,8 @@ struct Planner {
 
     // ------------------------------------------------------------------ layout conversions
     Loc to_clast_loc(const TInfo& t) {  // native [n,C,s..] -> channels-last copy in a temp
+        if (t.host_int) { TInfo d = t; d.host_int = false; d.layout = Layout::NATIVE; d.loc = host_to_device("", t); return to_clast_loc(d); }   // a plan-time value has no device bytes yet
+        OAR_CHECK(t.loc.kind != Loc::NONE, OAR_INTERNAL, "planner: a tensor without storage reaches a kernel (node " + node_label() + ")");
         if (t.layout == Layout::CLAST) return t.loc;
         OAR_CHECK(t.dims.size() >= 3 && t.dims.size() <= 5, OAR_UNSUPPORTED_OP, "channels-last conversion needs rank 3..5");
         int r = (int)t.dims.size();
@@ -1483,6 +1491,8 @@ struct Planner {
         return tmp;
     }
     Loc to_native_loc(const TInfo& t, Loc dst = Loc()) {
+        if (t.host_int) { TInfo d = t; d.host_int = false; d.layout = Layout::NATIVE; d.loc = host_to_device("", t); return to_native_loc(d, dst); }   // a plan-time value has no device bytes yet
+        OAR_CHECK(t.loc.kind != Loc::NONE, OAR_INTERNAL, "planner: a tensor without storage reaches a kernel (node " + node_label() + ")");
         bool need = t.layout == Layout::CLAST;
         int r = (int)t.dims.size();
         if (need) {
@@ -2298,6 +2308,7 @@ struct Planner {
     void op_unary(const GNode& n, Act a) {
         TInfo x = get(n.in[0]);
         TInfo& y = new_out(n.out[0], x.dims, x.layout);
+        y.is01 = a.kind == k::ACT_NOT;
         Loc xl = x.loc, yl = y.loc;
         int64_t cnt = numel(x.dims);
         step([=](const RunCtx& c) { k::unary(c.s, c.at(xl), c.mut(yl), cnt, a); }, 0, 8.0 * cnt);
@@ -2388,6 +2399,7 @@ struct Planner {
         if (commut && numel(pad) < numel(pbd)) { std::swap(al, bl); std::swap(sa, sb); }
         TInfo& y = new_out(n.out[0], od, clast ? Layout::CLAST : Layout::NATIVE);
         y.is_int = ints_in && (op == 0 || op == 1 || op == 2 || op == 6 || op == 7) && n.act.kind == k::ACT_NONE;   // index arithmetic (idx + offset, idx - dim) stays an index tensor
+        y.is01 = op >= 8 && op <= 12 && n.act.kind == k::ACT_NONE;   // Equal / Less / Greater / And / Or write 0.0f or 1.0f
         Loc yl = y.loc;
         Act post = n.act;
         int64_t cnt = numel(od);
@@ -2563,6 +2575,7 @@ struct Planner {
     }
     // device value of a host-known tensor (a bool / int mask or scalar that a device op consumes)
     Loc host_to_device(const std::string& name, const TInfo& t) {
+        OAR_CHECK(!t.hv.empty() && (int64_t)t.hv.size() == numel(t.dims), OAR_UNSUPPORTED_OP, "an empty plan-time value feeds a device operator (node " + node_label() + ")");
         std::vector<float> f(t.hv.size());
         for (size_t i = 0; i < f.size(); ++i) f[i] = t.host_f && i < t.hd.size() ? (float)t.hd[i] : (float)t.hv[i];
         std::string key = "hostval:" + name + ":";
@@ -2693,14 +2706,31 @@ struct Planner {
             set_host(n.out[0], in[0].dims, v, to_f);
             return true;
         }
-        if (op == "Where") {
-            std::vector<double> c = host_values(in[0]), a = host_values(in[1]), b = host_values(in[2]);
-            const size_t cnt = std::max({c.size(), a.size(), b.size()});
-            if (!((c.size() == cnt || c.size() == 1) && (a.size() == cnt || a.size() == 1) && (b.size() == cnt || b.size() == 1))) return false;   // device path broadcasts
-            std::vector<double> out(cnt);
-            for (size_t i = 0; i < cnt; ++i) out[i] = c[c.size() == 1 ? 0 : i] != 0 ? a[a.size() == 1 ? 0 : i] : b[b.size() == 1 ? 0 : i];
-            const TInfo& big = c.size() == cnt ? in[0] : a.size() == cnt ? in[1] : in[2];
-            set_host(n.out[0], big.dims, out, float_like(in[1]) || float_like(in[2]));
+        if (op == "Where") {   // numpy broadcasting over the aligned dims, like bin above (matching element COUNTS say nothing: [3,1] and [1,3] give [3,3])
+            std::vector<double> v[3] = {host_values(in[0]), host_values(in[1]), host_values(in[2])};
+            size_t r = 0;
+            for (int q = 0; q < 3; ++q) r = std::max(r, in[q].dims.size());
+            std::vector<int64_t> d[3], st[3], od(r, 1);
+            for (int q = 0; q < 3; ++q) {
+                if ((int64_t)v[q].size() != numel(in[q].dims)) return false;
+                d[q].assign(r - in[q].dims.size(), 1);
+                d[q].insert(d[q].end(), in[q].dims.begin(), in[q].dims.end());
+                st[q] = contig_strides(d[q]);
+                for (size_t i = 0; i < r; ++i) od[i] = std::max(od[i], d[q][i]);
+            }
+            for (int q = 0; q < 3; ++q)
+                for (size_t i = 0; i < r; ++i) if (d[q][i] != od[i] && d[q][i] != 1) return false;   // op_where reports the mismatch
+            std::vector<double> out((size_t)numel(od));
+            for (int64_t i = 0; i < (int64_t)out.size(); ++i) {
+                int64_t rem = i, o[3] = {0, 0, 0};
+                for (int k = (int)r - 1; k >= 0; --k) {
+                    const int64_t q = rem / od[k], ix = rem - q * od[k];
+                    rem = q;
+                    for (int t = 0; t < 3; ++t) o[t] += (d[t][k] == 1 ? 0 : ix) * st[t][k];
+                }
+                out[(size_t)i] = v[0][(size_t)o[0]] != 0 ? v[1][(size_t)o[1]] : v[2][(size_t)o[2]];
+            }
+            set_host(n.out[0], od, out, float_like(in[1]) || float_like(in[2]));
             return true;
         }
         if (op == "Expand") {
@@ -2810,8 +2840,9 @@ struct Planner {
         for (int d = 0; d < r; ++d) {
             od[d] = x.dims[d] + before[d] + after[d];
             OAR_CHECK(od[d] >= 0, OAR_SHAPE_MISMATCH, "Pad: negative output dimension");
-            OAR_CHECK(imode != 1 || (before[d] < std::max<int64_t>(x.dims[d], 1) && after[d] < std::max<int64_t>(x.dims[d], 1)) || x.dims[d] == 1, OAR_UNSUPPORTED_OP,
-                      "Pad: reflect padding wider than the axis");
+            // (negative pads crop first: the reflection is taken on what is left of the axis, so it has to stay inside that)
+            const int64_t kept = std::max<int64_t>(x.dims[d] + std::min<int64_t>(before[d], 0) + std::min<int64_t>(after[d], 0), 1);
+            OAR_CHECK(imode != 1 || (before[d] < kept && after[d] < kept) || x.dims[d] == 1, OAR_UNSUPPORTED_OP, "Pad: reflect padding wider than the axis");
         }
         const bool clast = x.layout == Layout::CLAST && r >= 3;
         std::vector<int64_t> pin = clast ? clast_phys_dims(x.dims) : x.dims, pout = clast ? clast_phys_dims(od) : od, pbef = clast ? clast_phys_dims(before) : before;
@@ -3855,6 +3886,31 @@ struct Planner {
         fuse_chains();
     }
 
+    // data inputs of the operators that only exist on the device (their other inputs are plan-time parameters: shapes, axes, pads, K)
+    static const std::vector<int>* device_data_inputs(const std::string& op) {
+        static const std::vector<int> first{0}, both{0, 1};
+        static const std::set<std::string> one = {"Clip", "ReduceMean", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "ArgMax", "ArgMin", "Softmax", "Expand", "Tile", "Transpose",
+                                                  "Pad", "Resize", "GlobalAveragePool", "AveragePool", "MaxPool", "LayerNormalization", "Linear", "Gemm", "TopK", "Flatten", "Split"};
+        if (op == "MatMul" || op == "GridSample") return &both;
+        return one.count(op) || is_unary_act(op) ? &first : nullptr;
+    }
+    static bool reads_host_values(const std::string& op) {
+        static const std::set<std::string> s = {"Add", "Sub", "Mul", "Div", "Pow", "PRelu", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Where", "Reshape", "Squeeze", "Unsqueeze",
+                                                "Slice", "Gather", "GatherND", "GatherElements", "Concat", "Identity", "Cast", "ConstantOfShape", "Shape", "Range", "SLADecode"};
+        return s.count(op) != 0;
+    }
+    std::string device_shadow(const std::string& name) {
+        const std::string sn = name + "::dev";
+        if (!vals.count(sn)) {
+            const TInfo& t = get(name);
+            TInfo d;
+            d.dims = t.dims; d.layout = Layout::NATIVE; d.root = ""; d.is_int = !t.host_f;
+            d.loc = host_to_device(name, t);
+            vals[sn] = d;
+        }
+        return sn;
+    }
+
     void dispatch(const GNode& n) {
         const std::string& op = n.op;
         // shape / kind of an input without forcing a deferred Resize to run (its consumer decides that)
@@ -3871,13 +3927,32 @@ struct Planner {
         for (auto& s : n.in) if (!s.empty()) { const TInfo& t = info(s); evaluable = evaluable && host_evaluable(t); any_host = any_host || t.host_int; }
         if (evaluable && (any_host || op == "Range") && op_host(n)) return;
         (void)host_inputs;
+        // A plan-time value that reaches an operator which exists only as a kernel has no device bytes (Loc::NONE: RunCtx::at gives nullptr for it): it is uploaded once as
+        // an f32 constant and the operator planned on that.  Operators that read host values themselves (the binary family, Where, the views, Gather, Concat, ...) are not listed.
+        if (const std::vector<int>* di = device_data_inputs(op)) {
+            GNode m;
+            bool any = false;
+            for (int i : *di)
+                if (has_input(n, (size_t)i) && info(n.in[(size_t)i]).host_int) { if (!any) { m = n; any = true; } m.in[(size_t)i] = device_shadow(n.in[(size_t)i]); }
+            if (any) return dispatch(m);
+        } else if (!reads_host_values(op) && !n.in.empty() && !n.in[0].empty()) {
+            OAR_CHECK(!info(n.in[0]).host_int, OAR_UNSUPPORTED_OP, "plan-time value '" + n.in[0] + "' feeds the device operator " + node_label());
+        }
+        // every stored input has a place to be read from (the captured Loc of a step cannot be inspected afterwards: this is where it is known)
+        for (auto& s : n.in) {
+            if (s.empty() || peek_pending(s) || pending_convt.count(s) || pending_concat.count(s)) continue;
+            const TInfo& t = info(s);
+            OAR_CHECK(t.host_int || t.loc.kind != Loc::NONE, OAR_INTERNAL, "planner: input '" + s + "' of " + node_label() + " has no storage");
+        }
         if (op == "ConstantOfShape") return op_constant_of_shape(n);
         if (op == "Conv") return op_conv(n);
         if (op == "ConvTranspose") return op_convt(n);
         if (op == "BatchNormalization") return op_bn(n);
         if (is_unary_act(op)) return op_unary(n, act_of(n));
         if (op == "Clip") {
-            Act a; a.kind = k::ACT_CLIP; a.alpha = n.af("min", -3.402823466e38f); a.beta = n.af("max", 3.402823466e38f);
+            // an absent bound is no bound: from opset 11 on (bounds as inputs) +-inf pass through; the attribute form (opset 6) defaults to +-FLT_MAX by its own text
+            const float none = (opset >= 11 || opset == 0) ? INFINITY : 3.402823466e38f;
+            Act a; a.kind = k::ACT_CLIP; a.alpha = n.af("min", -none); a.beta = n.af("max", none);
             if (has_input(n, 1)) { const TInfo& t = get(n.in[1]); OAR_CHECK(t.ht, OAR_UNSUPPORTED_OP, "Clip: dynamic min"); a.alpha = t.ht->f[0]; }
             if (has_input(n, 2)) { const TInfo& t = get(n.in[2]); OAR_CHECK(t.ht, OAR_UNSUPPORTED_OP, "Clip: dynamic max"); a.beta = t.ht->f[0]; }
             return op_unary(n, a);
@@ -3937,7 +4012,22 @@ struct Planner {
             const TInfo& x = get(n.in[0]);
             const int64_t to = n.ai("to", 1);
             OAR_CHECK(to == 1 || to == 9 || to == 10 || to == 11 || x.is_int, OAR_UNSUPPORTED_OP, "Cast of a device tensor to an integer type");
-            TInfo xx = x; alias_out(n.out[0], xx, xx.dims, xx.layout).is_int = x.is_int && !(to == 1 || to == 10 || to == 11);   // (a float Cast of an index tensor is a float tensor: views keep the mark now)
+            bool mask = x.is01;
+            if (to == 9 && !mask && x.ht) { mask = true; for (float v : x.ht->f) mask = mask && (v == 1.0f || (v == 0.0f && !std::signbit(v))); }   // (-0.0 would come back as -0.0)
+            if (to == 9 && !mask) {   // any other float: bool(x) is x != 0, one launch of the flat binary kernel as Or(x, x)
+                const TInfo xx = x;
+                TInfo& y = new_out(n.out[0], xx.dims, xx.layout);
+                y.is01 = true;
+                const Loc xl = xx.loc, yl = y.loc;
+                const int64_t cnt = numel(xx.dims);
+                const std::vector<int64_t> d{cnt}, st{1};
+                step([=](const RunCtx& c) { k::binary(c.s, c.at(xl), c.at(xl), c.mut(yl), 12, 1, d.data(), st.data(), st.data(), Act()); }, (double)cnt, 8.0 * cnt);
+                return;
+            }
+            TInfo xx = x;
+            TInfo& y = alias_out(n.out[0], xx, xx.dims, xx.layout);
+            y.is_int = x.is_int && !(to == 1 || to == 10 || to == 11);   // (a float Cast of an index tensor is a float tensor: views keep the mark now)
+            y.is01 = mask;
             return;
         }
         fail(OAR_UNSUPPORTED_OP, "operator '" + op + "' is not implemented (node output " + (n.out.empty() ? "?" : n.out[0]) + ")");

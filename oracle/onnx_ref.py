@@ -194,12 +194,17 @@ def _resize(x, node, env):
         def idx(o, s, n_in):
             # float32 coordinate arithmetic, as ONNX Runtime's (and the engine's): with sizes 21 -> 3 the scale 3 / 21 rounds UP in f32 and 1 / scale lands just below 7 --
             # the floor is 6 there and 7 in float64 (tools/op_fuzz.py, round 6: a knife edge of non-integer nearest reductions; PP-OCR graphs only enlarge by integers)
+            n_out = o
             o = np.arange(o, dtype=np.float32)
             s = np.float32(s)
             if ctm == "asymmetric":
                 x_ = o / s
-            elif ctm in ("half_pixel", "pytorch_half_pixel"):
+            elif ctm == "half_pixel" or (ctm == "pytorch_half_pixel" and n_out > 1):
                 x_ = (o + np.float32(0.5)) / s - np.float32(0.5)
+            elif ctm == "pytorch_half_pixel":                       # a single output element sits at coordinate 0
+                x_ = np.zeros_like(o)
+            elif ctm == "align_corners":                            # o * (in - 1) / (out - 1), 0 for a single output element; the scale plays no part
+                x_ = o * np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.zeros_like(o)
             else:
                 raise NotImplementedError(ctm)
             if nm == "floor":
@@ -308,26 +313,42 @@ def run(model, feeds: dict, want=None):
                     before[ax], after[ax] = pads[k_], pads[len(axes) + k_]
                 mode = {"constant": "constant", "reflect": "reflect", "edge": "replicate"}[a.get("mode", "constant")]
                 value = float(x[2]) if len(x) > 2 and x[2] is not None else float(a.get("value", 0.0))
-                flat = []
-                for d in range(r - 1, -1, -1):      # torch order: last axis first
-                    flat += [before[d], after[d]]
-                while len(flat) > 2 and flat[-1] == 0 and flat[-2] == 0:
-                    flat = flat[:-2]
-                y = F.pad(x[0], flat, mode=mode, value=value) if mode == "constant" else F.pad(x[0], flat, mode=mode)
+                # axis by axis (padding is separable): negative pads crop first, then F.pad on the axis moved last -- any rank, any axis, unlike F.pad's own reflect
+                y = x[0]
+                for d in range(r):
+                    b_, a_ = before[d], after[d]
+                    if b_ < 0 or a_ < 0:
+                        y = y.narrow(d, max(-b_, 0), y.shape[d] - max(-b_, 0) - max(-a_, 0))
+                        b_, a_ = max(b_, 0), max(a_, 0)
+                    if b_ or a_:
+                        yt = y.movedim(d, -1)
+                        shp = yt.shape
+                        flat3 = yt.reshape(1, -1, shp[-1])
+                        if mode == "constant":
+                            p3 = F.pad(flat3, (b_, a_), value=value)
+                        elif shp[-1] == 1:               # a single element reflects / repeats onto itself
+                            p3 = flat3.expand(1, flat3.shape[1], 1 + b_ + a_)
+                        else:
+                            p3 = F.pad(flat3, (b_, a_), mode=mode)
+                        y = p3.reshape(*shp[:-1], -1).movedim(-1, d)
+                y = y.contiguous()
             elif op == "PRelu":
                 y = torch.where(x[0] > 0, x[0], x[0] * x[1])
             elif op == "GridSample":
                 mode = {"linear": "bilinear", "bilinear": "bilinear", "nearest": "nearest"}[a.get("mode", "linear")]
                 y = F.grid_sample(x[0], x[1], mode=mode, padding_mode=a.get("padding_mode", "zeros"), align_corners=bool(a.get("align_corners", 0)))
             elif op == "Clip":
-                lo = float(x[1]) if len(x) > 1 and x[1] is not None else a.get("min", -3.4e38)
-                hi = float(x[2]) if len(x) > 2 and x[2] is not None else a.get("max", 3.4e38)
+                lo = float(x[1]) if len(x) > 1 and x[1] is not None else a.get("min", -np.inf)     # an absent bound is no bound: +-inf pass
+                hi = float(x[2]) if len(x) > 2 and x[2] is not None else a.get("max", np.inf)
                 y = torch.clamp(x[0], lo, hi)
             elif op == "LeakyRelu":
                 y = F.leaky_relu(x[0], a.get("alpha", 0.01))
             elif op in ("Add", "Mul", "Sub", "Div", "Pow"):
                 f = {"Add": torch.add, "Mul": torch.mul, "Sub": torch.sub, "Div": torch.div, "Pow": torch.pow}[op]
-                y = f(x[0], x[1])
+                if op == "Div" and not (x[0].is_floating_point() or x[1].is_floating_point()):
+                    y = torch.div(x[0], x[1], rounding_mode="trunc")   # integer Div is C division: toward zero
+                else:
+                    y = f(x[0], x[1])
             elif op == "GlobalAveragePool":
                 y = x[0].mean(dim=(2, 3), keepdim=True)
             elif op in ("AveragePool", "MaxPool"):
