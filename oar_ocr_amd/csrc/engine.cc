@@ -112,72 +112,70 @@ static Act act_of(const GNode& n) {
     return a;
 }
 
-// -------------------------------------------------------------------------------------------------
-// Loop -> SLADecode.  The body contract (DESIGN 4.30), with h [B,H], pre [B] the loop-carried state and fea [B,HW,C] from the outer scope:
-//   hp = Gemm(h, W_h2h, b_h2h, transB=1)        e = MatMul(Tanh(Add(MatMul(fea, W_i2h^T), Unsqueeze(hp, [1]))), w_score^T)
-//   ctx = Squeeze(MatMul(Transpose(Softmax(e, axis=1), [0,2,1]), fea), [1])      x = Concat(ctx, OneHot(pre, V, [0,1]), axis=1)
-//   xr,xz,xc = Split(Gemm(x, W_ih, b_ih, transB=1))   hr,hz,hc = Split(Gemm(h, W_hh, b_hh, transB=1))
-//   r = Sigmoid(xr+hr)  z = Sigmoid(xz+hz)  c = Tanh(xc + r*hc)  h_new = (h - c)*z + c
-//   logits = Gemm(Gemm(h_new, W_s1, b_s1), W_s2, b_s2)   loc = Sigmoid(Gemm(Gemm(h_new, W_l1, b_l1), W_l2, b_l2))   pre_new = ArgMax(logits, axis=1, keepdims=0)
-// Tolerated: MatMul(x, W^T) + Add(bias) for a Gemm, Cast around OneHot / ArgMax, weights as body or outer initializers (or Constant
-// nodes), axes as attribute or input, cond_out as Identity(cond_in) or a constant true.
-void Engine::match_sla_loop(const GNode& loop, GNode& lin_out, GNode& dec_out) {
-    const std::string where = "Loop (" + (loop.out.empty() ? std::string("?") : loop.out[0]) + ")";
-    auto refuse = [&](const std::string& why) { fail(OAR_UNSUPPORTED_OP, where + ": only the SLA decode step is supported as a Loop body: " + why); };
-    auto bit = loop.attrs.find("body");
-    if (bit == loop.attrs.end() || bit->second.kind != Attr::G || !bit->second.g) refuse("the node has no body graph");
-    const OnnxModel& body = *bit->second.g;
-    // constants: body initializers, body Constant nodes, then the outer scope
+// What the Loop matchers share: the body's constants (body initializers, body Constant nodes, then the outer scope), the producer of every body value,
+// the marks of the nodes a matcher has accounted for, and the refusal that names the Loop and the body node that did not fit.
+struct LoopBody {
+    const OnnxModel& body;
+    const std::map<std::string, HostTensor>& outer;
+    std::string prefix;   // "Loop (name): only ... is supported as a Loop body: "
+    std::string step;     // what the body must be, for messages: "SLA step"
     std::map<std::string, HostTensor> local;
     std::map<std::string, int> producer;
-    std::vector<bool> used(body.nodes.size(), false);
-    for (int i = 0; i < (int)body.nodes.size(); ++i) {
-        const OnnxNode& bn = body.nodes[i];
-        if (bn.op == "Constant") {
-            auto it = bn.attrs.find("value");
-            if (it != bn.attrs.end() && it->second.kind == Attr::T && !bn.outputs.empty()) { local[bn.outputs[0]] = it->second.t; used[i] = true; continue; }
+    std::vector<bool> used;
+    LoopBody(const OnnxModel& b, const std::map<std::string, HostTensor>& o, std::string pfx, std::string st)
+        : body(b), outer(o), prefix(std::move(pfx)), step(std::move(st)), used(b.nodes.size(), false) {
+        for (int i = 0; i < (int)body.nodes.size(); ++i) {
+            const OnnxNode& bn = body.nodes[i];
+            if (bn.op == "Constant") {
+                auto it = bn.attrs.find("value");
+                if (it != bn.attrs.end() && it->second.kind == Attr::T && !bn.outputs.empty()) { local[bn.outputs[0]] = it->second.t; used[i] = true; continue; }
+            }
+            for (auto& o2 : bn.outputs) producer[o2] = i;
         }
-        for (auto& o : bn.outputs) producer[o] = i;
     }
-    auto cst = [&](const std::string& s) -> const HostTensor* {
+    [[noreturn]] void refuse(const std::string& why) const { fail(OAR_UNSUPPORTED_OP, prefix + why); }
+    const HostTensor* cst(const std::string& s) const {
         auto a = body.initializers.find(s);
         if (a != body.initializers.end()) return &a->second;
         auto b = local.find(s);
         if (b != local.end()) return &b->second;
         if (producer.count(s)) return nullptr;
-        auto c = inits_.find(s);
-        return c == inits_.end() ? nullptr : &c->second;
-    };
-    auto node_desc = [&](int i) { const OnnxNode& bn = body.nodes[i]; return "body node '" + (bn.name.empty() ? (bn.outputs.empty() ? std::string("?") : bn.outputs[0]) : bn.name) + "' (" + bn.op + ")"; };
+        auto c = outer.find(s);
+        return c == outer.end() ? nullptr : &c->second;
+    }
+    std::string node_desc(int i) const {
+        const OnnxNode& bn = body.nodes[i];
+        return "body node '" + (bn.name.empty() ? (bn.outputs.empty() ? std::string("?") : bn.outputs[0]) : bn.name) + "' (" + bn.op + ")";
+    }
     // the node that produces `v`, which must be a `op`; marks it
-    auto expect = [&](const std::string& v, const char* op, const char* role) -> const OnnxNode& {
+    const OnnxNode& expect(const std::string& v, const char* op, const char* role) {
         auto it = producer.find(v);
         if (it == producer.end()) refuse(std::string("the ") + role + " '" + v + "' is not computed by a " + op + " in the body");
         const OnnxNode& bn = body.nodes[it->second];
         if (bn.op != op) refuse(node_desc(it->second) + " does not fit: the " + role + " must be a " + op);
         used[it->second] = true;
         return bn;
-    };
-    auto bad = [&](const OnnxNode& bn, const std::string& why) { refuse(node_desc((int)(&bn - body.nodes.data())) + " does not fit: " + why); };
-    auto is_op = [&](const std::string& v, const char* op) { auto it = producer.find(v); return it != producer.end() && body.nodes[it->second].op == op; };
-    auto strip_casts = [&](std::string v) {
+    }
+    [[noreturn]] void bad(const OnnxNode& bn, const std::string& why) const { refuse(node_desc((int)(&bn - body.nodes.data())) + " does not fit: " + why); }
+    bool is_op(const std::string& v, const char* op) const { auto it = producer.find(v); return it != producer.end() && body.nodes[it->second].op == op; }
+    std::string strip_casts(std::string v) {
         while (is_op(v, "Cast")) { const int i = producer[v]; used[i] = true; v = body.nodes[i].inputs[0]; }
         return v;
-    };
-    auto ints_arg = [&](const OnnxNode& bn, const char* attr, size_t input) -> std::vector<int64_t> {
+    }
+    std::vector<int64_t> ints_arg(const OnnxNode& bn, const char* attr, size_t input) const {
         if (bn.has(attr)) { auto& a = bn.attrs.at(attr); return a.kind == Attr::I ? std::vector<int64_t>{a.i} : a.is; }
         if (input < bn.inputs.size() && !bn.inputs[input].empty())
             if (const HostTensor* t = cst(bn.inputs[input])) return t->i;
         return {};
-    };
-    auto f32c = [&](const OnnxNode& bn, const std::string& s, size_t rank) -> const HostTensor& {
+    }
+    const HostTensor& f32c(const OnnxNode& bn, const std::string& s, size_t rank) const {
         const HostTensor* t = cst(s);
         if (!t || t->dtype != DType::F32 || t->dims.size() != rank || (int64_t)t->f.size() != t->numel() || t->numel() == 0) bad(bn, "'" + s + "' must be a constant f32 tensor of rank " + std::to_string(rank));
         return *t;
-    };
-    // y = x W^T + b as Gemm(x, W, b, transB) or [Add(] MatMul(x, W^T) [, b)]: W comes back as [N][K] row-major
+    }
+    // y = x W^T + b as Gemm(x, W, b, transB) or [Add(] MatMul(x, W^T) [, b)]: W comes back as [N][K] row-major.  want_bias: 1 required, 0 refused, -1 optional
     struct Lin { std::string x; std::vector<float> w, b; int64_t N = 0, K = 0; };
-    auto lin = [&](const std::string& v, const char* role, bool want_bias) -> Lin {
+    Lin lin(const std::string& v, const char* role, int want_bias) {
         Lin r;
         auto it = producer.find(v);
         if (it == producer.end()) refuse(std::string("the ") + role + " '" + v + "' is not computed in the body");
@@ -213,11 +211,41 @@ void Engine::match_sla_loop(const GNode& loop, GNode& lin_out, GNode& dec_out) {
             if (!r.b.empty() && (int64_t)r.b.size() != r.N) bad(*bn, "bias length");
             r.x = mm->inputs[0];
         }
-        if (want_bias && r.b.empty()) bad(*bn, std::string("the ") + role + " needs a bias");
-        if (!want_bias && !r.b.empty()) bad(*bn, std::string("the ") + role + " has no bias in the SLA step");
+        if (want_bias == 1 && r.b.empty()) bad(*bn, std::string("the ") + role + " needs a bias");
+        if (want_bias == 0 && !r.b.empty()) bad(*bn, std::string("the ") + role + " has no bias in the " + step);
         return r;
-    };
-    auto two = [&](const OnnxNode& bn) { if (bn.inputs.size() != 2) bad(bn, "needs two inputs"); };
+    }
+    void two(const OnnxNode& bn) const { if (bn.inputs.size() != 2) bad(bn, "needs two inputs"); }
+};
+
+// -------------------------------------------------------------------------------------------------
+// Loop -> SLADecode.  The body contract (DESIGN 4.30), with h [B,H], pre [B] the loop-carried state and fea [B,HW,C] from the outer scope:
+//   hp = Gemm(h, W_h2h, b_h2h, transB=1)        e = MatMul(Tanh(Add(MatMul(fea, W_i2h^T), Unsqueeze(hp, [1]))), w_score^T)
+//   ctx = Squeeze(MatMul(Transpose(Softmax(e, axis=1), [0,2,1]), fea), [1])      x = Concat(ctx, OneHot(pre, V, [0,1]), axis=1)
+//   xr,xz,xc = Split(Gemm(x, W_ih, b_ih, transB=1))   hr,hz,hc = Split(Gemm(h, W_hh, b_hh, transB=1))
+//   r = Sigmoid(xr+hr)  z = Sigmoid(xz+hz)  c = Tanh(xc + r*hc)  h_new = (h - c)*z + c
+//   logits = Gemm(Gemm(h_new, W_s1, b_s1), W_s2, b_s2)   loc = Sigmoid(Gemm(Gemm(h_new, W_l1, b_l1), W_l2, b_l2))   pre_new = ArgMax(logits, axis=1, keepdims=0)
+// Tolerated: MatMul(x, W^T) + Add(bias) for a Gemm, Cast around OneHot / ArgMax, weights as body or outer initializers (or Constant
+// nodes), axes as attribute or input, cond_out as Identity(cond_in) or a constant true.
+void Engine::match_sla_loop(const GNode& loop, GNode& lin_out, GNode& dec_out) {
+    const std::string where = "Loop (" + (loop.out.empty() ? std::string("?") : loop.out[0]) + ")";
+    auto bit = loop.attrs.find("body");
+    if (bit == loop.attrs.end() || bit->second.kind != Attr::G || !bit->second.g) fail(OAR_UNSUPPORTED_OP, where + ": only the SLA decode step is supported as a Loop body: the node has no body graph");
+    const OnnxModel& body = *bit->second.g;
+    LoopBody LB(body, inits_, where + ": only the SLA decode step is supported as a Loop body: ", "SLA step");
+    auto& producer = LB.producer;
+    auto& used = LB.used;
+    using Lin = LoopBody::Lin;
+    auto refuse = [&](const std::string& why) { LB.refuse(why); };
+    auto cst = [&](const std::string& s) { return LB.cst(s); };
+    auto node_desc = [&](int i) { return LB.node_desc(i); };
+    auto expect = [&](const std::string& v, const char* op, const char* role) -> const OnnxNode& { return LB.expect(v, op, role); };
+    auto bad = [&](const OnnxNode& bn, const std::string& why) { LB.bad(bn, why); };
+    auto is_op = [&](const std::string& v, const char* op) { return LB.is_op(v, op); };
+    auto strip_casts = [&](std::string v) { return LB.strip_casts(std::move(v)); };
+    auto ints_arg = [&](const OnnxNode& bn, const char* attr, size_t input) { return LB.ints_arg(bn, attr, input); };
+    auto lin = [&](const std::string& v, const char* role, bool want_bias) { return LB.lin(v, role, want_bias ? 1 : 0); };
+    auto two = [&](const OnnxNode& bn) { LB.two(bn); };
 
     if (body.inputs.size() != 4 || body.outputs.size() != 5) refuse("the body must have the inputs (i, cond, h, pre) and the outputs (cond, h, pre, logits, loc)");
     if (loop.in.size() != 4 || loop.out.size() != 4) refuse("the node must carry (M, cond, h0, pre0) and yield (h, pre, logits scan, loc scan)");
@@ -375,6 +403,332 @@ void Engine::match_sla_loop(const GNode& loop, GNode& lin_out, GNode& dec_out) {
     iattr("steps", M); iattr("hidden", H); iattr("channels", C); iattr("vocab", V); iattr("loc", L);
 }
 
+// -------------------------------------------------------------------------------------------------
+// Loop -> FormulaDecode.  The body contract: the greedy step of a pre-norm (MBart-order) transformer decoder with a key / value cache.
+// Carried: tok [B] int64, then K_l, V_l [B, nh, t, dh] per layer; from the outer scope KmT_l [B, nh, dh, S] and Vm_l [B, nh, S, dh].
+//   x = LN_emb(Gather(E_tok, tok) * s_emb + Gather(E_pos, i + c_pos))
+//   per layer:  y = LN1(x); q = lin(y) * dh^-0.5, k = lin(y), v = lin(y), each Reshape to [B, nh, 1, dh];  K' = Concat(K, k, 2), V' = Concat(V, v, 2)
+//               x = x + lin(Reshape(MatMul(Softmax(MatMul(q, Transpose(K', [0,1,3,2]))), V'), [B, D]))
+//               x = x + lin(Reshape(MatMul(Softmax(MatMul(Reshape(lin(LN2(x)) * dh^-0.5), KmT)), Vm), [B, D]))
+//               x = x + lin(Gelu(lin(LN3(x))))
+//   logits = lin(LN_f(x));  tok_new = ArgMax(logits, 1);  outputs (cond, tok_new, K_1', V_1', ..., scan tok_new [, scan logits])
+// Tolerated: Gemm(transB=1) or MatMul [+ Add]; the query scale as a Mul on either side of the bias Add or absent; weights as body / outer constants;
+// commuted Add / Mul; Cast around the Gather indices and the ArgMax; constant Reshape targets with 0 / -1 entries.
+void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& outer_nodes, GNode& dec_out, std::vector<std::string>& dropped_inputs) {
+    const std::string where = "Loop (" + (loop.out.empty() ? std::string("?") : loop.out[0]) + ")";
+    const OnnxModel& body = *loop.attrs.at("body").g;
+    LoopBody L(body, inits_, where + ": only the formula decode step is supported as a Loop body with a key / value cache: ", "formula decode step");
+    using Lin = LoopBody::Lin;
+    const int64_t Ld = ((int64_t)body.inputs.size() - 3) / 2;
+    const size_t n_state = (size_t)(1 + 2 * Ld);
+    if (Ld < 1 || Ld > k::kFdMaxLayers) L.refuse("the body carries " + std::to_string(Ld) + " layers of caches, outside 1 <= Ld <= " + std::to_string(k::kFdMaxLayers));
+    const bool with_logits = body.outputs.size() == n_state + 3;
+    if (body.outputs.size() != n_state + 2 && !with_logits) L.refuse("the body must yield (cond, tok, K_1', V_1', ..., scan tok [, scan logits])");
+    if (loop.in.size() != 2 + n_state || loop.out.size() != body.outputs.size() - 1) L.refuse("the node must carry (M, cond, tok0, K_1, V_1, ...) and yield (tok, K_1, V_1, ..., tok scan [, logits scan])");
+    if (opset_ < 17) L.refuse("LayerNormalization needs opset 17");
+    const std::string &iter = body.inputs[0], &cond_in = body.inputs[1], &tok = body.inputs[2];
+    const std::string &cond_out = body.outputs[0], &tok_new = body.outputs[1];
+    if (body.outputs[n_state + 1] != tok_new) L.refuse("the first scan output must be the new token '" + tok_new + "'");
+    // trip count and condition
+    const HostTensor* mt = nullptr;
+    if (!loop.in[0].empty()) { auto it = inits_.find(loop.in[0]); if (it != inits_.end()) mt = &it->second; }
+    if (!mt || mt->dtype == DType::F32 || mt->i.size() != 1) L.refuse("the trip count M must be a constant integer scalar");
+    const int64_t M = mt->i[0];
+    if (!loop.in[1].empty()) {
+        auto it = inits_.find(loop.in[1]);
+        if (it == inits_.end() || it->second.i.size() != 1 || it->second.i[0] == 0) L.refuse("the loop condition must be absent or a constant true");
+    }
+    if (const HostTensor* ct = L.cst(cond_out)) {
+        if (ct->i.size() != 1 || ct->i[0] == 0) L.refuse("cond_out must be Identity(cond_in) or a constant true");
+    } else {
+        const OnnxNode& id = L.expect(cond_out, "Identity", "loop condition");
+        if (id.inputs.size() != 1 || id.inputs[0] != cond_in) L.bad(id, "cond_out must be Identity(cond_in)");
+    }
+    // helpers of this body
+    auto scalar_f = [&](const std::string& v, float& out) {
+        const HostTensor* t = L.cst(v);
+        if (!t || t->dtype != DType::F32 || t->f.size() != 1) return false;
+        out = t->f[0];
+        return true;
+    };
+    struct LN { std::string x; std::vector<float> g, b; float eps; };
+    auto layer_norm = [&](const std::string& v, const char* role) -> LN {
+        const OnnxNode& n = L.expect(v, "LayerNormalization", role);
+        if (n.inputs.size() != 3 || n.inputs[2].empty()) L.bad(n, "LayerNormalization needs a scale and a bias");
+        const int64_t ax = n.ai("axis", -1);
+        if (ax != -1 && ax != 1) L.bad(n, "LayerNormalization must normalise the last axis");
+        LN r;
+        r.x = n.inputs[0]; r.g = L.f32c(n, n.inputs[1], 1).f; r.b = L.f32c(n, n.inputs[2], 1).f; r.eps = n.af("epsilon", 1e-5f);
+        if (r.g.size() != r.b.size()) L.bad(n, "scale and bias lengths differ");
+        return r;
+    };
+    // is `v` the output of a lin (Gemm, MatMul by a constant, or Add of one and a constant)?
+    auto const_matmul = [&](const std::string& v) { auto it = L.producer.find(v); return it != L.producer.end() && body.nodes[it->second].op == "MatMul" && body.nodes[it->second].inputs.size() == 2 && L.cst(body.nodes[it->second].inputs[1]); };
+    auto is_lin = [&](const std::string& v) {
+        if (L.is_op(v, "Gemm") || const_matmul(v)) return true;
+        if (!L.is_op(v, "Add")) return false;
+        const OnnxNode& a = body.nodes[L.producer[v]];
+        return a.inputs.size() == 2 && ((const_matmul(a.inputs[0]) && L.cst(a.inputs[1])) || (const_matmul(a.inputs[1]) && L.cst(a.inputs[0])));
+    };
+    // v = Add(residual, lin(..)) in either order
+    auto residual = [&](const std::string& v, const char* role, std::string& res) -> Lin {
+        const OnnxNode& a = L.expect(v, "Add", role);
+        L.two(a);
+        const int li = is_lin(a.inputs[1]) ? 1 : is_lin(a.inputs[0]) ? 0 : -1;
+        if (li < 0) L.bad(a, std::string("the ") + role + " must add a Gemm or MatMul [+ Add] to the residual");
+        res = a.inputs[1 - li];
+        return L.lin(a.inputs[li], role, 1);
+    };
+    // a projection with the query scale: mode 0 none, 1 (x W^T + b) * s, 2 (x W^T) * s + b
+    auto scaled_lin = [&](const std::string& v, const char* role, int& mode, float& scale) -> Lin {
+        mode = 0; scale = 1.0f;
+        if (L.is_op(v, "Mul")) {
+            const OnnxNode& m = L.expect(v, "Mul", role);
+            L.two(m);
+            const int ci = scalar_f(m.inputs[1], scale) ? 1 : scalar_f(m.inputs[0], scale) ? 0 : -1;
+            if (ci < 0) L.bad(m, "the query scale must be a constant scalar");
+            mode = 1;
+            return L.lin(m.inputs[1 - ci], role, 1);
+        }
+        if (L.is_op(v, "Add")) {
+            const OnnxNode& a = body.nodes[L.producer[v]];
+            L.two(a);
+            const int mi = L.is_op(a.inputs[0], "Mul") ? 0 : L.is_op(a.inputs[1], "Mul") ? 1 : -1;
+            if (mi >= 0) {
+                L.used[L.producer[v]] = true;
+                const OnnxNode& m = L.expect(a.inputs[mi], "Mul", role);
+                L.two(m);
+                const int ci = scalar_f(m.inputs[1], scale) ? 1 : scalar_f(m.inputs[0], scale) ? 0 : -1;
+                if (ci < 0) L.bad(m, "the query scale must be a constant scalar");
+                Lin r = L.lin(m.inputs[1 - ci], role, 0);
+                const HostTensor& b = L.f32c(a, a.inputs[1 - mi], 1);
+                if ((int64_t)b.f.size() != r.N) L.bad(a, "bias length");
+                r.b = b.f;
+                mode = 2;
+                return r;
+            }
+        }
+        return L.lin(v, role, 1);
+    };
+    auto reshape_target = [&](const OnnxNode& n) -> std::vector<int64_t> {
+        if (n.inputs.size() < 2) L.bad(n, "Reshape needs a constant target");
+        const HostTensor* t = L.cst(n.inputs[1]);
+        if (!t || t->dtype == DType::F32 || t->i.empty()) L.bad(n, "the Reshape target must be a constant");
+        return t->i;
+    };
+    int64_t D = 0, nh = 0, dh = 0;
+    // v = Reshape(u, [B, nh, 1, dh]): returns u
+    auto split_heads = [&](const std::string& v, const char* role) -> std::string {
+        const OnnxNode& n = L.expect(v, "Reshape", role);
+        std::vector<int64_t> t = reshape_target(n);
+        if (t.size() != 4 || t[2] != 1) L.bad(n, "must reshape to [B, heads, 1, head size]");
+        int64_t a = t[1], b = t[3];
+        if (a <= 0 && b > 0 && D % b == 0) a = D / b;
+        if (b <= 0 && a > 0 && D % a == 0) b = D / a;
+        if (a <= 0 || b <= 0 || a * b != D) L.bad(n, "heads x head size must be the model width " + std::to_string(D));
+        if (nh == 0) { nh = a; dh = b; }
+        if (a != nh || b != dh) L.bad(n, "every projection must split into the same heads");
+        return n.inputs[0];
+    };
+    // v = Reshape(MatMul(Softmax(MatMul(q4, keys), -1), values), [B, D]): returns q4 / keys / values
+    auto attention = [&](const std::string& v, const char* role, std::string& q4, std::string& keys, std::string& values) {
+        const OnnxNode& rs = L.expect(v, "Reshape", role);
+        std::vector<int64_t> t = reshape_target(rs);
+        if (t.size() != 2 || (t[1] != D && t[1] != -1)) L.bad(rs, "must reshape the attention output to [B, " + std::to_string(D) + "]");
+        const OnnxNode& pv = L.expect(rs.inputs[0], "MatMul", "attention-weighted sum");
+        L.two(pv);
+        values = pv.inputs[1];
+        const OnnxNode& sm = L.expect(pv.inputs[0], "Softmax", "attention weights");
+        const int64_t ax = sm.ai("axis", -1);
+        if (ax != -1 && ax != 3) L.bad(sm, "must be Softmax over the last axis");
+        const OnnxNode& qk = L.expect(sm.inputs[0], "MatMul", "attention scores");
+        L.two(qk);
+        q4 = qk.inputs[0]; keys = qk.inputs[1];
+    };
+    // greedy token and output projection
+    const OnnxNode& am = L.expect(L.strip_casts(tok_new), "ArgMax", "next token");
+    {
+        const int64_t ax = am.ai("axis", 0);
+        if (am.inputs.size() != 1 || (ax != 1 && ax != -1) || am.ai("keepdims", 1) != 0 || am.ai("select_last_index", 0) != 0) L.bad(am, "ArgMax must be axis=1, keepdims=0, first index");
+    }
+    const std::string logits = am.inputs[0];
+    if (with_logits && body.outputs[n_state + 2] != logits) L.refuse("the second scan output must be the logits '" + logits + "' the ArgMax reads");
+    Lin lm = L.lin(logits, "output projection", -1);
+    LN lnf = layer_norm(lm.x, "final LayerNorm");
+    D = lm.K;
+    const int64_t V = lm.N;
+    if ((int64_t)lnf.g.size() != D) L.refuse("the final LayerNorm does not have the model width " + std::to_string(D));
+    struct Layer { LN ln1, ln2, ln3; Lin q, k, v, o, cq, co, f1, f2; int qm = 0, cqm = 0; float qs = 1.f, cqs = 1.f; std::string kmT, vm; };
+    std::vector<Layer> layers((size_t)Ld);
+    std::string x = lnf.x;
+    int64_t F = 0;
+    for (int64_t l = Ld - 1; l >= 0; --l) {
+        Layer& Y = layers[(size_t)l];
+        const std::string &Kin = body.inputs[(size_t)(3 + 2 * l)], &Vin = body.inputs[(size_t)(4 + 2 * l)];
+        const std::string &Kout = body.outputs[(size_t)(2 + 2 * l)], &Vout = body.outputs[(size_t)(3 + 2 * l)];
+        std::string x2, x1, x0;
+        // feed-forward
+        Y.f2 = residual(x, "feed-forward output", x2);
+        const OnnxNode& ge = L.expect(Y.f2.x, "Gelu", "feed-forward activation");
+        if (ge.as("approximate", "none") != "none") L.bad(ge, "Gelu must be approximate = none");
+        Y.f1 = L.lin(ge.inputs[0], "feed-forward input", 1);
+        Y.ln3 = layer_norm(Y.f1.x, "feed-forward LayerNorm");
+        if (Y.ln3.x != x2) L.refuse("layer " + std::to_string(l + 1) + ": the feed-forward block must normalise its own residual '" + x2 + "'");
+        // cross attention
+        Y.co = residual(x2, "cross-attention output", x1);
+        std::string q4, keys, values;
+        attention(Y.co.x, "cross-attention output", q4, keys, values);
+        for (const std::string* m : {&keys, &values})
+            if (L.producer.count(*m) || L.cst(*m) || std::find(body.inputs.begin(), body.inputs.end(), *m) != body.inputs.end()) L.refuse("layer " + std::to_string(l + 1) + ": the memory keys / values '" + *m + "' must come from the outer scope");
+        Y.kmT = keys; Y.vm = values;
+        Y.cq = scaled_lin(split_heads(q4, "cross-attention query"), "cross-attention query", Y.cqm, Y.cqs);
+        Y.ln2 = layer_norm(Y.cq.x, "cross-attention LayerNorm");
+        if (Y.ln2.x != x1) L.refuse("layer " + std::to_string(l + 1) + ": the cross-attention block must normalise its own residual '" + x1 + "'");
+        // self attention over the cache
+        Y.o = residual(x1, "self-attention output", x0);
+        attention(Y.o.x, "self-attention output", q4, keys, values);
+        const OnnxNode& kt = L.expect(keys, "Transpose", "cached keys");
+        if (kt.ais("perm") != std::vector<int64_t>{0, 1, 3, 2} || kt.inputs[0] != Kout) L.bad(kt, "must be Transpose(K', [0, 1, 3, 2]) of the new key cache '" + Kout + "'");
+        if (values != Vout) L.refuse("layer " + std::to_string(l + 1) + ": the self-attention values must be the new value cache '" + Vout + "'");
+        const OnnxNode& kcat = L.expect(Kout, "Concat", "new key cache");
+        const OnnxNode& vcat = L.expect(Vout, "Concat", "new value cache");
+        if (kcat.inputs.size() != 2 || kcat.ai("axis", 0) != 2 || kcat.inputs[0] != Kin) L.bad(kcat, "must be Concat('" + Kin + "', k, axis=2)");
+        if (vcat.inputs.size() != 2 || vcat.ai("axis", 0) != 2 || vcat.inputs[0] != Vin) L.bad(vcat, "must be Concat('" + Vin + "', v, axis=2)");
+        Y.q = scaled_lin(split_heads(q4, "self-attention query"), "self-attention query", Y.qm, Y.qs);
+        Y.k = L.lin(split_heads(kcat.inputs[1], "self-attention key"), "self-attention key", 1);
+        Y.v = L.lin(split_heads(vcat.inputs[1], "self-attention value"), "self-attention value", 1);
+        Y.ln1 = layer_norm(Y.q.x, "self-attention LayerNorm");
+        if (Y.k.x != Y.q.x || Y.v.x != Y.q.x || Y.ln1.x != x0) L.refuse("layer " + std::to_string(l + 1) + ": q, k and v must read LN1 of the block's residual '" + x0 + "'");
+        if (l == Ld - 1) F = Y.f1.N;
+        auto shp = [&](const Lin& a, int64_t N, int64_t K) { return a.N == N && a.K == K; };
+        if (!(shp(Y.q, D, D) && shp(Y.k, D, D) && shp(Y.v, D, D) && shp(Y.o, D, D) && shp(Y.cq, D, D) && shp(Y.co, D, D) && shp(Y.f1, F, D) && shp(Y.f2, D, F) &&
+              (int64_t)Y.ln1.g.size() == D && (int64_t)Y.ln2.g.size() == D && (int64_t)Y.ln3.g.size() == D))
+            L.refuse("layer " + std::to_string(l + 1) + ": the weights do not have the shapes of a decoder layer with D = " + std::to_string(D) + ", F = " + std::to_string(F));
+        x = x0;
+    }
+    // embedding: x = LN_emb(Gather(E_tok, tok) * s_emb + Gather(E_pos, i + c_pos))
+    LN lne = layer_norm(x, "embedding LayerNorm");
+    const OnnxNode& eadd = L.expect(lne.x, "Add", "token + position embedding");
+    L.two(eadd);
+    const int mi = L.is_op(eadd.inputs[0], "Mul") ? 0 : 1;
+    const OnnxNode& emul = L.expect(eadd.inputs[mi], "Mul", "scaled token embedding");
+    L.two(emul);
+    float s_emb = 1.0f;
+    const int sci = scalar_f(emul.inputs[1], s_emb) ? 1 : scalar_f(emul.inputs[0], s_emb) ? 0 : -1;
+    if (sci < 0) L.bad(emul, "the embedding scale must be a constant scalar");
+    const OnnxNode& gt = L.expect(emul.inputs[1 - sci], "Gather", "token embedding");
+    const OnnxNode& gp = L.expect(eadd.inputs[1 - mi], "Gather", "position embedding");
+    if (gt.inputs.size() != 2 || gt.ai("axis", 0) != 0 || L.strip_casts(gt.inputs[1]) != tok) L.bad(gt, "must be Gather(E_tok, tok) on axis 0");
+    if (gp.inputs.size() != 2 || gp.ai("axis", 0) != 0) L.bad(gp, "must be Gather(E_pos, i + c_pos) on axis 0");
+    const HostTensor& Et = L.f32c(gt, gt.inputs[0], 2);
+    const HostTensor& Ep = L.f32c(gp, gp.inputs[0], 2);
+    int64_t c_pos = 0;
+    {
+        const std::string pi = L.strip_casts(gp.inputs[1]);
+        if (pi != iter) {
+            const OnnxNode& pa = L.expect(pi, "Add", "position index");
+            L.two(pa);
+            const int ii = L.strip_casts(pa.inputs[0]) == iter ? 0 : L.strip_casts(pa.inputs[1]) == iter ? 1 : -1;
+            const HostTensor* c = ii < 0 ? nullptr : L.cst(pa.inputs[1 - ii]);
+            if (!c || c->dtype == DType::F32 || c->i.size() != 1) L.bad(pa, "must be Add(i, c_pos) with a constant integer c_pos");
+            c_pos = c->i[0];
+        }
+    }
+    for (int i = 0; i < (int)body.nodes.size(); ++i)
+        if (!L.used[i]) L.refuse(L.node_desc(i) + " does not fit: it is not part of the formula decode step");
+    const int64_t P = Ep.dims[0];
+    if (Et.dims[0] != V || Et.dims[1] != D || Ep.dims[1] != D || (int64_t)lne.g.size() != D || (!lm.b.empty() && (int64_t)lm.b.size() != V))
+        L.refuse("the embeddings and the output projection do not agree on V = " + std::to_string(V) + ", D = " + std::to_string(D));
+    auto cl = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, 0), 1 << 26); };
+    if (nh < 1 || !k::formula_decode_supported(cl(D), cl(nh), cl(F), cl(V), cl(Ld), cl(M), 1) || c_pos < 0 || M + c_pos > P)
+        L.refuse("D = " + std::to_string(D) + ", heads = " + std::to_string(nh) + ", F = " + std::to_string(F) + ", V = " + std::to_string(V) + ", Ld = " + std::to_string(Ld) + ", M = " + std::to_string(M) +
+                 ", c_pos = " + std::to_string(c_pos) + ", P = " + std::to_string(P) + " is outside D <= " + std::to_string(k::kFdMaxD) + ", head size <= " + std::to_string(k::kFdMaxDh) + ", F <= " +
+                 std::to_string(k::kFdMaxF) + ", 2 <= V < 2^24, 1 <= M <= " + std::to_string(k::kFdMaxM) + ", M + c_pos <= P");
+    // initial state: every cache starts empty, and nothing else may read it or the final caches
+    auto producer_of = [&](const std::string& v) -> const GNode* {
+        for (const GNode& n : outer_nodes) for (auto& o : n.out) if (o == v) return &n;
+        return nullptr;
+    };
+    for (size_t c = 3; c < loop.in.size(); ++c) {
+        const std::string& nm = loop.in[c];
+        bool empty = false;
+        auto it = inits_.find(nm);
+        if (it != inits_.end()) empty = it->second.dims.size() == 4 && it->second.dims[2] == 0;
+        else if (const GNode* cs = producer_of(nm)) {
+            const GNode* cat = cs->op == "ConstantOfShape" && cs->in.size() == 1 ? producer_of(cs->in[0]) : nullptr;
+            if (cat && cat->op == "Concat" && cat->in.size() == 4) {
+                auto z = inits_.find(cat->in[2]);
+                empty = z != inits_.end() && z->second.dtype != DType::F32 && z->second.i.size() == 1 && z->second.i[0] == 0;
+            }
+        }
+        if (!empty) L.refuse("the initial cache '" + nm + "' must be empty: an initializer with dims[2] == 0, or ConstantOfShape over a Concat whose third element is the constant 0");
+        int readers = 0;
+        for (const GNode& n : outer_nodes) for (auto& s : n.in) if (s == nm) ++readers;
+        if (readers != 1 || std::find(output_names_.begin(), output_names_.end(), nm) != output_names_.end()) L.refuse("the initial cache '" + nm + "' is read outside the Loop");
+        dropped_inputs.push_back(nm);
+    }
+    for (size_t c = 1; c < n_state; ++c) {
+        const std::string& nm = loop.out[c];
+        if (nm.empty()) continue;
+        bool read = std::find(output_names_.begin(), output_names_.end(), nm) != output_names_.end();
+        for (const GNode& n : outer_nodes) for (auto& s : n.in) if (s == nm) read = true;
+        if (read) L.refuse("the final cache '" + nm + "' is read by the rest of the graph: the caches are not produced");
+    }
+    // constants in the kernels' layout (kernels.h: FormulaDecodeP): matrix rows padded to a multiple of four floats
+    const std::string pfx = "fd::" + loop.out[n_state] + "::";
+    auto put = [&](const std::string& nm, std::vector<int64_t> dims, std::vector<float> v) {
+        HostTensor t; t.name = pfx + nm; t.dtype = DType::F32; t.dims = std::move(dims); t.f = std::move(v);
+        const std::string key = t.name;
+        inits_[key] = std::move(t);
+        return key;
+    };
+    auto padded = [](const std::vector<const Lin*>& mats) {
+        const int64_t K = mats[0]->K, Kp = (K + 3) / 4 * 4;
+        std::vector<float> o;
+        for (const Lin* m : mats)
+            for (int64_t r = 0; r < m->N; ++r)
+                for (int64_t c = 0; c < Kp; ++c) o.push_back(c < K ? m->w[(size_t)(r * K + c)] : 0.0f);
+        return o;
+    };
+    auto cat3 = [](const std::vector<float>& a, const std::vector<float>& b, const std::vector<float>& c) { std::vector<float> o(a); o.insert(o.end(), b.begin(), b.end()); o.insert(o.end(), c.begin(), c.end()); return o; };
+    const int64_t Dp = (D + 3) / 4 * 4, Fp = (F + 3) / 4 * 4;
+    dec_out = GNode();
+    dec_out.op = "FormulaDecode";
+    dec_out.in = {loop.in[2]};
+    for (auto& Y : layers) { dec_out.in.push_back(Y.kmT); dec_out.in.push_back(Y.vm); }
+    dec_out.in.push_back(put("e_tok", {V, D}, Et.f));
+    dec_out.in.push_back(put("e_pos", {P, D}, Ep.f));
+    dec_out.in.push_back(put("lne_g", {D}, lne.g));
+    dec_out.in.push_back(put("lne_b", {D}, lne.b));
+    auto iattr = [&](const std::string& k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; dec_out.attrs[k] = a; };
+    auto fattr = [&](const std::string& k, float v) { Attr a; a.kind = Attr::F; a.f = v; dec_out.attrs[k] = a; };
+    for (size_t l = 0; l < layers.size(); ++l) {
+        Layer& Y = layers[l];
+        const std::string s = "l" + std::to_string(l) + "_";
+        dec_out.in.push_back(put(s + "ln1_g", {D}, Y.ln1.g)); dec_out.in.push_back(put(s + "ln1_b", {D}, Y.ln1.b));
+        dec_out.in.push_back(put(s + "w_qkv", {3 * D, Dp}, padded({&Y.q, &Y.k, &Y.v}))); dec_out.in.push_back(put(s + "b_qkv", {3 * D}, cat3(Y.q.b, Y.k.b, Y.v.b)));
+        dec_out.in.push_back(put(s + "w_o", {D, Dp}, padded({&Y.o}))); dec_out.in.push_back(put(s + "b_o", {D}, Y.o.b));
+        dec_out.in.push_back(put(s + "ln2_g", {D}, Y.ln2.g)); dec_out.in.push_back(put(s + "ln2_b", {D}, Y.ln2.b));
+        dec_out.in.push_back(put(s + "w_cq", {D, Dp}, padded({&Y.cq}))); dec_out.in.push_back(put(s + "b_cq", {D}, Y.cq.b));
+        dec_out.in.push_back(put(s + "w_co", {D, Dp}, padded({&Y.co}))); dec_out.in.push_back(put(s + "b_co", {D}, Y.co.b));
+        dec_out.in.push_back(put(s + "ln3_g", {D}, Y.ln3.g)); dec_out.in.push_back(put(s + "ln3_b", {D}, Y.ln3.b));
+        dec_out.in.push_back(put(s + "w_1", {F, Dp}, padded({&Y.f1}))); dec_out.in.push_back(put(s + "b_1", {F}, Y.f1.b));
+        dec_out.in.push_back(put(s + "w_2", {D, Fp}, padded({&Y.f2}))); dec_out.in.push_back(put(s + "b_2", {D}, Y.f2.b));
+        fattr(s + "eps1", Y.ln1.eps); fattr(s + "eps2", Y.ln2.eps); fattr(s + "eps3", Y.ln3.eps);
+        iattr(s + "q_mode", Y.qm); fattr(s + "q_scale", Y.qs); iattr(s + "cq_mode", Y.cqm); fattr(s + "cq_scale", Y.cqs);
+        Y = Layer();   // (the repacked copies are in inits_ now)
+    }
+    dec_out.in.push_back(put("lnf_g", {D}, lnf.g));
+    dec_out.in.push_back(put("lnf_b", {D}, lnf.b));
+    dec_out.in.push_back(put("w_lm", {V, Dp}, padded({&lm})));
+    if (!lm.b.empty()) dec_out.in.push_back(put("b_lm", {V}, lm.b));
+    dec_out.out = {loop.out[0], loop.out[n_state]};
+    if (with_logits) dec_out.out.push_back(loop.out[n_state + 1]);
+    iattr("steps", M); iattr("layers", Ld); iattr("width", D); iattr("heads", nh); iattr("ffn", F); iattr("vocab", V); iattr("positions", P); iattr("c_pos", c_pos);
+    iattr("lm_bias", lm.b.empty() ? 0 : 1);
+    fattr("s_emb", s_emb); fattr("eps_e", lne.eps); fattr("eps_f", lnf.eps);
+}
+
 void Engine::rewrite_graph(OnnxModel& m) {
     inits_ = std::move(m.initializers);
     std::vector<GNode> nodes;
@@ -402,20 +756,54 @@ void Engine::rewrite_graph(OnnxModel& m) {
     };
     auto is_init = [&](const std::string& s) { return inits_.count(s) != 0; };
 
-    // ---- pass 0: Loop whose body is the SLANet structure head's step (PaddleOCR SLAHead._decode: AttentionGRUCell + GRUCell + both
-    // output heads, greedy feedback of the arg max)  ->  Linear (the loop-invariant projection of the features) + ONE SLADecode node.
-    // No other Loop is executed: there is no generic sub-graph executor, and anything that is not this body, in one of the spellings
-    // match_sla_loop tolerates, is refused with the name of the first body node that did not fit.
+    // ---- pass 0: Loop.  There is no generic sub-graph executor: two bodies are recognised, by their interface, and replaced by fused operators.
+    //   4 inputs / 5 outputs: the SLANet structure head's step (PaddleOCR SLAHead._decode: AttentionGRUCell + GRUCell + both output heads, greedy feedback
+    //     of the arg max)  ->  Linear (the loop-invariant projection of the features) + ONE SLADecode node (match_sla_loop)
+    //   3 + 2 Ld inputs: the greedy step of a transformer decoder with a key / value cache (PP-FormulaNet)  ->  ONE FormulaDecode node; the empty initial
+    //     caches and their producers leave the graph (match_formula_loop)
+    // Anything else, or a body that is not one of these in a spelling its matcher tolerates, is refused with the name of the first body node that did not fit.
     {
         std::vector<GNode> out;
-        for (auto& n : nodes) {
-            if (n.op != "Loop") { out.push_back(std::move(n)); continue; }
-            GNode lin, dec;
-            match_sla_loop(n, lin, dec);
-            out.push_back(std::move(lin));
-            out.push_back(std::move(dec));
+        std::vector<std::string> dropped;
+        for (size_t ni = 0; ni < nodes.size(); ++ni) {
+            GNode& n = nodes[ni];
+            if (n.op != "Loop") { out.push_back(n); continue; }
+            auto bit = n.attrs.find("body");
+            const OnnxModel* body = bit != n.attrs.end() && bit->second.kind == Attr::G && bit->second.g ? bit->second.g.get() : nullptr;
+            if (!body || (body->inputs.size() == 4 && body->outputs.size() == 5)) {
+                GNode lin, dec;
+                match_sla_loop(n, lin, dec);
+                out.push_back(std::move(lin));
+                out.push_back(std::move(dec));
+            } else if (body->inputs.size() >= 5 && body->inputs.size() % 2 == 1) {
+                GNode dec;
+                match_formula_loop(n, nodes, dec, dropped);
+                out.push_back(std::move(dec));
+            } else {
+                fail(OAR_UNSUPPORTED_OP, "Loop (" + (n.out.empty() ? std::string("?") : n.out[0]) + "): a body with " + std::to_string(body->inputs.size()) + " inputs and " +
+                                             std::to_string(body->outputs.size()) + " outputs is not supported: only the SLA decode step (i, cond, h, pre -> cond, h, pre, logits, loc) and the formula decode " +
+                                             "step (i, cond, tok, K_1, V_1, ... -> cond, tok, K_1', V_1', ..., tok [, logits]) are executed as Loop bodies");
+            }
         }
         nodes.swap(out);
+        // the empty initial caches: their ConstantOfShape goes, and its shape Concat when nothing else reads it (the planner never sees a zero-extent tensor)
+        for (int round = 0; round < 2 && !dropped.empty(); ++round) {
+            std::vector<std::string> next;
+            for (const std::string& nm : dropped) {
+                bool read = graph_outs.count(nm) != 0;
+                for (const GNode& n : nodes) for (auto& s : n.in) if (s == nm) read = true;
+                if (read) continue;
+                for (size_t i = 0; i < nodes.size(); ++i) {
+                    if (std::find(nodes[i].out.begin(), nodes[i].out.end(), nm) == nodes[i].out.end()) continue;
+                    if (nodes[i].op == "ConstantOfShape" || (round == 1 && nodes[i].op == "Concat")) {
+                        if (round == 0) next.insert(next.end(), nodes[i].in.begin(), nodes[i].in.end());
+                        nodes.erase(nodes.begin() + (long)i);
+                    }
+                    break;
+                }
+            }
+            dropped.swap(next);
+        }
     }
 
     // ---- pass 1: fold BatchNormalization into the producing Conv / ConvTranspose
@@ -3391,6 +3779,72 @@ struct Planner {
         }, 2.0 * macs * M * B, 4.0 * (macs + 3.0 * H + V + L) * M * B);
     }
 
+    // The formula decode head (rewrite pass 0): M steps of 8 Ld + 2 short launches per chunk of 16 images (formula_decode.hip).  Nothing is allocated, read back or
+    // synchronised between steps, so the plan stays capturable; all `steps` steps run (exact Loop semantics with a constant-true condition), the host stops at eos.
+    void op_formula_decode(const GNode& n) {
+        const int64_t M = n.ai("steps", 0), Ld = n.ai("layers", 0), D = n.ai("width", 0), nh = n.ai("heads", 1), F = n.ai("ffn", 0), V = n.ai("vocab", 0), P = n.ai("positions", 0);
+        const int64_t dh = D / nh;
+        const std::string& name = n.out[1];
+        TInfo tok0 = get(n.in[0]);
+        const int64_t B = numel(tok0.dims);
+        OAR_CHECK(B >= 1 && B < (1 << 20), OAR_SHAPE_MISMATCH, "FormulaDecode: batch out of range at " + name);
+        OAR_CHECK(tok0.host_int ? !tok0.host_f : tok0.is_int, OAR_UNSUPPORTED_OP, "FormulaDecode: the start tokens must be an integer tensor at " + name);
+        Loc t0 = tok0.host_int ? host_to_device(n.in[0], tok0) : to_native_loc(tok0);
+        std::vector<Loc> mem;
+        int64_t S = 0;
+        for (int64_t l = 0; l < Ld; ++l) {
+            TInfo kt = get(n.in[(size_t)(1 + 2 * l)]), vm = get(n.in[(size_t)(2 + 2 * l)]);
+            OAR_CHECK(!kt.host_int && !vm.host_int && kt.dims.size() == 4 && vm.dims.size() == 4, OAR_SHAPE_MISMATCH, "FormulaDecode: the memory keys / values must be rank-4 tensors at " + name);
+            if (l == 0) S = kt.dims[3];
+            OAR_CHECK(S >= 1 && S <= k::kFdMaxS, OAR_UNSUPPORTED_OP, "Loop (" + name + "): S = " + std::to_string(S) + " is outside 1 <= S <= " + std::to_string(k::kFdMaxS));
+            OAR_CHECK(kt.dims == (std::vector<int64_t>{B, nh, dh, S}) && vm.dims == (std::vector<int64_t>{B, nh, S, dh}), OAR_SHAPE_MISMATCH,
+                      "FormulaDecode: layer " + std::to_string(l + 1) + " needs KmT [B, " + std::to_string(nh) + ", " + std::to_string(dh) + ", S] and Vm [B, " + std::to_string(nh) + ", S, " + std::to_string(dh) + "] at " + name);
+            mem.push_back(to_native_loc(kt));
+            mem.push_back(to_native_loc(vm));
+        }
+        k::FormulaDecodeP p{};
+        p.B = (int)B; p.D = (int)D; p.nh = (int)nh; p.F = (int)F; p.V = (int)V; p.Ld = (int)Ld; p.S = (int)S; p.M = (int)M; p.P = (int)P; p.c_pos = (int)n.ai("c_pos", 0);
+        p.s_emb = n.af("s_emb", 1.0f); p.eps_e = n.af("eps_e", 1e-5f); p.eps_f = n.af("eps_f", 1e-5f);
+        size_t ci = (size_t)(1 + 2 * Ld);
+        auto cw = [&]() -> const float* {
+            const TInfo& t = get(n.in[ci++]);
+            OAR_CHECK(t.ht && t.loc.kind == Loc::CONST, OAR_INTERNAL, "FormulaDecode: weight is not a constant");
+            return t.loc.cptr;
+        };
+        p.e_tok = cw(); p.e_pos = cw(); p.lne_g = cw(); p.lne_b = cw();
+        for (int64_t l = 0; l < Ld; ++l) {
+            k::FdLayerP& Y = p.layer[l];
+            const std::string s = "l" + std::to_string(l) + "_";
+            Y.ln1_g = cw(); Y.ln1_b = cw(); Y.w_qkv = cw(); Y.b_qkv = cw(); Y.w_o = cw(); Y.b_o = cw(); Y.ln2_g = cw(); Y.ln2_b = cw(); Y.w_cq = cw(); Y.b_cq = cw(); Y.w_co = cw(); Y.b_co = cw();
+            Y.ln3_g = cw(); Y.ln3_b = cw(); Y.w_1 = cw(); Y.b_1 = cw(); Y.w_2 = cw(); Y.b_2 = cw();
+            Y.eps1 = n.af((s + "eps1").c_str(), 1e-5f); Y.eps2 = n.af((s + "eps2").c_str(), 1e-5f); Y.eps3 = n.af((s + "eps3").c_str(), 1e-5f);
+            Y.q_scale_mode = (int)n.ai((s + "q_mode").c_str(), 0); Y.q_scale = n.af((s + "q_scale").c_str(), 1.0f);
+            Y.cq_scale_mode = (int)n.ai((s + "cq_mode").c_str(), 0); Y.cq_scale = n.af((s + "cq_scale").c_str(), 1.0f);
+        }
+        p.lnf_g = cw(); p.lnf_b = cw(); p.w_lm = cw();
+        p.b_lm = n.ai("lm_bias", 0) ? cw() : nullptr;
+        OAR_CHECK(k::formula_decode_supported((int)D, (int)nh, (int)F, (int)V, (int)Ld, (int)M, (int)S), OAR_UNSUPPORTED_OP, "Loop (" + name + "): shape outside the formula decode kernels' limits");
+        TInfo& ty = new_out(n.out[1], {M, B}, Layout::NATIVE);
+        ty.is_int = true;
+        const Loc tl = ty.loc;
+        Loc ll;
+        const bool with_logits = n.out.size() > 2 && !n.out[2].empty();
+        if (with_logits) ll = new_out(n.out[2], {M, B, V}, Layout::NATIVE).loc;
+        if (!n.out[0].empty()) alias_out(n.out[0], get(n.out[1]), {B}, Layout::NATIVE, (M - 1) * B * 4);   // the final token: the last row of the scan
+        Loc ws = alloc_temp(k::formula_decode_ws_floats((int)B, (int)D, (int)F, (int)V, (int)Ld, (int)M) * 4);
+        const int64_t chunks = (B + k::kFdChunk - 1) / k::kFdChunk;
+        const double Dp = (double)((D + 3) / 4 * 4), Fp = (double)((F + 3) / 4 * 4);
+        const double w_floats = Ld * (6.0 * D * Dp + F * Dp + D * Fp + 15.0 * D + F) + V * Dp + V + 4.0 * D;          // weights one step streams
+        const double macs = Ld * (6.0 * D * D + 2.0 * F * D + (double)S * D * 2.0 + (double)(M + 1) * D) + (double)V * D;   // per step and image (self attention at its mean length)
+        step([=](const RunCtx& c) {
+            k::FormulaDecodeP q = p;
+            q.tok0 = c.at(t0);
+            for (int l = 0; l < q.Ld; ++l) { q.layer[l].kmT = c.at(mem[(size_t)(2 * l)]); q.layer[l].vm = c.at(mem[(size_t)(2 * l + 1)]); }
+            q.ws = c.mut(ws); q.tokens = c.mut(tl); q.logits = with_logits ? c.mut(ll) : nullptr;
+            k::formula_decode(c.s, q);
+        }, 2.0 * macs * M * B, 4.0 * (w_floats * chunks + (double)B * (2.0 * Ld * S * D + (with_logits ? V : 0))) * M);
+    }
+
     // Gather with a tensor of indices: y = x[..., idx, ...] along `axis`
     void op_gather_device(const GNode& n) {
         TInfo x = get(n.in[0]), idx = get(n.in[1]);
@@ -3896,7 +4350,7 @@ struct Planner {
     }
     static bool reads_host_values(const std::string& op) {
         static const std::set<std::string> s = {"Add", "Sub", "Mul", "Div", "Pow", "PRelu", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Where", "Reshape", "Squeeze", "Unsqueeze",
-                                                "Slice", "Gather", "GatherND", "GatherElements", "Concat", "Identity", "Cast", "ConstantOfShape", "Shape", "Range", "SLADecode"};
+                                                "Slice", "Gather", "GatherND", "GatherElements", "Concat", "Identity", "Cast", "ConstantOfShape", "Shape", "Range", "SLADecode", "FormulaDecode"};
         return s.count(op) != 0;
     }
     std::string device_shadow(const std::string& name) {
@@ -4004,6 +4458,7 @@ struct Planner {
         if (op == "Softmax") return op_softmax(n);
         if (op == "Attention") return op_attention(n);
         if (op == "SLADecode") return op_sla_decode(n);
+        if (op == "FormulaDecode") return op_formula_decode(n);
         if (op == "SEGate") return op_se_gate(n);
         if (op == "DSBlock") return op_dsblock(n);
         if (op == "LayerNormalization") return op_layernorm(n);
@@ -4084,7 +4539,7 @@ const std::set<std::string>& Engine::supported_ops() {
         "ReduceMean", "GridSample", "Pad", "GlobalAveragePool", "AveragePool", "MaxPool", "Resize", "Concat", "Reshape", "Flatten", "Squeeze", "Unsqueeze",
         "Transpose", "Split", "Slice", "Gather", "Gemm", "MatMul", "Softmax", "LayerNormalization", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Not",
         "Floor", "Ceil", "Round", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "Expand", "Tile", "Where", "ConstantOfShape", "Range", "ArgMax", "ArgMin",
-        "TopK", "GatherND", "GatherElements", "Loop"};   // (Loop: the SLA decode step only, see match_sla_loop)
+        "TopK", "GatherND", "GatherElements", "Loop"};   // (Loop: the SLA decode step and the formula decode step only, see match_sla_loop / match_formula_loop)
     return ops;
 }
 

@@ -131,6 +131,9 @@ class Engine {
     friend struct Planner;
     void rewrite_graph(OnnxModel& m);
     void match_sla_loop(const GNode& loop, GNode& linear, GNode& decode);   // a Loop whose body is the SLA decode step -> Linear + SLADecode; throws OAR_UNSUPPORTED_OP otherwise
+    // a Loop whose body is the greedy step of a transformer decoder with a key / value cache -> FormulaDecode; `dropped_inputs` receives the (empty) initial caches,
+    // which leave the graph; throws OAR_UNSUPPORTED_OP otherwise
+    void match_formula_loop(const GNode& loop, const std::vector<GNode>& outer_nodes, GNode& decode, std::vector<std::string>& dropped_inputs);
     const float* upload_const(const std::string& key, const std::vector<float>& v);
 
     int device_ = 0;

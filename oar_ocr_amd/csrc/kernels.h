@@ -190,6 +190,31 @@ struct SlaDecodeP {
 bool sla_decode_supported(int HW, int C, int H, int V, int L, int M);
 size_t sla_decode_lds_bytes(int HW, int C, int H, int V);
 void sla_decode(hipStream_t s, const SlaDecodeP& p);
+// formula_decode.hip: the greedy decode of a PP-FormulaNet-style head (pre-norm transformer decoder with a key / value cache), `M` steps of
+// 8 Ld + 2 short launches each per chunk of <= kFdChunk images (no grid-wide barrier; see the file's header for the chain).
+//   tok0 [B] (f32-coded start token); e_tok [V][D], e_pos [P][D]; per layer the matrices with rows padded to a multiple of four floats:
+//   w_qkv [3D][Dp] = Wq ; Wk ; Wv with b_qkv [3D], w_o / w_cq / w_co [D][Dp], w_1 [F][Dp], w_2 [D][Fp]; kmT [B][nh][dh][S], vm [B][nh][S][dh];
+//   w_lm [V][Dp], b_lm [V] or null.  q_scale_mode / cq_scale_mode: 0 none, 1 (x W^T + b) * s, 2 (x W^T) * s + b -- where the graph had the Mul.
+//   -> tokens [M][B] (f32-coded), logits [M][B][V] when not null.  ws: formula_decode_ws_floats(...) floats of scratch (caches [l][k|v][b][nh][M][dh] + rows).
+constexpr int kFdMaxD = 1024, kFdMaxDh = 128, kFdMaxF = 4096, kFdMaxLayers = 12, kFdMaxV = 1 << 24, kFdMaxM = 4096, kFdMaxS = 4096, kFdChunk = 16;
+struct FdLayerP {
+    const float *ln1_g, *ln1_b, *w_qkv, *b_qkv, *w_o, *b_o, *ln2_g, *ln2_b, *w_cq, *b_cq, *w_co, *b_co, *ln3_g, *ln3_b, *w_1, *b_1, *w_2, *b_2;
+    float eps1, eps2, eps3, q_scale, cq_scale;
+    int q_scale_mode, cq_scale_mode;
+    const float *kmT, *vm;
+};
+struct FormulaDecodeP {
+    int B, D, nh, F, V, Ld, S, M, P, c_pos;
+    float s_emb, eps_e, eps_f;
+    const float *tok0, *e_tok, *e_pos, *lne_g, *lne_b, *lnf_g, *lnf_b, *w_lm, *b_lm;
+    FdLayerP layer[kFdMaxLayers];
+    float *ws, *tokens, *logits;
+};
+bool formula_decode_supported(int D, int nh, int F, int V, int Ld, int M, int S);
+int formula_decode_lm_workgroups(int V);          // (value, index) partials per image of the arg max
+int formula_decode_launches_per_step(int Ld);     // 8 Ld + 2, per chunk of kFdChunk images
+size_t formula_decode_ws_floats(int B, int D, int F, int V, int Ld, int M);
+void formula_decode(hipStream_t s, const FormulaDecodeP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

@@ -174,13 +174,16 @@ class OverallOCR:
 
     det / rec / text_line_orientation are `api.TextDetectionPredictor`, `api.TextRecognitionPredictor` and (optional)
     `api.ImageClassifier(input_hw=(80, 160), resize_short=0)`; `formula_recognition` says whether the structure pipeline
-    has a formula recogniser attached (only then are formula regions masked before detection, structure.rs:2228-2241)."""
+    has a formula recogniser attached (only then are formula regions masked before detection, structure.rs:2228-2241).
+    `formula_recognizer` (a `formula.FormulaRecognitionPredictor`, or anything with its `predict` / `recommended_batch_size`) attaches one: masking is
+    then on, and `recognize_formulas` turns the formula regions into LaTeX."""
 
     def __init__(self, det, rec, text_line_orientation=None, region_batch_size: Optional[int] = None, formula_recognition: bool = False,
-                 image_batch_size: Optional[int] = None, seal_text_detection: bool = False):
+                 image_batch_size: Optional[int] = None, seal_text_detection: bool = False, formula_recognizer=None):
         self.det, self.rec, self.line_ori = det, rec, text_line_orientation
         self.region_batch_size = region_batch_size
-        self.formula_recognition = formula_recognition
+        self.formula_recognizer = formula_recognizer
+        self.formula_recognition = formula_recognition or formula_recognizer is not None
         self.image_batch_size = image_batch_size          # pipeline.image_batch_size (cross-page detection batches)
         self.seal_text_detection = seal_text_detection    # a seal detector is attached: the cross-page path stands down (structure.rs:2874-2878)
 
@@ -195,6 +198,38 @@ class OverallOCR:
             texts.extend(r.texts)
             scores.extend(r.scores)
         return texts, scores
+
+    def recognize_formulas(self, page: np.ndarray, layout_elements: Sequence[LayoutElement]) -> list:
+        """`OARStructure::recognize_formulas` (src/oarocr/structure.rs:1952-2045) -> [formula.FormulaResult]: the formula-typed elements are cropped by their
+        bounding boxes (a failed crop drops the element), recognised in batches of the recognizer's batch size, and a result whose box has a non-positive
+        width or height is dropped.  Without a recognizer: nothing."""
+        from .formula import FormulaResult
+        if self.formula_recognizer is None:
+            return []
+        page = np.ascontiguousarray(page, np.uint8)
+        crops, bboxes = [], []
+        for e in layout_elements:
+            if e.element_type not in FORMULA_TYPES:
+                continue
+            c = crop_bounding_box(page, e.bbox)
+            if c is not None:
+                crops.append(c)
+                bboxes.append(np.asarray(e.bbox, np.float32).reshape(-1, 2).copy())
+        if not crops:
+            return []
+        bs = max(int(self.formula_recognizer.recommended_batch_size()), 1)
+        latex, scores = [], []
+        for s in range(0, len(crops), bs):
+            r = self.formula_recognizer.predict(crops[s:s + bs])
+            latex.extend(r.formulas)
+            scores.extend(r.scores)
+        out = []
+        for box, text, score in zip(bboxes, latex, scores):
+            x0, y0, x1, y1 = aabb(box)
+            if F(x1 - x0) <= 0 or F(y1 - y0) <= 0:
+                continue
+            out.append(FormulaResult(bbox=box, latex=text, confidence=float(score) if score is not None else 0.0))
+        return out
 
     def run(self, page: np.ndarray, layout_elements: Sequence[LayoutElement], region_blocks: Optional[Sequence[RegionBlock]] = None) -> List[api.TextRegion]:
         page = np.ascontiguousarray(page, np.uint8)

@@ -983,3 +983,196 @@ def build_slanet(C=96, H=256, V=50, L=8, M=501, image_shape=(64, 64), seed=0, he
     g.add_output("h_last", ["B", H])
     g.add_output("pre_last", ["B"], INT64)
     return g.model(), {"params": g.n_params, "weights": w, "C": C, "H": H, "V": V, "L": L, "M": M}
+
+
+# ---------------------------------------------------------------------------------------------- formula recognition: PP-FormulaNet
+FORMULA_LAYER_NAMES = ("ln1_g", "ln1_b", "wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln2_g", "ln2_b", "wcq", "bcq", "wck", "bck", "wcv", "bcv", "wco", "bco",
+                       "ln3_g", "ln3_b", "w1", "b1", "w2", "b2")
+
+
+def formula_weights(D, nh, F, V, Ld, P, seed=0):
+    """f32 weights of one PP-FormulaNet-style head (an MBart-order, pre-norm transformer decoder: self attention over a key / value cache, cross attention
+    over the encoder memory, GELU feed-forward; greedy feedback of the arg max), well conditioned for a free-running decode: matrices U(-1, 1) / sqrt(fan_in),
+    biases a tenth of that, LayerNorm scales 1 + 0.1 U and biases 0.1 U; then the query / key projections x2 (attention that is not uniform), the position
+    table x1.5 against a unit token table (the input changes every step even when the token repeats, so the emitted token keeps changing), and the output
+    projection x6 (top-1 / top-2 logit gaps far above f32 rounding).  Every block sits behind a LayerNorm, so no gain here makes the recurrence chaotic the way
+    a recurrent GRU gain does (sla_weights): f32 and f64 agree to ~1e-6 of the logits.  Scalars: s_emb (the embedding scale), c_pos (MBart's position offset 2),
+    q_scale = dh^-0.5, eps."""
+    rng = np.random.default_rng(seed)
+    u = lambda *s, k, g=1.0: ((rng.random(s) * 2.0 - 1.0) * (g / np.sqrt(k))).astype(np.float32)
+    ln = lambda: ((1.0 + 0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32), (0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32))
+    w = {"e_tok": rng.standard_normal((V, D)).astype(np.float32), "e_pos": (1.5 * rng.standard_normal((P, D))).astype(np.float32)}
+    w["lne_g"], w["lne_b"] = ln()
+    for l in range(Ld):
+        p = f"l{l}_"
+        w[p + "ln1_g"], w[p + "ln1_b"] = ln()
+        w[p + "ln2_g"], w[p + "ln2_b"] = ln()
+        w[p + "ln3_g"], w[p + "ln3_b"] = ln()
+        for nm, rows, cols, g in (("q", D, D, 2.0), ("k", D, D, 2.0), ("v", D, D, 1.0), ("o", D, D, 1.0), ("cq", D, D, 2.0), ("ck", D, D, 2.0), ("cv", D, D, 1.0), ("co", D, D, 1.0),
+                                  ("1", F, D, 1.0), ("2", D, F, 1.0)):
+            w[p + "w" + nm] = u(rows, cols, k=cols, g=g)
+            w[p + "b" + nm] = u(rows, k=cols, g=0.1 * g)
+    w["lnf_g"], w["lnf_b"] = ln()
+    w["w_lm"] = u(V, D, k=D, g=6.0)
+    w["b_lm"] = u(V, k=D, g=0.6)
+    w = {k: np.ascontiguousarray(v, np.float32) for k, v in w.items()}
+    w.update(s_emb=float(np.float32(np.sqrt(D))), c_pos=2, q_scale=float(np.float32((D // nh) ** -0.5)), eps=1e-5, nh=nh, Ld=Ld)
+    return w
+
+
+def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logits=True, outer=None):
+    """The Loop body of the formula head, one greedy step: inputs (i, cond, tok, K_1, V_1, ...), outputs (cond, tok_new, K_1', V_1', ..., scan tok_new
+    [, scan logits]); KmT_l / Vm_l are read from the outer scope.  spelling "gemm": Gemm(transB=1) with the weights as body initializers; "matmul": MatMul with
+    the transposed weight + Add (some operands commuted), the weights as initializers of `outer`.  q_scale: where the query scale stands -- "after" the bias
+    Add, "before" it (matmul spelling only), or "folded" (no Mul: the caller has scaled Wq / bq)."""
+    from .onnx_writer import BOOL, INT64
+    V, D = w["e_tok"].shape
+    nh, Ld = w["nh"], w["Ld"]
+    dh = D // nh
+    b = GraphBuilder("formula_step")
+    b.add_input("fd_i", [], INT64)
+    b.add_input("fd_cond_in", [], BOOL)
+    b.add_input("fd_tok", [B], INT64)
+    for l in range(Ld):
+        b.add_input(f"fd_K{l}", [B, nh, "t", dh])
+        b.add_input(f"fd_V{l}", [B, nh, "t", dh])
+    gemm = spelling == "gemm"
+    store = b if gemm else outer
+    c = lambda arr, p="c": b.init(np.asarray(arr), "fd_" + p)
+    W = lambda nm: store.init(w[nm], "fd_" + nm)
+    qs = c(np.array(w["q_scale"], np.float32), "qscale")
+
+    def lin(x, wn, bn, scale=False, outputs=None):
+        if gemm:
+            y = b.op("Gemm", [x, W(wn), W(bn)], outputs=None if scale else outputs, transB=1)
+            return b.op("Mul", [y, qs], outputs=outputs) if scale else y
+        y = b.op("MatMul", [x, store.init(np.ascontiguousarray(w[wn].T), "fd_" + wn + "_t")])
+        if scale and q_scale == "before":
+            return b.op("Add", [W(bn), b.op("Mul", [qs, y])], outputs=outputs)
+        y = b.op("Add", [y, W(bn)], outputs=None if scale else outputs)
+        return b.op("Mul", [qs, y], outputs=outputs) if scale else y
+
+    ln = lambda x, nm: b.op("LayerNormalization", [x, W(nm + "_g"), W(nm + "_b")], axis=-1, epsilon=float(w["eps"]))
+    res = lambda x, y: b.op("Add", [x, y]) if gemm else b.op("Add", [y, x])
+    heads = c(np.array([0, nh, 1, dh], np.int64), "heads")
+    flat = c(np.array([0, D] if gemm else [0, -1], np.int64), "flat")
+    scaled = q_scale != "folded"
+
+    emb = b.op("Mul", [b.op("Gather", [W("e_tok"), "fd_tok"], axis=0), c(np.array(w["s_emb"], np.float32), "s_emb")])
+    pos = b.op("Gather", [W("e_pos"), b.op("Add", ["fd_i", c(np.array(w["c_pos"], np.int64), "c_pos")])], axis=0)
+    x = ln(b.op("Add", [emb, pos]), "lne")
+    for l in range(Ld):
+        p = f"l{l}_"
+        y = ln(x, p + "ln1")
+        q = b.op("Reshape", [lin(y, p + "wq", p + "bq", scale=scaled), heads])
+        kk = b.op("Reshape", [lin(y, p + "wk", p + "bk"), heads])
+        vv = b.op("Reshape", [lin(y, p + "wv", p + "bv"), heads])
+        b.op("Concat", [f"fd_K{l}", kk], outputs=[f"fd_K{l}_new"], axis=2)
+        b.op("Concat", [f"fd_V{l}", vv], outputs=[f"fd_V{l}_new"], axis=2)
+        a = b.op("Softmax", [b.op("MatMul", [q, b.op("Transpose", [f"fd_K{l}_new"], perm=[0, 1, 3, 2])])], axis=-1)
+        o = b.op("Reshape", [b.op("MatMul", [a, f"fd_V{l}_new"]), flat])
+        x = res(x, lin(o, p + "wo", p + "bo"))
+        y = ln(x, p + "ln2")
+        qc = b.op("Reshape", [lin(y, p + "wcq", p + "bcq", scale=scaled), heads])
+        a = b.op("Softmax", [b.op("MatMul", [qc, f"fd_KmT{l}"])], axis=-1)
+        oc = b.op("Reshape", [b.op("MatMul", [a, f"fd_Vm{l}"]), flat])
+        x = res(x, lin(oc, p + "wco", p + "bco"))
+        y = ln(x, p + "ln3")
+        h = lin(y, p + "w1", p + "b1")
+        h = b.op("Gelu", [h], approximate="none") if act == "Gelu" else b.op(act, [h])
+        x = res(x, lin(h, p + "w2", p + "b2"))
+    lin(ln(x, "lnf"), "w_lm", "b_lm", outputs=["fd_logits"])
+    b.op("ArgMax", ["fd_logits"], outputs=["fd_tok_new"], axis=1, keepdims=0)
+    b.op("Identity", ["fd_cond_in"], outputs=["fd_cond_out"])
+    b.add_output("fd_cond_out", [], BOOL)
+    b.add_output("fd_tok_new", [B], INT64)
+    for l in range(Ld):
+        b.add_output(f"fd_K{l}_new", [B, nh, "t1", dh])
+        b.add_output(f"fd_V{l}_new", [B, nh, "t1", dh])
+    b.add_output("fd_tok_new", [B], INT64)
+    if with_logits:
+        b.add_output("fd_logits", [B, V])
+    return b
+
+
+def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(64, 64), seed=0, head_only=False, weights=None, spelling="gemm", with_logits=False,
+                     act="Gelu", q_scale="after", sos=0, initial_cache="empty", read_final_cache=False):
+    """PP-FormulaNet-shaped formula recognizer: a tiny conv backbone (one grey channel in; an 8 x 8 / stride 8 patch convolution, hard-swish, a 1 x 1
+    convolution; its weights are added to info["weights"] as bb_*) -> memory [B, S, D] -> per decoder layer the cross-attention
+    keys / values KmT_l [B, nh, dh, S], Vm_l [B, nh, S, dh] by ordinary nodes -> the decoder as an ONNX Loop of M greedy steps over a key / value cache that starts
+    empty -> token_ids [B, M] int64, the graph's only 2-D int64 output (models/recognition/pp_formulanet.rs picks it by that).  head_only: the graph input is
+    `memory` itself.  with_logits: the Loop's second scan output, as `logits` [B, M, V].  Without head_only `memory` is a declared output too, so that a test can
+    check the head apart from the backbone.  weights: formula_weights(...) (the default); spelling / q_scale: see _formula_body.  Knobs that write a graph the
+    engine must refuse: act other than "Gelu"; initial_cache="one" (caches that start with one position); read_final_cache (a final cache as graph output).
+    Returns (onnx_bytes, info) with info["weights"]: what the graph really computes (q_scale = 1 and a scaled Wq / bq when folded)."""
+    from .onnx_writer import INT64
+    P = P if P is not None else M + 2
+    w = dict(weights) if weights is not None else formula_weights(D, nh, F, V, Ld, P, seed)
+    if q_scale == "folded" and w["q_scale"] != 1.0:
+        s = np.float32(w["q_scale"])
+        for l in range(Ld):
+            for nm in ("wq", "bq", "wcq", "bcq"):
+                w[f"l{l}_{nm}"] = w[f"l{l}_{nm}"] * s
+        w["q_scale"] = 1.0
+    if q_scale == "before":
+        if spelling != "matmul":
+            raise ValueError('q_scale="before" needs spelling="matmul"')
+        w["q_scale_pos"] = "before"
+    dh = D // nh
+    net = _Net("formulanet", seed + 100)
+    g = net.g
+    if head_only:
+        g.add_input("memory", ["B", "S", D])
+    else:
+        g.add_input("x", ["B", 1, image_shape[0], image_shape[1]])
+        if "bb_w1" not in w:                                                                       # the backbone's weights travel with the head's: the reference runs both
+            w["bb_w1"], w["bb_b1"] = net._w((32, 1, 8, 8), 64), net._b(32)
+            w["bb_w2"], w["bb_b2"] = net._w((D, 32, 1, 1), 32), net._b(D)
+        t = net.conv("x", 1, 32, 8, 8, act="hswish", pad=(0, 0), w=w["bb_w1"].copy(), b=w["bb_b1"].copy())   # 8 x 8 patches
+        t = net.conv(t, 32, D, 1, 1, act=None, w=w["bb_w2"].copy(), b=w["bb_b2"].copy())             # [B, D, h / 8, w / 8]
+        t = g.op("Reshape", [t, g.init(np.array([0, D, -1], np.int64), "shape")])
+        g.nodes.append(node("Transpose", [t], ["memory"], name=g.uid("n"), perm=[0, 2, 1]))
+    split = g.init(np.array([0, 0, nh, dh], np.int64), "shape")
+    for l in range(Ld):
+        p = f"l{l}_"
+        for nm, out, perm in (("ck", f"fd_KmT{l}", [0, 2, 3, 1]), ("cv", f"fd_Vm{l}", [0, 2, 1, 3])):
+            y = g.op("Add", [g.op("MatMul", ["memory", g.init(np.ascontiguousarray(w[p + "w" + nm].T), "fd_" + p + nm)]), g.init(w[p + "b" + nm], "fd_" + p + "b" + nm)])
+            g.nodes.append(node("Transpose", [g.op("Reshape", [y, split])], [out], name=g.uid("n"), perm=perm))
+    shp = g.op("Shape", ["memory"])
+    bdim = g.op("Gather", [shp, g.init(np.array([0], np.int64), "idx")], axis=0)                  # [1]
+    tok0 = g.op("ConstantOfShape", [bdim], value=np.full(1, sos, np.int64))
+    t0 = {"empty": 0, "one": 1}[initial_cache]
+    cshape = g.op("Concat", [bdim, g.init(np.array([nh], np.int64), "nh"), g.init(np.array([t0], np.int64), "t0"), g.init(np.array([dh], np.int64), "dh")], axis=0)
+    caches = [g.op("ConstantOfShape", [cshape], value=np.zeros(1, np.float32)) for _ in range(2 * Ld)]
+    body = _formula_body(w, "B", spelling, act, q_scale, with_logits, outer=g)
+    m_name, cond = g.init(np.array(M, np.int64), "trip"), g.init(np.array(True), "cond")
+    outs = ["tok_last"] + [f"{kv}_last_{l}" for l in range(Ld) for kv in ("K", "V")] + ["tok_scan"] + (["logits_scan"] if with_logits else [])
+    g.op("Loop", [m_name, cond, tok0] + caches, outputs=outs, body=body)
+    g.nodes.append(node("Transpose", ["tok_scan"], ["token_ids"], name=g.uid("n"), perm=[1, 0]))
+    g.add_output("token_ids", ["B", M], INT64)
+    if with_logits:
+        g.nodes.append(node("Transpose", ["logits_scan"], ["logits"], name=g.uid("n"), perm=[1, 0, 2]))
+        g.add_output("logits", ["B", M, V])
+    if not head_only:
+        g.add_output("memory", ["B", "S", D])
+    if read_final_cache:
+        g.add_output("K_last_0", ["B", nh, M, dh])
+    return g.model(), {"params": g.n_params, "weights": w, "D": D, "nh": nh, "F": F, "V": V, "Ld": Ld, "M": M, "P": P, "sos": sos}
+
+
+def formula_tokenizer_spec(V, decoder="ByteLevel"):
+    """A Hugging Face `tokenizer.json` (as a dict) with V tokens for the synthetic formula models: <s> = 0, <pad> = 1, </s> = 2, <unk> = 3 as special added tokens, then
+    LaTeX-like byte-level tokens (a leading space is the byte table's U+0120; one token carries a two-byte character), padded with t<i>."""
+    from ..formula import _bytes_to_unicode
+    table = _bytes_to_unicode()
+    bl = lambda text: "".join(table[b] for b in text.encode("utf-8"))
+    specials = ["<s>", "<pad>", "</s>", "<unk>"]
+    words = ["\\frac", "{", "}", "^", "_", " ", "x", "y", "+", "=", "\\alpha", " \\beta", "1", "2", "(", ")", "\\mathrm", " a", " b", "\u00e9", "\\sum", "-", ",", " ="]
+    vocab = {t: i for i, t in enumerate(specials)}
+    for t in words:
+        if len(vocab) < V and bl(t) not in vocab:
+            vocab[bl(t)] = len(vocab)
+    while len(vocab) < V:
+        vocab[f"t{len(vocab)}"] = len(vocab)
+    return {"version": "1.0", "added_tokens": [{"id": i, "content": t, "special": True} for i, t in enumerate(specials)],
+            "decoder": {"type": decoder}, "model": {"type": "BPE", "vocab": vocab, "merges": []}}

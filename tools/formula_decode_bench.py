@@ -1,0 +1,105 @@
+"""Speed of the FormulaDecode operator on PP-FormulaNet-S- and -L-shaped heads: microseconds per decode step from the profiler's event intervals of
+class `formula_decode`, the weight bytes a step streams over that time, and the same math as an eager torch loop on the same card in the same process
+(alternating runs, medians).  Usage: python tools/formula_decode_bench.py [--reps 5] [--steps 64]"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from oar_ocr_amd import api                      # noqa: E402
+from oar_ocr_amd.synth import models             # noqa: E402
+
+HEADS = {"S": dict(D=384, nh=16, F=1536, Ld=2, V=50000, S=144), "L": dict(D=512, nh=16, F=2048, Ld=8, V=50000, S=144)}
+
+
+def torch_loop(w, mem, M):
+    """formula_reference.formula_head_reference on the device in f32, the arg max fed back without leaving the device; returns a closure that runs all M steps"""
+    import torch
+    import torch.nn.functional as Fn
+    dev = torch.device("cuda")
+    t = {k: torch.from_numpy(np.asarray(v)).to(dev) for k, v in w.items() if isinstance(v, np.ndarray)}
+    mem = torch.from_numpy(mem).to(dev)
+    B, S, D = mem.shape
+    nh, Ld, eps = int(w["nh"]), int(w["Ld"]), float(w["eps"])
+    dh = D // nh
+    s_emb, qs, c_pos = float(w["s_emb"]), float(w["q_scale"]), int(w["c_pos"])
+    ln = lambda x, nm: Fn.layer_norm(x, (D,), t[nm + "_g"], t[nm + "_b"], eps)
+    lin = lambda x, wn, bn: Fn.linear(x, t[wn], t[bn])
+
+    def run():
+        with torch.no_grad():
+            KmT = [lin(mem, f"l{l}_wck", f"l{l}_bck").reshape(B, S, nh, dh).permute(0, 2, 3, 1) for l in range(Ld)]
+            Vm = [lin(mem, f"l{l}_wcv", f"l{l}_bcv").reshape(B, S, nh, dh).permute(0, 2, 1, 3) for l in range(Ld)]
+            K = [torch.zeros(B, nh, M, dh, device=dev) for _ in range(Ld)]
+            Vc = [torch.zeros(B, nh, M, dh, device=dev) for _ in range(Ld)]
+            tok = torch.zeros(B, dtype=torch.long, device=dev)
+            toks = []
+            for i in range(M):
+                x = ln(t["e_tok"][tok] * s_emb + t["e_pos"][i + c_pos], "lne")
+                for l in range(Ld):
+                    p = f"l{l}_"
+                    y = ln(x, p + "ln1")
+                    q = (lin(y, p + "wq", p + "bq") * qs).reshape(B, nh, 1, dh)
+                    K[l][:, :, i] = lin(y, p + "wk", p + "bk").reshape(B, nh, dh)
+                    Vc[l][:, :, i] = lin(y, p + "wv", p + "bv").reshape(B, nh, dh)
+                    o = (torch.softmax(q @ K[l][:, :, :i + 1].transpose(2, 3), -1) @ Vc[l][:, :, :i + 1]).reshape(B, D)
+                    x = x + lin(o, p + "wo", p + "bo")
+                    y = ln(x, p + "ln2")
+                    qc = (lin(y, p + "wcq", p + "bcq") * qs).reshape(B, nh, 1, dh)
+                    x = x + lin((torch.softmax(qc @ KmT[l], -1) @ Vm[l]).reshape(B, D), p + "wco", p + "bco")
+                    x = x + lin(Fn.gelu(lin(ln(x, p + "ln3"), p + "w1", p + "b1")), p + "w2", p + "b2")
+                tok = torch.argmax(lin(ln(x, "lnf"), "w_lm", "b_lm"), 1)
+                toks.append(tok)
+            return torch.stack(toks, 1)
+    return run
+
+
+def main():
+    import torch
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--heads", default="S,L")
+    a = ap.parse_args()
+    M = a.steps
+    for name in a.heads.split(","):
+        h = HEADS[name]
+        w = models.formula_weights(h["D"], h["nh"], h["F"], h["V"], h["Ld"], M + 2, 0)
+        model, _ = models.build_formulanet(D=h["D"], nh=h["nh"], F=h["F"], V=h["V"], Ld=h["Ld"], M=M, head_only=True, weights=w)
+        eng = api.OrtInfer(model, profile=True)
+        D, F, Ld, V = h["D"], h["F"], h["Ld"], h["V"]
+        weight_bytes = 4.0 * (Ld * (6 * D * D + 2 * F * D) + V * D)
+        for B in (1, 8):
+            mem = np.random.default_rng(B).standard_normal((B, h["S"], D)).astype(np.float32)
+            loop = torch_loop(w, mem, M)
+            ids = dict(eng.infer(mem))["token_ids"]
+            same = bool(np.array_equal(ids, loop().cpu().numpy()))
+            ours, wall, theirs = [], [], []
+            for _ in range(a.reps):
+                api.prof_reset()
+                api.prof_enable(True)
+                t0 = time.perf_counter()
+                eng.infer(mem)
+                wall.append((time.perf_counter() - t0) * 1e6 / M)
+                snap = {e["name"]: e for e in api.prof_snapshot()}
+                api.prof_enable(False)
+                ours.append(snap["formula_decode"]["total_ms"] * 1e3 / M)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                loop()
+                e1.record()
+                torch.cuda.synchronize()
+                theirs.append(e0.elapsed_time(e1) * 1e3 / M)
+            us = float(np.median(ours))
+            print(json.dumps({"head": name, "B": B, "M": M, "us_per_step_kernels": round(us, 1), "us_per_step_wall_profiled": round(float(np.median(wall)), 1),
+                              "weight_MB_per_step": round(weight_bytes / 1e6, 1), "share_of_8TBps": round(weight_bytes / (us * 1e-6) / 8e12, 3),
+                              "torch_eager_us_per_step": round(float(np.median(theirs)), 1), "tokens_equal_torch_f32": same}), flush=True)
+        eng.close()
+
+
+if __name__ == "__main__":
+    main()
