@@ -127,13 +127,25 @@ oar_status oar_engine_run_first_f32(oar_engine* e, const oar_input* inputs, int3
 oar_status oar_engine_io(const oar_engine* e, oar_io_info* inputs, int32_t max_in, int32_t* n_in, oar_io_info* outputs,
                          int32_t max_out, int32_t* n_out);
 /* Analytic cost of the plan for a given input shape (what roofline.achieved is computed from):
- * flops = sum 2*MACs over conv/matmul steps; bytes = sum (activations in + out + weights once). */
+ * flops = sum 2*MACs over conv/matmul steps; bytes = sum (activations in + out + weights once).  A greedy decode Loop
+ * (FormulaDecode) is counted with all its M steps: an upper bound once oar_engine_set_decode_stop lets it end early. */
 oar_status oar_engine_cost(oar_engine* e, const int64_t* dims, int32_t rank, double* flops, double* bytes,
                            int32_t* n_kernels);
 
 /* Plan-cache statistics: plans are specialised per input shape and kept in an LRU of OAR_PLAN_CACHE (default 256)
  * entries per engine, so a long-running server on heterogeneous pages has bounded host memory. */
 oar_status oar_engine_cache_stats(oar_engine* e, uint64_t* cached_plans, uint64_t* evicted_plans);
+/* Stop token of the greedy decode Loop (FormulaDecode): a run-time setting of the engine, not a property of the graph.
+ * e >= 0: FormulaDecode may stop a chunk (<= 16 images) once every image has emitted e; rows after an image's first e read e
+ * (token_ids; the logits rows after it are unspecified).  e < 0: off (default): all M steps run.
+ * OAR_INVALID_INPUT for a token >= V of the graph's decode node, and for an engine without one. */
+oar_status oar_engine_set_decode_stop(oar_engine* e, int64_t token);
+/* Of the last run; all 0 without a FormulaDecode node.  steps_limit = M x chunks; steps_enqueued: what the host enqueued
+ * (= steps_limit with the stop off, and under hipGraph replay); steps_executed: the steps that did work on the device
+ * (sum over chunks of 1 + the last step at which an image was still decoding); lookahead: the host's bound,
+ * steps_enqueued <= steps_executed + lookahead per chunk. */
+typedef struct { int64_t steps_limit, steps_enqueued, steps_executed, lookahead; } oar_decode_stats;
+oar_status oar_engine_decode_stats(oar_engine* e, oar_decode_stats* out);
 /* Host-only model check (no GPU needed): parses the file exactly as oar_engine_create does and writes a one-line
  * summary "opset=.. input=.. nodes=.. | Op:count ..." (operators the engine does not implement are prefixed '!').
  * OAR_MODEL_LOAD for a malformed / truncated file (dims, payload sizes and ranks are validated before anything is

@@ -133,6 +133,13 @@ class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double), ("alg_flops", C.c_double)]
 
 
+class DecodeStats(C.Structure):
+    _fields_ = [("steps_limit", C.c_int64), ("steps_enqueued", C.c_int64), ("steps_executed", C.c_int64), ("lookahead", C.c_int64)]
+
+    def __repr__(self):
+        return f"DecodeStats(steps_limit={self.steps_limit}, steps_enqueued={self.steps_enqueued}, steps_executed={self.steps_executed}, lookahead={self.lookahead})"
+
+
 EXPORTS = [
     "oar_last_error", "oar_version", "oar_device_count", "oar_engine_create", "oar_engine_destroy", "oar_engine_input_name",
     "oar_engine_run", "oar_engine_run_named", "oar_engine_run_first_f32", "oar_engine_io", "oar_tensor_free", "oar_engine_cost", "oar_det_create", "oar_det_destroy", "oar_det_run", "oar_det_result_free",
@@ -146,6 +153,7 @@ EXPORTS = [
     "oar_engine_cache_stats", "oar_onnx_inspect", "oar_host_contours", "oar_ctc_dict_create", "oar_ctc_dict_destroy", "oar_ctc_dict_classes",
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
+    "oar_engine_set_decode_stop", "oar_engine_decode_stats",
 ]
 
 
@@ -176,6 +184,8 @@ def lib():
     L.oar_tensor_free.restype = None
     L.oar_engine_cost.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.oar_engine_cache_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.oar_engine_set_decode_stop.argtypes = [vp, C.c_int64]
+    L.oar_engine_decode_stats.argtypes = [vp, C.POINTER(DecodeStats)]
     L.oar_onnx_inspect.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_size_t]
     L.oar_det_create.argtypes = [vp, C.c_size_t, C.POINTER(DetCfg), C.POINTER(vp)]
     L.oar_det_destroy.argtypes = [vp]
@@ -501,6 +511,18 @@ class OrtInfer:
         a, b = C.c_uint64(0), C.c_uint64(0)
         _check(lib().oar_engine_cache_stats(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def set_decode_stop(self, token: int):
+        """Stop token of the greedy decode Loop (FormulaDecode): token >= 0 lets a chunk of <= 16 images end once each of them has emitted it -- token_ids then
+        read `token` after a row's first one, the logits rows after it are unspecified; token < 0 turns it off (the default: all M steps run).
+        OCRError(OAR_INVALID_INPUT) for a token outside the vocabulary and for a graph without such a Loop."""
+        _check(lib().oar_engine_set_decode_stop(self._h, int(token)))
+
+    def decode_stats(self) -> DecodeStats:
+        """steps_limit / steps_enqueued / steps_executed / lookahead of the last `infer` (all 0 without a decode Loop)."""
+        d = DecodeStats()
+        _check(lib().oar_engine_decode_stats(self._h, C.byref(d)))
+        return d
 
     def cost(self, shape):
         dims = (C.c_int64 * len(shape))(*shape)

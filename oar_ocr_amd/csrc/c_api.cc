@@ -375,6 +375,23 @@ oar_status oar_engine_cache_stats(oar_engine* e, uint64_t* cached_plans, uint64_
     });
 }
 
+oar_status oar_engine_set_decode_stop(oar_engine* e, int64_t token) {
+    return guard([&] {
+        OAR_CHECK(e, OAR_INVALID_INPUT, "oar_engine_set_decode_stop: engine is null");
+        std::lock_guard<std::mutex> lk(e->e->mutex());
+        e->e->set_decode_stop(token);
+    });
+}
+
+oar_status oar_engine_decode_stats(oar_engine* e, oar_decode_stats* out) {
+    return guard([&] {
+        OAR_CHECK(e && out, OAR_INVALID_INPUT, "oar_engine_decode_stats: bad arguments");
+        std::lock_guard<std::mutex> lk(e->e->mutex());
+        const Engine::DecodeStats d = e->e->decode_stats();
+        out->steps_limit = d.steps_limit; out->steps_enqueued = d.steps_enqueued; out->steps_executed = d.steps_executed; out->lookahead = d.lookahead;
+    });
+}
+
 oar_status oar_onnx_inspect(const uint8_t* onnx, size_t onnx_len, char* summary, size_t cap) {
     if (summary && cap) summary[0] = 0;
     return guard([&] {

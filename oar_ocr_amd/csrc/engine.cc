@@ -60,6 +60,10 @@ Engine::~Engine() {
     if (stream_) (void)hipStreamSynchronize(stream_);
     clear_graphs();
     Profiler::get().drop_events();   // no pooled event may outlive the stream it was recorded on
+    for (hipEvent_t ev : fd_.ev) if (ev) (void)hipEventDestroy(ev);
+    if (fd_.state) (void)hipFree(fd_.state);
+    if (fd_.fin) (void)hipHostFree(const_cast<unsigned*>(fd_.fin));
+    if (fd_executed_) (void)hipHostFree(fd_executed_);
     for (void* p : dev_allocs_) (void)hipFree(p);
     if (stream_ && owns_stream_) (void)hipStreamDestroy(stream_);
     (void)hipGetLastError();
@@ -3779,8 +3783,11 @@ struct Planner {
         }, 2.0 * macs * M * B, 4.0 * (macs + 3.0 * H + V + L) * M * B);
     }
 
-    // The formula decode head (rewrite pass 0): M steps of 8 Ld + 2 short launches per chunk of 16 images (formula_decode.hip).  Nothing is allocated, read back or
-    // synchronised between steps, so the plan stays capturable; all `steps` steps run (exact Loop semantics with a constant-true condition), the host stops at eos.
+    // The formula decode head (rewrite pass 0): M steps of 8 Ld + 2 short launches per chunk of 16 images (formula_decode.hip).  By default all `steps` steps run
+    // (exact Loop semantics with a constant-true condition; the host stops at eos) and nothing is allocated, read back or synchronised between them, so the plan
+    // stays capturable.  With Engine::set_decode_stop on (read at run time, not planned) a chunk ends once each of its images has emitted the stop token: outside
+    // a capture the host waits on an event kFdLookahead steps back, reads one mapped word and stops enqueuing at most kFdLookahead steps late; inside a capture
+    // all steps are enqueued and skipped on the device.  The cost below stays the full-M figure: an upper bound in that mode.
     void op_formula_decode(const GNode& n) {
         const int64_t M = n.ai("steps", 0), Ld = n.ai("layers", 0), D = n.ai("width", 0), nh = n.ai("heads", 1), F = n.ai("ffn", 0), V = n.ai("vocab", 0), P = n.ai("positions", 0);
         const int64_t dh = D / nh;
@@ -3836,8 +3843,12 @@ struct Planner {
         const double Dp = (double)((D + 3) / 4 * 4), Fp = (double)((F + 3) / 4 * 4);
         const double w_floats = Ld * (6.0 * D * Dp + F * Dp + D * Fp + 15.0 * D + F) + V * Dp + V + 4.0 * D;          // weights one step streams
         const double macs = Ld * (6.0 * D * D + 2.0 * F * D + (double)S * D * 2.0 + (double)(M + 1) * D) + (double)V * D;   // per step and image (self attention at its mean length)
+        this->P.decode_steps += M * chunks;
+        Engine* const eng = &E;
         step([=](const RunCtx& c) {
             k::FormulaDecodeP q = p;
+            q.stop = eng->fd_.token >= 0 ? &eng->fd_ : nullptr;
+            q.stats = &eng->fd_stats_;
             q.tok0 = c.at(t0);
             for (int l = 0; l < q.Ld; ++l) { q.layer[l].kmT = c.at(mem[(size_t)(2 * l)]); q.layer[l].vm = c.at(mem[(size_t)(2 * l + 1)]); }
             q.ws = c.mut(ws); q.tokens = c.mut(tl); q.logits = with_logits ? c.mut(ll) : nullptr;
@@ -4594,6 +4605,74 @@ void Engine::evict_plans() {
     }
 }
 
+void Engine::set_decode_stop(int64_t token) {
+    int64_t V = -1;
+    for (const GNode& n : nodes_) if (n.op == "FormulaDecode") { V = n.ai("vocab", 0); break; }
+    OAR_CHECK(V >= 0, OAR_INVALID_INPUT, "set_decode_stop: the graph has no FormulaDecode node (no greedy decode Loop was recognised)");
+    OAR_CHECK(token < V, OAR_INVALID_INPUT, "set_decode_stop: token " + std::to_string(token) + " is outside the decode node's vocabulary (V = " + std::to_string(V) + ")");
+    const int tok = token < 0 ? -1 : (int)token;
+    if (tok == fd_.token) return;
+    OAR_HIP(hipSetDevice(device_));
+    OAR_HIP(hipStreamSynchronize(stream_));
+    clear_graphs();   // their kernel arguments hold the old setting
+    if (tok >= 0 && !fd_.state) {   // everything goes into locals and is committed at the end: a failure half way leaves the engine as it was
+        void *d = nullptr, *fin = nullptr, *fin_dev = nullptr, *exe = nullptr;
+        hipEvent_t ev[k::kFdLookahead + 1] = {};
+        try {
+            OAR_HIP(hipMalloc(&d, sizeof(k::FdStopState)));
+            OAR_HIP(hipMemset(d, 0, sizeof(k::FdStopState)));
+            OAR_HIP(hipHostMalloc(&fin, 64, hipHostMallocMapped | hipHostMallocCoherent));
+            std::memset(fin, 0, 64);
+            OAR_HIP(hipHostGetDevicePointer(&fin_dev, fin, 0));
+            OAR_HIP(hipHostMalloc(&exe, 64, hipHostMallocDefault));
+            std::memset(exe, 0, 64);
+            for (hipEvent_t& e : ev) OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        } catch (...) {
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+            if (exe) (void)hipHostFree(exe);
+            if (fin) (void)hipHostFree(fin);
+            if (d) (void)hipFree(d);
+            throw;
+        }
+        fd_.fin = static_cast<volatile unsigned*>(fin);
+        fd_.fin_dev = static_cast<unsigned*>(fin_dev);
+        fd_executed_ = static_cast<unsigned long long*>(exe);
+        for (int i = 0; i <= k::kFdLookahead; ++i) fd_.ev[i] = ev[i];
+        fd_.state = static_cast<k::FdStopState*>(d);
+    }
+    fd_.token = tok;
+}
+
+Engine::DecodeStats Engine::decode_stats() {
+    DecodeStats d;
+    d.steps_limit = fd_stats_.steps_limit;
+    d.steps_enqueued = fd_stats_.steps_enqueued;
+    d.steps_executed = fd_stats_.steps_enqueued;
+    if (d.steps_limit == 0) return d;
+    d.lookahead = k::kFdLookahead;
+    if (fd_executed_valid_) {
+        OAR_HIP(hipSetDevice(device_));
+        OAR_HIP(hipStreamSynchronize(stream_));
+        d.steps_executed = (int64_t)*fd_executed_;
+    }
+    return d;
+}
+
+void Engine::begin_run() {
+    fd_stats_ = k::FdRunStats{};
+    fd_.first_chunk = true;
+    fd_executed_valid_ = false;
+}
+
+// replayed: an existing graph was launched, so no step lambda ran and the plan's own figure stands in for the host's count (a replay enqueues every step)
+void Engine::end_run(const Plan& p, bool replayed) {
+    if (replayed && fd_stats_.steps_limit == 0) fd_stats_.steps_limit = fd_stats_.steps_enqueued = p.decode_steps;
+    if (fd_.token >= 0 && p.decode_steps > 0) {   // read back with the outputs: the caller's fetch synchronises the stream
+        OAR_HIP(hipMemcpyAsync(fd_executed_, &fd_.state->steps_executed, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+        fd_executed_valid_ = true;
+    }
+}
+
 void Engine::clear_graphs() {
     for (auto& kv : graphs_) {
         if (kv.second.events) Profiler::get().release(*kv.second.events);
@@ -4666,7 +4745,10 @@ const Plan& Engine::run(const float* d_in, const std::vector<int64_t>& dims, boo
     }
     RunCtx c{stream_, d_in, arena_.as<char>()};
     last_input_ = d_in;
-    if (!replay(p, c)) {
+    begin_run();
+    const bool replayed = replay(p, c);
+    if (!replayed) {
+        begin_run();   // (a capture that failed half way has already counted some steps)
         if (!p.step_ops.empty() && p.step_ops.size() == p.steps.size()) {   // OAR_DEBUG_STEPS=1 (and no chain fusion re-indexing): which step leaves a HIP error behind?
             for (size_t i = 0; i < p.steps.size(); ++i) {
                 p.steps[i](c);
@@ -4678,6 +4760,7 @@ const Plan& Engine::run(const float* d_in, const std::vector<int64_t>& dims, boo
         }
         ++p.runs;
     }
+    end_run(p, replayed);
     OAR_HIP(hipGetLastError());
     return p;
 }
@@ -4696,7 +4779,9 @@ const Plan& Engine::run_multi(const std::vector<const float*>& d_ins, const std:
     last_extra_ = d_ins;
     RunCtx c{stream_, d_ins[0], arena_.as<char>(), last_extra_.data()};
     last_input_ = d_ins[0];
+    begin_run();
     for (auto& st : p.steps) st(c);   // no hipGraph replay here: a captured graph bakes in one input pointer only
+    end_run(p, false);
     ++p.runs;
     OAR_HIP(hipGetLastError());
     return p;
@@ -4714,7 +4799,9 @@ const Plan& Engine::run_stem(const k::StemU8& st, const std::vector<int64_t>& di
     }
     RunCtx c{stream_, nullptr, arena_.as<char>(), nullptr, &st};
     last_input_ = nullptr;
+    begin_run();
     for (auto& stp : p.steps) stp(c);   // no hipGraph replay: the page pointers change from call to call
+    end_run(p, false);
     ++p.runs;
     OAR_HIP(hipGetLastError());
     return p;

@@ -82,6 +82,7 @@ struct Plan {
     bool skipped_softmax = false;
     mutable uint64_t last_used = 0;   // Engine's LRU tick
     mutable int runs = 0;   // completed uncaptured runs (a plan is captured into a hipGraph from its second run on)
+    int64_t decode_steps = 0;   // FormulaDecode nodes: sum of steps x chunks (what a replayed graph enqueues)
     int logits_valid = 0;   // > 0: output[0]'s rows are padded; only the first logits_valid columns are logits
     Loc ctc_part;           // kind != NONE: output[0] was never materialised; softmax partials [rows][ctc_tiles] float4 live here
     int ctc_tiles = 0;
@@ -126,6 +127,12 @@ class Engine {
     static void validate_model(const OnnxModel& m);   // throws OAR_MODEL_LOAD; host-only
     size_t cached_plans() const { return plans_.size(); }
     uint64_t evicted_plans() const { return plans_evicted_; }
+    // FormulaDecode's stop token (a run-time setting, not a property of the graph): token >= 0 lets a chunk end once each of its images has emitted it, rows
+    // after an image's first one read it; token < 0: off (the default).  OAR_INVALID_INPUT for a graph without a FormulaDecode node or token >= its V.
+    // Changing it drops the captured graphs (their kernel arguments hold the old setting); plans stay.
+    void set_decode_stop(int64_t token);
+    struct DecodeStats { int64_t steps_limit = 0, steps_enqueued = 0, steps_executed = 0, lookahead = 0; };
+    DecodeStats decode_stats();   // of the last run (waits for it); all 0 without a FormulaDecode node
 
    private:
     friend struct Planner;
@@ -168,6 +175,13 @@ class Engine {
     bool replay(const Plan& p, const RunCtx& c);
     std::mutex mu_;
     const float* last_input_ = nullptr;
+    // FormulaDecode stop token: fd_.token < 0 while off; the device / pinned state is created by the first set_decode_stop(token >= 0) and lives as long as the engine
+    k::FdStop fd_;
+    k::FdRunStats fd_stats_;                       // of the run in flight / the last run (host side)
+    unsigned long long* fd_executed_ = nullptr;    // pinned: the device's step counter, copied after every run with the stop token on
+    bool fd_executed_valid_ = false;
+    void begin_run();
+    void end_run(const Plan& p, bool replayed);
 };
 
 }  // namespace oar

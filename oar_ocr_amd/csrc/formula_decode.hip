@@ -17,6 +17,15 @@
 //                                LN_emb(E_tok[tok] * s_emb + E_pos[t + 1 + c_pos]): the embedding costs no launch of its own
 // One more fd_combine launch per chunk embeds the start token before step 0 (profiler class formula_embed).
 //
+// Stop token (opt-in, FormulaDecodeP::stop; off = every pointer below is null and nothing here differs from the chain above).  Per chunk the engine keeps
+// FdStopState in device memory of its own: done[b] (0 while image b decodes, f + 1 once it emitted the stop token at step f), alive (images still decoding)
+// and a 64-bit count of executed steps.  fd_combine is the only writer: it forces the stop token for a finished image (as scan output AND as the next input),
+// marks an image that has just emitted it and takes it off `alive` with one atomicSub.  Every other kernel of the chain reads `alive` before it touches
+// anything and returns when it is 0 -- the kernel boundary after fd_combine orders the write.  The workgroup that brings `alive` to 0 also stores the
+// chunk's generation number into a word of mapped host memory; the host, which waits on the event recorded kFdLookahead steps back before it enqueues
+// a step (so at most t_stop + kFdLookahead steps of a chunk are enqueued), stops enqueuing once it reads its own generation there, and fd_fill_tail writes the stop token into the rows that were never enqueued.  While a
+// hipGraph is captured the host reads nothing: all M steps are enqueued and the guards alone skip the work.
+//
 // fd_rows: y[B][N] = epi(LN?(x[B][K]) W^T + b).  A workgroup of 4 waves owns a slice of W's rows; it stages the B input rows in LDS in chunks of
 // 768 columns (48 KB at 16 rows: two workgroups per CU), applying the LayerNorm itself (the row statistics come from a two-pass prologue over the
 // B x K inputs, L2 resident), and streams its weight rows once with 16-byte loads: a wave takes two rows at a time, every lane multiplies its float4
@@ -51,6 +60,7 @@ struct FdRowsP {
     float *kc, *vc; int D, dh, M, t;     // FD_QKV: rows [D, 2D) -> kc[b][head][t][d], [2D, 3D) -> vc
     float* logits;                       // FD_LM: [B][N] or null
     float2* part; int nwg;               // FD_LM: part[b][workgroup] = (value, index)
+    const int* alive;                    // stop token on: images of the chunk still decoding (0: return at once); null: off
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -66,6 +76,7 @@ __device__ __forceinline__ void fd_rows_body(const FdRowsP& p) {
     __shared__ float red_v[kFdWaves][16];
     __shared__ int red_i[kFdWaves][16];
     float* xs = reinterpret_cast<float*>(fd_lds4);
+    if (p.alive && *p.alive == 0) return;   // (uniform over the grid: only fd_combine writes it)
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int KCs = p.Kp < kFdKC ? p.Kp : kFdKC;
     const bool ln = p.ln_g != nullptr;
@@ -206,6 +217,7 @@ struct FdAttnP {
     size_t k_img, k_head, v_img, v_head; // strides in floats
     int ks_j, ks_d, n, dh;
     float* o; int o_ld;                  // [B][D]
+    const int* alive;                    // as FdRowsP::alive
 };
 
 __device__ __forceinline__ void fd_attn_body(const FdAttnP& p) {
@@ -213,6 +225,7 @@ __device__ __forceinline__ void fd_attn_body(const FdAttnP& p) {
     __shared__ float sc[kFdMaxS];
     __shared__ float part[kFdAttnThreads];
     __shared__ float red[kFdAttnThreads / 64];
+    if (p.alive && *p.alive == 0) return;
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, head = (int)blockIdx.x, b = (int)blockIdx.y;
     const int n = p.n, dh = p.dh;
     const float* kb = p.kb + (size_t)b * p.k_img + (size_t)head * p.k_head;
@@ -268,6 +281,10 @@ struct FdCombineP {
     const float *e_tok, *e_pos, *ln_g, *ln_b;
     float s_emb, eps;
     float* x;                            // [B][D]
+    FdStopState* st;                     // stop token on (null: off).  Start-token launch: reset the chunk's state; step launch: see the header
+    int stop_tok, t;                     // the stop token; this launch's step
+    int reset_count;                     // start-token launch of a run's first chunk: steps_executed = 0
+    unsigned* fin_host; unsigned gen;    // mapped host word that receives `gen` once the chunk has finished (null while capturing)
 };
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -286,8 +303,40 @@ __global__ __launch_bounds__(kFdThreads) void fd_combine_kernel(FdCombineP p) {
     __shared__ int red_i[kFdWaves];
     __shared__ float red[kFdWaves];
     __shared__ int tok_s;
+    __shared__ int skip_s, done_s;
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, b = (int)blockIdx.x;
-    if (p.part) {
+    FdStopState* st = p.st;
+    if (st && !p.part) {   // start token: a new chunk
+        if (tid == 0) {
+            __atomic_store_n(&st->done[b], 0, __ATOMIC_RELAXED);
+            if (b == 0) {
+                st->alive = (int)gridDim.x;
+                if (p.reset_count) st->steps_executed = 0;
+            }
+        }
+    } else if (st) {
+        if (tid == 0) {
+            // done[] holds f + 1, so an image that finishes in this very launch (another workgroup may already have said so) still counts as decoding on
+            // entry: the step is counted exactly when at least one image entered it alive, whatever the order of the workgroups
+            if (b == 0) {
+                bool any = false;
+                for (int j = 0; j < (int)gridDim.x; ++j) {
+                    const int d = __atomic_load_n(&st->done[j], __ATOMIC_RELAXED);
+                    any = any || d == 0 || d == p.t + 1;
+                }
+                if (any) st->steps_executed = st->steps_executed + 1;
+            }
+            done_s = __atomic_load_n(&st->done[b], __ATOMIC_RELAXED);   // (only this workgroup writes done[b]; workgroup 0 may read it meanwhile)
+            // 0 here means every image has finished, this one included (it has not left `alive` in this launch before this read): nothing is left to do
+            skip_s = __atomic_load_n(&st->alive, __ATOMIC_RELAXED) == 0;
+        }
+        __syncthreads();
+        if (skip_s || done_s) {
+            if (tid == 0) { tok_s = p.stop_tok; p.tok_out[b] = (float)p.stop_tok; }
+            if (skip_s) return;
+        }
+    }
+    if (p.part && !(st && done_s)) {
         float v = -INFINITY;
         int ix = 0x7fffffff;
         for (int i = tid; i < p.nwg; i += kFdThreads) {
@@ -309,8 +358,15 @@ __global__ __launch_bounds__(kFdThreads) void fd_combine_kernel(FdCombineP p) {
             if (ix < 0 || ix >= p.V) ix = 0;   // (all logits NaN: no candidate ever won)
             tok_s = ix;
             p.tok_out[b] = (float)ix;
+            if (st && ix == p.stop_tok) {
+                __atomic_store_n(&st->done[b], p.t + 1, __ATOMIC_RELAXED);
+                if (atomicSub(&st->alive, 1) == 1 && p.fin_host) {   // the chunk's last image: tell the host (visible at the latest when this launch ends)
+                    __atomic_store_n(p.fin_host, p.gen, __ATOMIC_RELAXED);
+                    __threadfence_system();
+                }
+            }
         }
-    } else if (tid == 0) {
+    } else if (!p.part && tid == 0) {
         int ix = (int)p.tok_in[b];
         tok_s = ix < 0 ? 0 : ix >= p.V ? p.V - 1 : ix;
     }
@@ -340,6 +396,15 @@ __global__ __launch_bounds__(kFdThreads) void fd_combine_kernel(FdCombineP p) {
     for (int q = 0; q < kFdMaxD / kFdThreads; ++q) {
         const int i = tid + q * kFdThreads;
         if (i < D) p.x[(size_t)b * D + i] = (e[q] - mean) * rstd * p.ln_g[i] + p.ln_b[i];
+    }
+}
+
+// rows [t0, M) of a chunk's token columns: the steps the host never enqueued read the stop token
+__global__ __launch_bounds__(kFdThreads) void fd_fill_tail_kernel(float* tok, int ld, int bc, int t0, int M, float v) {
+    const int n = (M - t0) * bc;
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x)) {
+        const int r = i / bc, b = i - r * bc;
+        tok[(size_t)(t0 + r) * ld + b] = v;
     }
 }
 
@@ -404,17 +469,32 @@ void formula_decode(hipStream_t s, const FormulaDecodeP& p) {
     float* h = o + (size_t)bc_max * D;
     const size_t part_off = ((size_t)(h - p.ws) + (size_t)bc_max * F + 1) & ~(size_t)1;   // 8-byte aligned (ws is)
     float2* part = reinterpret_cast<float2*>(p.ws + part_off);
+    FdStop* const stop = p.stop;
+    OAR_CHECK(!stop || (stop->token >= 0 && stop->token < V && stop->state), OAR_INTERNAL, "FormulaDecode: stop token without its state");
+    const bool poll = stop && !Profiler::capturing;   // (a captured graph reads nothing back: the device guards alone skip the work)
+    const int* const alive = stop ? &stop->state->alive : nullptr;
+    constexpr int kRing = kFdLookahead + 1;
     for (int c0 = 0; c0 < p.B; c0 += kFdChunk) {
         const int bc = std::min(kFdChunk, p.B - c0);
         FdCombineP cb{};
         cb.V = V; cb.D = D; cb.e_tok = p.e_tok; cb.e_pos = p.e_pos; cb.ln_g = p.lne_g; cb.ln_b = p.lne_b; cb.s_emb = p.s_emb; cb.eps = p.eps_e; cb.x = x;
+        if (stop) {
+            if (++stop->gen == 0) stop->gen = 1;
+            cb.st = stop->state; cb.stop_tok = stop->token; cb.gen = stop->gen; cb.fin_host = poll ? stop->fin_dev : nullptr;
+        }
         {
             FdCombineP c = cb;
             c.tok_in = p.tok0 + c0; c.pos = p.c_pos;
+            if (stop) { c.reset_count = stop->first_chunk ? 1 : 0; stop->first_chunk = false; }
             ProfScope ps(s, "formula_embed", 4.0 * 3 * bc * D, 0);
             hipLaunchKernelGGL(fd_combine_kernel, dim3((unsigned)bc), dim3(kFdThreads), 0, s, c);
         }
-        for (int t = 0; t < M; ++t) {
+        int t = 0;
+        for (; t < M; ++t) {
+            if (poll && t >= kFdLookahead) {   // steps 0 .. t - kFdLookahead have ended: did the last image finish in one of them?
+                OAR_HIP(hipEventSynchronize(stop->ev[(t - kFdLookahead) % kRing]));
+                if (*stop->fin == stop->gen) break;
+            }
             for (int l = 0; l < Ld; ++l) {
                 const FdLayerP& L = p.layer[l];
                 float* kc = kc0 + (size_t)(2 * l) * cache_l;
@@ -422,48 +502,57 @@ void formula_decode(hipStream_t s, const FormulaDecodeP& p) {
                 FdRowsP r{};
                 r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = 3 * D; r.W = L.w_qkv; r.bias = L.b_qkv; r.ln_g = L.ln1_g; r.ln_b = L.ln1_b; r.eps = L.eps1;
                 r.y = q; r.y_ld = D; r.scale_mode = L.q_scale_mode; r.scale = L.q_scale; r.scale_rows = D; r.kc = kc; r.vc = vc; r.D = D; r.dh = dh; r.M = M; r.t = t;
-                launch_rows<FD_QKV>(s, r);
+                r.alive = alive; launch_rows<FD_QKV>(s, r);
                 FdAttnP a{};
                 a.q = q; a.q_ld = D; a.kb = kc; a.vb = vc; a.k_img = a.v_img = (size_t)M * D; a.k_head = a.v_head = (size_t)M * dh; a.ks_j = dh; a.ks_d = 1; a.n = t + 1; a.dh = dh;
-                a.o = o; a.o_ld = D;
+                a.o = o; a.o_ld = D; a.alive = alive;
                 {
                     ProfScope ps(s, "formula_decode", 4.0 * bc * (2.0 * (t + 1) * D + 2 * D), 4.0 * bc * (double)(t + 1) * D);
                     hipLaunchKernelGGL(fd_self_attn_kernel, dim3((unsigned)nh, (unsigned)bc), dim3(kFdAttnThreads), 0, s, a);
                 }
                 r = FdRowsP{};
                 r.x = o; r.x_ld = D; r.B = bc; r.K = D; r.N = D; r.W = L.w_o; r.bias = L.b_o; r.y = x; r.y_ld = D; r.res = x;
-                launch_rows<FD_PLAIN>(s, r);
+                r.alive = alive; launch_rows<FD_PLAIN>(s, r);
                 r = FdRowsP{};
                 r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = D; r.W = L.w_cq; r.bias = L.b_cq; r.ln_g = L.ln2_g; r.ln_b = L.ln2_b; r.eps = L.eps2;
                 r.y = q; r.y_ld = D; r.scale_mode = L.cq_scale_mode; r.scale = L.cq_scale; r.scale_rows = D;
-                launch_rows<FD_PLAIN>(s, r);
+                r.alive = alive; launch_rows<FD_PLAIN>(s, r);
                 a = FdAttnP{};
                 a.q = q; a.q_ld = D; a.kb = L.kmT + (size_t)c0 * D * S; a.vb = L.vm + (size_t)c0 * D * S; a.k_img = a.v_img = (size_t)D * S; a.k_head = a.v_head = (size_t)dh * S;
-                a.ks_j = 1; a.ks_d = S; a.n = S; a.dh = dh; a.o = o; a.o_ld = D;
+                a.ks_j = 1; a.ks_d = S; a.n = S; a.dh = dh; a.o = o; a.o_ld = D; a.alive = alive;
                 {
                     ProfScope ps(s, "formula_decode", 4.0 * bc * (2.0 * S * D + 2 * D), 4.0 * bc * (double)S * D);
                     hipLaunchKernelGGL(fd_cross_attn_kernel, dim3((unsigned)nh, (unsigned)bc), dim3(kFdAttnThreads), 0, s, a);
                 }
                 r = FdRowsP{};
                 r.x = o; r.x_ld = D; r.B = bc; r.K = D; r.N = D; r.W = L.w_co; r.bias = L.b_co; r.y = x; r.y_ld = D; r.res = x;
-                launch_rows<FD_PLAIN>(s, r);
+                r.alive = alive; launch_rows<FD_PLAIN>(s, r);
                 r = FdRowsP{};
                 r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = F; r.W = L.w_1; r.bias = L.b_1; r.ln_g = L.ln3_g; r.ln_b = L.ln3_b; r.eps = L.eps3; r.y = h; r.y_ld = F; r.gelu = 1;
-                launch_rows<FD_PLAIN>(s, r);
+                r.alive = alive; launch_rows<FD_PLAIN>(s, r);
                 r = FdRowsP{};
                 r.x = h; r.x_ld = F; r.B = bc; r.K = F; r.N = D; r.W = L.w_2; r.bias = L.b_2; r.y = x; r.y_ld = D; r.res = x;
-                launch_rows<FD_PLAIN>(s, r);
+                r.alive = alive; launch_rows<FD_PLAIN>(s, r);
             }
             FdRowsP r{};
             r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = V; r.W = p.w_lm; r.bias = p.b_lm; r.ln_g = p.lnf_g; r.ln_b = p.lnf_b; r.eps = p.eps_f;
             r.logits = p.logits ? p.logits + ((size_t)t * p.B + c0) * V : nullptr; r.part = part;
-            launch_rows<FD_LM>(s, r);
+            r.alive = alive; launch_rows<FD_LM>(s, r);
             FdCombineP c = cb;
             c.part = part; c.nwg = wgs_for(V); c.tok_out = p.tokens + (size_t)t * p.B + c0; c.pos = t + 1 < M ? t + 1 + p.c_pos : -1;
+            c.t = t;
             {
                 ProfScope ps(s, "formula_decode", 4.0 * bc * (2.0 * c.nwg + 3.0 * D), 0);
                 hipLaunchKernelGGL(fd_combine_kernel, dim3((unsigned)bc), dim3(kFdThreads), 0, s, c);
             }
+            if (poll) OAR_HIP(hipEventRecord(stop->ev[t % kRing], s));
+        }
+        if (p.stats) { p.stats->steps_limit += M; p.stats->steps_enqueued += t; }
+        if (t < M) {   // (only ever with the stop token on)
+            const int n = (M - t) * bc;
+            ProfScope ps(s, "formula_stop", 4.0 * n, 0);
+            hipLaunchKernelGGL(fd_fill_tail_kernel, dim3((unsigned)std::min((n + kFdThreads - 1) / kFdThreads, 64)), dim3(kFdThreads), 0, s, p.tokens + c0, p.B, bc, t, M,
+                               (float)stop->token);
         }
     }
 }

@@ -203,12 +203,33 @@ struct FdLayerP {
     int q_scale_mode, cq_scale_mode;
     const float *kmT, *vm;
 };
+// Stop token (opt-in; formula_decode.hip's header has the protocol).  FdStopState: the per-chunk state, device memory the engine owns for its lifetime.
+// FdStop: what one run needs on top -- the host side of the look-ahead and the run's counters.  kFdLookahead: how many steps the host may be ahead of the
+// last step it knows to have ended.  4 is the best of the 2 / 4 / 8 / 16 sweep on the S-shaped head (Speed; profiles/r8/formula_decode_stop.txt).  Every
+// translation unit must see the same value: it sizes FdStop::ev.
+#ifndef OAR_FD_LOOKAHEAD
+#define OAR_FD_LOOKAHEAD 4
+#endif
+constexpr int kFdLookahead = OAR_FD_LOOKAHEAD;
+struct FdStopState { int done[kFdChunk]; int alive; int pad; unsigned long long steps_executed; };
+struct FdStop {
+    int token = -1;                      // 0 <= token < V
+    FdStopState* state = nullptr;        // device
+    volatile unsigned* fin = nullptr;    // mapped, coherent host word: the generation of the last chunk that finished early
+    unsigned* fin_dev = nullptr;         // the same word as the device sees it
+    hipEvent_t ev[kFdLookahead + 1] = {};// ring: ev[t % (kFdLookahead + 1)] is recorded after step t
+    unsigned gen = 0;                    // one per chunk, never 0
+    bool first_chunk = true;             // the next chunk is the first of its run: its start launch clears the device's step counter
+};
+struct FdRunStats { int64_t steps_limit = 0, steps_enqueued = 0; };
 struct FormulaDecodeP {
     int B, D, nh, F, V, Ld, S, M, P, c_pos;
     float s_emb, eps_e, eps_f;
     const float *tok0, *e_tok, *e_pos, *lne_g, *lne_b, *lnf_g, *lnf_b, *w_lm, *b_lm;
     FdLayerP layer[kFdMaxLayers];
     float *ws, *tokens, *logits;
+    FdStop* stop;                        // null: off
+    FdRunStats* stats;                   // null, or the counters this call adds to (host side only)
 };
 bool formula_decode_supported(int D, int nh, int F, int V, int Ld, int M, int S);
 int formula_decode_lm_workgroups(int V);          // (value, index) partials per image of the arg max

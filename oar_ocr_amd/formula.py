@@ -4,11 +4,12 @@
 A PP-FormulaNet file is one ONNX graph from image to token ids: the greedy decode sits inside it as a Loop, which the engine runs as its FormulaDecode
 operator (csrc/formula_decode.hip).  Everything here is host orchestration around `api.OrtInfer`: margin crop, Triangle resize through the
 existing `api.k_resize_triangle`, the f32 normalisation in the reference's operation order, the token filter, a ByteLevel tokenizer decode and the LaTeX
-clean-up.  The host stops at eos; the graph always runs all its steps.
+clean-up.  The host stops at eos.  The graph runs all its steps unless the predictor is built with `stop_at_eos=True`: the engine then ends a chunk of 16
+images once each of them has emitted eos (`api.OrtInfer.set_decode_stop`) and fills the rest of their rows with eos, which the token filter never reads.
 
 Not pinned against the reference's dependencies: `to_luma8` of a pixel that is not grey (the image crate's integer weights are restated here from its
 documentation: (2126 R + 7152 G + 722 B) / 10000; a grey pixel maps to itself under any weights that sum to one), and the spelling of the real
-`pp-formulanet*.onnx` files.  Tokenizers whose decoder is not ByteLevel, the UniMERNet preprocessor and an early exit at eos are not built."""
+`pp-formulanet*.onnx` files.  Tokenizers whose decoder is not ByteLevel and the UniMERNet preprocessor are not built."""
 from __future__ import annotations
 
 import json
@@ -287,13 +288,22 @@ class FormulaRecognitionPredictor:
     """FormulaRecognitionAdapter::execute (:170-286) over PPFormulaNetModel: batches of `batch_size` crops -> FormulaPreprocessor -> the graph through the engine
     -> the unique 2-D int64 output -> filter_tokens -> truncation to max_length -> tokenizer decode -> normalize_latex.  A formula in which an id at or above
     the tokenizer's vocabulary size survives the filter comes back as an empty string.  The preprocessor's target size is the model's input size when the
-    file declares it (pp_formulanet.rs:340-353)."""
+    file declares it (pp_formulanet.rs:340-353).
 
-    def __init__(self, model: bytes, tokenizer, config: Optional[FormulaRecognitionConfig] = None, target_size: Optional[tuple] = None, device_id: int = 0):
+    stop_at_eos: the decode ends a chunk of 16 images once every one of them has emitted the tokenizer's eos instead of running all `M` steps of the Loop.
+    `predict` and `decode` give the same strings either way (the filter stops at a row's first eos; only ids after it differ: they read eos), and `M` is of the
+    order of 1536 where a formula has a few dozen to a few hundred tokens, so real use wants it on.  The default is off: `infer` then returns exactly what the
+    graph's Loop computes."""
+
+    def __init__(self, model: bytes, tokenizer, config: Optional[FormulaRecognitionConfig] = None, target_size: Optional[tuple] = None, device_id: int = 0,
+                 stop_at_eos: bool = False):
         self.config = config or FormulaRecognitionConfig()
         self.tokenizer = tokenizer if isinstance(tokenizer, FormulaTokenizer) else FormulaTokenizer.from_file(tokenizer)
         self.sos_token_id, self.eos_token_id = self.tokenizer.special_token_ids()
         self._eng = api.OrtInfer(model, device_id=device_id)
+        self.stop_at_eos = bool(stop_at_eos)
+        if self.stop_at_eos:
+            self._eng.set_decode_stop(self.eos_token_id)
         size = (384, 384) if target_size is None else (int(target_size[0]), int(target_size[1]))
         if size == (384, 384):
             dims = self._eng.primary_input_shape()
@@ -312,6 +322,10 @@ class FormulaRecognitionPredictor:
             seen = [(n, str(a.dtype), list(a.shape)) for n, a in outs]
             raise api.OCRError(api.OAR_INVALID_INPUT, f"invalid input: PP-FormulaNet: expected exactly one 2-D i64 output (token ids); found {len(ids)} candidate(s) among outputs {seen}")
         return ids[0]
+
+    def decode_stats(self) -> "api.DecodeStats":
+        """steps of the last `infer`: the Loop's limit, what the host enqueued and what did work on the device"""
+        return self._eng.decode_stats()
 
     def decode(self, token_ids: np.ndarray, config: Optional[FormulaRecognitionConfig] = None) -> List[str]:
         cfg = config or self.config

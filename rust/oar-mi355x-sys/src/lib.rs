@@ -121,6 +121,15 @@ pub struct oar_io_info {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
+pub struct oar_decode_stats {
+    pub steps_limit: i64,
+    pub steps_enqueued: i64,
+    pub steps_executed: i64,
+    pub lookahead: i64,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
 pub struct oar_det_cfg {
     pub device_id: i32,
     pub limit_side_len: u32,
@@ -335,6 +344,8 @@ unsafe extern "C" {
     pub fn oar_engine_io(e: *const oar_engine, inputs: *mut oar_io_info, max_in: i32, n_in: *mut i32, outputs: *mut oar_io_info, max_out: i32, n_out: *mut i32) -> oar_status;
     pub fn oar_engine_cost(e: *mut oar_engine, dims: *const i64, rank: i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
     pub fn oar_engine_cache_stats(e: *mut oar_engine, cached_plans: *mut u64, evicted_plans: *mut u64) -> oar_status;
+    pub fn oar_engine_set_decode_stop(e: *mut oar_engine, token: i64) -> oar_status;
+    pub fn oar_engine_decode_stats(e: *mut oar_engine, out: *mut oar_decode_stats) -> oar_status;
     pub fn oar_onnx_inspect(onnx: *const u8, onnx_len: usize, summary: *mut c_char, cap: usize) -> oar_status;
     pub fn oar_det_create(onnx: *const u8, onnx_len: usize, cfg: *const oar_det_cfg, out: *mut *mut oar_det) -> oar_status;
     pub fn oar_det_destroy(d: *mut oar_det);

@@ -1,6 +1,14 @@
 """Speed of the FormulaDecode operator on PP-FormulaNet-S- and -L-shaped heads: microseconds per decode step from the profiler's event intervals of
 class `formula_decode`, the weight bytes a step streams over that time, and the same math as an eager torch loop on the same card in the same process
-(alternating runs, medians).  Usage: python tools/formula_decode_bench.py [--reps 5] [--steps 64]"""
+(alternating runs, medians).  Usage: python tools/formula_decode_bench.py [--reps 5] [--steps 64]
+
+--stop adds the stop token of `OrtInfer.set_decode_stop` (one more JSON line per head, batch and mode, the modes alternating inside every repetition):
+  off      the setting off: all M steps run (the only mode of a build that has no stop token: `--lib` / a copy of this file in an older tree)
+  never    on, with a token the torch loop never emits: all M steps run and every poll point is paid -- the cost of the feature where it gains nothing
+  eighth   on, with the token of the torch loop's own output whose last first occurrence over the rows lies nearest M / 8
+  all      the three of them
+Per line: microseconds per step of class `formula_decode` (its total over M, and over the steps that did work), every repetition's figure, the wall time of an
+unprofiled `infer`, steps_executed and steps_enqueued.  --lib times another build of the library (e.g. one compiled with another -DOAR_FD_LOOKAHEAD)."""
 import argparse
 import json
 import sys
@@ -58,14 +66,35 @@ def torch_loop(w, mem, M):
     return run
 
 
+def pick_stop(tokens, V, where):
+    """(token, the step after which a chunk holding all rows ends) -- `never`: the lowest id that occurs nowhere; `eighth`: see the module docstring"""
+    B, M = tokens.shape
+    if where == "never":
+        return int(np.setdiff1d(np.arange(V), tokens.ravel())[0]), M - 1
+    best = None
+    for e in np.unique(tokens):
+        t_stop = max(int(np.nonzero(r == e)[0][0]) if np.any(r == e) else M - 1 for r in tokens)
+        if best is None or abs(t_stop - M // 8) < abs(best[1] - M // 8):
+            best = (int(e), t_stop)
+    return best
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--heads", default="S,L")
+    ap.add_argument("--stop", choices=["off", "never", "eighth", "all"], default=None)
+    ap.add_argument("--lib", default=None, help="time this build of the library instead of the tree's own")
     a = ap.parse_args()
+    if a.lib:
+        api.LIB_PATH = Path(a.lib).resolve()
     M = a.steps
+    has_stop = hasattr(api.OrtInfer, "set_decode_stop")
+    modes = [] if a.stop is None else ["off", "never", "eighth"] if a.stop == "all" else [a.stop]
+    if not has_stop:
+        modes = [m for m in modes if m == "off"]
     for name in a.heads.split(","):
         h = HEADS[name]
         w = models.formula_weights(h["D"], h["nh"], h["F"], h["V"], h["Ld"], M + 2, 0)
@@ -77,7 +106,8 @@ def main():
             mem = np.random.default_rng(B).standard_normal((B, h["S"], D)).astype(np.float32)
             loop = torch_loop(w, mem, M)
             ids = dict(eng.infer(mem))["token_ids"]
-            same = bool(np.array_equal(ids, loop().cpu().numpy()))
+            torch_ids = loop().cpu().numpy()
+            same = bool(np.array_equal(ids, torch_ids))
             ours, wall, theirs = [], [], []
             for _ in range(a.reps):
                 api.prof_reset()
@@ -98,6 +128,37 @@ def main():
             print(json.dumps({"head": name, "B": B, "M": M, "us_per_step_kernels": round(us, 1), "us_per_step_wall_profiled": round(float(np.median(wall)), 1),
                               "weight_MB_per_step": round(weight_bytes / 1e6, 1), "share_of_8TBps": round(weight_bytes / (us * 1e-6) / 8e12, 3),
                               "torch_eager_us_per_step": round(float(np.median(theirs)), 1), "tokens_equal_torch_f32": same}), flush=True)
+            if not modes:
+                continue
+            stops = {m: (None, M - 1) if m == "off" else pick_stop(torch_ids, V, m) for m in modes}
+            rec = {m: dict(us=[], wall=[], executed=[], enqueued=[]) for m in modes}
+            for _ in range(a.reps):
+                for m in modes:                                    # alternating: every repetition visits every mode
+                    if has_stop:
+                        eng.set_decode_stop(-1 if m == "off" else stops[m][0])
+                    api.prof_reset()
+                    api.prof_enable(True)
+                    eng.infer(mem)
+                    snap = {e["name"]: e for e in api.prof_snapshot()}
+                    api.prof_enable(False)
+                    rec[m]["us"].append(snap["formula_decode"]["total_ms"] * 1e3)
+                    t0 = time.perf_counter()
+                    eng.infer(mem)                                 # unprofiled: the wall time a caller sees
+                    rec[m]["wall"].append((time.perf_counter() - t0) * 1e3)
+                    st = eng.decode_stats() if has_stop else None
+                    rec[m]["executed"].append(st.steps_executed if st else M)
+                    rec[m]["enqueued"].append(st.steps_enqueued if st else M)
+            for m in modes:
+                r = rec[m]
+                tot = float(np.median(r["us"]))
+                print(json.dumps({"head": name, "B": B, "M": M, "mode": m, "stop_token": stops[m][0], "t_stop_expected": stops[m][1],
+                                  "us_per_step_kernels": round(tot / M, 2), "us_per_step_kernels_reps": [round(v / M, 2) for v in r["us"]],
+                                  "us_per_executed_step": round(tot / max(int(np.median(r["executed"])), 1), 2),
+                                  "formula_decode_ms": round(tot / 1e3, 3), "wall_ms": round(float(np.median(r["wall"])), 3), "wall_ms_reps": [round(v, 3) for v in r["wall"]],
+                                  "steps_executed": int(np.median(r["executed"])), "steps_enqueued": int(np.median(r["enqueued"])),
+                                  "lookahead": int(st.lookahead) if st else None}), flush=True)
+            if has_stop:
+                eng.set_decode_stop(-1)
         eng.close()
 
 
