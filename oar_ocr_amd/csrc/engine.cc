@@ -409,7 +409,9 @@ void Engine::match_sla_loop(const GNode& loop, GNode& lin_out, GNode& dec_out) {
 
 // -------------------------------------------------------------------------------------------------
 // Loop -> FormulaDecode.  The body contract: the greedy step of a pre-norm (MBart-order) transformer decoder with a key / value cache.
-// Carried: tok [B] int64, then K_l, V_l [B, nh, t, dh] per layer; from the outer scope KmT_l [B, nh, dh, S] and Vm_l [B, nh, S, dh].
+// Carried: tok [B] int64, then K_l [B, nh, t, dq], V_l [B, nh, t, dh] per layer; from the outer scope KmT_l [B, nh, dh, S] and Vm_l [B, nh, S, dh].
+// Squeeze attention (UniMERNet's MBart decoder): the SELF-attention queries and keys may be narrower than the values, Wq / Wk [nh dq, D] with 1 <= dq <= 128,
+// their Reshape targets [B, nh, 1, dq]; dq == dh is the plain head.  The cross attention is never squeezed.
 //   x = LN_emb(Gather(E_tok, tok) * s_emb + Gather(E_pos, i + c_pos))
 //   per layer:  y = LN1(x); q = lin(y) * dh^-0.5, k = lin(y), v = lin(y), each Reshape to [B, nh, 1, dh];  K' = Concat(K, k, 2), V' = Concat(V, v, 2)
 //               x = x + lin(Reshape(MatMul(Softmax(MatMul(q, Transpose(K', [0,1,3,2]))), V'), [B, D]))
@@ -520,18 +522,26 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
         if (!t || t->dtype == DType::F32 || t->i.empty()) L.bad(n, "the Reshape target must be a constant");
         return t->i;
     };
-    int64_t D = 0, nh = 0, dh = 0;
-    // v = Reshape(u, [B, nh, 1, dh]): returns u
-    auto split_heads = [&](const std::string& v, const char* role) -> std::string {
+    int64_t D = 0, nh = 0, dh = 0, dq = 0;
+    // v = Reshape(u, [B, nh, 1, dh]): returns u.  kind 0: a value / cross-attention projection, nh x dh = D.  kind 1: the cross-attention query, the same, with
+    // a word on squeeze attention where the product is not D.  kind 2: the self-attention query / key, [B, nh, 1, dq] with its own head size (squeeze attention:
+    // dq need not be dh; an entry <= 0 is inferred from D as for the others)
+    auto split_heads = [&](const std::string& v, const char* role, int kind = 0) -> std::string {
         const OnnxNode& n = L.expect(v, "Reshape", role);
         std::vector<int64_t> t = reshape_target(n);
         if (t.size() != 4 || t[2] != 1) L.bad(n, "must reshape to [B, heads, 1, head size]");
         int64_t a = t[1], b = t[3];
+        const bool explicit_qk = kind == 2 && a > 0 && b > 0;
         if (a <= 0 && b > 0 && D % b == 0) a = D / b;
         if (b <= 0 && a > 0 && D % a == 0) b = D / a;
-        if (a <= 0 || b <= 0 || a * b != D) L.bad(n, "heads x head size must be the model width " + std::to_string(D));
+        if (a <= 0 || b <= 0 || (a * b != D && !explicit_qk))
+            L.bad(n, "heads x head size must be the model width " + std::to_string(D) +
+                         (kind == 1 && a > 0 && b > 0 ? " (the cross-attention query is " + std::to_string(a * b) + " wide: squeeze attention is supported in the self-attention only)" : std::string()));
         if (nh == 0) { nh = a; dh = b; }
-        if (a != nh || b != dh) L.bad(n, "every projection must split into the same heads");
+        if (kind == 2) {
+            if (dq == 0) dq = b;
+            if (a != nh || b != dq) L.bad(n, "every projection must split into the same heads");
+        } else if (a != nh || b != dh) L.bad(n, "every projection must split into the same heads");
         return n.inputs[0];
     };
     // v = Reshape(MatMul(Softmax(MatMul(q4, keys), -1), values), [B, D]): returns q4 / keys / values
@@ -585,7 +595,7 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
         for (const std::string* m : {&keys, &values})
             if (L.producer.count(*m) || L.cst(*m) || std::find(body.inputs.begin(), body.inputs.end(), *m) != body.inputs.end()) L.refuse("layer " + std::to_string(l + 1) + ": the memory keys / values '" + *m + "' must come from the outer scope");
         Y.kmT = keys; Y.vm = values;
-        Y.cq = scaled_lin(split_heads(q4, "cross-attention query"), "cross-attention query", Y.cqm, Y.cqs);
+        Y.cq = scaled_lin(split_heads(q4, "cross-attention query", 1), "cross-attention query", Y.cqm, Y.cqs);
         Y.ln2 = layer_norm(Y.cq.x, "cross-attention LayerNorm");
         if (Y.ln2.x != x1) L.refuse("layer " + std::to_string(l + 1) + ": the cross-attention block must normalise its own residual '" + x1 + "'");
         // self attention over the cache
@@ -598,14 +608,15 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
         const OnnxNode& vcat = L.expect(Vout, "Concat", "new value cache");
         if (kcat.inputs.size() != 2 || kcat.ai("axis", 0) != 2 || kcat.inputs[0] != Kin) L.bad(kcat, "must be Concat('" + Kin + "', k, axis=2)");
         if (vcat.inputs.size() != 2 || vcat.ai("axis", 0) != 2 || vcat.inputs[0] != Vin) L.bad(vcat, "must be Concat('" + Vin + "', v, axis=2)");
-        Y.q = scaled_lin(split_heads(q4, "self-attention query"), "self-attention query", Y.qm, Y.qs);
-        Y.k = L.lin(split_heads(kcat.inputs[1], "self-attention key"), "self-attention key", 1);
+        Y.q = scaled_lin(split_heads(q4, "self-attention query", 2), "self-attention query", Y.qm, Y.qs);
+        Y.k = L.lin(split_heads(kcat.inputs[1], "self-attention key", 2), "self-attention key", 1);
+        if (Y.q.N != Y.k.N) L.refuse("layer " + std::to_string(l + 1) + ": the self-attention keys have " + std::to_string(Y.k.N) + " columns, the queries " + std::to_string(Y.q.N) + ": Wq and Wk must have the same row count");
         Y.v = L.lin(split_heads(vcat.inputs[1], "self-attention value"), "self-attention value", 1);
         Y.ln1 = layer_norm(Y.q.x, "self-attention LayerNorm");
         if (Y.k.x != Y.q.x || Y.v.x != Y.q.x || Y.ln1.x != x0) L.refuse("layer " + std::to_string(l + 1) + ": q, k and v must read LN1 of the block's residual '" + x0 + "'");
         if (l == Ld - 1) F = Y.f1.N;
         auto shp = [&](const Lin& a, int64_t N, int64_t K) { return a.N == N && a.K == K; };
-        if (!(shp(Y.q, D, D) && shp(Y.k, D, D) && shp(Y.v, D, D) && shp(Y.o, D, D) && shp(Y.cq, D, D) && shp(Y.co, D, D) && shp(Y.f1, F, D) && shp(Y.f2, D, F) &&
+        if (!(shp(Y.q, nh * dq, D) && shp(Y.k, nh * dq, D) && shp(Y.v, D, D) && shp(Y.o, D, D) && shp(Y.cq, D, D) && shp(Y.co, D, D) && shp(Y.f1, F, D) && shp(Y.f2, D, F) &&
               (int64_t)Y.ln1.g.size() == D && (int64_t)Y.ln2.g.size() == D && (int64_t)Y.ln3.g.size() == D))
             L.refuse("layer " + std::to_string(l + 1) + ": the weights do not have the shapes of a decoder layer with D = " + std::to_string(D) + ", F = " + std::to_string(F));
         x = x0;
@@ -644,7 +655,9 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
     if (Et.dims[0] != V || Et.dims[1] != D || Ep.dims[1] != D || (int64_t)lne.g.size() != D || (!lm.b.empty() && (int64_t)lm.b.size() != V))
         L.refuse("the embeddings and the output projection do not agree on V = " + std::to_string(V) + ", D = " + std::to_string(D));
     auto cl = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, 0), 1 << 26); };
-    if (nh < 1 || !k::formula_decode_supported(cl(D), cl(nh), cl(F), cl(V), cl(Ld), cl(M), 1) || c_pos < 0 || M + c_pos > P)
+    if (dq < 1 || dq > k::kFdMaxDh || nh * dq > k::kFdMaxD)
+        L.refuse("the self-attention queries and keys have head size " + std::to_string(dq) + " in " + std::to_string(nh) + " heads, outside 1 <= dq <= " + std::to_string(k::kFdMaxDh) + ", heads x dq <= " + std::to_string(k::kFdMaxD));
+    if (nh < 1 || !k::formula_decode_supported(cl(D), cl(nh), cl(F), cl(V), cl(Ld), cl(M), 1, cl(dq)) || c_pos < 0 || M + c_pos > P)
         L.refuse("D = " + std::to_string(D) + ", heads = " + std::to_string(nh) + ", F = " + std::to_string(F) + ", V = " + std::to_string(V) + ", Ld = " + std::to_string(Ld) + ", M = " + std::to_string(M) +
                  ", c_pos = " + std::to_string(c_pos) + ", P = " + std::to_string(P) + " is outside D <= " + std::to_string(k::kFdMaxD) + ", head size <= " + std::to_string(k::kFdMaxDh) + ", F <= " +
                  std::to_string(k::kFdMaxF) + ", 2 <= V < 2^24, 1 <= M <= " + std::to_string(k::kFdMaxM) + ", M + c_pos <= P");
@@ -695,7 +708,7 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
         return o;
     };
     auto cat3 = [](const std::vector<float>& a, const std::vector<float>& b, const std::vector<float>& c) { std::vector<float> o(a); o.insert(o.end(), b.begin(), b.end()); o.insert(o.end(), c.begin(), c.end()); return o; };
-    const int64_t Dp = (D + 3) / 4 * 4, Fp = (F + 3) / 4 * 4;
+    const int64_t Dp = (D + 3) / 4 * 4, Fp = (F + 3) / 4 * 4, Dq = nh * dq;
     dec_out = GNode();
     dec_out.op = "FormulaDecode";
     dec_out.in = {loop.in[2]};
@@ -710,7 +723,7 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
         Layer& Y = layers[l];
         const std::string s = "l" + std::to_string(l) + "_";
         dec_out.in.push_back(put(s + "ln1_g", {D}, Y.ln1.g)); dec_out.in.push_back(put(s + "ln1_b", {D}, Y.ln1.b));
-        dec_out.in.push_back(put(s + "w_qkv", {3 * D, Dp}, padded({&Y.q, &Y.k, &Y.v}))); dec_out.in.push_back(put(s + "b_qkv", {3 * D}, cat3(Y.q.b, Y.k.b, Y.v.b)));
+        dec_out.in.push_back(put(s + "w_qkv", {2 * Dq + D, Dp}, padded({&Y.q, &Y.k, &Y.v}))); dec_out.in.push_back(put(s + "b_qkv", {2 * Dq + D}, cat3(Y.q.b, Y.k.b, Y.v.b)));
         dec_out.in.push_back(put(s + "w_o", {D, Dp}, padded({&Y.o}))); dec_out.in.push_back(put(s + "b_o", {D}, Y.o.b));
         dec_out.in.push_back(put(s + "ln2_g", {D}, Y.ln2.g)); dec_out.in.push_back(put(s + "ln2_b", {D}, Y.ln2.b));
         dec_out.in.push_back(put(s + "w_cq", {D, Dp}, padded({&Y.cq}))); dec_out.in.push_back(put(s + "b_cq", {D}, Y.cq.b));
@@ -730,6 +743,7 @@ void Engine::match_formula_loop(const GNode& loop, const std::vector<GNode>& out
     if (with_logits) dec_out.out.push_back(loop.out[n_state + 1]);
     iattr("steps", M); iattr("layers", Ld); iattr("width", D); iattr("heads", nh); iattr("ffn", F); iattr("vocab", V); iattr("positions", P); iattr("c_pos", c_pos);
     iattr("lm_bias", lm.b.empty() ? 0 : 1);
+    if (dq != dh) iattr("qk_head", dq);   // (squeeze attention; absent: the head size)
     fattr("s_emb", s_emb); fattr("eps_e", lne.eps); fattr("eps_f", lnf.eps);
 }
 
@@ -1015,6 +1029,136 @@ void Engine::rewrite_graph(OnnxModel& m) {
         }
     }
 
+    // ---- pass 3b: the attention of a Swin block without shifted windows (UniMERNet's encoder), y [B, H W, C] with static H, W, ws, N = ws^2:
+    //   p = Reshape(y, [0, H/ws, ws, W/ws, ws, C]) -> Transpose[0,1,3,2,4,5] -> Reshape[-1, N, C]                     (window partition)
+    //   q, k, v = Linear(p);  qh, kh, vh = Transpose[0,2,1,3](Reshape(., [0, N, nh, dh]))
+    //   a = Softmax(Add(Div(MatMul(qh, Transpose[0,1,3,2](kh)), c) | Mul(.., c), bias [1, nh, N, N]), -1)
+    //   o = Linear(Reshape(Transpose[0,2,1,3](MatMul(a, vh)), [0, N, C]))
+    //   r = Reshape(o, [-1, H/ws, W/ws, ws, ws, C]) -> Transpose[0,1,3,2,4,5] -> Reshape[-1, H W, C]                    (window reverse)
+    // A Linear is per token, so the partition commutes with it: q, k, v read y in image order, ONE WindowAttention node (csrc/window_attention.hip) gathers and
+    // scatters a window's tokens by address, the projection runs on its output, and both the partition and the reverse triple leave the graph (18
+    // launches per block, four of them rank-6 copies of the whole token tensor, become 6).  Every intermediate must be single-use and no graph output.  It runs before
+    // pass 4 so that the block's residual Add folds into the projection.  OAR_FUSE_WINDOW_ATTENTION=0, a shape k::window_attention_supported rejects (every
+    // size is static here, so that is known at load time), the padded spelling (H or W no multiple of ws) and a masked (shifted) block keep the op-by-op route.
+    {
+        const char* fe = getenv("OAR_FUSE_WINDOW_ATTENTION");
+        const bool fuse = !fe || atoi(fe) != 0;
+        auto cons = consumers(nodes);
+        std::map<std::string, int> producer;
+        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
+        std::vector<bool> dead(nodes.size(), false);
+        auto prod = [&](const std::string& v, const char* op) -> int {
+            auto it = producer.find(v);
+            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op) return -1;
+            return it->second;
+        };
+        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
+        auto only_reader = [&](const std::string& v, const char* op) -> int {   // the single consumer of v, which must be a live `op` reading it first
+            if (!single_use(v)) return -1;
+            const int c = cons[v][0];
+            return !dead[c] && nodes[c].op == op && nodes[c].in[0] == v ? c : -1;
+        };
+        auto target = [&](const GNode& r) -> std::vector<int64_t> {
+            if (r.in.size() < 2 || r.ai("allowzero", 0) != 0) return {};
+            auto it = inits_.find(r.in[1]);
+            return it == inits_.end() || it->second.dtype == DType::F32 ? std::vector<int64_t>{} : it->second.i;
+        };
+        auto perm_is = [&](const GNode& t, std::initializer_list<int64_t> want) { return t.ais("perm") == std::vector<int64_t>(want); };
+        auto plain_linear = [&](const GNode& l, int64_t C) {
+            if (l.op != "Linear" || l.act.kind != k::ACT_NONE || !l.residual.empty() || l.in.size() < 2 || !is_init(l.in[1])) return false;
+            const HostTensor& w = inits_[l.in[1]];
+            return w.dims.size() == 2 && w.dims[0] == C && w.dims[1] == C;
+        };
+        for (int i = 0; fuse && i < (int)nodes.size(); ++i) {
+            if (nodes[i].op != "Softmax" || dead[i]) continue;
+            const GNode& sm = nodes[i];
+            const int64_t sax = sm.ai("axis", -1);
+            if (sax != -1 && sax != 3) continue;
+            // scores: Add(scaled, bias) in either order, scaled = Div(MatMul, c) or Mul(MatMul, c) / Mul(c, MatMul)
+            const int ad = prod(sm.in[0], "Add");
+            if (ad < 0 || !single_use(sm.in[0]) || !single_use(sm.out[0]) || nodes[ad].act.kind != k::ACT_NONE) continue;
+            const int bi = is_init(nodes[ad].in[1]) ? 1 : is_init(nodes[ad].in[0]) ? 0 : -1;
+            if (bi < 0) continue;
+            const HostTensor& bias = inits_[nodes[ad].in[bi]];
+            if (bias.dtype != DType::F32 || bias.dims.size() != 4 || bias.dims[0] != 1 || bias.dims[2] != bias.dims[3] || (int64_t)bias.f.size() != numel(bias.dims)) continue;
+            const int64_t nh = bias.dims[1], N = bias.dims[2];
+            const std::string& scaled = nodes[ad].in[1 - bi];
+            if (!single_use(scaled)) continue;
+            int sc = prod(scaled, "Div"), scale_div = 1, ci = 1;
+            if (sc < 0) { sc = prod(scaled, "Mul"); scale_div = 0; if (sc >= 0) ci = is_init(nodes[sc].in[1]) ? 1 : 0; }
+            if (sc < 0 || nodes[sc].act.kind != k::ACT_NONE || !is_init(nodes[sc].in[ci])) continue;
+            const HostTensor& sct = inits_[nodes[sc].in[ci]];
+            if (sct.dtype != DType::F32 || sct.f.size() != 1) continue;
+            const int mm1 = prod(nodes[sc].in[1 - ci], "MatMul");
+            if (mm1 < 0 || !single_use(nodes[sc].in[1 - ci])) continue;
+            const int mm2 = only_reader(sm.out[0], "MatMul");
+            if (mm2 < 0) continue;
+            // heads: Transpose[0,2,1,3](Reshape(Linear, [0, N, nh, dh])), the keys once more through Transpose[0,1,3,2]
+            const int tk = prod(nodes[mm1].in[1], "Transpose");
+            if (tk < 0 || !single_use(nodes[mm1].in[1]) || !perm_is(nodes[tk], {0, 1, 3, 2})) continue;
+            int64_t dh = 0;
+            int tr[3], rs[3], ln[3];
+            const std::string* hv[3] = {&nodes[mm1].in[0], &nodes[tk].in[0], &nodes[mm2].in[1]};
+            bool ok = true;
+            for (int t = 0; t < 3 && ok; ++t) {
+                tr[t] = prod(*hv[t], "Transpose");
+                ok = tr[t] >= 0 && single_use(*hv[t]) && perm_is(nodes[tr[t]], {0, 2, 1, 3});
+                if (!ok) break;
+                rs[t] = prod(nodes[tr[t]].in[0], "Reshape");
+                ok = rs[t] >= 0 && single_use(nodes[tr[t]].in[0]);
+                if (!ok) break;
+                const std::vector<int64_t> tg = target(nodes[rs[t]]);
+                ok = tg.size() == 4 && tg[0] == 0 && tg[1] == N && tg[2] == nh && tg[3] > 0 && (dh == 0 || tg[3] == dh);
+                if (!ok) break;
+                dh = tg[3];
+                ln[t] = prod(nodes[rs[t]].in[0], "Linear");
+                ok = ln[t] >= 0 && single_use(nodes[rs[t]].in[0]) && plain_linear(nodes[ln[t]], nh * dh);
+            }
+            if (!ok || ln[0] == ln[1] || ln[0] == ln[2] || ln[1] == ln[2]) continue;
+            const int64_t C = nh * dh;
+            // window partition: the three projections are the only readers of p
+            const std::string pv = nodes[ln[0]].in[0];
+            if (nodes[ln[1]].in[0] != pv || nodes[ln[2]].in[0] != pv || cons[pv].size() != 3 || graph_outs.count(pv)) continue;
+            const int p3 = prod(pv, "Reshape");
+            if (p3 < 0 || target(nodes[p3]) != std::vector<int64_t>{-1, N, C}) continue;
+            const int p2 = prod(nodes[p3].in[0], "Transpose");
+            if (p2 < 0 || !single_use(nodes[p3].in[0]) || !perm_is(nodes[p2], {0, 1, 3, 2, 4, 5})) continue;
+            const int p1 = prod(nodes[p2].in[0], "Reshape");
+            if (p1 < 0 || !single_use(nodes[p2].in[0])) continue;
+            const std::vector<int64_t> pt = target(nodes[p1]);
+            if (pt.size() != 6 || pt[0] != 0 || pt[1] <= 0 || pt[2] <= 0 || pt[3] <= 0 || pt[4] != pt[2] || pt[5] != C || pt[2] * pt[2] != N) continue;
+            const int64_t hb = pt[1], ws = pt[2], wb = pt[3], H = hb * ws, W = wb * ws;
+            if (!k::window_attention_supported((int)std::min<int64_t>(ws, 1 << 20), (int)std::min<int64_t>(nh, 1 << 20), (int)std::min<int64_t>(dh, 1 << 20))) continue;
+            // output side: Transpose[0,2,1,3] -> Reshape[0, N, C] -> Linear -> window reverse
+            const int t2 = only_reader(nodes[mm2].out[0], "Transpose");
+            if (t2 < 0 || !perm_is(nodes[t2], {0, 2, 1, 3})) continue;
+            const int r2 = only_reader(nodes[t2].out[0], "Reshape");
+            if (r2 < 0 || target(nodes[r2]) != std::vector<int64_t>{0, N, C}) continue;
+            const int pj = only_reader(nodes[r2].out[0], "Linear");
+            if (pj < 0 || !plain_linear(nodes[pj], C)) continue;
+            const int v1 = only_reader(nodes[pj].out[0], "Reshape");
+            if (v1 < 0 || target(nodes[v1]) != std::vector<int64_t>{-1, hb, wb, ws, ws, C}) continue;
+            const int v2 = only_reader(nodes[v1].out[0], "Transpose");
+            if (v2 < 0 || !perm_is(nodes[v2], {0, 1, 3, 2, 4, 5})) continue;
+            const int v3 = only_reader(nodes[v2].out[0], "Reshape");
+            if (v3 < 0 || target(nodes[v3]) != std::vector<int64_t>{-1, H * W, C}) continue;
+            GNode wa;
+            wa.op = "WindowAttention";
+            wa.in = {nodes[ln[0]].out[0], nodes[ln[1]].out[0], nodes[ln[2]].out[0], nodes[ad].in[bi]};
+            wa.out = {nodes[r2].out[0]};
+            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; wa.attrs[k] = a; };
+            iattr("ws", ws); iattr("H", H); iattr("W", W); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_div", scale_div);
+            Attr as; as.kind = Attr::F; as.f = sct.f[0]; wa.attrs["scale"] = as;
+            const std::string y = nodes[p1].in[0], out = nodes[v3].out[0];
+            for (int t = 0; t < 3; ++t) nodes[ln[t]].in[0] = y;
+            nodes[pj].out[0] = out;
+            for (int d : {p1, p2, p3, rs[0], rs[1], rs[2], tr[0], tr[1], tr[2], tk, mm1, sc, ad, i, mm2, t2, v1, v2, v3}) dead[d] = true;
+            nodes[r2] = std::move(wa);   // behind q, k and v, in front of the projection
+        }
+        std::vector<GNode> keep;
+        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
+        nodes.swap(keep);
+    }
     // ---- pass 4: Linear / Conv -> Add(residual): fold the residual into the producer's epilogue (no act between);
     // shapes are only known at plan time: op_conv / op_linear fall back to a separate add when they do not match
     {
@@ -3790,7 +3934,7 @@ struct Planner {
     // all steps are enqueued and skipped on the device.  The cost below stays the full-M figure: an upper bound in that mode.
     void op_formula_decode(const GNode& n) {
         const int64_t M = n.ai("steps", 0), Ld = n.ai("layers", 0), D = n.ai("width", 0), nh = n.ai("heads", 1), F = n.ai("ffn", 0), V = n.ai("vocab", 0), P = n.ai("positions", 0);
-        const int64_t dh = D / nh;
+        const int64_t dh = D / nh, dq = n.ai("qk_head", dh), Dq = nh * dq;
         const std::string& name = n.out[1];
         TInfo tok0 = get(n.in[0]);
         const int64_t B = numel(tok0.dims);
@@ -3811,6 +3955,7 @@ struct Planner {
         }
         k::FormulaDecodeP p{};
         p.B = (int)B; p.D = (int)D; p.nh = (int)nh; p.F = (int)F; p.V = (int)V; p.Ld = (int)Ld; p.S = (int)S; p.M = (int)M; p.P = (int)P; p.c_pos = (int)n.ai("c_pos", 0);
+        p.dq = (int)dq;
         p.s_emb = n.af("s_emb", 1.0f); p.eps_e = n.af("eps_e", 1e-5f); p.eps_f = n.af("eps_f", 1e-5f);
         size_t ci = (size_t)(1 + 2 * Ld);
         auto cw = [&]() -> const float* {
@@ -3830,7 +3975,7 @@ struct Planner {
         }
         p.lnf_g = cw(); p.lnf_b = cw(); p.w_lm = cw();
         p.b_lm = n.ai("lm_bias", 0) ? cw() : nullptr;
-        OAR_CHECK(k::formula_decode_supported((int)D, (int)nh, (int)F, (int)V, (int)Ld, (int)M, (int)S), OAR_UNSUPPORTED_OP, "Loop (" + name + "): shape outside the formula decode kernels' limits");
+        OAR_CHECK(k::formula_decode_supported((int)D, (int)nh, (int)F, (int)V, (int)Ld, (int)M, (int)S, (int)dq), OAR_UNSUPPORTED_OP, "Loop (" + name + "): shape outside the formula decode kernels' limits");
         TInfo& ty = new_out(n.out[1], {M, B}, Layout::NATIVE);
         ty.is_int = true;
         const Loc tl = ty.loc;
@@ -3838,11 +3983,12 @@ struct Planner {
         const bool with_logits = n.out.size() > 2 && !n.out[2].empty();
         if (with_logits) ll = new_out(n.out[2], {M, B, V}, Layout::NATIVE).loc;
         if (!n.out[0].empty()) alias_out(n.out[0], get(n.out[1]), {B}, Layout::NATIVE, (M - 1) * B * 4);   // the final token: the last row of the scan
-        Loc ws = alloc_temp(k::formula_decode_ws_floats((int)B, (int)D, (int)F, (int)V, (int)Ld, (int)M) * 4);
+        Loc ws = alloc_temp(k::formula_decode_ws_floats((int)B, (int)D, (int)F, (int)V, (int)Ld, (int)M, (int)Dq) * 4);
         const int64_t chunks = (B + k::kFdChunk - 1) / k::kFdChunk;
         const double Dp = (double)((D + 3) / 4 * 4), Fp = (double)((F + 3) / 4 * 4);
-        const double w_floats = Ld * (6.0 * D * Dp + F * Dp + D * Fp + 15.0 * D + F) + V * Dp + V + 4.0 * D;          // weights one step streams
-        const double macs = Ld * (6.0 * D * D + 2.0 * F * D + (double)S * D * 2.0 + (double)(M + 1) * D) + (double)V * D;   // per step and image (self attention at its mean length)
+        // (squeeze attention: Wq / Wk have Dq rows and the key cache is Dq wide; Dq == D gives the figures of the plain head)
+        const double w_floats = Ld * ((4.0 * D + 2.0 * Dq) * Dp + F * Dp + D * Fp + 13.0 * D + 2.0 * Dq + F) + V * Dp + V + 4.0 * D;          // weights one step streams
+        const double macs = Ld * ((4.0 * D + 2.0 * Dq) * D + 2.0 * F * D + (double)S * D * 2.0 + (double)(M + 1) * (Dq + D) / 2.0) + (double)V * D;   // per step and image (self attention at its mean length)
         this->P.decode_steps += M * chunks;
         Engine* const eng = &E;
         step([=](const RunCtx& c) {
@@ -4128,6 +4274,27 @@ struct Planner {
         } else {
             step(run, flops, bytes);
         }
+    }
+    // fused Swin window attention (rewrite pass 3b): q, k, v [B, H W, heads * head_dim] in image order, bias [1, heads, N, N] -> [B, H W, heads * head_dim] in image order
+    void op_window_attention(const GNode& n) {
+        TInfo q = get(n.in[0]), kk = get(n.in[1]), v = get(n.in[2]);
+        const TInfo& bt = get(n.in[3]);
+        const int64_t ws = n.ai("ws", 1), H = n.ai("H", 1), W = n.ai("W", 1), h = n.ai("heads", 1), d = n.ai("head_dim", 1), N = ws * ws, C = h * d;
+        OAR_CHECK(k::window_attention_supported((int)ws, (int)h, (int)d) && H % ws == 0 && W % ws == 0, OAR_INTERNAL, "WindowAttention: the rewrite let an unsupported shape through at " + n.out[0]);
+        OAR_CHECK(!q.host_int && !q.dims.empty() && q.dims.back() == C && numel(q.dims) % (H * W * C) == 0 && kk.dims == q.dims && v.dims == q.dims, OAR_SHAPE_MISMATCH,
+                  "WindowAttention: q, k and v must be [B, " + std::to_string(H * W) + ", " + std::to_string(C) + "] at " + n.out[0]);
+        OAR_CHECK(bt.ht && bt.loc.kind == Loc::CONST && (int64_t)bt.ht->f.size() == h * N * N, OAR_INTERNAL, "WindowAttention: the bias is not a constant of heads x N x N values at " + n.out[0]);
+        const int64_t B = numel(q.dims) / (H * W * C);
+        OAR_CHECK(B >= 1 && B * H * W < (int64_t)1 << 31, OAR_SHAPE_MISMATCH, "WindowAttention: batch out of range at " + n.out[0]);
+        Loc ql = to_native_loc(q), kl = to_native_loc(kk), vl = to_native_loc(v);
+        TInfo& y = new_out(n.out[0], {B, H * W, C}, Layout::NATIVE);   // (what the window reverse's Reshape [-1, H W, C] gives, whatever the rank of q)
+        Loc yl = y.loc;
+        k::WindowAttnP p{};
+        p.bias = bt.loc.cptr; p.ldq = p.ldk = p.ldv = p.ldo = (int)C; p.B = (int)B; p.H = (int)H; p.W = (int)W; p.ws = (int)ws; p.nh = (int)h; p.dh = (int)d;
+        p.scale = n.af("scale", 1.0f); p.scale_div = (int)n.ai("scale_div", 0);
+        const double tokens = (double)B * H * W;
+        step([=](const RunCtx& c) { k::WindowAttnP r = p; r.q = c.at(ql); r.k = c.at(kl); r.v = c.at(vl); r.o = c.mut(yl); k::window_attention(c.s, r); },
+             4.0 * tokens * N * C, 4.0 * (4.0 * tokens * C + tokens / N * h * N * N));
     }
     bool E_opset13() const { return opset >= 13 || opset == 0; }
     int64_t opset = 17;
@@ -4468,6 +4635,7 @@ struct Planner {
         if (op == "MatMul") return op_matmul(n);
         if (op == "Softmax") return op_softmax(n);
         if (op == "Attention") return op_attention(n);
+        if (op == "WindowAttention") return op_window_attention(n);
         if (op == "SLADecode") return op_sla_decode(n);
         if (op == "FormulaDecode") return op_formula_decode(n);
         if (op == "SEGate") return op_se_gate(n);

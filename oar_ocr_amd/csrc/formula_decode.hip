@@ -5,6 +5,7 @@
 // boundary is the all-to-all seam each LayerNorm / GEMV pair needs.  There is no grid-wide barrier and no flag in global memory: nothing here
 // ever waits on another workgroup.  Per step (t = 0 .. M-1) and chunk of <= 16 images, 8 Ld + 2 launches:
 //   per layer   1 fd_rows        LN1 -> [Wq ; Wk ; Wv] (one stacked matrix): q to its row buffer, k / v straight into the cache at position t
+//                                (squeeze attention: Wq / Wk have Dq = nh dq rows, 1 <= dq <= 128 whatever dh is, the key cache is dq wide per head, the value cache dh)
 //               2 fd_self_attn   softmax(q K'^T) V' over the t + 1 cached positions, one workgroup per (image, head)
 //               3 fd_rows        Wo + bias + residual
 //               4 fd_rows        LN2 -> Wcq (the query scale where the graph had it)
@@ -57,7 +58,7 @@ struct FdRowsP {
     const float* res;                    // residual [B][y_ld] or null (may alias y)
     int gelu;
     int scale_mode; float scale; int scale_rows;   // rows < scale_rows: 1 = (v + b) * s, 2 = v * s + b
-    float *kc, *vc; int D, dh, M, t;     // FD_QKV: rows [D, 2D) -> kc[b][head][t][d], [2D, 3D) -> vc
+    float *kc, *vc; int Dq, dq, dh, nh, M, t;   // FD_QKV: rows [Dq, 2Dq) -> kc[b][head][t][dq], [2Dq, 2Dq + D) -> vc[b][head][t][dh]
     float* logits;                       // FD_LM: [B][N] or null
     float2* part; int nwg;               // FD_LM: part[b][workgroup] = (value, index)
     const int* alive;                    // stop token on: images of the chunk still decoding (0: return at once); null: off
@@ -177,10 +178,10 @@ __device__ __forceinline__ void fd_rows_body(const FdRowsP& p) {
             if (p.bias) v = v + bias;
             if (sm == 1) v = v * p.scale;
             if (p.gelu) v = apply_act(v, ACT_GELU_ERF, 0.f, 0.f);
-            if (MODE == FD_QKV && row >= p.D) {
-                const int which = row >= 2 * p.D, n = row - (which ? 2 : 1) * p.D, head = n / p.dh, d = n - head * p.dh;
+            if (MODE == FD_QKV && row >= p.Dq) {
+                const int which = row >= 2 * p.Dq, n = row - (which ? 2 : 1) * p.Dq, w = which ? p.dh : p.dq, head = n / w, d = n - head * w;
                 float* cache = which ? p.vc : p.kc;
-                cache[(((size_t)eb * (p.D / p.dh) + head) * p.M + p.t) * p.dh + d] = v;
+                cache[(((size_t)eb * p.nh + head) * p.M + p.t) * w + d] = v;
             } else {
                 if (p.res) v = p.res[(size_t)eb * p.y_ld + row] + v;
                 p.y[(size_t)eb * p.y_ld + row] = v;
@@ -210,12 +211,13 @@ __global__ __launch_bounds__(kFdThreads) void fd_qkv_rows_kernel(FdRowsP p) { fd
 template <int NB>
 __global__ __launch_bounds__(kFdThreads) void fd_lm_head_kernel(FdRowsP p) { fd_rows_body<NB, FD_LM>(p); }
 
-// softmax(q K^T) V of one (image, head): key element (j, d) at kb[j * ks_j + d * ks_d], value row j at vb + j * dh; n positions
+// softmax(q K^T) V of one (image, head): key element (j, d) at kb[j * ks_j + d * ks_d], d < dq (the q . k width); value row j at vb + j * dh; n positions.
+// q is [B][nh dq] within rows of q_ld floats, o is [B][nh dh].  Both widths are run-time fields: squeeze attention (dq < dh) runs the same code object
 struct FdAttnP {
     const float* q; int q_ld;            // [B][D]
     const float *kb, *vb;                // image 0, head 0
     size_t k_img, k_head, v_img, v_head; // strides in floats
-    int ks_j, ks_d, n, dh;
+    int ks_j, ks_d, n, dq, dh;
     float* o; int o_ld;                  // [B][D]
     const int* alive;                    // as FdRowsP::alive
 };
@@ -227,16 +229,16 @@ __device__ __forceinline__ void fd_attn_body(const FdAttnP& p) {
     __shared__ float red[kFdAttnThreads / 64];
     if (p.alive && *p.alive == 0) return;
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, head = (int)blockIdx.x, b = (int)blockIdx.y;
-    const int n = p.n, dh = p.dh;
+    const int n = p.n, dq = p.dq, dh = p.dh;
     const float* kb = p.kb + (size_t)b * p.k_img + (size_t)head * p.k_head;
     const float* vb = p.vb + (size_t)b * p.v_img + (size_t)head * p.v_head;
-    if (tid < dh) qs[tid] = p.q[(size_t)b * p.q_ld + head * dh + tid];
+    if (tid < dq) qs[tid] = p.q[(size_t)b * p.q_ld + head * dq + tid];
     __syncthreads();
     float m = -INFINITY;
     for (int j = tid; j < n; j += kFdAttnThreads) {
         float a = 0.0f;
         const float* kr = kb + (size_t)j * p.ks_j;
-        for (int d = 0; d < dh; ++d) a = fmaf(qs[d], kr[(size_t)d * p.ks_d], a);
+        for (int d = 0; d < dq; ++d) a = fmaf(qs[d], kr[(size_t)d * p.ks_d], a);
         sc[j] = a;
         m = fmaxf(m, a);
     }
@@ -443,29 +445,30 @@ void launch_rows(hipStream_t s, FdRowsP p) {
 
 }  // namespace
 
-bool formula_decode_supported(int D, int nh, int F, int V, int Ld, int M, int S) {
-    return nh >= 1 && D >= nh && D % nh == 0 && D <= kFdMaxD && D / nh <= kFdMaxDh && F >= 1 && F <= kFdMaxF && Ld >= 1 && Ld <= kFdMaxLayers && V >= 2 && V < kFdMaxV &&
+bool formula_decode_supported(int D, int nh, int F, int V, int Ld, int M, int S, int dq) {
+    return nh >= 1 && D >= nh && D % nh == 0 && D <= kFdMaxD && D / nh <= kFdMaxDh && dq >= 1 && dq <= kFdMaxDh && nh * dq <= kFdMaxD && F >= 1 && F <= kFdMaxF && Ld >= 1 && Ld <= kFdMaxLayers && V >= 2 && V < kFdMaxV &&
            M >= 1 && M <= kFdMaxM && S >= 1 && S <= kFdMaxS;
 }
 int formula_decode_lm_workgroups(int V) { return wgs_for(V); }
 int formula_decode_launches_per_step(int Ld) { return 8 * Ld + 2; }
 
-size_t formula_decode_ws_floats(int B, int D, int F, int V, int Ld, int M) {
+size_t formula_decode_ws_floats(int B, int D, int F, int V, int Ld, int M, int Dq) {
     const size_t bc = (size_t)std::min(B, kFdChunk);
-    // caches | x q o [bc][D] each | h [bc][F] | tok [bc] | partials [bc][wgs] float2
-    return 2 * (size_t)Ld * bc * (size_t)M * D + 3 * bc * D + bc * (size_t)F + 16 + 2 * bc * (size_t)wgs_for(V) + 16;
+    // caches (keys Dq wide, values D) | x o [bc][D] each, q [bc][max(D, Dq)] | h [bc][F] | tok [bc] | partials [bc][wgs] float2
+    return (size_t)Ld * bc * (size_t)M * ((size_t)Dq + D) + 2 * bc * D + bc * (size_t)std::max(D, Dq) + bc * (size_t)F + 16 + 2 * bc * (size_t)wgs_for(V) + 16;
 }
 
 void formula_decode(hipStream_t s, const FormulaDecodeP& p) {
-    const int D = p.D, nh = p.nh, dh = D / nh, F = p.F, V = p.V, Ld = p.Ld, M = p.M, S = p.S;
-    OAR_CHECK(formula_decode_supported(D, nh, F, V, Ld, M, S) && p.c_pos >= 0 && (int64_t)M + p.c_pos <= p.P, OAR_UNSUPPORTED_OP, "FormulaDecode: shape outside the kernels' limits");
+    const int D = p.D, nh = p.nh, dh = D / nh, dq = p.dq, Dq = nh * dq, F = p.F, V = p.V, Ld = p.Ld, M = p.M, S = p.S;
+    OAR_CHECK(formula_decode_supported(D, nh, F, V, Ld, M, S, dq) && p.c_pos >= 0 && (int64_t)M + p.c_pos <= p.P, OAR_UNSUPPORTED_OP, "FormulaDecode: shape outside the kernels' limits");
     if (p.B <= 0) return;
     const int bc_max = std::min(p.B, kFdChunk);
-    const size_t cache_l = (size_t)bc_max * M * D;   // one layer's K (or V) cache: [bc][nh][M][dh]
+    const size_t kcache_l = (size_t)bc_max * M * Dq, vcache_l = (size_t)bc_max * M * D;   // one layer's caches: K [bc][nh][M][dq], V [bc][nh][M][dh]
     float* kc0 = p.ws;
-    float* x = kc0 + 2 * (size_t)Ld * cache_l;
+    float* x = kc0 + (size_t)Ld * (kcache_l + vcache_l);
+    const int q_ld = std::max(D, Dq);   // the row buffer of the self-attention query (Dq wide; dq may exceed dh) and of the cross-attention query (D wide)
     float* q = x + (size_t)bc_max * D;
-    float* o = q + (size_t)bc_max * D;
+    float* o = q + (size_t)bc_max * q_ld;
     float* h = o + (size_t)bc_max * D;
     const size_t part_off = ((size_t)(h - p.ws) + (size_t)bc_max * F + 1) & ~(size_t)1;   // 8-byte aligned (ws is)
     float2* part = reinterpret_cast<float2*>(p.ws + part_off);
@@ -497,17 +500,18 @@ void formula_decode(hipStream_t s, const FormulaDecodeP& p) {
             }
             for (int l = 0; l < Ld; ++l) {
                 const FdLayerP& L = p.layer[l];
-                float* kc = kc0 + (size_t)(2 * l) * cache_l;
-                float* vc = kc + cache_l;
+                float* kc = kc0 + (size_t)l * (kcache_l + vcache_l);
+                float* vc = kc + kcache_l;
                 FdRowsP r{};
-                r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = 3 * D; r.W = L.w_qkv; r.bias = L.b_qkv; r.ln_g = L.ln1_g; r.ln_b = L.ln1_b; r.eps = L.eps1;
-                r.y = q; r.y_ld = D; r.scale_mode = L.q_scale_mode; r.scale = L.q_scale; r.scale_rows = D; r.kc = kc; r.vc = vc; r.D = D; r.dh = dh; r.M = M; r.t = t;
+                r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = 2 * Dq + D; r.W = L.w_qkv; r.bias = L.b_qkv; r.ln_g = L.ln1_g; r.ln_b = L.ln1_b; r.eps = L.eps1;
+                r.y = q; r.y_ld = q_ld; r.scale_mode = L.q_scale_mode; r.scale = L.q_scale; r.scale_rows = Dq; r.kc = kc; r.vc = vc; r.Dq = Dq; r.dq = dq; r.dh = dh; r.nh = nh; r.M = M; r.t = t;
                 r.alive = alive; launch_rows<FD_QKV>(s, r);
                 FdAttnP a{};
-                a.q = q; a.q_ld = D; a.kb = kc; a.vb = vc; a.k_img = a.v_img = (size_t)M * D; a.k_head = a.v_head = (size_t)M * dh; a.ks_j = dh; a.ks_d = 1; a.n = t + 1; a.dh = dh;
+                a.q = q; a.q_ld = q_ld; a.kb = kc; a.vb = vc; a.k_img = (size_t)M * Dq; a.v_img = (size_t)M * D; a.k_head = (size_t)M * dq; a.v_head = (size_t)M * dh; a.ks_j = dq; a.ks_d = 1; a.n = t + 1;
+                a.dq = dq; a.dh = dh;
                 a.o = o; a.o_ld = D; a.alive = alive;
                 {
-                    ProfScope ps(s, "formula_decode", 4.0 * bc * (2.0 * (t + 1) * D + 2 * D), 4.0 * bc * (double)(t + 1) * D);
+                    ProfScope ps(s, "formula_decode", 4.0 * bc * ((double)(t + 1) * (Dq + D) + Dq + D), 2.0 * bc * (double)(t + 1) * (Dq + D));
                     hipLaunchKernelGGL(fd_self_attn_kernel, dim3((unsigned)nh, (unsigned)bc), dim3(kFdAttnThreads), 0, s, a);
                 }
                 r = FdRowsP{};
@@ -515,11 +519,11 @@ void formula_decode(hipStream_t s, const FormulaDecodeP& p) {
                 r.alive = alive; launch_rows<FD_PLAIN>(s, r);
                 r = FdRowsP{};
                 r.x = x; r.x_ld = D; r.B = bc; r.K = D; r.N = D; r.W = L.w_cq; r.bias = L.b_cq; r.ln_g = L.ln2_g; r.ln_b = L.ln2_b; r.eps = L.eps2;
-                r.y = q; r.y_ld = D; r.scale_mode = L.cq_scale_mode; r.scale = L.cq_scale; r.scale_rows = D;
+                r.y = q; r.y_ld = q_ld; r.scale_mode = L.cq_scale_mode; r.scale = L.cq_scale; r.scale_rows = D;
                 r.alive = alive; launch_rows<FD_PLAIN>(s, r);
                 a = FdAttnP{};
-                a.q = q; a.q_ld = D; a.kb = L.kmT + (size_t)c0 * D * S; a.vb = L.vm + (size_t)c0 * D * S; a.k_img = a.v_img = (size_t)D * S; a.k_head = a.v_head = (size_t)dh * S;
-                a.ks_j = 1; a.ks_d = S; a.n = S; a.dh = dh; a.o = o; a.o_ld = D; a.alive = alive;
+                a.q = q; a.q_ld = q_ld; a.kb = L.kmT + (size_t)c0 * D * S; a.vb = L.vm + (size_t)c0 * D * S; a.k_img = a.v_img = (size_t)D * S; a.k_head = a.v_head = (size_t)dh * S;
+                a.ks_j = 1; a.ks_d = S; a.n = S; a.dq = dh; a.dh = dh; a.o = o; a.o_ld = D; a.alive = alive;
                 {
                     ProfScope ps(s, "formula_decode", 4.0 * bc * (2.0 * S * D + 2 * D), 4.0 * bc * (double)S * D);
                     hipLaunchKernelGGL(fd_cross_attn_kernel, dim3((unsigned)nh, (unsigned)bc), dim3(kFdAttnThreads), 0, s, a);

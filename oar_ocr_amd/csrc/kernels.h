@@ -193,9 +193,9 @@ void sla_decode(hipStream_t s, const SlaDecodeP& p);
 // formula_decode.hip: the greedy decode of a PP-FormulaNet-style head (pre-norm transformer decoder with a key / value cache), `M` steps of
 // 8 Ld + 2 short launches each per chunk of <= kFdChunk images (no grid-wide barrier; see the file's header for the chain).
 //   tok0 [B] (f32-coded start token); e_tok [V][D], e_pos [P][D]; per layer the matrices with rows padded to a multiple of four floats:
-//   w_qkv [3D][Dp] = Wq ; Wk ; Wv with b_qkv [3D], w_o / w_cq / w_co [D][Dp], w_1 [F][Dp], w_2 [D][Fp]; kmT [B][nh][dh][S], vm [B][nh][S][dh];
+//   w_qkv [2Dq + D][Dp] = Wq ; Wk ; Wv with b_qkv [2Dq + D] (Dq = nh dq: the q . k width of squeeze attention, dq = D / nh without it), w_o / w_cq / w_co [D][Dp], w_1 [F][Dp], w_2 [D][Fp]; kmT [B][nh][dh][S], vm [B][nh][S][dh];
 //   w_lm [V][Dp], b_lm [V] or null.  q_scale_mode / cq_scale_mode: 0 none, 1 (x W^T + b) * s, 2 (x W^T) * s + b -- where the graph had the Mul.
-//   -> tokens [M][B] (f32-coded), logits [M][B][V] when not null.  ws: formula_decode_ws_floats(...) floats of scratch (caches [l][k|v][b][nh][M][dh] + rows).
+//   -> tokens [M][B] (f32-coded), logits [M][B][V] when not null.  ws: formula_decode_ws_floats(...) floats of scratch (caches [l]{k [b][nh][M][dq], v [b][nh][M][dh]} + rows).
 constexpr int kFdMaxD = 1024, kFdMaxDh = 128, kFdMaxF = 4096, kFdMaxLayers = 12, kFdMaxV = 1 << 24, kFdMaxM = 4096, kFdMaxS = 4096, kFdChunk = 16;
 struct FdLayerP {
     const float *ln1_g, *ln1_b, *w_qkv, *b_qkv, *w_o, *b_o, *ln2_g, *ln2_b, *w_cq, *b_cq, *w_co, *b_co, *ln3_g, *ln3_b, *w_1, *b_1, *w_2, *b_2;
@@ -224,6 +224,7 @@ struct FdStop {
 struct FdRunStats { int64_t steps_limit = 0, steps_enqueued = 0; };
 struct FormulaDecodeP {
     int B, D, nh, F, V, Ld, S, M, P, c_pos;
+    int dq;                              // head width of the self-attention queries / keys, 1 <= dq <= kFdMaxDh, nh dq <= kFdMaxD; below, at or above D / nh (D / nh: no squeeze)
     float s_emb, eps_e, eps_f;
     const float *tok0, *e_tok, *e_pos, *lne_g, *lne_b, *lnf_g, *lnf_b, *w_lm, *b_lm;
     FdLayerP layer[kFdMaxLayers];
@@ -231,11 +232,29 @@ struct FormulaDecodeP {
     FdStop* stop;                        // null: off
     FdRunStats* stats;                   // null, or the counters this call adds to (host side only)
 };
-bool formula_decode_supported(int D, int nh, int F, int V, int Ld, int M, int S);
+bool formula_decode_supported(int D, int nh, int F, int V, int Ld, int M, int S, int dq);
 int formula_decode_lm_workgroups(int V);          // (value, index) partials per image of the arg max
 int formula_decode_launches_per_step(int Ld);     // 8 Ld + 2, per chunk of kFdChunk images
-size_t formula_decode_ws_floats(int B, int D, int F, int V, int Ld, int M);
+size_t formula_decode_ws_floats(int B, int D, int F, int V, int Ld, int M, int Dq);
 void formula_decode(hipStream_t s, const FormulaDecodeP& p);
+// window_attention.hip: the attention of one Swin block without shifted windows, one launch.  q, k, v [B H W][nh dh] in IMAGE order (token (b, y, x) is row
+// (b H + y) W + x, row strides ldq / ldk / ldv floats), bias [nh][N][N] with N = ws^2 (the relative-position bias, added to the scaled scores);
+// o [B H W][nh dh] in image order.  A window's tokens are gathered and scattered by address: no partitioned copy exists.  H % ws == W % ws == 0.
+// scale_div: scores / scale (the graph's Div) instead of scores * scale (its Mul).
+struct WindowAttnP {
+    const float *q, *k, *v, *bias;
+    float* o;
+    int ldq, ldk, ldv, ldo;
+    int B, H, W, ws, nh, dh;
+    float scale; int scale_div;
+};
+constexpr int kWinThreads = 256, kWinWaves = kWinThreads / 64, kWinMaxN = 256, kWinMaxDh = 64, kWinMaxNd = 8192;
+bool window_attention_supported(int ws, int heads, int head_dim);   // N = ws^2 <= kWinMaxN, head_dim <= kWinMaxDh, N head_dim <= kWinMaxNd
+// the kernel's LDS, all of it dynamic: K [N][dh | 1], V [N][dh], one q row and one row of probabilities per wave (tests/test_unimernet_cpu.py compiles this)
+inline size_t window_attention_lds_bytes(int N, int head_dim) {
+    return ((size_t)N * (size_t)(head_dim | 1) + (size_t)N * head_dim + (size_t)kWinWaves * kWinMaxDh + (size_t)kWinWaves * N) * sizeof(float);
+}
+void window_attention(hipStream_t s, const WindowAttnP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

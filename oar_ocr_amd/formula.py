@@ -1,5 +1,6 @@
 """Formula recognition: `FormulaRecognitionAdapter` (domain/adapters/formula_recognition_adapter.rs) over `PPFormulaNetModel`
-(models/recognition/pp_formulanet.rs) with `FormulaPreprocessor` and `normalize_latex` (processors/formula_preprocess.rs).
+(models/recognition/pp_formulanet.rs) with `FormulaPreprocessor` and `normalize_latex` (processors/formula_preprocess.rs), and over `UniMERNetModel`
+(models/recognition/unimernet.rs) with `UniMERNetPreprocessor` (processors/unimernet_preprocess.rs): `FormulaRecognitionPredictor(model_type="unimernet")`.
 
 A PP-FormulaNet file is one ONNX graph from image to token ids: the greedy decode sits inside it as a Loop, which the engine runs as its FormulaDecode
 operator (csrc/formula_decode.hip).  Everything here is host orchestration around `api.OrtInfer`: margin crop, Triangle resize through the
@@ -9,7 +10,8 @@ images once each of them has emitted eos (`api.OrtInfer.set_decode_stop`) and fi
 
 Not pinned against the reference's dependencies: `to_luma8` of a pixel that is not grey (the image crate's integer weights are restated here from its
 documentation: (2126 R + 7152 G + 722 B) / 10000; a grey pixel maps to itself under any weights that sum to one), and the spelling of the real
-`pp-formulanet*.onnx` files.  Tokenizers whose decoder is not ByteLevel and the UniMERNet preprocessor are not built."""
+`pp-formulanet*.onnx` and `unimernet.onnx` files, and what the image crate does when a resize target truncates to 0 pixels (here: an
+all-white canvas for UniMERNet, an all-black one for PP-FormulaNet).  Tokenizers whose decoder is not ByteLevel are not built."""
 from __future__ import annotations
 
 import json
@@ -148,6 +150,117 @@ class FormulaPreprocessor:
             img = np.ascontiguousarray(img, np.uint8)
             t[i, 0, :th, :tw] = self.normalize_and_to_grayscale(self.resize_and_pad(self.crop_margin(img)))
         return t
+
+
+class UniMERNetPreprocessor:
+    """unimernet_preprocess.rs:43-281.  target_size is (width, height), as in the reference.  Other than FormulaPreprocessor: the margin crop has no
+    `min_x >= max_x` fall-back (a single dark pixel crops to 1 x 1), the resize brings the SMALLER side to min(target) and shrinks a second time only when a side
+    still exceeds the target, the canvas is white, grey comes before the normalisation, and the tensor is exactly the padded target."""
+
+    def __init__(self, target_size=(672, 192), crop_threshold: int = 200, padding_multiple: int = 32, normalize_mean=(0.7931, 0.7931, 0.7931),
+                 normalize_std=(0.1738, 0.1738, 0.1738)):
+        self.target_size = (int(target_size[0]), int(target_size[1]))
+        self.crop_threshold = int(crop_threshold)
+        self.padding_multiple = int(padding_multiple)
+        self.mean = np.asarray(normalize_mean, np.float32)
+        self.std = np.asarray(normalize_std, np.float32)
+
+    def crop_rect(self, img: np.ndarray):
+        """:50-121 -> (x, y, w, h) of the inclusive foreground box, or None where the reference returns the image as it is"""
+        gray = to_luma8(img)
+        if gray.size == 0:
+            return None
+        mn, mx = gray.min(), gray.max()
+        if mx == mn:                                                                               # :69
+            return None
+        norm = _as_u8((gray.astype(np.float32) - F(mn)) / F(F(mx) - F(mn)) * F(255.0))            # :78-80
+        ys, xs = np.nonzero(norm < self.crop_threshold)
+        if ys.size == 0:                                                                           # :114
+            return None
+        x0, x1, y0, y1 = int(xs.min()), int(xs.max()), int(ys.min()), int(ys.max())
+        return x0, y0, x1 - x0 + 1, y1 - y0 + 1                                                    # :119
+
+    def crop_margin(self, img: np.ndarray) -> np.ndarray:
+        r = self.crop_rect(img)
+        if r is None:
+            return img
+        x, y, w, h = r
+        return np.ascontiguousarray(img[y:y + h, x:x + w])
+
+    def resized_sizes(self, w: int, h: int):
+        """:125-158 -> ((new_width, new_height), (final_width, final_height) or None): f32 scales, truncating casts; the second resize only when the first
+        leaves a side above the target"""
+        tw, th = self.target_size
+        scale = F(F(min(tw, th)) / F(w if w <= h else h))
+        nw, nh = _as_u32(F(F(w) * scale)), _as_u32(F(F(h) * scale))
+        if not (nw > tw or nh > th):
+            return (nw, nh), None
+        s2 = min(F(F(tw) / F(nw)), F(F(th) / F(nh)))
+        return (nw, nh), (_as_u32(F(F(nw) * s2)), _as_u32(F(F(nh) * s2)))
+
+    @staticmethod
+    def _resize(img: np.ndarray, nw: int, nh: int) -> np.ndarray:
+        h, w = img.shape[:2]
+        if (nw, nh) == (w, h):                         # (a Triangle resize to the same size is the identity)
+            return img[..., :3]
+        if w == 1 and h == 1:                          # (one source pixel: every output pixel is that pixel, whatever the filter)
+            return np.broadcast_to(img[0, 0, :3], (nh, nw, 3)).copy()
+        return api.k_resize_triangle(img, nw, nh)
+
+    def resize_unimernet(self, img: np.ndarray):
+        """:125-161 -> RGB, or None when a side is or truncates to 0 (what the image crate does then is not pinned: the canvas stays white)"""
+        h, w = img.shape[:2]
+        if w == 0 or h == 0:
+            return None
+        for size in self.resized_sizes(w, h):
+            if size is None:
+                break
+            if size[0] == 0 or size[1] == 0:
+                return None
+            img = self._resize(np.ascontiguousarray(img), size[0], size[1])
+        return img
+
+    def add_padding(self, img) -> np.ndarray:
+        """:164-188 -> RGB [th, tw, 3], the image centred on white (delta // 2 left and top)"""
+        tw, th = self.target_size
+        out = np.full((th, tw, 3), 255, np.uint8)
+        if img is None:
+            return out
+        h, w = img.shape[:2]
+        left, top = max(tw - w, 0) // 2, max(th - h, 0) // 2
+        hh, ww = min(h, th - top), min(w, tw - left)                                               # :182
+        out[top:top + hh, left:left + ww] = img[:hh, :ww, :3]
+        return out
+
+    def padded_size(self):
+        """:209-211 -> (padded_height, padded_width)"""
+        tw, th = self.target_size
+        m = self.padding_multiple
+        return -(-th // m) * m, -(-tw // m) * m
+
+    def border_value(self) -> np.float32:
+        """:235-236 the normalised white that fills the tensor outside the image"""
+        return F(F(F(1.0) - self.mean[0]) / self.std[0])
+
+    def image_to_tensor(self, img: np.ndarray) -> np.ndarray:
+        """:205-249 -> [Hp, Wp] f32: grey = (0.299 r + 0.587 g + 0.114 b) / 255 summed left to right, then (grey - mean[0]) / std[0]"""
+        h, w = img.shape[:2]
+        ph, pw = self.padded_size()
+        t = np.full((ph, pw), self.border_value(), np.float32)
+        c = np.asarray(img, np.uint8).astype(np.float32)
+        grey = ((F(0.299) * c[..., 0] + F(0.587) * c[..., 1]) + F(0.114) * c[..., 2]) / F(255.0)
+        t[:h, :w] = (grey - self.mean[0]) / self.std[0]
+        return t
+
+    def preprocess_single(self, img: np.ndarray) -> np.ndarray:
+        """:191-202 -> RGB [th, tw, 3]"""
+        return self.add_padding(self.resize_unimernet(self.crop_margin(np.ascontiguousarray(img, np.uint8))))
+
+    def preprocess_batch(self, images: Sequence[np.ndarray]) -> np.ndarray:
+        """:252-280 -> [n, 1, Hp, Wp] f32"""
+        if len(images) == 0:
+            raise api.OCRError(api.OAR_INVALID_INPUT, "invalid input: Empty image batch")
+        return np.stack([self.image_to_tensor(self.preprocess_single(img)) for img in images])[:, None]
 
 
 # ------------------------------------------------------------------------------------------------ tokens
@@ -293,10 +406,20 @@ class FormulaRecognitionPredictor:
     stop_at_eos: the decode ends a chunk of 16 images once every one of them has emitted the tokenizer's eos instead of running all `M` steps of the Loop.
     `predict` and `decode` give the same strings either way (the filter stops at a row's first eos; only ids after it differ: they read eos), and `M` is of the
     order of 1536 where a formula has a few dozen to a few hundred tokens, so real use wants it on.  The default is off: `infer` then returns exactly what the
-    graph's Loop computes."""
+    graph's Loop computes.
+
+    model_type: "pp_formulanet" (the default) or "unimernet" (formula_recognition_adapter.rs builds either).  "unimernet" selects UniMERNetPreprocessor and its
+    default target (672, 192), takes the graph's FIRST output as the token ids (unimernet.rs:137-151) and makes the messages say `UniMERNet:`; the tokenizer,
+    the token filter, normalize_latex and stop_at_eos are shared."""
+
+    MODEL_TYPES = {"pp_formulanet": ("PP-FormulaNet", (384, 384)), "unimernet": ("UniMERNet", (672, 192))}
 
     def __init__(self, model: bytes, tokenizer, config: Optional[FormulaRecognitionConfig] = None, target_size: Optional[tuple] = None, device_id: int = 0,
-                 stop_at_eos: bool = False):
+                 stop_at_eos: bool = False, model_type: str = "pp_formulanet"):
+        if model_type not in self.MODEL_TYPES:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"invalid input: unknown formula model type {model_type!r}: expected one of {sorted(self.MODEL_TYPES)}")
+        self.model_type = model_type
+        self.model_name, default_size = self.MODEL_TYPES[model_type]
         self.config = config or FormulaRecognitionConfig()
         self.tokenizer = tokenizer if isinstance(tokenizer, FormulaTokenizer) else FormulaTokenizer.from_file(tokenizer)
         self.sos_token_id, self.eos_token_id = self.tokenizer.special_token_ids()
@@ -304,19 +427,26 @@ class FormulaRecognitionPredictor:
         self.stop_at_eos = bool(stop_at_eos)
         if self.stop_at_eos:
             self._eng.set_decode_stop(self.eos_token_id)
-        size = (384, 384) if target_size is None else (int(target_size[0]), int(target_size[1]))
-        if size == (384, 384):
+        size = default_size if target_size is None else (int(target_size[0]), int(target_size[1]))
+        if size == default_size:                       # (pp_formulanet.rs:340-353, unimernet.rs:280-290)
             dims = self._eng.primary_input_shape()
             if dims is not None and len(dims) >= 4 and dims[-2] > 0 and dims[-1] > 0:
                 size = (int(dims[-1]), int(dims[-2]))
-        self.preprocessor = FormulaPreprocessor(target_size=size)
+        self.preprocessor = UniMERNetPreprocessor(target_size=size) if model_type == "unimernet" else FormulaPreprocessor(target_size=size)
 
     def recommended_batch_size(self) -> int:
         return self.config.batch_size
 
     def infer(self, batch: np.ndarray) -> np.ndarray:
-        """pp_formulanet.rs:117-186 -> token ids [n, T] int64"""
+        """pp_formulanet.rs:117-186, unimernet.rs:118-152 -> token ids [n, T] int64"""
         outs = self._eng.infer(batch)
+        if self.model_type == "unimernet":
+            if not outs:
+                raise api.OCRError(api.OAR_INVALID_INPUT, "invalid input: UniMERNet: no output returned from inference")
+            name, a = outs[0]
+            if a.dtype != np.int64 or a.ndim != 2:
+                raise api.OCRError(api.OAR_INVALID_INPUT, f"invalid input: UniMERNet: failed to convert output to 2D i64 array: the first output '{name}' is {a.dtype} {list(a.shape)}")
+            return a
         ids = [a for _, a in outs if a.dtype == np.int64 and a.ndim == 2]
         if len(ids) != 1:
             seen = [(n, str(a.dtype), list(a.shape)) for n, a in outs]

@@ -7,7 +7,8 @@ import numpy as np
 
 def formula_head_reference(w, memory, M, dtype="float64", sos=0):
     """w: the arrays and scalars of synth.models.formula_weights (info["weights"] of build_formulanet; its "q_scale_pos" says on which side of the bias Add
-    the query scale stands, default "after"); memory [B, S, D].  Returns logits [B, M, V] and tokens
+    the query scale stands, default "after"; with squeeze attention Wq / Wk have nh dq < D rows and "cq_scale" is the cross-attention's own scale);
+    memory [B, S, D].  Returns logits [B, M, V] and tokens
     [B, M] (arg max, first index among equals) as numpy arrays."""
     import torch
     import torch.nn.functional as Fn
@@ -17,17 +18,18 @@ def formula_head_reference(w, memory, M, dtype="float64", sos=0):
         mem = torch.from_numpy(np.asarray(memory)).to(dt)
         B, S, D = mem.shape
         nh, Ld, eps = int(w["nh"]), int(w["Ld"]), float(w["eps"])
-        dh = D // nh
+        dh, dq, dc = D // nh, t["l0_wq"].shape[0] // nh, t["l0_wcq"].shape[0] // nh     # value / self q.k / cross q.k head sizes
+        cqs = torch.tensor(np.float32(w.get("cq_scale", w["q_scale"]))).to(dt)
         s_emb, qs, c_pos = torch.tensor(np.float32(w["s_emb"])).to(dt), torch.tensor(np.float32(w["q_scale"])).to(dt), int(w["c_pos"])
         ln = lambda x, nm: Fn.layer_norm(x, (D,), t[nm + "_g"], t[nm + "_b"], eps)
         lin = lambda x, wn, bn: x @ t[wn].T + t[bn]
         if w.get("q_scale_pos", "after") == "before":            # the graph scales the product and adds the bias afterwards
-            qlin = lambda x, wn, bn: (x @ t[wn].T) * qs + t[bn]
+            qlin = lambda x, wn, bn, s=qs: (x @ t[wn].T) * s + t[bn]
         else:
-            qlin = lambda x, wn, bn: lin(x, wn, bn) * qs
-        KmT = [lin(mem, f"l{l}_wck", f"l{l}_bck").reshape(B, S, nh, dh).permute(0, 2, 3, 1) for l in range(Ld)]
+            qlin = lambda x, wn, bn, s=qs: lin(x, wn, bn) * s
+        KmT = [lin(mem, f"l{l}_wck", f"l{l}_bck").reshape(B, S, nh, dc).permute(0, 2, 3, 1) for l in range(Ld)]
         Vm = [lin(mem, f"l{l}_wcv", f"l{l}_bcv").reshape(B, S, nh, dh).permute(0, 2, 1, 3) for l in range(Ld)]
-        K = [torch.zeros(B, nh, 0, dh, dtype=dt) for _ in range(Ld)]
+        K = [torch.zeros(B, nh, 0, dq, dtype=dt) for _ in range(Ld)]
         Vc = [torch.zeros(B, nh, 0, dh, dtype=dt) for _ in range(Ld)]
         tok = torch.full((B,), int(sos), dtype=torch.long)
         logits, toks = [], []
@@ -36,13 +38,13 @@ def formula_head_reference(w, memory, M, dtype="float64", sos=0):
             for l in range(Ld):
                 p = f"l{l}_"
                 y = ln(x, p + "ln1")
-                q = qlin(y, p + "wq", p + "bq").reshape(B, nh, 1, dh)
-                K[l] = torch.cat([K[l], lin(y, p + "wk", p + "bk").reshape(B, nh, 1, dh)], 2)
+                q = qlin(y, p + "wq", p + "bq").reshape(B, nh, 1, dq)
+                K[l] = torch.cat([K[l], lin(y, p + "wk", p + "bk").reshape(B, nh, 1, dq)], 2)
                 Vc[l] = torch.cat([Vc[l], lin(y, p + "wv", p + "bv").reshape(B, nh, 1, dh)], 2)
                 o = (torch.softmax(q @ K[l].transpose(2, 3), -1) @ Vc[l]).reshape(B, D)
                 x = x + lin(o, p + "wo", p + "bo")
                 y = ln(x, p + "ln2")
-                qc = qlin(y, p + "wcq", p + "bcq").reshape(B, nh, 1, dh)
+                qc = qlin(y, p + "wcq", p + "bcq", cqs).reshape(B, nh, 1, dc)
                 oc = (torch.softmax(qc @ KmT[l], -1) @ Vm[l]).reshape(B, D)
                 x = x + lin(oc, p + "wco", p + "bco")
                 y = ln(x, p + "ln3")

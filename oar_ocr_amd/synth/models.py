@@ -990,14 +990,23 @@ FORMULA_LAYER_NAMES = ("ln1_g", "ln1_b", "wq", "bq", "wk", "bk", "wv", "bv", "wo
                        "ln3_g", "ln3_b", "w1", "b1", "w2", "b2")
 
 
-def formula_weights(D, nh, F, V, Ld, P, seed=0):
+def formula_weights(D, nh, F, V, Ld, P, seed=0, qk_squeeze=1, cross_squeeze=False, qk_head=None):
     """f32 weights of one PP-FormulaNet-style head (an MBart-order, pre-norm transformer decoder: self attention over a key / value cache, cross attention
     over the encoder memory, GELU feed-forward; greedy feedback of the arg max), well conditioned for a free-running decode: matrices U(-1, 1) / sqrt(fan_in),
     biases a tenth of that, LayerNorm scales 1 + 0.1 U and biases 0.1 U; then the query / key projections x2 (attention that is not uniform), the position
     table x1.5 against a unit token table (the input changes every step even when the token repeats, so the emitted token keeps changing), and the output
     projection x6 (top-1 / top-2 logit gaps far above f32 rounding).  Every block sits behind a LayerNorm, so no gain here makes the recurrence chaotic the way
     a recurrent GRU gain does (sla_weights): f32 and f64 agree to ~1e-6 of the logits.  Scalars: s_emb (the embedding scale), c_pos (MBart's position offset 2),
-    q_scale = dh^-0.5, eps."""
+    q_scale = dh^-0.5, eps.
+    qk_squeeze = r > 1 (UniMERNet's squeeze attention): the self-attention Wq / Wk are [D / r, D] (the x2 gain stays), q_scale = (dh / r)^-0.5 and cq_scale =
+    dh^-0.5 is recorded apart; r = 1 draws exactly the numbers it always drew.  cross_squeeze narrows Wcq / Wck the same way: a head the engine refuses.
+    qk_head = dq sets the self-attention query / key head size outright (Wq / Wk [nh dq, D], q_scale = dq^-0.5); it may exceed dh."""
+    r = int(qk_squeeze)
+    if r < 1 or (D // nh) % r:
+        raise ValueError("qk_squeeze must divide the head size")
+    Dq, Dc = D // r, D // r if cross_squeeze else D
+    if qk_head is not None:
+        Dq = nh * int(qk_head)
     rng = np.random.default_rng(seed)
     u = lambda *s, k, g=1.0: ((rng.random(s) * 2.0 - 1.0) * (g / np.sqrt(k))).astype(np.float32)
     ln = lambda: ((1.0 + 0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32), (0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32))
@@ -1008,7 +1017,7 @@ def formula_weights(D, nh, F, V, Ld, P, seed=0):
         w[p + "ln1_g"], w[p + "ln1_b"] = ln()
         w[p + "ln2_g"], w[p + "ln2_b"] = ln()
         w[p + "ln3_g"], w[p + "ln3_b"] = ln()
-        for nm, rows, cols, g in (("q", D, D, 2.0), ("k", D, D, 2.0), ("v", D, D, 1.0), ("o", D, D, 1.0), ("cq", D, D, 2.0), ("ck", D, D, 2.0), ("cv", D, D, 1.0), ("co", D, D, 1.0),
+        for nm, rows, cols, g in (("q", Dq, D, 2.0), ("k", Dq, D, 2.0), ("v", D, D, 1.0), ("o", D, D, 1.0), ("cq", Dc, D, 2.0), ("ck", Dc, D, 2.0), ("cv", D, D, 1.0), ("co", D, D, 1.0),
                                   ("1", F, D, 1.0), ("2", D, F, 1.0)):
             w[p + "w" + nm] = u(rows, cols, k=cols, g=g)
             w[p + "b" + nm] = u(rows, k=cols, g=0.1 * g)
@@ -1016,7 +1025,9 @@ def formula_weights(D, nh, F, V, Ld, P, seed=0):
     w["w_lm"] = u(V, D, k=D, g=6.0)
     w["b_lm"] = u(V, k=D, g=0.6)
     w = {k: np.ascontiguousarray(v, np.float32) for k, v in w.items()}
-    w.update(s_emb=float(np.float32(np.sqrt(D))), c_pos=2, q_scale=float(np.float32((D // nh) ** -0.5)), eps=1e-5, nh=nh, Ld=Ld)
+    w.update(s_emb=float(np.float32(np.sqrt(D))), c_pos=2, q_scale=float(np.float32((Dq // nh) ** -0.5)), eps=1e-5, nh=nh, Ld=Ld)
+    if r != 1 or qk_head is not None:
+        w.update(qk_squeeze=r, cq_scale=float(np.float32((Dc // nh) ** -0.5)))
     return w
 
 
@@ -1024,25 +1035,28 @@ def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logit
     """The Loop body of the formula head, one greedy step: inputs (i, cond, tok, K_1, V_1, ...), outputs (cond, tok_new, K_1', V_1', ..., scan tok_new
     [, scan logits]); KmT_l / Vm_l are read from the outer scope.  spelling "gemm": Gemm(transB=1) with the weights as body initializers; "matmul": MatMul with
     the transposed weight + Add (some operands commuted), the weights as initializers of `outer`.  q_scale: where the query scale stands -- "after" the bias
-    Add, "before" it (matmul spelling only), or "folded" (no Mul: the caller has scaled Wq / bq)."""
+    Add, "before" it (matmul spelling only), or "folded" (no Mul: the caller has scaled Wq / bq).  The head sizes follow the weights: K_l is [B, nh, t, dq] with
+    dq = rows(Wq) / nh (squeeze attention when dq < dh), and the cross-attention query is scaled by w["cq_scale"] where the weights record one."""
     from .onnx_writer import BOOL, INT64
     V, D = w["e_tok"].shape
     nh, Ld = w["nh"], w["Ld"]
-    dh = D // nh
+    dh, dq, dc = D // nh, w["l0_wq"].shape[0] // nh, w["l0_wcq"].shape[0] // nh
     b = GraphBuilder("formula_step")
     b.add_input("fd_i", [], INT64)
     b.add_input("fd_cond_in", [], BOOL)
     b.add_input("fd_tok", [B], INT64)
     for l in range(Ld):
-        b.add_input(f"fd_K{l}", [B, nh, "t", dh])
+        b.add_input(f"fd_K{l}", [B, nh, "t", dq])
         b.add_input(f"fd_V{l}", [B, nh, "t", dh])
     gemm = spelling == "gemm"
     store = b if gemm else outer
     c = lambda arr, p="c": b.init(np.asarray(arr), "fd_" + p)
     W = lambda nm: store.init(w[nm], "fd_" + nm)
-    qs = c(np.array(w["q_scale"], np.float32), "qscale")
+    qs_self = c(np.array(w["q_scale"], np.float32), "qscale")
+    qs_cross = c(np.array(w["cq_scale"], np.float32), "cqscale") if "cq_scale" in w else qs_self
 
     def lin(x, wn, bn, scale=False, outputs=None):
+        qs = qs_cross if wn.endswith("wcq") else qs_self
         if gemm:
             y = b.op("Gemm", [x, W(wn), W(bn)], outputs=None if scale else outputs, transB=1)
             return b.op("Mul", [y, qs], outputs=outputs) if scale else y
@@ -1056,6 +1070,8 @@ def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logit
     res = lambda x, y: b.op("Add", [x, y]) if gemm else b.op("Add", [y, x])
     heads = c(np.array([0, nh, 1, dh], np.int64), "heads")
     flat = c(np.array([0, D] if gemm else [0, -1], np.int64), "flat")
+    heads_qk = heads if dq == dh else c(np.array([0, nh, 1, dq], np.int64), "heads_qk")
+    heads_c = heads if dc == dh else c(np.array([0, nh, 1, dc], np.int64), "heads_c")
     scaled = q_scale != "folded"
 
     emb = b.op("Mul", [b.op("Gather", [W("e_tok"), "fd_tok"], axis=0), c(np.array(w["s_emb"], np.float32), "s_emb")])
@@ -1064,8 +1080,8 @@ def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logit
     for l in range(Ld):
         p = f"l{l}_"
         y = ln(x, p + "ln1")
-        q = b.op("Reshape", [lin(y, p + "wq", p + "bq", scale=scaled), heads])
-        kk = b.op("Reshape", [lin(y, p + "wk", p + "bk"), heads])
+        q = b.op("Reshape", [lin(y, p + "wq", p + "bq", scale=scaled), heads_qk])
+        kk = b.op("Reshape", [lin(y, p + "wk", p + "bk"), heads_qk])
         vv = b.op("Reshape", [lin(y, p + "wv", p + "bv"), heads])
         b.op("Concat", [f"fd_K{l}", kk], outputs=[f"fd_K{l}_new"], axis=2)
         b.op("Concat", [f"fd_V{l}", vv], outputs=[f"fd_V{l}_new"], axis=2)
@@ -1073,7 +1089,7 @@ def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logit
         o = b.op("Reshape", [b.op("MatMul", [a, f"fd_V{l}_new"]), flat])
         x = res(x, lin(o, p + "wo", p + "bo"))
         y = ln(x, p + "ln2")
-        qc = b.op("Reshape", [lin(y, p + "wcq", p + "bcq", scale=scaled), heads])
+        qc = b.op("Reshape", [lin(y, p + "wcq", p + "bcq", scale=scaled), heads_c])
         a = b.op("Softmax", [b.op("MatMul", [qc, f"fd_KmT{l}"])], axis=-1)
         oc = b.op("Reshape", [b.op("MatMul", [a, f"fd_Vm{l}"]), flat])
         x = res(x, lin(oc, p + "wco", p + "bco"))
@@ -1087,7 +1103,7 @@ def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logit
     b.add_output("fd_cond_out", [], BOOL)
     b.add_output("fd_tok_new", [B], INT64)
     for l in range(Ld):
-        b.add_output(f"fd_K{l}_new", [B, nh, "t1", dh])
+        b.add_output(f"fd_K{l}_new", [B, nh, "t1", dq])
         b.add_output(f"fd_V{l}_new", [B, nh, "t1", dh])
     b.add_output("fd_tok_new", [B], INT64)
     if with_logits:
@@ -1095,30 +1111,66 @@ def _formula_body(w, B, spelling="gemm", act="Gelu", q_scale="after", with_logit
     return b
 
 
+def _formula_head(g, w, M, spelling="gemm", with_logits=False, act="Gelu", q_scale="after", sos=0, initial_cache="empty"):
+    """`memory` [B, S, D] of graph `g` -> the per-layer cross-attention keys / values, the decode Loop and the outputs token_ids [B, M] (and logits): the part
+    build_formulanet and build_unimernet share"""
+    from .onnx_writer import INT64
+    V, D = w["e_tok"].shape
+    nh, Ld = w["nh"], w["Ld"]
+    dh, dq, dc = D // nh, w["l0_wq"].shape[0] // nh, w["l0_wcq"].shape[0] // nh
+    split = g.init(np.array([0, 0, nh, dh], np.int64), "shape")
+    split_k = split if dc == dh else g.init(np.array([0, 0, nh, dc], np.int64), "shape")
+    for l in range(Ld):
+        p = f"l{l}_"
+        for nm, out, perm in (("ck", f"fd_KmT{l}", [0, 2, 3, 1]), ("cv", f"fd_Vm{l}", [0, 2, 1, 3])):
+            y = g.op("Add", [g.op("MatMul", ["memory", g.init(np.ascontiguousarray(w[p + "w" + nm].T), "fd_" + p + nm)]), g.init(w[p + "b" + nm], "fd_" + p + "b" + nm)])
+            g.nodes.append(node("Transpose", [g.op("Reshape", [y, split_k if nm == "ck" else split])], [out], name=g.uid("n"), perm=perm))
+    shp = g.op("Shape", ["memory"])
+    bdim = g.op("Gather", [shp, g.init(np.array([0], np.int64), "idx")], axis=0)                  # [1]
+    tok0 = g.op("ConstantOfShape", [bdim], value=np.full(1, sos, np.int64))
+    t0 = {"empty": 0, "one": 1}[initial_cache]
+    cshape = g.op("Concat", [bdim, g.init(np.array([nh], np.int64), "nh"), g.init(np.array([t0], np.int64), "t0"), g.init(np.array([dh], np.int64), "dh")], axis=0)
+    kshape = cshape if dq == dh else g.op("Concat", [bdim, g.init(np.array([nh], np.int64), "nh"), g.init(np.array([t0], np.int64), "t0"), g.init(np.array([dq], np.int64), "dq")], axis=0)
+    caches = [g.op("ConstantOfShape", [cshape if i % 2 else kshape], value=np.zeros(1, np.float32)) for i in range(2 * Ld)]
+    body = _formula_body(w, "B", spelling, act, q_scale, with_logits, outer=g)
+    m_name, cond = g.init(np.array(M, np.int64), "trip"), g.init(np.array(True), "cond")
+    outs = ["tok_last"] + [f"{kv}_last_{l}" for l in range(Ld) for kv in ("K", "V")] + ["tok_scan"] + (["logits_scan"] if with_logits else [])
+    g.op("Loop", [m_name, cond, tok0] + caches, outputs=outs, body=body)
+    g.nodes.append(node("Transpose", ["tok_scan"], ["token_ids"], name=g.uid("n"), perm=[1, 0]))
+    g.add_output("token_ids", ["B", M], INT64)
+    if with_logits:
+        g.nodes.append(node("Transpose", ["logits_scan"], ["logits"], name=g.uid("n"), perm=[1, 0, 2]))
+        g.add_output("logits", ["B", M, V])
+
+
 def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(64, 64), seed=0, head_only=False, weights=None, spelling="gemm", with_logits=False,
-                     act="Gelu", q_scale="after", sos=0, initial_cache="empty", read_final_cache=False):
+                     act="Gelu", q_scale="after", sos=0, initial_cache="empty", read_final_cache=False, qk_squeeze=1, cross_squeeze=False):
     """PP-FormulaNet-shaped formula recognizer: a tiny conv backbone (one grey channel in; an 8 x 8 / stride 8 patch convolution, hard-swish, a 1 x 1
     convolution; its weights are added to info["weights"] as bb_*) -> memory [B, S, D] -> per decoder layer the cross-attention
     keys / values KmT_l [B, nh, dh, S], Vm_l [B, nh, S, dh] by ordinary nodes -> the decoder as an ONNX Loop of M greedy steps over a key / value cache that starts
     empty -> token_ids [B, M] int64, the graph's only 2-D int64 output (models/recognition/pp_formulanet.rs picks it by that).  head_only: the graph input is
     `memory` itself.  with_logits: the Loop's second scan output, as `logits` [B, M, V].  Without head_only `memory` is a declared output too, so that a test can
     check the head apart from the backbone.  weights: formula_weights(...) (the default); spelling / q_scale: see _formula_body.  Knobs that write a graph the
-    engine must refuse: act other than "Gelu"; initial_cache="one" (caches that start with one position); read_final_cache (a final cache as graph output).
+    engine must refuse: act other than "Gelu"; initial_cache="one" (caches that start with one position); read_final_cache (a final cache as graph output);
+    cross_squeeze (with qk_squeeze > 1: the cross-attention queries / keys narrowed too).  qk_squeeze = r: UniMERNet's squeeze attention, see formula_weights
+    (given `weights`, the head sizes follow them); r = 1 writes the bytes it always wrote.
     Returns (onnx_bytes, info) with info["weights"]: what the graph really computes (q_scale = 1 and a scaled Wq / bq when folded)."""
     from .onnx_writer import INT64
     P = P if P is not None else M + 2
-    w = dict(weights) if weights is not None else formula_weights(D, nh, F, V, Ld, P, seed)
+    w = dict(weights) if weights is not None else (formula_weights(D, nh, F, V, Ld, P, seed) if qk_squeeze == 1 else formula_weights(D, nh, F, V, Ld, P, seed, qk_squeeze, cross_squeeze))
     if q_scale == "folded" and w["q_scale"] != 1.0:
-        s = np.float32(w["q_scale"])
+        s, sc = np.float32(w["q_scale"]), np.float32(w.get("cq_scale", w["q_scale"]))
         for l in range(Ld):
-            for nm in ("wq", "bq", "wcq", "bcq"):
-                w[f"l{l}_{nm}"] = w[f"l{l}_{nm}"] * s
+            for nm, f in (("wq", s), ("bq", s), ("wcq", sc), ("bcq", sc)):
+                w[f"l{l}_{nm}"] = w[f"l{l}_{nm}"] * f
         w["q_scale"] = 1.0
+        if "cq_scale" in w:
+            w["cq_scale"] = 1.0
     if q_scale == "before":
         if spelling != "matmul":
             raise ValueError('q_scale="before" needs spelling="matmul"')
         w["q_scale_pos"] = "before"
-    dh = D // nh
+    dh, dq, dc = D // nh, w["l0_wq"].shape[0] // nh, w["l0_wcq"].shape[0] // nh
     net = _Net("formulanet", seed + 100)
     g = net.g
     if head_only:
@@ -1132,32 +1184,147 @@ def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(
         t = net.conv(t, 32, D, 1, 1, act=None, w=w["bb_w2"].copy(), b=w["bb_b2"].copy())             # [B, D, h / 8, w / 8]
         t = g.op("Reshape", [t, g.init(np.array([0, D, -1], np.int64), "shape")])
         g.nodes.append(node("Transpose", [t], ["memory"], name=g.uid("n"), perm=[0, 2, 1]))
-    split = g.init(np.array([0, 0, nh, dh], np.int64), "shape")
-    for l in range(Ld):
-        p = f"l{l}_"
-        for nm, out, perm in (("ck", f"fd_KmT{l}", [0, 2, 3, 1]), ("cv", f"fd_Vm{l}", [0, 2, 1, 3])):
-            y = g.op("Add", [g.op("MatMul", ["memory", g.init(np.ascontiguousarray(w[p + "w" + nm].T), "fd_" + p + nm)]), g.init(w[p + "b" + nm], "fd_" + p + "b" + nm)])
-            g.nodes.append(node("Transpose", [g.op("Reshape", [y, split])], [out], name=g.uid("n"), perm=perm))
-    shp = g.op("Shape", ["memory"])
-    bdim = g.op("Gather", [shp, g.init(np.array([0], np.int64), "idx")], axis=0)                  # [1]
-    tok0 = g.op("ConstantOfShape", [bdim], value=np.full(1, sos, np.int64))
-    t0 = {"empty": 0, "one": 1}[initial_cache]
-    cshape = g.op("Concat", [bdim, g.init(np.array([nh], np.int64), "nh"), g.init(np.array([t0], np.int64), "t0"), g.init(np.array([dh], np.int64), "dh")], axis=0)
-    caches = [g.op("ConstantOfShape", [cshape], value=np.zeros(1, np.float32)) for _ in range(2 * Ld)]
-    body = _formula_body(w, "B", spelling, act, q_scale, with_logits, outer=g)
-    m_name, cond = g.init(np.array(M, np.int64), "trip"), g.init(np.array(True), "cond")
-    outs = ["tok_last"] + [f"{kv}_last_{l}" for l in range(Ld) for kv in ("K", "V")] + ["tok_scan"] + (["logits_scan"] if with_logits else [])
-    g.op("Loop", [m_name, cond, tok0] + caches, outputs=outs, body=body)
-    g.nodes.append(node("Transpose", ["tok_scan"], ["token_ids"], name=g.uid("n"), perm=[1, 0]))
-    g.add_output("token_ids", ["B", M], INT64)
-    if with_logits:
-        g.nodes.append(node("Transpose", ["logits_scan"], ["logits"], name=g.uid("n"), perm=[1, 0, 2]))
-        g.add_output("logits", ["B", M, V])
+    _formula_head(g, w, M, spelling, with_logits, act, q_scale, sos, initial_cache)
     if not head_only:
         g.add_output("memory", ["B", "S", D])
     if read_final_cache:
         g.add_output("K_last_0", ["B", nh, M, dh])
     return g.model(), {"params": g.n_params, "weights": w, "D": D, "nh": nh, "F": F, "V": V, "Ld": Ld, "M": M, "P": P, "sos": sos}
+
+
+# ---------------------------------------------------------------------------------------------- formula recognition: UniMERNet
+def swin_block_weights(C, nh, ws, hidden, seed=0, prefix=""):
+    """f32 weights of one Swin block without shifted windows (UniMERNet's encoder): LN1, the q / k / v / projection Linears as [out, in] matrices (q and k x2: an
+    attention that is not uniform), the relative-position bias as the [nh, N, N] table the exporter materialises -- U(-2, 2) per entry, so neither symmetric in
+    (i, j) nor equal between heads --, the depthwise 3 x 3 "conv enhance", LN2 and the two MLP Linears."""
+    rng = np.random.default_rng(seed)
+    u = lambda *s, k, g=1.0: ((rng.random(s) * 2.0 - 1.0) * (g / np.sqrt(k))).astype(np.float32)
+    ln = lambda n: ((1.0 + 0.1 * (rng.random(n) * 2.0 - 1.0)).astype(np.float32), (0.1 * (rng.random(n) * 2.0 - 1.0)).astype(np.float32))
+    N = ws * ws
+    w = {}
+    w["ln1_g"], w["ln1_b"] = ln(C)
+    for nm, g in (("q", 2.0), ("k", 2.0), ("v", 1.0), ("p", 1.0)):
+        w["w" + nm], w["b" + nm] = u(C, C, k=C, g=g), u(C, k=C, g=0.1 * g)
+    w["bias"] = ((rng.random((nh, N, N)) * 2.0 - 1.0) * 2.0).astype(np.float32)
+    w["ce_w"], w["ce_b"] = u(C, 1, 3, 3, k=9), u(C, k=9, g=0.1)
+    w["ln2_g"], w["ln2_b"] = ln(C)
+    w["w1"], w["b1"] = u(hidden, C, k=C), u(hidden, k=C, g=0.1)
+    w["w2"], w["b2"] = u(C, hidden, k=hidden), u(C, k=hidden, g=0.1)
+    return {prefix + k: v for k, v in w.items()}
+
+
+def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div"):
+    """x [B, H W, C] -> x + window attention of LN1(x), in the spelling DESIGN 4.33 fixes (the engine's rewrite pass 3b matches it).  scale: "div" writes
+    Div(s, sqrt(dh)), "mul" Mul(s, dh^-0.5).  H or W no multiple of ws is refused here: the padded spelling is not written."""
+    if H % ws or W % ws or C % nh:
+        raise ValueError("H and W must be multiples of ws and C of the heads")
+    N, dh = ws * ws, C // nh
+    ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(np.ascontiguousarray(w[p + "w" + nm].T), "sw_" + p + "w" + nm)]), g.init(w[p + "b" + nm], "sw_" + p + "b" + nm)])
+    y = g.op("LayerNormalization", [x, g.init(w[p + "ln1_g"], "sw_" + p + "ln1_g"), g.init(w[p + "ln1_b"], "sw_" + p + "ln1_b")], axis=-1, epsilon=1e-5)
+    t = g.op("Reshape", [y, ci([0, H // ws, ws, W // ws, ws, C])])
+    t = g.op("Reshape", [g.op("Transpose", [t], perm=[0, 1, 3, 2, 4, 5]), ci([-1, N, C])])
+    heads = ci([0, N, nh, dh])
+    qh, kh, vh = (g.op("Transpose", [g.op("Reshape", [lin(t, nm), heads])], perm=[0, 2, 1, 3]) for nm in ("q", "k", "v"))
+    sc = g.op("MatMul", [qh, g.op("Transpose", [kh], perm=[0, 1, 3, 2])])
+    if scale == "div":
+        sc = g.op("Div", [sc, g.init(np.array(np.sqrt(dh), np.float32), "c")])
+    elif scale == "mul":
+        sc = g.op("Mul", [sc, g.init(np.array(dh ** -0.5, np.float32), "c")])
+    else:
+        raise ValueError(scale)
+    a = g.op("Softmax", [g.op("Add", [sc, g.init(w[p + "bias"][None], "sw_" + p + "bias")])], axis=-1)
+    o = g.op("Reshape", [g.op("Transpose", [g.op("MatMul", [a, vh])], perm=[0, 2, 1, 3]), ci([0, N, C])])
+    o = lin(o, "p")
+    r = g.op("Transpose", [g.op("Reshape", [o, ci([-1, H // ws, W // ws, ws, ws, C])])], perm=[0, 1, 3, 2, 4, 5])
+    return g.op("Add", [x, g.op("Reshape", [r, ci([-1, H * W, C])])])
+
+
+def _swin_block(g, x, w, p, H, W, C, nh, ws, scale="div"):
+    """the attention block, the depthwise 3 x 3 "conv enhance" residual on the tokens viewed as an image, and LN2 -> Linear -> GELU -> Linear with its residual"""
+    ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(np.ascontiguousarray(w[p + "w" + nm].T), "sw_" + p + "w" + nm)]), g.init(w[p + "b" + nm], "sw_" + p + "b" + nm)])
+    x = _swin_attention(g, x, w, p, H, W, C, nh, ws, scale)
+    img = g.op("Reshape", [g.op("Transpose", [x], perm=[0, 2, 1]), ci([0, C, H, W])])
+    img = g.op("Conv", [img, g.init(w[p + "ce_w"], "sw_" + p + "ce_w"), g.init(w[p + "ce_b"], "sw_" + p + "ce_b")], kernel_shape=[3, 3], strides=[1, 1], pads=[1, 1, 1, 1], group=C, dilations=[1, 1])
+    x = g.op("Add", [x, g.op("Transpose", [g.op("Reshape", [img, ci([0, C, -1])])], perm=[0, 2, 1])])
+    y = g.op("LayerNormalization", [x, g.init(w[p + "ln2_g"], "sw_" + p + "ln2_g"), g.init(w[p + "ln2_b"], "sw_" + p + "ln2_b")], axis=-1, epsilon=1e-5)
+    return g.op("Add", [x, lin(g.op("Gelu", [lin(y, "1")], approximate="none"), "2")])
+
+
+def build_swin_block(H, W, C, nh, ws, seed=0, scale="div", whole=False):
+    """One Swin block as a graph of its own: x [B, H W, C] -> `y` [B, H W, C].  whole = False: the attention part only (LN1 .. the residual Add)."""
+    w = swin_block_weights(C, nh, ws, 2 * C, seed)
+    g = GraphBuilder("swin_block", 17)
+    g.add_input("x", ["B", H * W, C])
+    y = (_swin_block if whole else _swin_attention)(g, "x", w, "", H, W, C, nh, ws, scale)
+    g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
+    g.add_output("y", ["B", H * W, C])
+    return g.model(), {"params": g.n_params, "weights": w, "H": H, "W": W, "C": C, "nh": nh, "ws": ws, "scale": scale, "whole": whole}
+
+
+def unimernet_weights(C=32, heads=(2, 4), depths=(2, 2), ws=4, mlp_ratio=2, seed=0):
+    """the encoder's weights: the stem (two 3 x 3 stride-2 convolutions: 1 -> C / 2 -> C), per stage `depths[s]` Swin blocks at width C 2^s (prefix s<s>b<b>_),
+    between stages the patch merging (m<s>_ln_g / _ln_b over 4 C', m<s>_w [2 C', 4 C'], no bias), and the final LayerNorm lnf_g / lnf_b"""
+    rng = np.random.default_rng(seed + 7)
+    u = lambda *s, k, g=1.0: ((rng.random(s) * 2.0 - 1.0) * (g / np.sqrt(k))).astype(np.float32)
+    ln = lambda n: ((1.0 + 0.1 * (rng.random(n) * 2.0 - 1.0)).astype(np.float32), (0.1 * (rng.random(n) * 2.0 - 1.0)).astype(np.float32))
+    w = {"st_w1": u(C // 2, 1, 3, 3, k=9, g=3.0), "st_b1": u(C // 2, k=9, g=0.3), "st_w2": u(C, C // 2, 3, 3, k=9 * (C // 2), g=3.0), "st_b2": u(C, k=9 * (C // 2), g=0.3)}
+    for si, (nh, depth) in enumerate(zip(heads, depths)):
+        Cs = C << si
+        for bi in range(depth):
+            w.update(swin_block_weights(Cs, nh, ws, mlp_ratio * Cs, seed * 1000 + 10 * si + bi + 1, f"s{si}b{bi}_"))
+        if si + 1 < len(depths):
+            w[f"m{si}_ln_g"], w[f"m{si}_ln_b"] = ln(4 * Cs)
+            w[f"m{si}_w"] = u(2 * Cs, 4 * Cs, k=4 * Cs)
+    w["lnf_g"], w["lnf_b"] = ln(C << (len(depths) - 1))
+    w.update(C=C, heads=tuple(heads), depths=tuple(depths), ws=ws, mlp_ratio=mlp_ratio)
+    return w
+
+
+def build_unimernet(image_shape=(192, 672), C=32, heads=(2, 4), depths=(2, 2), ws=4, mlp_ratio=2, nh=4, F=128, V=300, Ld=2, M=32, P=None, seed=0, qk_squeeze=2, scale="div",
+                    encoder_only=False, with_logits=False, sos=0):
+    """UniMERNet-shaped formula recognizer, in the spelling DESIGN 4.33 fixes: x [B, 1, H, W] (image_shape = (H, W); the preprocessor's target (672, 192) is
+    (W, H)) -> stem: two 3 x 3 stride-2 convolutions with GELU -> tokens [B, (H / 4) (W / 4), C] -> `len(depths)` stages of Swin blocks without shifted windows
+    (_swin_block; window ws, heads[s] heads at width C 2^s), patch merging between stages (Reshape [0, H/2, 2, W/2, 2, C] -> Transpose [0,1,3,2,4,5] -> Reshape
+    [0, -1, 4C] -> LayerNorm -> Linear 4C -> 2C) -> a final LayerNorm -> `memory` [B, S, D], D = C 2^(stages - 1), a declared output -> the per-layer KmT_l / Vm_l
+    nodes and the squeeze-attention decode Loop of build_formulanet(qk_squeeze) -> token_ids [B, M] int64, the graph's FIRST output.  encoder_only: `memory` is
+    the only output and no decoder is written.  scale: how the blocks spell the attention scale ("div" or "mul").
+    Returns (onnx_bytes, info): info["encoder"] the encoder's weights (unimernet_weights), info["weights"] the decoder's (formula_weights)."""
+    Hi, Wi = image_shape
+    stages = len(depths)
+    if Hi % (4 << (stages - 1)) or Wi % (4 << (stages - 1)):
+        raise ValueError("the image sides must be multiples of 4 * 2^(stages - 1)")
+    D = C << (stages - 1)
+    P = P if P is not None else M + 2
+    we = unimernet_weights(C, heads, depths, ws, mlp_ratio, seed)
+    g = GraphBuilder("unimernet", 17)
+    ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    g.add_input("x", ["B", 1, Hi, Wi])
+    t = "x"
+    for nm, cin, cout in (("1", 1, C // 2), ("2", C // 2, C)):
+        t = g.op("Conv", [t, g.init(we["st_w" + nm], "st_w" + nm), g.init(we["st_b" + nm], "st_b" + nm)], kernel_shape=[3, 3], strides=[2, 2], pads=[1, 1, 1, 1], group=1, dilations=[1, 1])
+        t = g.op("Gelu", [t], approximate="none")
+    H, W = Hi // 4, Wi // 4
+    t = g.op("Transpose", [g.op("Reshape", [t, ci([0, C, -1])])], perm=[0, 2, 1])
+    for si in range(stages):
+        Cs = C << si
+        for bi in range(depths[si]):
+            t = _swin_block(g, t, we, f"s{si}b{bi}_", H, W, Cs, heads[si], ws, scale)
+        if si + 1 < stages:
+            t = g.op("Reshape", [g.op("Transpose", [g.op("Reshape", [t, ci([0, H // 2, 2, W // 2, 2, Cs])])], perm=[0, 1, 3, 2, 4, 5]), ci([0, -1, 4 * Cs])])
+            t = g.op("LayerNormalization", [t, g.init(we[f"m{si}_ln_g"], f"m{si}_ln_g"), g.init(we[f"m{si}_ln_b"], f"m{si}_ln_b")], axis=-1, epsilon=1e-5)
+            t = g.op("MatMul", [t, g.init(np.ascontiguousarray(we[f"m{si}_w"].T), f"m{si}_w")])
+            H, W = H // 2, W // 2
+    g.nodes.append(node("LayerNormalization", [t, g.init(we["lnf_g"], "enc_lnf_g"), g.init(we["lnf_b"], "enc_lnf_b")], ["memory"], name=g.uid("n"), axis=-1, epsilon=1e-5))
+    info = {"encoder": we, "image_shape": (Hi, Wi), "S": H * W, "D": D, "M": M, "V": V, "Ld": Ld, "nh": nh, "F": F, "P": P, "sos": sos}
+    if not encoder_only:
+        w = formula_weights(D, nh, F, V, Ld, P, seed, qk_squeeze)
+        _formula_head(g, w, M, "gemm", with_logits, sos=sos)
+        info["weights"] = w
+    g.add_output("memory", ["B", H * W, D])
+    info["params"] = g.n_params
+    return g.model(), info
 
 
 def formula_tokenizer_spec(V, decoder="ByteLevel"):

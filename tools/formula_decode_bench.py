@@ -1,6 +1,8 @@
 """Speed of the FormulaDecode operator on PP-FormulaNet-S- and -L-shaped heads: microseconds per decode step from the profiler's event intervals of
 class `formula_decode`, the weight bytes a step streams over that time, and the same math as an eager torch loop on the same card in the same process
-(alternating runs, medians).  Usage: python tools/formula_decode_bench.py [--reps 5] [--steps 64]
+(alternating runs, medians).  Usage: python tools/formula_decode_bench.py [--reps 5] [--steps 64] [--heads S,L,U] [--squeeze r]
+Head U is UniMERNet's MBart decoder (D 1024, 16 heads, F 4096, 8 layers, V 50000) with squeeze attention r = 2; --squeeze r overrides a
+head's own r (1 for S and L).
 
 --stop adds the stop token of `OrtInfer.set_decode_stop` (one more JSON line per head, batch and mode, the modes alternating inside every repetition):
   off      the setting off: all M steps run (the only mode of a build that has no stop token: `--lib` / a copy of this file in an older tree)
@@ -21,7 +23,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from oar_ocr_amd import api                      # noqa: E402
 from oar_ocr_amd.synth import models             # noqa: E402
 
-HEADS = {"S": dict(D=384, nh=16, F=1536, Ld=2, V=50000, S=144), "L": dict(D=512, nh=16, F=2048, Ld=8, V=50000, S=144)}
+HEADS = {"S": dict(D=384, nh=16, F=1536, Ld=2, V=50000, S=144), "L": dict(D=512, nh=16, F=2048, Ld=8, V=50000, S=144),
+         "U": dict(D=1024, nh=16, F=4096, Ld=8, V=50000, S=144, r=2)}
 
 
 def torch_loop(w, mem, M):
@@ -33,8 +36,8 @@ def torch_loop(w, mem, M):
     mem = torch.from_numpy(mem).to(dev)
     B, S, D = mem.shape
     nh, Ld, eps = int(w["nh"]), int(w["Ld"]), float(w["eps"])
-    dh = D // nh
-    s_emb, qs, c_pos = float(w["s_emb"]), float(w["q_scale"]), int(w["c_pos"])
+    dh, dq = D // nh, w["l0_wq"].shape[0] // nh
+    s_emb, qs, cqs, c_pos = float(w["s_emb"]), float(w["q_scale"]), float(w.get("cq_scale", w["q_scale"])), int(w["c_pos"])
     ln = lambda x, nm: Fn.layer_norm(x, (D,), t[nm + "_g"], t[nm + "_b"], eps)
     lin = lambda x, wn, bn: Fn.linear(x, t[wn], t[bn])
 
@@ -42,7 +45,7 @@ def torch_loop(w, mem, M):
         with torch.no_grad():
             KmT = [lin(mem, f"l{l}_wck", f"l{l}_bck").reshape(B, S, nh, dh).permute(0, 2, 3, 1) for l in range(Ld)]
             Vm = [lin(mem, f"l{l}_wcv", f"l{l}_bcv").reshape(B, S, nh, dh).permute(0, 2, 1, 3) for l in range(Ld)]
-            K = [torch.zeros(B, nh, M, dh, device=dev) for _ in range(Ld)]
+            K = [torch.zeros(B, nh, M, dq, device=dev) for _ in range(Ld)]
             Vc = [torch.zeros(B, nh, M, dh, device=dev) for _ in range(Ld)]
             tok = torch.zeros(B, dtype=torch.long, device=dev)
             toks = []
@@ -51,13 +54,13 @@ def torch_loop(w, mem, M):
                 for l in range(Ld):
                     p = f"l{l}_"
                     y = ln(x, p + "ln1")
-                    q = (lin(y, p + "wq", p + "bq") * qs).reshape(B, nh, 1, dh)
-                    K[l][:, :, i] = lin(y, p + "wk", p + "bk").reshape(B, nh, dh)
+                    q = (lin(y, p + "wq", p + "bq") * qs).reshape(B, nh, 1, dq)
+                    K[l][:, :, i] = lin(y, p + "wk", p + "bk").reshape(B, nh, dq)
                     Vc[l][:, :, i] = lin(y, p + "wv", p + "bv").reshape(B, nh, dh)
                     o = (torch.softmax(q @ K[l][:, :, :i + 1].transpose(2, 3), -1) @ Vc[l][:, :, :i + 1]).reshape(B, D)
                     x = x + lin(o, p + "wo", p + "bo")
                     y = ln(x, p + "ln2")
-                    qc = (lin(y, p + "wcq", p + "bcq") * qs).reshape(B, nh, 1, dh)
+                    qc = (lin(y, p + "wcq", p + "bcq") * cqs).reshape(B, nh, 1, dh)
                     x = x + lin((torch.softmax(qc @ KmT[l], -1) @ Vm[l]).reshape(B, D), p + "wco", p + "bco")
                     x = x + lin(Fn.gelu(lin(ln(x, p + "ln3"), p + "w1", p + "b1")), p + "w2", p + "b2")
                 tok = torch.argmax(lin(ln(x, "lnf"), "w_lm", "b_lm"), 1)
@@ -85,6 +88,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--heads", default="S,L")
+    ap.add_argument("--squeeze", type=int, default=None, help="squeeze attention: Wq / Wk project to D / r (default: the head's own, 1 for S and L)")
     ap.add_argument("--stop", choices=["off", "never", "eighth", "all"], default=None)
     ap.add_argument("--lib", default=None, help="time this build of the library instead of the tree's own")
     a = ap.parse_args()
@@ -97,11 +101,12 @@ def main():
         modes = [m for m in modes if m == "off"]
     for name in a.heads.split(","):
         h = HEADS[name]
-        w = models.formula_weights(h["D"], h["nh"], h["F"], h["V"], h["Ld"], M + 2, 0)
+        r = a.squeeze if a.squeeze is not None else h.get("r", 1)
+        w = models.formula_weights(h["D"], h["nh"], h["F"], h["V"], h["Ld"], M + 2, 0) if r == 1 else models.formula_weights(h["D"], h["nh"], h["F"], h["V"], h["Ld"], M + 2, 0, qk_squeeze=r)
         model, _ = models.build_formulanet(D=h["D"], nh=h["nh"], F=h["F"], V=h["V"], Ld=h["Ld"], M=M, head_only=True, weights=w)
         eng = api.OrtInfer(model, profile=True)
         D, F, Ld, V = h["D"], h["F"], h["Ld"], h["V"]
-        weight_bytes = 4.0 * (Ld * (6 * D * D + 2 * F * D) + V * D)
+        weight_bytes = 4.0 * (Ld * ((4 + 2.0 / r) * D * D + 2 * F * D) + V * D)
         for B in (1, 8):
             mem = np.random.default_rng(B).standard_normal((B, h["S"], D)).astype(np.float32)
             loop = torch_loop(w, mem, M)
@@ -125,7 +130,7 @@ def main():
                 torch.cuda.synchronize()
                 theirs.append(e0.elapsed_time(e1) * 1e3 / M)
             us = float(np.median(ours))
-            print(json.dumps({"head": name, "B": B, "M": M, "us_per_step_kernels": round(us, 1), "us_per_step_wall_profiled": round(float(np.median(wall)), 1),
+            print(json.dumps({"head": name, "squeeze": r, "B": B, "M": M, "us_per_step_kernels": round(us, 1), "us_per_step_wall_profiled": round(float(np.median(wall)), 1),
                               "weight_MB_per_step": round(weight_bytes / 1e6, 1), "share_of_8TBps": round(weight_bytes / (us * 1e-6) / 8e12, 3),
                               "torch_eager_us_per_step": round(float(np.median(theirs)), 1), "tokens_equal_torch_f32": same}), flush=True)
             if not modes:
