@@ -1029,7 +1029,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
         }
     }
 
-    // ---- pass 3b: the attention of a Swin block without shifted windows (UniMERNet's encoder), y [B, H W, C] with static H, W, ws, N = ws^2:
+    // ---- pass 3b: the attention of a Swin block (UniMERNet's encoder), y [B, H W, C] with static H, W, ws, N = ws^2:
     //   p = Reshape(y, [0, H/ws, ws, W/ws, ws, C]) -> Transpose[0,1,3,2,4,5] -> Reshape[-1, N, C]                     (window partition)
     //   q, k, v = Linear(p);  qh, kh, vh = Transpose[0,2,1,3](Reshape(., [0, N, nh, dh]))
     //   a = Softmax(Add(Div(MatMul(qh, Transpose[0,1,3,2](kh)), c) | Mul(.., c), bias [1, nh, N, N]), -1)
@@ -1039,7 +1039,16 @@ void Engine::rewrite_graph(OnnxModel& m) {
     // scatters a window's tokens by address, the projection runs on its output, and both the partition and the reverse triple leave the graph (18
     // launches per block, four of them rank-6 copies of the whole token tensor, become 6).  Every intermediate must be single-use and no graph output.  It runs before
     // pass 4 so that the block's residual Add folds into the projection.  OAR_FUSE_WINDOW_ATTENTION=0, a shape k::window_attention_supported rejects (every
-    // size is static here, so that is known at load time), the padded spelling (H or W no multiple of ws) and a masked (shifted) block keep the op-by-op route.
+    // size is static here, so that is known at load time) keep the op-by-op route.
+    // The padded, shifted and masked spellings are matched too, each independently of the others; with Hp = hb ws, Wp = wb ws:
+    //   front:  g = Reshape(y, [0, H, W, C]) -> Pad(g, [0,0,0,0, 0,Hp-H,Wp-W,0], constant 0) -> roll by -s on axis 1, then on axis 2, each
+    //           Concat(Slice(g, s:end), Slice(g, 0:s)) -> the partition's Reshape
+    //   mask:   Add(.., bias) -> Reshape[-1, nW, nh, N, N] -> Add(mask [1, nW, 1, N, N]) -> Reshape[-1, nh, N, N] -> Softmax, nW = hb wb
+    //   tail:   the reverse's last Reshape gives [-1, Hp, Wp, C] -> roll by +s (Concat(Slice(r, Hp-s:end), Slice(r, 0:Hp-s)); axis 2 with Wp) ->
+    //           Slice(0:H, axis 1), Slice(0:W, axis 2) where that axis is padded -> Reshape[0, H W, C]
+    // All of it is address arithmetic in the kernel (k::window_token_row): the node gets shift / Hp / Wp, the mask as a fifth input and, where the block pads,
+    // the k and v Linears' biases (a padded token reaches them as zeros).  A Pad with another value, mode or side, a reverse roll that is not the inverse of
+    // the forward one, a mask with another window count and a dynamic H / W are not matched and keep the op-by-op route.
     {
         const char* fe = getenv("OAR_FUSE_WINDOW_ATTENTION");
         const bool fuse = !fe || atoi(fe) != 0;
@@ -1064,6 +1073,42 @@ void Engine::rewrite_graph(OnnxModel& m) {
             return it == inits_.end() || it->second.dtype == DType::F32 ? std::vector<int64_t>{} : it->second.i;
         };
         auto perm_is = [&](const GNode& t, std::initializer_list<int64_t> want) { return t.ais("perm") == std::vector<int64_t>(want); };
+        auto ints = [&](const std::string& v) -> std::vector<int64_t> {
+            auto it = inits_.find(v);
+            return it == inits_.end() || it->second.dtype == DType::F32 ? std::vector<int64_t>{} : it->second.i;
+        };
+        struct Sl { std::string src; int64_t ax, st, en; };
+        auto slice1 = [&](int idx, Sl& o) {   // a single-axis unit-step Slice with constant non-negative operands
+            const GNode& sl = nodes[idx];
+            if (sl.op != "Slice" || sl.in.size() < 4 || sl.in.size() > 5) return false;
+            const std::vector<int64_t> st = ints(sl.in[1]), en = ints(sl.in[2]), ax = ints(sl.in[3]);
+            if (st.size() != 1 || en.size() != 1 || ax.size() != 1 || st[0] < 0 || en[0] < 0 || ax[0] < 0) return false;
+            if (sl.in.size() == 5 && !sl.in[4].empty() && ints(sl.in[4]) != std::vector<int64_t>{1}) return false;
+            o = Sl{sl.in[0], ax[0], st[0], en[0]};
+            return true;
+        };
+        // Concat(Slice(src, k:end), Slice(src, 0:k)) on `axis` of extent n, 0 < k < n: roll(src, -k).  src is read by the two Slices alone, each of them by the Concat alone.
+        auto roll = [&](int c, int64_t axis, int64_t n, std::string& src, int64_t& by, int* sl) {
+            const GNode& cc = nodes[c];
+            if (cc.op != "Concat" || cc.in.size() != 2 || cc.ai("axis", 0) != axis || cc.act.kind != k::ACT_NONE) return false;
+            Sl a[2];
+            for (int t = 0; t < 2; ++t) {
+                sl[t] = prod(cc.in[t], "Slice");
+                if (sl[t] < 0 || !single_use(cc.in[t]) || !slice1(sl[t], a[t]) || a[t].ax != axis) return false;
+            }
+            if (a[0].src != a[1].src || a[1].st != 0 || a[0].st != a[1].en || a[0].st <= 0 || a[0].st >= n || a[0].en < n) return false;
+            if (cons[a[0].src].size() != 2 || graph_outs.count(a[0].src)) return false;
+            src = a[0].src; by = a[0].st;
+            return true;
+        };
+        auto roll_of = [&](const std::string& v, int64_t axis, int64_t n, int64_t want, int* sl) -> int {   // the Concat of roll(v, -want), or -1
+            if (cons[v].size() != 2 || graph_outs.count(v)) return -1;
+            const int a = cons[v][0];
+            if (dead[a] || nodes[a].op != "Slice" || !single_use(nodes[a].out[0])) return -1;
+            const int c = cons[nodes[a].out[0]][0];
+            std::string src; int64_t by = 0;
+            return !dead[c] && roll(c, axis, n, src, by, sl) && src == v && by == want ? c : -1;
+        };
         auto plain_linear = [&](const GNode& l, int64_t C) {
             if (l.op != "Linear" || l.act.kind != k::ACT_NONE || !l.residual.empty() || l.in.size() < 2 || !is_init(l.in[1])) return false;
             const HostTensor& w = inits_[l.in[1]];
@@ -1074,14 +1119,37 @@ void Engine::rewrite_graph(OnnxModel& m) {
             const GNode& sm = nodes[i];
             const int64_t sax = sm.ai("axis", -1);
             if (sax != -1 && sax != 3) continue;
+            // the per-window mask, where there is one: Reshape[-1, nW, nh, N, N] -> Add(mask [1, nW, 1, N, N]) -> Reshape[-1, nh, N, N]
+            std::string sv = sm.in[0], maskn;
+            int m1 = -1, m2 = -1;
+            const int m3 = prod(sv, "Reshape");
+            if (m3 >= 0) {
+                if (!single_use(sv)) continue;
+                m2 = prod(nodes[m3].in[0], "Add");
+                if (m2 < 0 || !single_use(nodes[m3].in[0]) || nodes[m2].act.kind != k::ACT_NONE) continue;
+                const int mi = is_init(nodes[m2].in[1]) ? 1 : is_init(nodes[m2].in[0]) ? 0 : -1;
+                if (mi < 0) continue;
+                maskn = nodes[m2].in[mi];
+                const HostTensor& mk = inits_[maskn];
+                if (mk.dtype != DType::F32 || mk.dims.size() != 5 || mk.dims[0] != 1 || mk.dims[2] != 1 || mk.dims[3] != mk.dims[4] || (int64_t)mk.f.size() != numel(mk.dims)) continue;
+                m1 = prod(nodes[m2].in[1 - mi], "Reshape");
+                if (m1 < 0 || !single_use(nodes[m2].in[1 - mi])) continue;
+                sv = nodes[m1].in[0];
+            }
             // scores: Add(scaled, bias) in either order, scaled = Div(MatMul, c) or Mul(MatMul, c) / Mul(c, MatMul)
-            const int ad = prod(sm.in[0], "Add");
-            if (ad < 0 || !single_use(sm.in[0]) || !single_use(sm.out[0]) || nodes[ad].act.kind != k::ACT_NONE) continue;
+            const int ad = prod(sv, "Add");
+            if (ad < 0 || !single_use(sv) || !single_use(sm.out[0]) || nodes[ad].act.kind != k::ACT_NONE) continue;
             const int bi = is_init(nodes[ad].in[1]) ? 1 : is_init(nodes[ad].in[0]) ? 0 : -1;
             if (bi < 0) continue;
             const HostTensor& bias = inits_[nodes[ad].in[bi]];
             if (bias.dtype != DType::F32 || bias.dims.size() != 4 || bias.dims[0] != 1 || bias.dims[2] != bias.dims[3] || (int64_t)bias.f.size() != numel(bias.dims)) continue;
             const int64_t nh = bias.dims[1], N = bias.dims[2];
+            int64_t nWm = 0;
+            if (m3 >= 0) {
+                const HostTensor& mk = inits_[maskn];
+                nWm = mk.dims[1];
+                if (mk.dims[3] != N || target(nodes[m3]) != std::vector<int64_t>{-1, nh, N, N} || target(nodes[m1]) != std::vector<int64_t>{-1, nWm, nh, N, N}) continue;
+            }
             const std::string& scaled = nodes[ad].in[1 - bi];
             if (!single_use(scaled)) continue;
             int sc = prod(scaled, "Div"), scale_div = 1, ci = 1;
@@ -1127,8 +1195,9 @@ void Engine::rewrite_graph(OnnxModel& m) {
             if (p1 < 0 || !single_use(nodes[p2].in[0])) continue;
             const std::vector<int64_t> pt = target(nodes[p1]);
             if (pt.size() != 6 || pt[0] != 0 || pt[1] <= 0 || pt[2] <= 0 || pt[3] <= 0 || pt[4] != pt[2] || pt[5] != C || pt[2] * pt[2] != N) continue;
-            const int64_t hb = pt[1], ws = pt[2], wb = pt[3], H = hb * ws, W = wb * ws;
+            const int64_t hb = pt[1], ws = pt[2], wb = pt[3], Hp = hb * ws, Wp = wb * ws;
             if (!k::window_attention_supported((int)std::min<int64_t>(ws, 1 << 20), (int)std::min<int64_t>(nh, 1 << 20), (int)std::min<int64_t>(dh, 1 << 20))) continue;
+            if (Hp >= (int64_t)1 << 30 || Wp >= (int64_t)1 << 30 || (m3 >= 0 && nWm != hb * wb)) continue;
             // output side: Transpose[0,2,1,3] -> Reshape[0, N, C] -> Linear -> window reverse
             const int t2 = only_reader(nodes[mm2].out[0], "Transpose");
             if (t2 < 0 || !perm_is(nodes[t2], {0, 2, 1, 3})) continue;
@@ -1141,18 +1210,86 @@ void Engine::rewrite_graph(OnnxModel& m) {
             const int v2 = only_reader(nodes[v1].out[0], "Transpose");
             if (v2 < 0 || !perm_is(nodes[v2], {0, 1, 3, 2, 4, 5})) continue;
             const int v3 = only_reader(nodes[v2].out[0], "Reshape");
-            if (v3 < 0 || target(nodes[v3]) != std::vector<int64_t>{-1, H * W, C}) continue;
+            if (v3 < 0) continue;
+            // the reverse ends in [-1, Hp Wp, C]: the plain block, y feeds the partition.  It ends in [-1, Hp, Wp, C]: the tokens are handled as a grid, with
+            // Reshape[0, H, W, C] -> Pad (bottom / right, constant 0) -> roll by -s on axis 1, then on axis 2 in front of the partition, Pad and roll each optional
+            const bool grid = target(nodes[v3]) == std::vector<int64_t>{-1, Hp, Wp, C};
+            if (!grid && target(nodes[v3]) != std::vector<int64_t>{-1, Hp * Wp, C}) continue;
+            std::vector<int> extra;
+            std::string cur = nodes[p1].in[0];
+            int64_t shift = 0, H = Hp, W = Wp;
+            if (grid) {
+                bool counted = false;                // cur's readers are already known to be the two Slices of a roll
+                if (const int c2 = prod(cur, "Concat"); c2 >= 0) {
+                    std::string s2, s1;
+                    int64_t k2 = 0, k1 = 0;
+                    int sa[2], sb[2];
+                    if (!single_use(cur) || !roll(c2, 2, Wp, s2, k2, sa)) continue;
+                    const int c1 = prod(s2, "Concat");
+                    if (c1 < 0 || !roll(c1, 1, Hp, s1, k1, sb) || k1 != k2) continue;
+                    shift = k1; cur = s1; counted = true;
+                    extra.insert(extra.end(), {c2, c1, sa[0], sa[1], sb[0], sb[1]});
+                }
+                if (const int pd = prod(cur, "Pad"); pd >= 0) {
+                    const GNode& pn = nodes[pd];
+                    if (!(counted || single_use(cur)) || pn.as("mode", "constant") != "constant" || pn.in.size() < 2 || pn.in.size() > 3) continue;
+                    const std::vector<int64_t> pads = ints(pn.in[1]);
+                    if (pads.size() != 8 || pads[0] || pads[1] || pads[2] || pads[3] || pads[4] || pads[7] || pads[5] < 0 || pads[6] < 0 || pads[5] >= ws || pads[6] >= ws) continue;
+                    if (pn.in.size() == 3 && !pn.in[2].empty()) {
+                        auto it = inits_.find(pn.in[2]);
+                        if (it == inits_.end() || it->second.dtype != DType::F32 || it->second.f.size() != 1 || it->second.f[0] != 0.0f) continue;
+                    }
+                    H = Hp - pads[5]; W = Wp - pads[6];
+                    cur = pn.in[0]; counted = false;
+                    extra.push_back(pd);
+                }
+                const int fr = prod(cur, "Reshape");
+                if (fr < 0 || !(counted || single_use(cur)) || target(nodes[fr]) != std::vector<int64_t>{0, H, W, C}) continue;   // (constants: a dynamic H / W is not matched)
+                cur = nodes[fr].in[0];
+                extra.push_back(fr);
+            }
+            const std::string y = cur;
+            std::string out = nodes[v3].out[0];
+            if (grid) {   // behind the reverse: roll by +s (the exact inverse of the forward one) -> crop -> Reshape[0, H W, C]
+                bool ok2 = true;
+                if (shift > 0) {
+                    int sa[2], sb[2];
+                    const int c1 = roll_of(out, 1, Hp, Hp - shift, sa);
+                    const int c2 = c1 < 0 ? -1 : roll_of(nodes[c1].out[0], 2, Wp, Wp - shift, sb);
+                    ok2 = c2 >= 0;
+                    if (ok2) { out = nodes[c2].out[0]; extra.insert(extra.end(), {c1, c2, sa[0], sa[1], sb[0], sb[1]}); }
+                }
+                for (int ax = 1; ax <= 2 && ok2; ++ax) {
+                    if ((ax == 1 ? Hp - H : Wp - W) == 0) continue;
+                    const int cr = only_reader(out, "Slice");
+                    Sl c;
+                    ok2 = cr >= 0 && slice1(cr, c) && c.ax == ax && c.st == 0 && c.en == (ax == 1 ? H : W);
+                    if (ok2) { out = nodes[cr].out[0]; extra.push_back(cr); }
+                }
+                if (!ok2) continue;
+                const int fin = only_reader(out, "Reshape");
+                if (fin < 0) continue;
+                const std::vector<int64_t> ft = target(nodes[fin]);
+                if (ft != std::vector<int64_t>{0, H * W, C} && ft != std::vector<int64_t>{-1, H * W, C}) continue;
+                out = nodes[fin].out[0];
+                extra.push_back(fin);
+            }
             GNode wa;
             wa.op = "WindowAttention";
             wa.in = {nodes[ln[0]].out[0], nodes[ln[1]].out[0], nodes[ln[2]].out[0], nodes[ad].in[bi]};
+            if (m3 >= 0 || Hp != H || Wp != W) {   // the mask, and what a padded token becomes behind the k and v Linears: their biases
+                const bool pads = Hp != H || Wp != W;
+                wa.in.insert(wa.in.end(), {maskn, pads ? nodes[ln[1]].bias : std::string(), pads ? nodes[ln[2]].bias : std::string()});
+            }
             wa.out = {nodes[r2].out[0]};
             auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; wa.attrs[k] = a; };
-            iattr("ws", ws); iattr("H", H); iattr("W", W); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_div", scale_div);
+            iattr("ws", ws); iattr("H", H); iattr("W", W); iattr("Hp", Hp); iattr("Wp", Wp); iattr("shift", shift); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_div", scale_div);
             Attr as; as.kind = Attr::F; as.f = sct.f[0]; wa.attrs["scale"] = as;
-            const std::string y = nodes[p1].in[0], out = nodes[v3].out[0];
             for (int t = 0; t < 3; ++t) nodes[ln[t]].in[0] = y;
             nodes[pj].out[0] = out;
             for (int d : {p1, p2, p3, rs[0], rs[1], rs[2], tr[0], tr[1], tr[2], tk, mm1, sc, ad, i, mm2, t2, v1, v2, v3}) dead[d] = true;
+            for (int d : extra) dead[d] = true;
+            for (int d : {m1, m2, m3}) if (d >= 0) dead[d] = true;
             nodes[r2] = std::move(wa);   // behind q, k and v, in front of the projection
         }
         std::vector<GNode> keep;
@@ -4275,26 +4412,39 @@ struct Planner {
             step(run, flops, bytes);
         }
     }
-    // fused Swin window attention (rewrite pass 3b): q, k, v [B, H W, heads * head_dim] in image order, bias [1, heads, N, N] -> [B, H W, heads * head_dim] in image order
+    // fused Swin window attention (rewrite pass 3b): q, k, v [B, H W, heads * head_dim] in image order, bias [1, heads, N, N] -> [B, H W, heads * head_dim] in image order.
+    // Optional inputs 4 .. 6: the per-window mask [1, nW, 1, N, N] and the k / v Linears' biases of a block that pads
     void op_window_attention(const GNode& n) {
         TInfo q = get(n.in[0]), kk = get(n.in[1]), v = get(n.in[2]);
         const TInfo& bt = get(n.in[3]);
         const int64_t ws = n.ai("ws", 1), H = n.ai("H", 1), W = n.ai("W", 1), h = n.ai("heads", 1), d = n.ai("head_dim", 1), N = ws * ws, C = h * d;
-        OAR_CHECK(k::window_attention_supported((int)ws, (int)h, (int)d) && H % ws == 0 && W % ws == 0, OAR_INTERNAL, "WindowAttention: the rewrite let an unsupported shape through at " + n.out[0]);
+        const int64_t Hp = n.ai("Hp", H), Wp = n.ai("Wp", W), shift = n.ai("shift", 0);
+        OAR_CHECK(k::window_attention_supported((int)ws, (int)h, (int)d) && H >= 1 && W >= 1 && Hp % ws == 0 && Wp % ws == 0 && Hp >= H && Wp >= W && Hp - H < ws && Wp - W < ws &&
+                      shift >= 0 && shift < std::min(Hp, Wp), OAR_INTERNAL, "WindowAttention: the rewrite let an unsupported shape through at " + n.out[0]);
         OAR_CHECK(!q.host_int && !q.dims.empty() && q.dims.back() == C && numel(q.dims) % (H * W * C) == 0 && kk.dims == q.dims && v.dims == q.dims, OAR_SHAPE_MISMATCH,
                   "WindowAttention: q, k and v must be [B, " + std::to_string(H * W) + ", " + std::to_string(C) + "] at " + n.out[0]);
         OAR_CHECK(bt.ht && bt.loc.kind == Loc::CONST && (int64_t)bt.ht->f.size() == h * N * N, OAR_INTERNAL, "WindowAttention: the bias is not a constant of heads x N x N values at " + n.out[0]);
-        const int64_t B = numel(q.dims) / (H * W * C);
-        OAR_CHECK(B >= 1 && B * H * W < (int64_t)1 << 31, OAR_SHAPE_MISMATCH, "WindowAttention: batch out of range at " + n.out[0]);
-        Loc ql = to_native_loc(q), kl = to_native_loc(kk), vl = to_native_loc(v);
-        TInfo& y = new_out(n.out[0], {B, H * W, C}, Layout::NATIVE);   // (what the window reverse's Reshape [-1, H W, C] gives, whatever the rank of q)
-        Loc yl = y.loc;
+        const int64_t B = numel(q.dims) / (H * W * C), nW = (Hp / ws) * (Wp / ws);
+        OAR_CHECK(B >= 1 && B * H * W < (int64_t)1 << 31 && B * nW < (int64_t)1 << 31, OAR_SHAPE_MISMATCH, "WindowAttention: batch out of range at " + n.out[0]);
         k::WindowAttnP p{};
+        auto constant = [&](size_t i, int64_t count, const char* what) -> const float* {   // an optional constant input of `count` floats
+            if (!has_input(n, i)) return nullptr;
+            const TInfo& t = get(n.in[i]);
+            OAR_CHECK(t.ht && t.loc.kind == Loc::CONST && (int64_t)t.ht->f.size() == count, OAR_INTERNAL, std::string("WindowAttention: ") + what + " is not a constant of the expected size at " + n.out[0]);
+            return t.loc.cptr;
+        };
+        p.mask = constant(4, nW * N * N, "the mask");
+        p.kbias = constant(5, C, "the k bias");
+        p.vbias = constant(6, C, "the v bias");
+        Loc ql = to_native_loc(q), kl = to_native_loc(kk), vl = to_native_loc(v);
+        TInfo& y = new_out(n.out[0], {B, H * W, C}, Layout::NATIVE);   // (what the window reverse's last Reshape gives, whatever the rank of q)
+        Loc yl = y.loc;
         p.bias = bt.loc.cptr; p.ldq = p.ldk = p.ldv = p.ldo = (int)C; p.B = (int)B; p.H = (int)H; p.W = (int)W; p.ws = (int)ws; p.nh = (int)h; p.dh = (int)d;
         p.scale = n.af("scale", 1.0f); p.scale_div = (int)n.ai("scale_div", 0);
-        const double tokens = (double)B * H * W;
+        p.shift = (int)shift; p.Hp = (int)Hp; p.Wp = (int)Wp; p.nW = (int)nW;
+        const double tokens = (double)B * H * W, windows = (double)B * nW;   // real tokens only: a padding token costs neither a query nor a row of q, k, v or o
         step([=](const RunCtx& c) { k::WindowAttnP r = p; r.q = c.at(ql); r.k = c.at(kl); r.v = c.at(vl); r.o = c.mut(yl); k::window_attention(c.s, r); },
-             4.0 * tokens * N * C, 4.0 * (4.0 * tokens * C + tokens / N * h * N * N));
+             4.0 * tokens * N * C, 4.0 * (4.0 * tokens * C + windows * h * N * N * (p.mask ? 2 : 1)));
     }
     bool E_opset13() const { return opset >= 13 || opset == 0; }
     int64_t opset = 17;

@@ -237,17 +237,32 @@ int formula_decode_lm_workgroups(int V);          // (value, index) partials per
 int formula_decode_launches_per_step(int Ld);     // 8 Ld + 2, per chunk of kFdChunk images
 size_t formula_decode_ws_floats(int B, int D, int F, int V, int Ld, int M, int Dq);
 void formula_decode(hipStream_t s, const FormulaDecodeP& p);
-// window_attention.hip: the attention of one Swin block without shifted windows, one launch.  q, k, v [B H W][nh dh] in IMAGE order (token (b, y, x) is row
+// window_attention.hip: the attention of one Swin block, one launch.  q, k, v [B H W][nh dh] in IMAGE order (token (b, y, x) is row
 // (b H + y) W + x, row strides ldq / ldk / ldv floats), bias [nh][N][N] with N = ws^2 (the relative-position bias, added to the scaled scores);
-// o [B H W][nh dh] in image order.  A window's tokens are gathered and scattered by address: no partitioned copy exists.  H % ws == W % ws == 0.
+// o [B H W][nh dh] in image order.  A window's tokens are gathered and scattered by address: no partitioned copy exists.
 // scale_div: scores / scale (the graph's Div) instead of scores * scale (its Mul).
+// The windows tile the grid padded at the bottom / right to Hp x Wp (multiples of ws, Hp - H < ws, Wp - W < ws) and rolled by -shift on both axes
+// (window_token_row below).  A padding token is a key whose k / v rows are kbias / vbias (null: zeros) -- the graph pads in front of the Linears --
+// and is skipped as a query.  mask: null, or [nW][N][N] with nW = (Hp / ws) (Wp / ws), added to the scores behind the bias.
 struct WindowAttnP {
     const float *q, *k, *v, *bias;
     float* o;
     int ldq, ldk, ldv, ldo;
     int B, H, W, ws, nh, dh;
     float scale; int scale_div;
+    int shift, Hp, Wp, nW;
+    const float *mask, *kbias, *vbias;
 };
+// The address map of a Swin window: local token n = (r, c) of window (wy, wx) sits at (Y, X) = (wy ws + r, wx ws + c) of the padded, rolled grid and comes
+// from (y, x) = ((Y + shift) mod Hp, (X + shift) mod Wp) of the padded grid.  Returns the token's row y W + x within its image, or -1 for padding
+// (y >= H or x >= W).  The reverse roll and the crop are the inverse map, so the output goes to the same row.  (tests/test_swin_shift_cpu.py compiles this)
+__host__ __device__ inline int window_token_row(int wy, int wx, int n, int ws, int H, int W, int Hp, int Wp, int shift) {
+    const int r = n / ws, c = n - r * ws;
+    int y = wy * ws + r + shift, x = wx * ws + c + shift;
+    if (y >= Hp) y -= Hp;
+    if (x >= Wp) x -= Wp;
+    return y < H && x < W ? y * W + x : -1;
+}
 constexpr int kWinThreads = 256, kWinWaves = kWinThreads / 64, kWinMaxN = 256, kWinMaxDh = 64, kWinMaxNd = 8192;
 bool window_attention_supported(int ws, int heads, int head_dim);   // N = ws^2 <= kWinMaxN, head_dim <= kWinMaxDh, N head_dim <= kWinMaxNd
 // the kernel's LDS, all of it dynamic: K [N][dh | 1], V [N][dh], one q row and one row of probabilities per wave (tests/test_unimernet_cpu.py compiles this)

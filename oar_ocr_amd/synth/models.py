@@ -1194,7 +1194,7 @@ def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(
 
 # ---------------------------------------------------------------------------------------------- formula recognition: UniMERNet
 def swin_block_weights(C, nh, ws, hidden, seed=0, prefix=""):
-    """f32 weights of one Swin block without shifted windows (UniMERNet's encoder): LN1, the q / k / v / projection Linears as [out, in] matrices (q and k x2: an
+    """f32 weights of one Swin block (UniMERNet's encoder; a shift and its mask are the builder's, not weights): LN1, the q / k / v / projection Linears as [out, in] matrices (q and k x2: an
     attention that is not uniform), the relative-position bias as the [nh, N, N] table the exporter materialises -- U(-2, 2) per entry, so neither symmetric in
     (i, j) nor equal between heads --, the depthwise 3 x 3 "conv enhance", LN2 and the two MLP Linears."""
     rng = np.random.default_rng(seed)
@@ -1213,16 +1213,52 @@ def swin_block_weights(C, nh, ws, hidden, seed=0, prefix=""):
     return {prefix + k: v for k, v in w.items()}
 
 
-def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div"):
+def swin_shift_mask(H, W, ws, shift):
+    """the standard shifted-window mask [nW, N, N] on the grid padded to multiples of ws: per axis the three bands [0, Hp - ws), [Hp - ws, Hp - shift),
+    [Hp - shift, Hp) number the regions; -100 where the regions of tokens i and j of a window differ, 0 elsewhere"""
+    Hp, Wp = -(-H // ws) * ws, -(-W // ws) * ws
+    band = lambda n: np.digitize(np.arange(n), [n - ws, n - shift])
+    ids = band(Hp)[:, None] * 3 + band(Wp)[None, :]
+    ids = ids.reshape(Hp // ws, ws, Wp // ws, ws).transpose(0, 2, 1, 3).reshape(-1, ws * ws)
+    return np.where(ids[:, :, None] != ids[:, None, :], np.float32(-100.0), np.float32(0.0)).astype(np.float32)
+
+
+def _roll(g, t, axis, k, n):
+    """Concat(Slice(t, k:n), Slice(t, 0:k)) on `axis` of extent n: what roll(t, -k, axis) gives.  Each Slice is single-axis with unit step."""
+    i64 = lambda v, nm: g.init(np.array([v], np.int64), nm)
+    ax = i64(axis, "axes")
+    return g.op("Concat", [g.op("Slice", [t, i64(k, "starts"), i64(n, "ends"), ax]), g.op("Slice", [t, i64(0, "starts"), i64(k, "ends"), ax])], axis=axis)
+
+
+def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None, pad_value=0.0, unroll=None):
     """x [B, H W, C] -> x + window attention of LN1(x), in the spelling DESIGN 4.33 fixes (the engine's rewrite pass 3b matches it).  scale: "div" writes
-    Div(s, sqrt(dh)), "mul" Mul(s, dh^-0.5).  H or W no multiple of ws is refused here: the padded spelling is not written."""
-    if H % ws or W % ws or C % nh:
-        raise ValueError("H and W must be multiples of ws and C of the heads")
+    Div(s, sqrt(dh)), "mul" Mul(s, dh^-0.5).  H or W no multiple of ws: LN1's output is padded at the bottom / right with pad_value (Pad) and the result
+    cropped (Slice).  shift > 0: the padded grid is rolled by -shift on both axes in front of the partition and by +`unroll` (default: shift) behind the
+    reverse (Slice + Concat per axis).  mask: None, "swin" (swin_shift_mask) or an [nW, N, N] array, added per window behind the bias.  DESIGN 4.33.1."""
+    if H < 1 or W < 1 or C % nh:
+        raise ValueError("H and W must be positive and C a multiple of the heads")
     N, dh = ws * ws, C // nh
+    hb, wb = -(-H // ws), -(-W // ws)
+    Hp, Wp, nW = hb * ws, wb * ws, hb * wb
+    unroll = shift if unroll is None else unroll
+    if not (0 <= shift < min(Hp, Wp) and 0 <= unroll < min(Hp, Wp)):
+        raise ValueError("the shift must be in [0, min(Hp, Wp))")
+    if isinstance(mask, str):
+        if mask != "swin":
+            raise ValueError(mask)
+        mask = swin_shift_mask(H, W, ws, shift)
+    grid = (Hp, Wp) != (H, W) or shift > 0 or unroll > 0             # the 4-D view [B, Hp, Wp, C] is written only where it is needed
     ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    i64 = lambda v, nm: g.init(np.array([v], np.int64), nm)
     lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(np.ascontiguousarray(w[p + "w" + nm].T), "sw_" + p + "w" + nm)]), g.init(w[p + "b" + nm], "sw_" + p + "b" + nm)])
     y = g.op("LayerNormalization", [x, g.init(w[p + "ln1_g"], "sw_" + p + "ln1_g"), g.init(w[p + "ln1_b"], "sw_" + p + "ln1_b")], axis=-1, epsilon=1e-5)
-    t = g.op("Reshape", [y, ci([0, H // ws, ws, W // ws, ws, C])])
+    if grid:
+        y = g.op("Reshape", [y, ci([0, H, W, C])])
+    if (Hp, Wp) != (H, W):
+        y = g.op("Pad", [y, g.init(np.array([0, 0, 0, 0, 0, Hp - H, Wp - W, 0], np.int64), "pads"), g.init(np.array(pad_value, np.float32), "pad_value")], mode="constant")
+    if shift > 0:
+        y = _roll(g, _roll(g, y, 1, shift, Hp), 2, shift, Wp)
+    t = g.op("Reshape", [y, ci([0, hb, ws, wb, ws, C])])
     t = g.op("Reshape", [g.op("Transpose", [t], perm=[0, 1, 3, 2, 4, 5]), ci([-1, N, C])])
     heads = ci([0, N, nh, dh])
     qh, kh, vh = (g.op("Transpose", [g.op("Reshape", [lin(t, nm), heads])], perm=[0, 2, 1, 3]) for nm in ("q", "k", "v"))
@@ -1233,18 +1269,34 @@ def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div"):
         sc = g.op("Mul", [sc, g.init(np.array(dh ** -0.5, np.float32), "c")])
     else:
         raise ValueError(scale)
-    a = g.op("Softmax", [g.op("Add", [sc, g.init(w[p + "bias"][None], "sw_" + p + "bias")])], axis=-1)
+    a = g.op("Add", [sc, g.init(w[p + "bias"][None], "sw_" + p + "bias")])
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, np.float32)
+        if mask.ndim != 3 or mask.shape[1:] != (N, N):
+            raise ValueError("the mask must be [nW, N, N]")
+        a = g.op("Reshape", [a, ci([-1, mask.shape[0], nh, N, N])])
+        a = g.op("Reshape", [g.op("Add", [a, g.init(mask[None, :, None], "sw_" + p + "mask")]), ci([-1, nh, N, N])])
+    a = g.op("Softmax", [a], axis=-1)
     o = g.op("Reshape", [g.op("Transpose", [g.op("MatMul", [a, vh])], perm=[0, 2, 1, 3]), ci([0, N, C])])
     o = lin(o, "p")
-    r = g.op("Transpose", [g.op("Reshape", [o, ci([-1, H // ws, W // ws, ws, ws, C])])], perm=[0, 1, 3, 2, 4, 5])
-    return g.op("Add", [x, g.op("Reshape", [r, ci([-1, H * W, C])])])
+    r = g.op("Transpose", [g.op("Reshape", [o, ci([-1, hb, wb, ws, ws, C])])], perm=[0, 1, 3, 2, 4, 5])
+    if not grid:
+        return g.op("Add", [x, g.op("Reshape", [r, ci([-1, H * W, C])])])
+    r = g.op("Reshape", [r, ci([-1, Hp, Wp, C])])
+    if unroll > 0:
+        r = _roll(g, _roll(g, r, 1, Hp - unroll, Hp), 2, Wp - unroll, Wp)
+    if Hp != H:
+        r = g.op("Slice", [r, i64(0, "starts"), i64(H, "ends"), i64(1, "axes")])
+    if Wp != W:
+        r = g.op("Slice", [r, i64(0, "starts"), i64(W, "ends"), i64(2, "axes")])
+    return g.op("Add", [x, g.op("Reshape", [r, ci([0, H * W, C])])])
 
 
-def _swin_block(g, x, w, p, H, W, C, nh, ws, scale="div"):
+def _swin_block(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None, pad_value=0.0, unroll=None):
     """the attention block, the depthwise 3 x 3 "conv enhance" residual on the tokens viewed as an image, and LN2 -> Linear -> GELU -> Linear with its residual"""
     ci = lambda v: g.init(np.array(v, np.int64), "shape")
     lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(np.ascontiguousarray(w[p + "w" + nm].T), "sw_" + p + "w" + nm)]), g.init(w[p + "b" + nm], "sw_" + p + "b" + nm)])
-    x = _swin_attention(g, x, w, p, H, W, C, nh, ws, scale)
+    x = _swin_attention(g, x, w, p, H, W, C, nh, ws, scale, shift, mask, pad_value, unroll)
     img = g.op("Reshape", [g.op("Transpose", [x], perm=[0, 2, 1]), ci([0, C, H, W])])
     img = g.op("Conv", [img, g.init(w[p + "ce_w"], "sw_" + p + "ce_w"), g.init(w[p + "ce_b"], "sw_" + p + "ce_b")], kernel_shape=[3, 3], strides=[1, 1], pads=[1, 1, 1, 1], group=C, dilations=[1, 1])
     x = g.op("Add", [x, g.op("Transpose", [g.op("Reshape", [img, ci([0, C, -1])])], perm=[0, 2, 1])])
@@ -1252,18 +1304,28 @@ def _swin_block(g, x, w, p, H, W, C, nh, ws, scale="div"):
     return g.op("Add", [x, lin(g.op("Gelu", [lin(y, "1")], approximate="none"), "2")])
 
 
-def build_swin_block(H, W, C, nh, ws, seed=0, scale="div", whole=False):
-    """One Swin block as a graph of its own: x [B, H W, C] -> `y` [B, H W, C].  whole = False: the attention part only (LN1 .. the residual Add)."""
+def build_swin_block(H, W, C, nh, ws, seed=0, scale="div", whole=False, shift=0, mask=None, pad_value=None, unroll=None):
+    """One Swin block as a graph of its own: x [B, H W, C] -> `y` [B, H W, C].  whole = False: the attention part only (LN1 .. the residual Add).
+    shift, mask, pad_value, unroll: _swin_attention's.  A grid that is no multiple of ws is written padded only when pad_value is given (0.0 is the Swin
+    spelling); with pad_value = None such a grid is refused, as it always was."""
+    if pad_value is None:
+        if H % ws or W % ws:
+            raise ValueError("H and W must be multiples of ws unless pad_value is given")
+        pad_value = 0.0
     w = swin_block_weights(C, nh, ws, 2 * C, seed)
     g = GraphBuilder("swin_block", 17)
     g.add_input("x", ["B", H * W, C])
-    y = (_swin_block if whole else _swin_attention)(g, "x", w, "", H, W, C, nh, ws, scale)
+    y = (_swin_block if whole else _swin_attention)(g, "x", w, "", H, W, C, nh, ws, scale, shift, mask, pad_value, unroll)
     g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
     g.add_output("y", ["B", H * W, C])
-    return g.model(), {"params": g.n_params, "weights": w, "H": H, "W": W, "C": C, "nh": nh, "ws": ws, "scale": scale, "whole": whole}
+    info = {"params": g.n_params, "weights": w, "H": H, "W": W, "C": C, "nh": nh, "ws": ws, "scale": scale, "whole": whole}
+    if shift or unroll or mask is not None or pad_value != 0.0:
+        info.update(shift=shift, unroll=shift if unroll is None else unroll, pad_value=float(pad_value),
+                    mask=swin_shift_mask(H, W, ws, shift) if isinstance(mask, str) else mask)
+    return g.model(), info
 
 
-def unimernet_weights(C=32, heads=(2, 4), depths=(2, 2), ws=4, mlp_ratio=2, seed=0):
+def unimernet_weights(C=32, heads=(2, 4), depths=(2, 2), ws=4, mlp_ratio=2, seed=0, shifted=False):
     """the encoder's weights: the stem (two 3 x 3 stride-2 convolutions: 1 -> C / 2 -> C), per stage `depths[s]` Swin blocks at width C 2^s (prefix s<s>b<b>_),
     between stages the patch merging (m<s>_ln_g / _ln_b over 4 C', m<s>_w [2 C', 4 C'], no bias), and the final LayerNorm lnf_g / lnf_b"""
     rng = np.random.default_rng(seed + 7)
@@ -1279,17 +1341,21 @@ def unimernet_weights(C=32, heads=(2, 4), depths=(2, 2), ws=4, mlp_ratio=2, seed
             w[f"m{si}_w"] = u(2 * Cs, 4 * Cs, k=4 * Cs)
     w["lnf_g"], w["lnf_b"] = ln(C << (len(depths) - 1))
     w.update(C=C, heads=tuple(heads), depths=tuple(depths), ws=ws, mlp_ratio=mlp_ratio)
+    if shifted:
+        w.update(shifted=True)
     return w
 
 
 def build_unimernet(image_shape=(192, 672), C=32, heads=(2, 4), depths=(2, 2), ws=4, mlp_ratio=2, nh=4, F=128, V=300, Ld=2, M=32, P=None, seed=0, qk_squeeze=2, scale="div",
-                    encoder_only=False, with_logits=False, sos=0):
+                    encoder_only=False, with_logits=False, sos=0, shifted=False):
     """UniMERNet-shaped formula recognizer, in the spelling DESIGN 4.33 fixes: x [B, 1, H, W] (image_shape = (H, W); the preprocessor's target (672, 192) is
-    (W, H)) -> stem: two 3 x 3 stride-2 convolutions with GELU -> tokens [B, (H / 4) (W / 4), C] -> `len(depths)` stages of Swin blocks without shifted windows
+    (W, H)) -> stem: two 3 x 3 stride-2 convolutions with GELU -> tokens [B, (H / 4) (W / 4), C] -> `len(depths)` stages of Swin blocks
     (_swin_block; window ws, heads[s] heads at width C 2^s), patch merging between stages (Reshape [0, H/2, 2, W/2, 2, C] -> Transpose [0,1,3,2,4,5] -> Reshape
     [0, -1, 4C] -> LayerNorm -> Linear 4C -> 2C) -> a final LayerNorm -> `memory` [B, S, D], D = C 2^(stages - 1), a declared output -> the per-layer KmT_l / Vm_l
     nodes and the squeeze-attention decode Loop of build_formulanet(qk_squeeze) -> token_ids [B, M] int64, the graph's FIRST output.  encoder_only: `memory` is
-    the only output and no decoder is written.  scale: how the blocks spell the attention scale ("div" or "mul").
+    the only output and no decoder is written.  scale: how the blocks spell the attention scale ("div" or "mul").  shifted: the odd blocks of a stage roll
+    the grid by ws // 2 and add the "swin" mask (DESIGN 4.33.1).  A ws that does not divide a stage's grid makes that stage's blocks pad; patch merging of an
+    odd grid is refused.
     Returns (onnx_bytes, info): info["encoder"] the encoder's weights (unimernet_weights), info["weights"] the decoder's (formula_weights)."""
     Hi, Wi = image_shape
     stages = len(depths)
@@ -1297,7 +1363,7 @@ def build_unimernet(image_shape=(192, 672), C=32, heads=(2, 4), depths=(2, 2), w
         raise ValueError("the image sides must be multiples of 4 * 2^(stages - 1)")
     D = C << (stages - 1)
     P = P if P is not None else M + 2
-    we = unimernet_weights(C, heads, depths, ws, mlp_ratio, seed)
+    we = unimernet_weights(C, heads, depths, ws, mlp_ratio, seed, shifted)
     g = GraphBuilder("unimernet", 17)
     ci = lambda v: g.init(np.array(v, np.int64), "shape")
     g.add_input("x", ["B", 1, Hi, Wi])
@@ -1310,7 +1376,8 @@ def build_unimernet(image_shape=(192, 672), C=32, heads=(2, 4), depths=(2, 2), w
     for si in range(stages):
         Cs = C << si
         for bi in range(depths[si]):
-            t = _swin_block(g, t, we, f"s{si}b{bi}_", H, W, Cs, heads[si], ws, scale)
+            sh = ws // 2 if shifted and bi % 2 else 0
+            t = _swin_block(g, t, we, f"s{si}b{bi}_", H, W, Cs, heads[si], ws, scale, sh, "swin" if sh else None)
         if si + 1 < stages:
             t = g.op("Reshape", [g.op("Transpose", [g.op("Reshape", [t, ci([0, H // 2, 2, W // 2, 2, Cs])])], perm=[0, 1, 3, 2, 4, 5]), ci([0, -1, 4 * Cs])])
             t = g.op("LayerNormalization", [t, g.init(we[f"m{si}_ln_g"], f"m{si}_ln_g"), g.init(we[f"m{si}_ln_b"], f"m{si}_ln_b")], axis=-1, epsilon=1e-5)
