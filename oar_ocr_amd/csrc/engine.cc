@@ -1296,6 +1296,178 @@ void Engine::rewrite_graph(OnnxModel& m) {
         for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
         nodes.swap(keep);
     }
+    // ---- pass 3c: multi-scale deformable attention (the cross-attention core of an RT-DETR decoder layer), in the exported spelling, with static
+    //   nh, c, Q, P and levels (h_l, w_l), Lv = sum h_l w_l:
+    //   weights:  Reshape(logit, [0, Q, nh, L P]) -> Softmax(-1) -> Reshape[0, Q, nh, L, P]           (the Softmax may be missing: the input holds the weights)
+    //             -> Transpose[0,2,1,3,4] -> Reshape[-1, 1, Q, L P]
+    //   value:    Reshape(value, [0, Lv, nh, c]) -> Split(axis 1, [h_l w_l]);   grid = Sub(Mul(loc, 2), 1),  loc [N, Q, nh, L, P, 2]
+    //   level l:  Reshape(v_l, [0, h w, nh c]) -> Transpose[0,2,1] -> Reshape[-1, c, h, w]
+    //             Slice(grid, l : l + 1, axis 3) -> Squeeze[3] -> Transpose[0,2,1,3,4] -> Reshape[-1, Q, P, 2]
+    //             GridSample(bilinear, zeros, align_corners = 0) -> Unsqueeze[3]
+    //   combine:  Concat(axis 3) -> Reshape[0, c, Q, L P] -> Mul(., weights) -> ReduceSum(-1, keepdims 0) -> Reshape[-1, nh c, Q] -> Transpose[0,2,1]
+    // becomes ONE DeformableAttention node (csrc/deformable_attention.hip) on value, loc and the logits (or weights): the value already holds the c channels of
+    // a (location, head) contiguously, so the taps are read from it by address.  The match is exact: another GridSample mode / padding / alignment, another
+    // permutation, levels that do not sum to Lv, an intermediate with a second reader (or that is a graph output), or a shape
+    // k::deformable_attention_supported rejects keep the op-by-op route, and so does OAR_FUSE_DEFORMABLE_ATTENTION=0.
+    {
+        const char* fe = getenv("OAR_FUSE_DEFORMABLE_ATTENTION");
+        const bool fuse = !fe || atoi(fe) != 0;
+        auto cons = consumers(nodes);
+        std::map<std::string, int> producer;
+        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
+        std::vector<bool> dead(nodes.size(), false);
+        using V = std::vector<int64_t>;
+        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
+        auto prod1 = [&](const std::string& v, const char* op) -> int {   // the live producer `op` of v, v read by nobody else
+            auto it = producer.find(v);
+            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op || nodes[it->second].act.kind != k::ACT_NONE || !single_use(v)) return -1;
+            return it->second;
+        };
+        auto reader1 = [&](const std::string& v, const char* op) -> int {   // the single consumer of v, a live `op` reading it first
+            if (!single_use(v)) return -1;
+            const int c = cons[v][0];
+            return !dead[c] && nodes[c].op == op && nodes[c].act.kind == k::ACT_NONE && nodes[c].in[0] == v ? c : -1;
+        };
+        auto ints = [&](const std::string& v) -> V {
+            auto it = inits_.find(v);
+            return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
+        };
+        auto target = [&](const GNode& r) -> V { return r.in.size() < 2 || r.ai("allowzero", 0) != 0 ? V{} : ints(r.in[1]); };
+        auto axes_are = [&](const GNode& n, int64_t a, int64_t rank) {   // opset 13 input or the older attribute; a or a - rank
+            const V ax = n.in.size() > 1 && !n.in[1].empty() ? ints(n.in[1]) : n.ais("axes");
+            return ax.size() == 1 && (ax[0] == a || ax[0] == a - rank);
+        };
+        auto scalar_is = [&](const std::string& v, float want) {
+            auto it = inits_.find(v);
+            return it != inits_.end() && it->second.dtype == DType::F32 && it->second.f.size() == 1 && it->second.f[0] == want;
+        };
+        for (int i = 0; fuse && i < (int)nodes.size(); ++i) {
+            const GNode& cc = nodes[i];
+            if (cc.op != "Concat" || dead[i] || cc.ai("axis", 0) != 3 || cc.act.kind != k::ACT_NONE || cc.in.empty() || (int)cc.in.size() > k::kDefMaxLevels) continue;
+            const int64_t L = (int64_t)cc.in.size();
+            int64_t c = 0, nh = 0, Q = 0, P = 0, Lv = 0;
+            std::vector<int64_t> lv;                 // h, w per level
+            std::vector<int> kill;
+            std::string gridn;
+            int sp = -1;
+            bool ok = true;
+            for (int64_t l = 0; l < L && ok; ++l) {
+                ok = false;
+                const int us = prod1(cc.in[l], "Unsqueeze");
+                if (us < 0 || !axes_are(nodes[us], 3, 5)) break;
+                const int gs = prod1(nodes[us].in[0], "GridSample");
+                if (gs < 0 || nodes[gs].in.size() != 2) break;
+                const std::string mode = nodes[gs].as("mode", "linear");
+                if ((mode != "linear" && mode != "bilinear") || nodes[gs].as("padding_mode", "zeros") != "zeros" || nodes[gs].ai("align_corners", 0) != 0) break;
+                // value side
+                const int r2 = prod1(nodes[gs].in[0], "Reshape");
+                if (r2 < 0) break;
+                const V t2 = target(nodes[r2]);
+                if (t2.size() != 4 || t2[0] != -1 || t2[1] < 1 || t2[2] < 1 || t2[3] < 1 || (c && t2[1] != c)) break;
+                c = t2[1];
+                const int64_t h = t2[2], w = t2[3];
+                if (h >= (int64_t)1 << 30 || w >= (int64_t)1 << 30) break;
+                const int t1 = prod1(nodes[r2].in[0], "Transpose");
+                if (t1 < 0 || nodes[t1].ais("perm") != V{0, 2, 1}) break;
+                const int r1 = prod1(nodes[t1].in[0], "Reshape");
+                if (r1 < 0) break;
+                const V tg1 = target(nodes[r1]);
+                if (tg1.size() != 3 || tg1[0] != 0 || tg1[1] != h * w || tg1[2] < c || tg1[2] % c || (nh && tg1[2] != nh * c)) break;
+                nh = tg1[2] / c;
+                const int s = prod1(nodes[r1].in[0], "Split");
+                if (s < 0 || (sp >= 0 && s != sp) || (int64_t)nodes[s].out.size() != L || nodes[s].out[(size_t)l] != nodes[r1].in[0]) break;
+                sp = s;
+                // grid side
+                const int r3 = prod1(nodes[gs].in[1], "Reshape");
+                if (r3 < 0) break;
+                const V t3 = target(nodes[r3]);
+                if (t3.size() != 4 || t3[0] != -1 || t3[1] < 1 || t3[2] < 1 || t3[3] != 2 || (Q && (t3[1] != Q || t3[2] != P))) break;
+                Q = t3[1]; P = t3[2];
+                const int tg = prod1(nodes[r3].in[0], "Transpose");
+                if (tg < 0 || nodes[tg].ais("perm") != V{0, 2, 1, 3, 4}) break;
+                const int sq = prod1(nodes[tg].in[0], "Squeeze");
+                if (sq < 0 || !axes_are(nodes[sq], 3, 6)) break;
+                const int sl = prod1(nodes[sq].in[0], "Slice");
+                if (sl < 0 || nodes[sl].in.size() < 4 || nodes[sl].in.size() > 5) break;
+                if (ints(nodes[sl].in[1]) != V{l} || ints(nodes[sl].in[2]) != V{l + 1} || ints(nodes[sl].in[3]) != V{3}) break;
+                if (nodes[sl].in.size() == 5 && !nodes[sl].in[4].empty() && ints(nodes[sl].in[4]) != V{1}) break;
+                if (!gridn.empty() && nodes[sl].in[0] != gridn) break;
+                gridn = nodes[sl].in[0];
+                lv.push_back(h); lv.push_back(w);
+                Lv += h * w;
+                kill.insert(kill.end(), {us, gs, r2, t1, r1, r3, tg, sq, sl});
+                ok = true;
+            }
+            if (!ok || sp < 0) continue;
+            // the Split: axis 1, the levels' sizes in order; in front of it Reshape(value, [0, Lv, nh, c])
+            const GNode& spn = nodes[sp];
+            V parts = spn.in.size() > 1 && !spn.in[1].empty() ? ints(spn.in[1]) : spn.ais("split");
+            if (spn.ai("axis", 0) != 1 || (int64_t)parts.size() != L) continue;
+            bool parts_ok = true;
+            for (int64_t l = 0; l < L; ++l) parts_ok = parts_ok && parts[(size_t)l] == lv[(size_t)(2 * l)] * lv[(size_t)(2 * l + 1)];
+            if (!parts_ok) continue;
+            const int rv = prod1(spn.in[0], "Reshape");
+            if (rv < 0 || target(nodes[rv]) != V{0, Lv, nh, c}) continue;
+            // the grid: Sub(Mul(loc, 2), 1), read by the L Slices alone
+            if ((int64_t)cons[gridn].size() != L || graph_outs.count(gridn)) continue;
+            auto git = producer.find(gridn);
+            if (git == producer.end() || dead[git->second]) continue;
+            const int sb = git->second;
+            if (nodes[sb].op != "Sub" || nodes[sb].act.kind != k::ACT_NONE || nodes[sb].in.size() != 2 || !scalar_is(nodes[sb].in[1], 1.0f)) continue;
+            const int ml = prod1(nodes[sb].in[0], "Mul");
+            if (ml < 0 || nodes[ml].in.size() != 2) continue;
+            const int ci = scalar_is(nodes[ml].in[1], 2.0f) ? 1 : scalar_is(nodes[ml].in[0], 2.0f) ? 0 : -1;
+            if (ci < 0) continue;
+            const std::string locn = nodes[ml].in[1 - ci];
+            // combine
+            const int rc = reader1(cc.out[0], "Reshape");
+            if (rc < 0 || target(nodes[rc]) != V{0, c, Q, L * P}) continue;
+            const int mu = reader1(nodes[rc].out[0], "Mul");
+            if (mu < 0 || nodes[mu].in.size() != 2) continue;
+            const int rw = prod1(nodes[mu].in[1], "Reshape");
+            if (rw < 0 || target(nodes[rw]) != V{-1, 1, Q, L * P}) continue;
+            const int tw = prod1(nodes[rw].in[0], "Transpose");
+            if (tw < 0 || nodes[tw].ais("perm") != V{0, 2, 1, 3, 4}) continue;
+            const int r5 = prod1(nodes[tw].in[0], "Reshape");
+            if (r5 < 0 || target(nodes[r5]) != V{0, Q, nh, L, P}) continue;
+            int sm = prod1(nodes[r5].in[0], "Softmax"), r4 = -1;
+            std::string wn = nodes[r5].in[0];
+            if (sm >= 0) {
+                const int64_t ax = nodes[sm].ai("axis", -1);
+                if (ax != -1 && ax != 3) continue;
+                r4 = prod1(nodes[sm].in[0], "Reshape");
+                if (r4 < 0 || target(nodes[r4]) != V{0, Q, nh, L * P}) continue;
+                wn = nodes[r4].in[0];
+            } else if (producer.count(wn) && nodes[producer[wn]].op == "Softmax") {
+                continue;                            // a Softmax that did not fit (a second reader, another axis): not ours
+            } else if (const int r = prod1(wn, "Reshape"); r >= 0 && target(nodes[r]) == V{0, Q, nh, L * P}) {
+                r4 = r;                              // the weights as an input: the same two Reshapes without the Softmax between them
+                wn = nodes[r4].in[0];
+            }
+            const int rd = reader1(nodes[mu].out[0], "ReduceSum");
+            if (rd < 0 || !axes_are(nodes[rd], 3, 4) || nodes[rd].ai("keepdims", 1) != 0) continue;
+            const int ro = reader1(nodes[rd].out[0], "Reshape");
+            if (ro < 0 || target(nodes[ro]) != V{-1, nh * c, Q}) continue;
+            const int tf = reader1(nodes[ro].out[0], "Transpose");
+            if (tf < 0 || nodes[tf].ais("perm") != V{0, 2, 1}) continue;
+            if (!k::deformable_attention_supported(1, Q, nh, c, L, P, Lv)) continue;
+            GNode da;
+            da.op = "DeformableAttention";
+            da.in = {nodes[rv].in[0], locn, wn};
+            da.out = {nodes[tf].out[0]};
+            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; da.attrs[k] = a; };
+            iattr("heads", nh); iattr("points", P); iattr("softmax", sm >= 0 ? 1 : 0);
+            Attr la; la.kind = Attr::IS; la.is = lv; da.attrs["levels"] = la;
+            for (int d : kill) dead[d] = true;
+            for (int d : {i, sp, rv, sb, ml, rc, mu, rw, tw, r5, rd, ro}) dead[d] = true;
+            if (sm >= 0) dead[sm] = true;
+            if (r4 >= 0) dead[r4] = true;
+            nodes[tf] = std::move(da);               // the pattern's last node: every input is computed in front of it
+        }
+        std::vector<GNode> keep;
+        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
+        nodes.swap(keep);
+    }
     // ---- pass 4: Linear / Conv -> Add(residual): fold the residual into the producer's epilogue (no act between);
     // shapes are only known at plan time: op_conv / op_linear fall back to a separate add when they do not match
     {
@@ -4446,6 +4618,31 @@ struct Planner {
         step([=](const RunCtx& c) { k::WindowAttnP r = p; r.q = c.at(ql); r.k = c.at(kl); r.v = c.at(vl); r.o = c.mut(yl); k::window_attention(c.s, r); },
              4.0 * tokens * N * C, 4.0 * (4.0 * tokens * C + windows * h * N * N * (p.mask ? 2 : 1)));
     }
+    // fused multi-scale deformable attention (rewrite pass 3c): value [N, Lv, heads * c], loc [N, Q, heads, L, P, 2], logits or weights [N, Q, heads * L * P]
+    // -> [N, Q, heads * c]
+    void op_deformable_attention(const GNode& n) {
+        TInfo v = get(n.in[0]), lc = get(n.in[1]), w = get(n.in[2]);
+        const std::vector<int64_t> lv = n.ais("levels");
+        const int64_t nh = n.ai("heads", 1), P = n.ai("points", 1), L = (int64_t)lv.size() / 2;
+        OAR_CHECK(L >= 1 && L <= k::kDefMaxLevels && lv.size() == (size_t)(2 * L) && !v.host_int && !lc.host_int && !w.host_int, OAR_INTERNAL, "DeformableAttention: bad node at " + n.out[0]);
+        OAR_CHECK(lc.dims.size() == 6 && lc.dims[2] == nh && lc.dims[3] == L && lc.dims[4] == P && lc.dims[5] == 2 && lc.dims[0] >= 1 && lc.dims[1] >= 1, OAR_SHAPE_MISMATCH,
+                  "DeformableAttention: the locations must be [N, Q, heads, levels, points, 2] at " + n.out[0]);
+        const int64_t N = lc.dims[0], Q = lc.dims[1];
+        k::DeformAttnP p{};
+        int64_t Lv = 0;
+        for (int64_t l = 0; l < L; ++l) { p.h[l] = (int)lv[(size_t)(2 * l)]; p.wd[l] = (int)lv[(size_t)(2 * l + 1)]; p.start[l] = (int)Lv; Lv += lv[(size_t)(2 * l)] * lv[(size_t)(2 * l + 1)]; }
+        const int64_t per = N * Lv * nh, c = per > 0 && numel(v.dims) % per == 0 ? numel(v.dims) / per : 0;
+        OAR_CHECK(c >= 1 && numel(w.dims) == N * Q * nh * L * P, OAR_SHAPE_MISMATCH,
+                  "DeformableAttention: value must hold N x " + std::to_string(Lv) + " x heads x c floats and the weights N x Q x heads x levels x points at " + n.out[0]);
+        OAR_CHECK(k::deformable_attention_supported(N, Q, nh, c, L, P, Lv), OAR_UNSUPPORTED_OP, "DeformableAttention: batch or query count outside the kernel's limits at " + n.out[0]);
+        Loc vl = to_native_loc(v), ll = to_native_loc(lc), wl = to_native_loc(w);
+        TInfo& y = new_out(n.out[0], {N, Q, nh * c}, Layout::NATIVE);
+        Loc yl = y.loc;
+        p.N = (int)N; p.Q = (int)Q; p.nh = (int)nh; p.c = (int)c; p.L = (int)L; p.P = (int)P; p.Lv = (int)Lv; p.softmax = (int)n.ai("softmax", 1);
+        const double samples = (double)N * Q * nh * L * P;
+        step([=](const RunCtx& cx) { k::DeformAttnP r = p; r.value = cx.at(vl); r.loc = cx.at(ll); r.w = cx.at(wl); r.y = cx.mut(yl); k::deformable_attention(cx.s, r); },
+             samples * (9.0 * c + 24.0), 4.0 * (samples * (4.0 * c + 3.0) + (double)N * Q * nh * c));
+    }
     bool E_opset13() const { return opset >= 13 || opset == 0; }
     int64_t opset = 17;
 
@@ -4786,6 +4983,7 @@ struct Planner {
         if (op == "Softmax") return op_softmax(n);
         if (op == "Attention") return op_attention(n);
         if (op == "WindowAttention") return op_window_attention(n);
+        if (op == "DeformableAttention") return op_deformable_attention(n);
         if (op == "SLADecode") return op_sla_decode(n);
         if (op == "FormulaDecode") return op_formula_decode(n);
         if (op == "SEGate") return op_se_gate(n);

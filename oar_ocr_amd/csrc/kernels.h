@@ -270,6 +270,20 @@ inline size_t window_attention_lds_bytes(int N, int head_dim) {
     return ((size_t)N * (size_t)(head_dim | 1) + (size_t)N * head_dim + (size_t)kWinWaves * kWinMaxDh + (size_t)kWinWaves * N) * sizeof(float);
 }
 void window_attention(hipStream_t s, const WindowAttnP& p);
+// deformable_attention.hip: multi-scale deformable attention (RT-DETR's decoder), one launch.  value [N][Lv][nh][c] with Lv = sum of h w over the levels,
+// level l starting at row start[l]; loc [N][Q][nh][L][P][2] = (x, y) in units of the level's width / height; w [N][Q][nh][L P]: logits (softmax = 1: the
+// kernel takes their softmax over L P) or the weights themselves; y [N][Q][nh c].  Every sample is a bilinear tap with zero padding (GridSample, align_corners
+// = 0): a corner outside [0, w) x [0, h) is tested in float, contributes 0 and never becomes an address.
+constexpr int kDefMaxLevels = 4, kDefMaxSamples = 32, kDefMaxC = 64, kDefThreads = 256;
+struct DeformAttnP {
+    const float *value, *loc, *w;
+    float* y;
+    int N, Q, nh, c, L, P, Lv, softmax;
+    int h[kDefMaxLevels], wd[kDefMaxLevels], start[kDefMaxLevels];
+};
+// c % 4 == 0, c <= kDefMaxC, L <= kDefMaxLevels, L P <= kDefMaxSamples, and token / thread counts that fit 32 bits (N = Q = 1: the static part of the question)
+bool deformable_attention_supported(int64_t N, int64_t Q, int64_t nh, int64_t c, int64_t L, int64_t P, int64_t Lv);
+void deformable_attention(hipStream_t s, const DeformAttnP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

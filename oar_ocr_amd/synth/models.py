@@ -789,7 +789,7 @@ def build_layout(kind="picodet", n_classes=5, seed=11, image_shape=(800, 608), f
 
 
 # ---------------------------------------------------------------------------------------------- table cell detector: a graph that SELECTS
-def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classes=1, seed=21):
+def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classes=1, seed=21, decoder_layers=0, decoder_heads=4, decoder_points=4):
     """An RT-DETR-shaped table cell detector with synthetic weights whose query selection really runs in the graph (build_layout's "rtdetr" is
     a CNN head with RT-DETR's column order).  Inputs, bound by name as RTDetrModel::infer binds them (models/detection/rtdetr.rs:160-180):
     "image" [N,3,H,W] (declared first: the engine's primary input), "scale_factor" [N,2] = (ratio_h, ratio_w), "im_shape" [N,2] = resized (h, w).
@@ -797,6 +797,9 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
       select    encoder score head -> ReduceMax over classes -> enc_scores [N, A] -> TopK(queries) -> topk_idx [N, Q]
       gather    memory through GatherND(batch_dims = 1); the constant anchor logits through GatherElements with the index Expanded to [N, Q, 4]
       decode    two-layer MLP; box = sigmoid(anchor logit + delta) as (cx, cy, w, h) -> x1 y1 x2 y2, * im_shape, / scale_factor; class scores
+                decoder_layers > 0: an RT-DETR decoder of that many layers (_rtdetr_decoder: self-attention over the queries, multi-scale deformable
+                cross-attention into `memory` with decoder_heads heads and decoder_points points per level, FFN, box refinement) sits between the
+                gathers and these heads, which then read its last layer's queries and reference logits.  0 (the default) leaves the graph as it was
       order     TopK(keep) over the per-query best score; a tensor-indexed Gather over the batch-flattened rows assembles
                 output 0 "boxes" [N * keep, 6] = (class, score, x1, y1, x2, y2), sorted by score like the real export's
     Every TopK has its input and its index output declared as further graph outputs (info["topk"]), so a test can check each selection exactly
@@ -846,6 +849,10 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
     zero = g.op("Mul", [g.op("Unsqueeze", [enc_scores, i64([2], "axes")]), g.init(np.zeros((1, 1, 4), np.float32), "zero")])
     anchors_n = g.op("Add", [zero, g.init(anchor_logit, "anchors")])                                                    # the constant, once per image: [N, A, 4]
     ref = g.op("GatherElements", [anchors_n, g.op("Expand", [idx3, i64([1, 1, 4])])], axis=1)                           # [N, Q, 4]
+    if decoder_layers:
+        levels = [(H // st, W // st) for st in (8, 16, 32)]
+        dw = rtdetr_decoder_weights(D, decoder_heads, levels, decoder_points, decoder_layers, n_classes, seed=seed + 1)
+        tgt, ref = _rtdetr_decoder(g, dw, memory, tgt, ref, D, decoder_heads, levels, decoder_points, decoder_layers, queries)[-1]
     hdn = g.op("Relu", [linear(tgt, D, D)])
     hdn = g.op("Relu", [linear(hdn, D, D)])
     delta = linear(hdn, D, 4, gain=0.5)
@@ -877,7 +884,155 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
     for t, cols in zip(topk, ("A", "Q")):
         g.add_output(t["input"], ["N", A if cols == "A" else queries])
         g.add_output(t["index"], ["N", t["k"]], elem_type=7)
-    return g.model(), {"params": g.n_params, "kind": "rtdetr", "classes": n_classes, "anchors": A, "queries": queries, "keep": keep, "feat": 6, "topk": topk}
+    return g.model(), {"params": g.n_params, "kind": "rtdetr", "classes": n_classes, "anchors": A, "queries": queries, "keep": keep, "feat": 6, "topk": topk,
+                       **({"decoder_layers": decoder_layers} if decoder_layers else {})}
+
+
+# ---------------------------------------------------------------------------------------------- RT-DETR decoder: multi-scale deformable attention
+def _deformable_core(g, value, loc, logit, Q, nh, c, levels, P, weights="softmax", align_corners=0, out=None):
+    """value [N, Lv, nh c], loc [N, Q, nh, L, P, 2], logit [N, Q, nh L P] -> [N, Q, nh c]: PaddleDetection's deformable_attention_core_func as its export
+    spells it (the engine's rewrite pass 3c matches exactly this).  weights = "input": no Softmax, `logit` holds the normalised weights."""
+    if weights not in ("softmax", "input"):
+        raise ValueError(weights)
+    L, Lv = len(levels), sum(h * w for h, w in levels)
+    ci = lambda v, nm="shape": g.init(np.array(v, np.int64), nm)
+    w = g.op("Reshape", [logit, ci([0, Q, nh, L * P])])
+    if weights == "softmax":
+        w = g.op("Softmax", [w], axis=-1)
+    w = g.op("Reshape", [w, ci([0, Q, nh, L, P])])
+    v = g.op("Reshape", [value, ci([0, Lv, nh, c])])
+    vs = g.op("Split", [v, ci([h * w_ for h, w_ in levels], "split")], n_out=L, axis=1)
+    vs = [vs] if L == 1 else vs
+    grid = g.op("Sub", [g.op("Mul", [loc, g.init(np.array(2.0, np.float32), "c")]), g.init(np.array(1.0, np.float32), "c")])
+    samples = []
+    for l, (h, w_) in enumerate(levels):
+        vl = g.op("Reshape", [g.op("Transpose", [g.op("Reshape", [vs[l], ci([0, h * w_, nh * c])])], perm=[0, 2, 1]), ci([-1, c, h, w_])])
+        gl = g.op("Squeeze", [g.op("Slice", [grid, ci([l], "starts"), ci([l + 1], "ends"), ci([3], "axes")]), ci([3], "axes")])
+        gl = g.op("Reshape", [g.op("Transpose", [gl], perm=[0, 2, 1, 3, 4]), ci([-1, Q, P, 2])])
+        sm = g.op("GridSample", [vl, gl], mode="bilinear", padding_mode="zeros", align_corners=int(align_corners))
+        samples.append(g.op("Unsqueeze", [sm, ci([3], "axes")]))
+    s = g.op("Reshape", [g.op("Concat", samples, axis=3), ci([0, c, Q, L * P])])
+    wt = g.op("Reshape", [g.op("Transpose", [w], perm=[0, 2, 1, 3, 4]), ci([-1, 1, Q, L * P])])
+    o = g.op("ReduceSum", [g.op("Mul", [s, wt]), ci([-1], "axes")], keepdims=0)
+    o = g.op("Reshape", [o, ci([-1, nh * c, Q])])
+    if out is None:
+        return g.op("Transpose", [o], perm=[0, 2, 1])
+    g.nodes.append(node("Transpose", [o], [out], name=g.uid("n"), perm=[0, 2, 1]))
+    return out
+
+
+def build_deformable_attention(N, Q, nh, c, levels, P, weights="softmax", seed=0, align_corners=0):
+    """The core of multi-scale deformable attention as a graph of its own (no weights: `seed` is unused and kept for the builders' common signature):
+    value [N, Lv, nh c], loc [N, Q, nh, L, P, 2] ((x, y) in units of the level's width / height), logit [N, Q, nh L P] -> y [N, Q, nh c].
+    The batch is dynamic; N is recorded in info for the caller's inputs."""
+    levels = [(int(h), int(w)) for h, w in levels]
+    L, Lv = len(levels), sum(h * w for h, w in levels)
+    g = GraphBuilder("deformable_attention", 17)
+    g.add_input("value", ["N", Lv, nh * c])
+    g.add_input("loc", ["N", Q, nh, L, P, 2])
+    g.add_input("logit", ["N", Q, nh * L * P])
+    _deformable_core(g, "value", "loc", "logit", Q, nh, c, levels, P, weights, align_corners, out="y")
+    g.add_output("y", ["N", Q, nh * c])
+    return g.model(), {"params": 0, "N": N, "Q": Q, "nh": nh, "c": c, "levels": levels, "P": P, "weights": weights, "align_corners": int(align_corners)}
+
+
+def rtdetr_decoder_weights(D, nh, levels, P, layers, n_classes, F=None, seed=0):
+    """f32 weights of an RT-DETR-shaped decoder, every Linear as an [in, out] matrix: the query position MLP (4 -> D -> D, shared by the layers), per layer
+    l<i>_ the self-attention q / k / v / o, the cross-attention's value_proj, sampling_offsets (gain 4: offsets of a few reference-box halves), attention_weights
+    (gain 6: a peaked softmax) and output_proj, three LayerNorms, the FFN (D -> F -> D) and the box head (D -> D -> 4); the class head of the last layer."""
+    rng = np.random.default_rng(seed)
+    F = F or 2 * D
+    L = len(levels)
+    w = {}
+
+    def lin(nm, cin, cout, gain=1.0, bias=0.1):
+        w[nm + "_w"] = ((rng.random((cin, cout)) * 2.0 - 1.0) * (gain / np.sqrt(cin))).astype(np.float32)
+        w[nm + "_b"] = ((rng.random(cout) * 2.0 - 1.0) * bias).astype(np.float32)
+
+    def ln(nm):
+        w[nm + "_g"] = (1.0 + 0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32)
+        w[nm + "_b"] = (0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32)
+
+    lin("pos1", 4, D, 2.0); lin("pos2", D, D)
+    for i in range(layers):
+        p = f"l{i}_"
+        for nm, gain in (("q", 2.0), ("k", 2.0), ("v", 1.0), ("o", 1.0)):
+            lin(p + "sa_" + nm, D, D, gain)
+        ln(p + "ln1")
+        lin(p + "value", D, D); lin(p + "offs", D, nh * L * P * 2, 4.0, 1.0); lin(p + "attw", D, nh * L * P, 6.0); lin(p + "out", D, D)
+        ln(p + "ln2")
+        lin(p + "ffn1", D, F); lin(p + "ffn2", F, D)
+        ln(p + "ln3")
+        lin(p + "box1", D, D); lin(p + "box2", D, 4, 0.5)
+    lin("cls", D, n_classes, 4.0)
+    return w
+
+
+def _rtdetr_decoder(g, w, memory, tgt, ref_logit, D, nh, levels, P, layers, Q, prefix="rd_"):
+    """memory [N, Lv, D], tgt [N, Q, D], ref_logit [N, Q, 4] -> per layer (out [N, Q, D], ref_logit [N, Q, 4]).  The reference box is carried as its logit:
+    inverse_sigmoid(sigmoid(z)) = z, so  ref' = sigmoid(bbox_head(out) + inverse_sigmoid(ref))  is  sigmoid(bbox_head(out) + z)  without a Log in the graph."""
+    dh, L, c = D // nh, len(levels), D // nh
+    ci = lambda v, nm="shape": g.init(np.array(v, np.int64), nm)
+    cf = lambda v: g.init(np.array(v, np.float32), "c")
+    lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(w[nm + "_w"], prefix + nm + "_w")]), g.init(w[nm + "_b"], prefix + nm + "_b")])
+    lnorm = lambda t, nm: g.op("LayerNormalization", [t, g.init(w[nm + "_g"], prefix + nm + "_g"), g.init(w[nm + "_b"], prefix + nm + "_b")], axis=-1, epsilon=1e-5)
+    heads = lambda t: g.op("Transpose", [g.op("Reshape", [t, ci([0, Q, nh, dh])])], perm=[0, 2, 1, 3])
+    outs = []
+    for i in range(layers):
+        p = f"l{i}_"
+        ref = g.op("Sigmoid", [ref_logit])
+        pos = lin(g.op("Relu", [lin(ref, "pos1")]), "pos2")
+        qk = g.op("Add", [tgt, pos])
+        sc = g.op("Mul", [g.op("MatMul", [heads(lin(qk, p + "sa_q")), g.op("Transpose", [heads(lin(qk, p + "sa_k"))], perm=[0, 1, 3, 2])]), cf(dh ** -0.5)])
+        sa = g.op("MatMul", [g.op("Softmax", [sc], axis=-1), heads(lin(tgt, p + "sa_v"))])
+        sa = lin(g.op("Reshape", [g.op("Transpose", [sa], perm=[0, 2, 1, 3]), ci([0, Q, D])]), p + "sa_o")
+        tgt = lnorm(g.op("Add", [tgt, sa]), p + "ln1")
+        query = g.op("Add", [tgt, pos])
+        value = lin(memory, p + "value")
+        offs = g.op("Reshape", [lin(query, p + "offs"), ci([0, Q, nh, L, P, 2])])
+        logit = lin(query, p + "attw")
+        ax = ci([2, 3, 4], "axes")
+        xy = g.op("Unsqueeze", [g.op("Slice", [ref, ci([0], "starts"), ci([2], "ends"), ci([2], "axes")]), ax])          # [N, Q, 1, 1, 1, 2]
+        wh = g.op("Unsqueeze", [g.op("Slice", [ref, ci([2], "starts"), ci([4], "ends"), ci([2], "axes")]), ax])
+        loc = g.op("Add", [xy, g.op("Mul", [g.op("Mul", [g.op("Div", [offs, cf(float(P))]), wh]), cf(0.5)])])
+        ca = lin(_deformable_core(g, value, loc, logit, Q, nh, c, levels, P), p + "out")
+        tgt = lnorm(g.op("Add", [tgt, ca]), p + "ln2")
+        ffn = lin(g.op("Relu", [lin(tgt, p + "ffn1")]), p + "ffn2")
+        tgt = lnorm(g.op("Add", [tgt, ffn]), p + "ln3")
+        ref_logit = g.op("Add", [lin(g.op("Relu", [lin(tgt, p + "box1")]), p + "box2"), ref_logit])
+        outs.append((tgt, ref_logit))
+    return outs
+
+
+def build_rtdetr_decoder(D=32, nh=4, levels=((8, 8), (4, 4), (2, 2)), P=4, layers=2, Q=20, n_classes=3, seed=0):
+    """An RT-DETR-shaped decoder on its own: memory [N, Lv, D], tgt [N, Q, D], ref_logit [N, Q, 4] -> boxes [N, Q, 4] (cx, cy, w, h in [0, 1]),
+    logits [N, Q, n_classes], and per layer out<i> [N, Q, D] and ref<i> [N, Q, 4] (info["layer_outputs"]), so that a test sees where an error enters.
+    Per layer: self-attention over the queries with q = k = tgt + MLP(sigmoid(ref)), Add + LayerNorm, deformable cross-attention (value_proj,
+    sampling_offsets, attention_weights; box-form reference points loc = ref_xy + offsets / P * ref_wh * 0.5; _deformable_core; output_proj), Add +
+    LayerNorm, FFN, Add + LayerNorm, box refinement."""
+    if D % nh:
+        raise ValueError("D must be a multiple of the heads")
+    levels = [(int(h), int(w)) for h, w in levels]
+    Lv = sum(h * w for h, w in levels)
+    w = rtdetr_decoder_weights(D, nh, levels, P, layers, n_classes, seed=seed)
+    g = GraphBuilder("rtdetr_decoder", 17)
+    g.add_input("memory", ["N", Lv, D])
+    g.add_input("tgt", ["N", Q, D])
+    g.add_input("ref_logit", ["N", Q, 4])
+    outs = _rtdetr_decoder(g, w, "memory", "tgt", "ref_logit", D, nh, levels, P, layers, Q)
+    g.nodes.append(node("Sigmoid", [outs[-1][1]], ["boxes"], name=g.uid("n")))
+    g.nodes.append(node("Add", [g.op("MatMul", [outs[-1][0], g.init(w["cls_w"], "rd_cls_w")]), g.init(w["cls_b"], "rd_cls_b")], ["logits"], name=g.uid("n")))
+    g.add_output("boxes", ["N", Q, 4])
+    g.add_output("logits", ["N", Q, n_classes])
+    names = []
+    for i, (o, r) in enumerate(outs):
+        g.nodes.append(node("Identity", [o], [f"out{i}"], name=g.uid("n")))
+        g.nodes.append(node("Sigmoid", [r], [f"ref{i}"], name=g.uid("n")))
+        g.add_output(f"out{i}", ["N", Q, D])
+        g.add_output(f"ref{i}", ["N", Q, 4])
+        names += [f"out{i}", f"ref{i}"]
+    return g.model(), {"params": g.n_params, "weights": w, "D": D, "nh": nh, "levels": levels, "P": P, "layers": layers, "Q": Q, "classes": n_classes,
+                       "layer_outputs": names}
 
 
 # ---------------------------------------------------------------------------------------------- table structure recognition: SLANet
