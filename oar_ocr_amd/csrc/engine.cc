@@ -1296,6 +1296,250 @@ void Engine::rewrite_graph(OnnxModel& m) {
         for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
         nodes.swap(keep);
     }
+    // ---- pass 3d: the attention of a SAM / Vary ViT block with the decomposed relative-position bias (the encoder of the larger PP-FormulaNet files; DESIGN
+    //   4.35), y [B, H W, C] with static H, W; (h, w) = (H, W) for global attention, (ws, ws) for windows; N = h w, G = B (windows) nh:
+    //   g = Reshape(y, [0, H, W, C]);   windows: [Pad(g, bottom / right, constant 0) ->] Reshape[0, Hp/ws, ws, Wp/ws, ws, C] -> Transpose[0,1,3,2,4,5] -> Reshape[-1, ws, ws, C]
+    //   qkv = Linear(Reshape(g, [0, N, C]), [C, 3 C]) -> Reshape[0, -1, 3, nh, dh] -> Transpose[2,0,3,1,4] -> Reshape[3, -1, N, dh] -> Split(axis 0) -> 3 x Squeeze[0]
+    //   s = MatMul(Mul(q, c), Transpose[0,2,1](k))   or   Mul(MatMul(q, Transpose[0,2,1](k)), c)
+    //   rq = Reshape(q, [0, h, w, dh])                                                          (the UNSCALED q: the Squeeze's output itself)
+    //   rh = Transpose[1,0,2,3](Reshape(MatMul(Reshape(Transpose[1,0,2,3](rq), [h, -1, dh]), RhT [h, dh, h]), [h, -1, w, h]))
+    //   rw = Transpose[1,2,0,3](Reshape(MatMul(Reshape(Transpose[2,0,1,3](rq), [w, -1, dh]), RwT [w, dh, w]), [w, -1, h, w]))
+    //   a = Softmax(Reshape(Add(Add(Reshape(s, [0, h, w, h, w]), Unsqueeze(rh, -1)), Unsqueeze(rw, -2)), [0, N, N]), -1)
+    //   o = Linear(Reshape(Transpose[0,2,3,1,4](Reshape(MatMul(a, v), [-1, nh, h, w, dh])), [0, N, C]))
+    //   windows: Reshape[-1, Hp/ws, Wp/ws, ws, ws, C] -> Transpose[0,1,3,2,4,5] -> Reshape[-1, Hp, Wp, C] -> Slice(0:H, axis 1), Slice(0:W, axis 2) where padded;
+    //   Reshape(o, [0, H W, C])
+    // becomes the fused Linear on y in image order, ONE RelPosAttention node (csrc/relpos_attention.hip) and the projection: the pad, partition, reverse, crop
+    // and the whole score / bias subgraph leave the graph.  The match is exact, operand order included: RhT or RwT that is no initializer, a rel term taken
+    // from the scaled q, an intermediate with a second reader (or that is a graph output), another permutation or target, a Pad with another value, mode or
+    // side and a shape k::relpos_attention_supported rejects keep the op-by-op route.  The pass is opt-in: OAR_FUSE_RELPOS_ATTENTION=1, read at load time, turns
+    // it on; unset or 0 keeps the op-by-op route.  It runs before pass 4 so that the
+    // block's residual Add folds into the projection.
+    {
+        const char* fe = getenv("OAR_FUSE_RELPOS_ATTENTION");
+        const bool fuse = fe && atoi(fe) != 0;           // opt-in until the three-arm speed measurement of DESIGN 4.35 exists: unset or 0 keeps the op-by-op route
+        auto cons = consumers(nodes);
+        std::map<std::string, int> producer;
+        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
+        std::vector<bool> dead(nodes.size(), false);
+        using V = std::vector<int64_t>;
+        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
+        auto prodn = [&](const std::string& v, const char* op) -> int {    // the live producer `op` of v (v may have several readers)
+            auto it = producer.find(v);
+            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op || nodes[it->second].act.kind != k::ACT_NONE || !nodes[it->second].residual.empty()) return -1;
+            return it->second;
+        };
+        auto prod1 = [&](const std::string& v, const char* op) -> int { return single_use(v) ? prodn(v, op) : -1; };   // ... and v read by nobody else
+        auto reader1 = [&](const std::string& v, const char* op) -> int {  // the single consumer of v, a live `op` reading it first
+            if (!single_use(v)) return -1;
+            const int c = cons[v][0];
+            return !dead[c] && nodes[c].op == op && nodes[c].act.kind == k::ACT_NONE && nodes[c].residual.empty() && nodes[c].in[0] == v ? c : -1;
+        };
+        auto ints = [&](const std::string& v) -> V {
+            auto it = inits_.find(v);
+            return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
+        };
+        auto target = [&](int r) -> V { return nodes[r].in.size() < 2 || nodes[r].ai("allowzero", 0) != 0 ? V{} : ints(nodes[r].in[1]); };
+        auto perm_is = [&](int t, std::initializer_list<int64_t> want) { return nodes[t].ais("perm") == V(want); };
+        auto axes_are = [&](const GNode& n, int64_t a, int64_t rank) {   // opset 13 input or the older attribute; a or a - rank
+            const V ax = n.in.size() > 1 && !n.in[1].empty() ? ints(n.in[1]) : n.ais("axes");
+            return ax.size() == 1 && (ax[0] == a || ax[0] == a - rank);
+        };
+        auto f32_scalar = [&](const std::string& v) -> const HostTensor* {
+            auto it = inits_.find(v);
+            return it != inits_.end() && it->second.dtype == DType::F32 && it->second.f.size() == 1 ? &it->second : nullptr;
+        };
+        auto table = [&](const std::string& v, int64_t n, int64_t dh) {  // a constant f32 [n, dh, n]
+            auto it = inits_.find(v);
+            return it != inits_.end() && it->second.dtype == DType::F32 && it->second.dims == V{n, dh, n} && (int64_t)it->second.f.size() == n * dh * n;
+        };
+        auto slice01 = [&](int idx, int64_t ax, int64_t en) {            // Slice(0 : en) on `ax`, unit step, constant operands
+            const GNode& sl = nodes[idx];
+            if (sl.in.size() < 4 || sl.in.size() > 5 || ints(sl.in[1]) != V{0} || ints(sl.in[2]) != V{en} || ints(sl.in[3]) != V{ax}) return false;
+            return sl.in.size() == 4 || sl.in[4].empty() || ints(sl.in[4]) == V{1};
+        };
+        for (int i = 0; fuse && i < (int)nodes.size(); ++i) {
+            if (nodes[i].op != "Softmax" || dead[i]) continue;
+            const int64_t sax = nodes[i].ai("axis", -1);
+            if (sax != -1 && sax != 2) continue;
+            // scores: Reshape[0, N, N](Add(Add(Reshape(s, [0, h, w, h, w]), Unsqueeze(rh, -1)), Unsqueeze(rw, -2)))
+            const int ra = prod1(nodes[i].in[0], "Reshape");
+            if (ra < 0) continue;
+            const V ta = target(ra);
+            if (ta.size() != 3 || ta[0] != 0 || ta[1] < 1 || ta[1] != ta[2]) continue;
+            const int64_t N = ta[1];
+            const int a2 = prod1(nodes[ra].in[0], "Add");
+            if (a2 < 0 || nodes[a2].in.size() != 2) continue;
+            const int a1 = prod1(nodes[a2].in[0], "Add"), uw = prod1(nodes[a2].in[1], "Unsqueeze");
+            if (a1 < 0 || uw < 0 || nodes[a1].in.size() != 2 || !axes_are(nodes[uw], 3, 5)) continue;
+            const int s5 = prod1(nodes[a1].in[0], "Reshape"), uh = prod1(nodes[a1].in[1], "Unsqueeze");
+            if (s5 < 0 || uh < 0 || !axes_are(nodes[uh], 4, 5)) continue;
+            const V t5 = target(s5);
+            if (t5.size() != 5 || t5[0] != 0 || t5[1] < 1 || t5[2] < 1 || t5[3] != t5[1] || t5[4] != t5[2] || t5[1] > (1 << 20) || t5[2] > (1 << 20) || t5[1] * t5[2] != N) continue;
+            const int64_t h = t5[1], w = t5[2];
+            // the scale, where the graph has it: on q in front of the product, or on the product
+            const std::string& sv = nodes[s5].in[0];
+            int mul = prod1(sv, "Mul"), mm1 = -1, scale_pre = 0;
+            if (mul >= 0) {
+                mm1 = prod1(nodes[mul].in[0], "MatMul");
+            } else {
+                mm1 = prod1(sv, "MatMul");
+                mul = mm1 < 0 ? -1 : prod1(nodes[mm1].in[0], "Mul");
+                scale_pre = 1;
+            }
+            if (mm1 < 0 || mul < 0 || nodes[mul].in.size() != 2 || nodes[mm1].in.size() != 2) continue;
+            const HostTensor* sct = f32_scalar(nodes[mul].in[1]);
+            if (!sct) continue;
+            const std::string qn = scale_pre ? nodes[mul].in[0] : nodes[mm1].in[0];   // the unscaled q
+            const int tk = prod1(nodes[mm1].in[1], "Transpose");
+            if (tk < 0 || !perm_is(tk, {0, 2, 1})) continue;
+            const int mm2 = reader1(nodes[i].out[0], "MatMul");
+            if (mm2 < 0 || nodes[mm2].in.size() != 2) continue;
+            // q, k, v: Squeeze[0] of the three outputs of Split(axis 0) of Reshape[3, -1, N, dh](Transpose[2,0,3,1,4](Reshape[0, -1, 3, nh, dh](Linear)))
+            const std::string* hv[3] = {&qn, &nodes[tk].in[0], &nodes[mm2].in[1]};
+            int sq[3], sp = -1;
+            bool ok = true;
+            for (int t = 0; t < 3 && ok; ++t) {
+                sq[t] = t == 0 ? prodn(*hv[t], "Squeeze") : prod1(*hv[t], "Squeeze");
+                ok = sq[t] >= 0 && axes_are(nodes[sq[t]], 0, 4);
+                if (!ok) break;
+                const int s = prod1(nodes[sq[t]].in[0], "Split");
+                ok = s >= 0 && (sp < 0 || s == sp) && nodes[s].out.size() == 3 && nodes[s].out[(size_t)t] == nodes[sq[t]].in[0];
+                sp = s;
+            }
+            if (!ok || cons[qn].size() != 2 || graph_outs.count(qn)) continue;
+            {
+                const GNode& spn = nodes[sp];
+                const V parts = spn.in.size() > 1 && !spn.in[1].empty() ? ints(spn.in[1]) : spn.ais("split");
+                if (spn.ai("axis", 0) != 0 || !(parts.empty() || parts == V{1, 1, 1})) continue;
+            }
+            const int h3 = prod1(nodes[sp].in[0], "Reshape");
+            if (h3 < 0) continue;
+            const V t3 = target(h3);
+            if (t3.size() != 4 || t3[0] != 3 || t3[1] != -1 || t3[2] != N || t3[3] < 1) continue;
+            const int64_t dh = t3[3];
+            const int h2 = prod1(nodes[h3].in[0], "Transpose");
+            if (h2 < 0 || !perm_is(h2, {2, 0, 3, 1, 4})) continue;
+            const int h1 = prod1(nodes[h2].in[0], "Reshape");
+            if (h1 < 0) continue;
+            const V t1 = target(h1);
+            if (t1.size() != 5 || t1[0] != 0 || t1[1] != -1 || t1[2] != 3 || t1[3] < 1 || t1[3] > (1 << 20) || t1[4] != dh) continue;
+            const int64_t nh = t1[3], C = nh * dh;
+            const int lq = prod1(nodes[h1].in[0], "Linear");
+            if (lq < 0 || nodes[lq].in.size() < 2 || !is_init(nodes[lq].in[1])) continue;
+            {
+                const HostTensor& wq = inits_[nodes[lq].in[1]];
+                if (wq.dims != V{C, 3 * C}) continue;
+                if (!nodes[lq].bias.empty() && (!is_init(nodes[lq].bias) || inits_[nodes[lq].bias].dtype != DType::F32 || (int64_t)inits_[nodes[lq].bias].f.size() != 3 * C)) continue;
+            }
+            // the rel terms, both from rq = Reshape(q, [0, h, w, dh]), q's other reader
+            const int qreader = scale_pre ? mul : mm1;
+            const int rq = cons[qn][0] == qreader ? cons[qn][1] : cons[qn][0];
+            if (rq == qreader || dead[rq] || nodes[rq].op != "Reshape" || nodes[rq].in[0] != qn || target(rq) != V{0, h, w, dh}) continue;
+            const std::string& rqv = nodes[rq].out[0];
+            if (cons[rqv].size() != 2 || graph_outs.count(rqv)) continue;
+            const int th2 = prod1(nodes[uh].in[0], "Transpose"), tw2 = prod1(nodes[uw].in[0], "Transpose");
+            if (th2 < 0 || tw2 < 0 || !perm_is(th2, {1, 0, 2, 3}) || !perm_is(tw2, {1, 2, 0, 3})) continue;
+            const int rh2 = prod1(nodes[th2].in[0], "Reshape"), rw2 = prod1(nodes[tw2].in[0], "Reshape");
+            if (rh2 < 0 || rw2 < 0 || target(rh2) != V{h, -1, w, h} || target(rw2) != V{w, -1, h, w}) continue;
+            const int mh = prod1(nodes[rh2].in[0], "MatMul"), mw = prod1(nodes[rw2].in[0], "MatMul");
+            if (mh < 0 || mw < 0 || nodes[mh].in.size() != 2 || nodes[mw].in.size() != 2 || !table(nodes[mh].in[1], h, dh) || !table(nodes[mw].in[1], w, dh)) continue;
+            const int rh1 = prod1(nodes[mh].in[0], "Reshape"), rw1 = prod1(nodes[mw].in[0], "Reshape");
+            if (rh1 < 0 || rw1 < 0 || target(rh1) != V{h, -1, dh} || target(rw1) != V{w, -1, dh}) continue;
+            const int th1 = prod1(nodes[rh1].in[0], "Transpose"), tw1 = prod1(nodes[rw1].in[0], "Transpose");
+            if (th1 < 0 || tw1 < 0 || th1 == tw1 || !perm_is(th1, {1, 0, 2, 3}) || !perm_is(tw1, {2, 0, 1, 3}) || nodes[th1].in[0] != rqv || nodes[tw1].in[0] != rqv) continue;
+            // output side: Reshape[-1, nh, h, w, dh] -> Transpose[0,2,3,1,4] -> Reshape[0, N, C] -> Linear
+            const int o1 = reader1(nodes[mm2].out[0], "Reshape");
+            if (o1 < 0 || target(o1) != V{-1, nh, h, w, dh}) continue;
+            const int o2 = reader1(nodes[o1].out[0], "Transpose");
+            if (o2 < 0 || !perm_is(o2, {0, 2, 3, 1, 4})) continue;
+            const int o3 = reader1(nodes[o2].out[0], "Reshape");
+            if (o3 < 0 || target(o3) != V{0, N, C}) continue;
+            const int pj = reader1(nodes[o3].out[0], "Linear");
+            if (pj < 0 || nodes[pj].in.size() < 2 || !is_init(nodes[pj].in[1]) || inits_[nodes[pj].in[1]].dims != V{C, C}) continue;
+            // front side
+            const int r0 = prod1(nodes[lq].in[0], "Reshape");
+            if (r0 < 0 || target(r0) != V{0, N, C}) continue;
+            const int f0 = prod1(nodes[r0].in[0], "Reshape");
+            if (f0 < 0) continue;
+            std::vector<int> extra;
+            int64_t ws = 0, H = h, W = w;
+            std::string y, out;
+            bool padded = false;
+            if (target(f0) == V{0, h, w, C}) {           // global: the key grid is the token grid
+                y = nodes[f0].in[0];
+                const int fin = reader1(nodes[pj].out[0], "Reshape");
+                if (fin < 0 || target(fin) != V{0, H * W, C}) continue;
+                out = nodes[fin].out[0];
+                extra.push_back(fin);
+            } else if (h == w && target(f0) == V{-1, h, h, C}) {   // windows
+                ws = h;
+                const int p2 = prod1(nodes[f0].in[0], "Transpose");
+                if (p2 < 0 || !perm_is(p2, {0, 1, 3, 2, 4, 5})) continue;
+                const int p1 = prod1(nodes[p2].in[0], "Reshape");
+                if (p1 < 0) continue;
+                const V pt = target(p1);
+                if (pt.size() != 6 || pt[0] != 0 || pt[1] < 1 || pt[1] > (1 << 20) || pt[2] != ws || pt[3] < 1 || pt[3] > (1 << 20) || pt[4] != ws || pt[5] != C) continue;
+                const int64_t hb = pt[1], wb = pt[3], Hp = hb * ws, Wp = wb * ws;
+                H = Hp; W = Wp;
+                std::string cur = nodes[p1].in[0];
+                if (const int pd = prod1(cur, "Pad"); pd >= 0) {
+                    const GNode& pn = nodes[pd];
+                    if (pn.as("mode", "constant") != "constant" || pn.in.size() < 2 || pn.in.size() > 3) continue;
+                    const V pads = ints(pn.in[1]);
+                    if (pads.size() != 8 || pads[0] || pads[1] || pads[2] || pads[3] || pads[4] || pads[7] || pads[5] < 0 || pads[6] < 0 || pads[5] >= ws || pads[6] >= ws) continue;
+                    if (pn.in.size() == 3 && !pn.in[2].empty()) {
+                        const HostTensor* pv = f32_scalar(pn.in[2]);
+                        if (!pv || pv->f[0] != 0.0f) continue;
+                    }
+                    H = Hp - pads[5]; W = Wp - pads[6];
+                    padded = pads[5] || pads[6];
+                    cur = pn.in[0];
+                    extra.push_back(pd);
+                }
+                const int fr = prod1(cur, "Reshape");
+                if (fr < 0 || target(fr) != V{0, H, W, C}) continue;   // (constants: a dynamic H / W is not matched)
+                y = nodes[fr].in[0];
+                const int v1 = reader1(nodes[pj].out[0], "Reshape");
+                if (v1 < 0 || target(v1) != V{-1, hb, wb, ws, ws, C}) continue;
+                const int v2 = reader1(nodes[v1].out[0], "Transpose");
+                if (v2 < 0 || !perm_is(v2, {0, 1, 3, 2, 4, 5})) continue;
+                const int v3 = reader1(nodes[v2].out[0], "Reshape");
+                if (v3 < 0 || target(v3) != V{-1, Hp, Wp, C}) continue;
+                out = nodes[v3].out[0];
+                bool ok2 = true;
+                for (int ax = 1; ax <= 2 && ok2; ++ax) {
+                    if ((ax == 1 ? Hp - H : Wp - W) == 0) continue;
+                    const int cr = reader1(out, "Slice");
+                    ok2 = cr >= 0 && slice01(cr, ax, ax == 1 ? H : W);
+                    if (ok2) { out = nodes[cr].out[0]; extra.push_back(cr); }
+                }
+                if (!ok2) continue;
+                const int fin = reader1(out, "Reshape");
+                if (fin < 0 || (target(fin) != V{0, H * W, C} && target(fin) != V{-1, H * W, C})) continue;
+                out = nodes[fin].out[0];
+                extra.insert(extra.end(), {p2, p1, fr, v1, v2, v3, fin});
+            } else {
+                continue;
+            }
+            if (!k::relpos_attention_supported(1, H, W, ws, nh, dh)) continue;
+            GNode ra_node;
+            ra_node.op = "RelPosAttention";
+            ra_node.in = {nodes[lq].out[0], nodes[mh].in[1], nodes[mw].in[1]};
+            if (padded) ra_node.in.push_back(nodes[lq].bias);   // what a padding token is behind the Linear (empty: zeros)
+            ra_node.out = {nodes[o3].out[0]};
+            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; ra_node.attrs[k] = a; };
+            iattr("H", H); iattr("W", W); iattr("ws", ws); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_pos", scale_pre ? 0 : 1);
+            Attr as; as.kind = Attr::F; as.f = sct->f[0]; ra_node.attrs["scale"] = as;
+            nodes[lq].in[0] = y;
+            nodes[pj].out[0] = out;
+            for (int d : {i, ra, a2, a1, uw, uh, s5, mul, mm1, tk, mm2, sq[0], sq[1], sq[2], sp, h3, h2, h1, rq, th2, tw2, rh2, rw2, mh, mw, rh1, rw1, th1, tw1, o1, o2, r0, f0}) dead[d] = true;
+            for (int d : extra) dead[d] = true;
+            nodes[o3] = std::move(ra_node);              // behind the fused Linear, in front of the projection
+        }
+        std::vector<GNode> keep;
+        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
+        nodes.swap(keep);
+    }
     // ---- pass 3c: multi-scale deformable attention (the cross-attention core of an RT-DETR decoder layer), in the exported spelling, with static
     //   nh, c, Q, P and levels (h_l, w_l), Lv = sum h_l w_l:
     //   weights:  Reshape(logit, [0, Q, nh, L P]) -> Softmax(-1) -> Reshape[0, Q, nh, L, P]           (the Softmax may be missing: the input holds the weights)
@@ -4618,6 +4862,36 @@ struct Planner {
         step([=](const RunCtx& c) { k::WindowAttnP r = p; r.q = c.at(ql); r.k = c.at(kl); r.v = c.at(vl); r.o = c.mut(yl); k::window_attention(c.s, r); },
              4.0 * tokens * N * C, 4.0 * (4.0 * tokens * C + windows * h * N * N * (p.mask ? 2 : 1)));
     }
+    // fused ViT attention with the decomposed relative-position bias (rewrite pass 3d): qkv [B, H W, 3 heads head_dim] in image order, RhT [h, head_dim, h],
+    // RwT [w, head_dim, w] with (h, w) the key grid -> [B, H W, heads * head_dim] in image order.  Optional input 3: the fused Linear's bias of a block that pads
+    void op_relpos_attention(const GNode& n) {
+        TInfo x = get(n.in[0]);
+        const TInfo& rh = get(n.in[1]);
+        const TInfo& rw = get(n.in[2]);
+        const int64_t H = n.ai("H", 1), W = n.ai("W", 1), ws = n.ai("ws", 0), h = n.ai("heads", 1), d = n.ai("head_dim", 1), C = h * d;
+        OAR_CHECK(k::relpos_attention_supported(1, H, W, ws, h, d), OAR_INTERNAL, "RelPosAttention: the rewrite let an unsupported shape through at " + n.out[0]);
+        const int64_t gh = ws ? ws : H, gw = ws ? ws : W;
+        OAR_CHECK(!x.host_int && !x.dims.empty() && x.dims.back() == 3 * C && numel(x.dims) % (H * W * 3 * C) == 0, OAR_SHAPE_MISMATCH,
+                  "RelPosAttention: qkv must be [B, " + std::to_string(H * W) + ", " + std::to_string(3 * C) + "] at " + n.out[0]);
+        OAR_CHECK(rh.ht && rh.loc.kind == Loc::CONST && (int64_t)rh.ht->f.size() == gh * d * gh && rw.ht && rw.loc.kind == Loc::CONST && (int64_t)rw.ht->f.size() == gw * d * gw, OAR_INTERNAL,
+                  "RelPosAttention: RhT / RwT are not constants of h x head_dim x h and w x head_dim x w values at " + n.out[0]);
+        const int64_t B = numel(x.dims) / (H * W * 3 * C);
+        OAR_CHECK(B >= 1 && k::relpos_attention_supported(B, H, W, ws, h, d), OAR_SHAPE_MISMATCH, "RelPosAttention: batch out of range at " + n.out[0]);
+        k::RelPosAttnP p{};
+        if (has_input(n, 3)) {
+            const TInfo& t = get(n.in[3]);
+            OAR_CHECK(t.ht && t.loc.kind == Loc::CONST && (int64_t)t.ht->f.size() == 3 * C, OAR_INTERNAL, "RelPosAttention: the qkv bias is not a constant of the expected size at " + n.out[0]);
+            p.bqkv = t.loc.cptr;
+        }
+        Loc xl = to_native_loc(x);
+        TInfo& y = new_out(n.out[0], {B, H * W, C}, Layout::NATIVE);
+        Loc yl = y.loc;
+        p.rh = rh.loc.cptr; p.rw = rw.loc.cptr; p.B = (int)B; p.H = (int)H; p.W = (int)W; p.ws = (int)ws; p.nh = (int)h; p.dh = (int)d;
+        p.scale = n.af("scale", 1.0f); p.scale_pre = n.ai("scale_pos", 0) == 0;
+        const double N = (double)gh * gw, sets = (double)B * (ws ? (double)((H + ws - 1) / ws) * (double)((W + ws - 1) / ws) : 1.0) * h, tokens = (double)B * H * W;
+        step([=](const RunCtx& c) { k::RelPosAttnP r = p; r.qkv = c.at(xl); r.o = c.mut(yl); k::relpos_attention(c.s, r); },
+             sets * N * (4.0 * N * d + 2.0 * (gh + gw) * d), 4.0 * (4.0 * tokens * C + sets * std::ceil(N / k::kRpQueries) * 2.0 * N * d));
+    }
     // fused multi-scale deformable attention (rewrite pass 3c): value [N, Lv, heads * c], loc [N, Q, heads, L, P, 2], logits or weights [N, Q, heads * L * P]
     // -> [N, Q, heads * c]
     void op_deformable_attention(const GNode& n) {
@@ -4984,6 +5258,7 @@ struct Planner {
         if (op == "Attention") return op_attention(n);
         if (op == "WindowAttention") return op_window_attention(n);
         if (op == "DeformableAttention") return op_deformable_attention(n);
+        if (op == "RelPosAttention") return op_relpos_attention(n);
         if (op == "SLADecode") return op_sla_decode(n);
         if (op == "FormulaDecode") return op_formula_decode(n);
         if (op == "SEGate") return op_se_gate(n);

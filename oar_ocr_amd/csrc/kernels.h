@@ -284,6 +284,30 @@ struct DeformAttnP {
 // c % 4 == 0, c <= kDefMaxC, L <= kDefMaxLevels, L P <= kDefMaxSamples, and token / thread counts that fit 32 bits (N = Q = 1: the static part of the question)
 bool deformable_attention_supported(int64_t N, int64_t Q, int64_t nh, int64_t c, int64_t L, int64_t P, int64_t Lv);
 void deformable_attention(hipStream_t s, const DeformAttnP& p);
+// relpos_attention.hip: the attention of one SAM / Vary ViT block with the decomposed relative-position bias, one launch.
+// qkv [B H W][3][nh][dh]: the fused projection of the UNPADDED tokens in IMAGE order (token (b, y, x) is row (b H + y) W + x); o [B H W][nh dh] in image order.
+// ws = 0: every query attends to the whole H x W grid; ws > 0: inside ws x ws windows of the grid padded at the bottom / right to multiples of ws.  A padding
+// token is a key whose k / v rows are bqkv's (null: zeros) -- the graph pads in front of the Linear -- and takes part in the soft-max (there is no mask); as a
+// query it is skipped.  With (gh, gw) = (ws, ws) or (H, W) the key grid: rh [gh][dh][gh], rw [gw][dh][gw] (query row / column, component, key row / column), and
+//   score[(qy, qx), (ky, kx)] = scaled q . k + q . rh[qy][:][ky] + q . rw[qx][:][kx]   with the UNSCALED q in both rel terms;
+// scale_pre: q is multiplied by `scale` in front of the product (the graph's Mul on q), otherwise the product is (its Mul on the scores).
+// The key set is streamed in blocks of kRpKeys with a running maximum and sum: no score row exists in memory and gh gw has no upper limit.
+struct RelPosAttnP {
+    const float *qkv, *rh, *rw, *bqkv;
+    float* o;
+    int B, H, W, ws, nh, dh;
+    float scale; int scale_pre;
+};
+constexpr int kRpThreads = 256, kRpQueries = 64, kRpKeys = 32, kRpLd = 68, kRpMaxDh = 64, kRpMaxGrid = 64;
+// head_dim % 4 == 0 and <= kRpMaxDh; key grid sides <= kRpMaxGrid (ws <= 64, or H, W <= 64 when ws = 0); token and workgroup counts that fit 32 bits (B = 1: the
+// static part of the question)
+bool relpos_attention_supported(int64_t B, int64_t H, int64_t W, int64_t ws, int64_t heads, int64_t head_dim);
+// the kernel's LDS, all of it dynamic: K and V blocks [2 stages][kRpKeys][kRpLd] each, the blocks' key coordinates [2][kRpKeys], and rh / rw of the workgroup's
+// queries [kRpQueries][gh | 1], [kRpQueries][gw | 1] (tests/test_vit_relpos_cpu.py compiles this)
+inline size_t relpos_attention_lds_bytes(int gh, int gw) {
+    return ((size_t)4 * kRpKeys * kRpLd + (size_t)2 * kRpKeys + (size_t)kRpQueries * ((size_t)(gh | 1) + (size_t)(gw | 1))) * sizeof(float);
+}
+void relpos_attention(hipStream_t s, const RelPosAttnP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

@@ -1299,7 +1299,7 @@ def _formula_head(g, w, M, spelling="gemm", with_logits=False, act="Gelu", q_sca
 
 
 def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(64, 64), seed=0, head_only=False, weights=None, spelling="gemm", with_logits=False,
-                     act="Gelu", q_scale="after", sos=0, initial_cache="empty", read_final_cache=False, qk_squeeze=1, cross_squeeze=False):
+                     act="Gelu", q_scale="after", sos=0, initial_cache="empty", read_final_cache=False, qk_squeeze=1, cross_squeeze=False, encoder=None, vit=None):
     """PP-FormulaNet-shaped formula recognizer: a tiny conv backbone (one grey channel in; an 8 x 8 / stride 8 patch convolution, hard-swish, a 1 x 1
     convolution; its weights are added to info["weights"] as bb_*) -> memory [B, S, D] -> per decoder layer the cross-attention
     keys / values KmT_l [B, nh, dh, S], Vm_l [B, nh, S, dh] by ordinary nodes -> the decoder as an ONNX Loop of M greedy steps over a key / value cache that starts
@@ -1308,7 +1308,9 @@ def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(
     check the head apart from the backbone.  weights: formula_weights(...) (the default); spelling / q_scale: see _formula_body.  Knobs that write a graph the
     engine must refuse: act other than "Gelu"; initial_cache="one" (caches that start with one position); read_final_cache (a final cache as graph output);
     cross_squeeze (with qk_squeeze > 1: the cross-attention queries / keys narrowed too).  qk_squeeze = r: UniMERNet's squeeze attention, see formula_weights
-    (given `weights`, the head sizes follow them); r = 1 writes the bytes it always wrote.
+    (given `weights`, the head sizes follow them); r = 1 writes the bytes it always wrote.  encoder = "vit": the image side is the Vary / SAM ViT of the -L files
+    (_vary_vit) built from vary_vit_weights(image_shape, D=D, seed=seed, **vit); its weights are info["encoder"].  encoder = None writes the
+    bytes it always wrote.
     Returns (onnx_bytes, info) with info["weights"]: what the graph really computes (q_scale = 1 and a scaled Wq / bq when folded)."""
     from .onnx_writer import INT64
     P = P if P is not None else M + 2
@@ -1328,8 +1330,15 @@ def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(
     dh, dq, dc = D // nh, w["l0_wq"].shape[0] // nh, w["l0_wcq"].shape[0] // nh
     net = _Net("formulanet", seed + 100)
     g = net.g
+    if encoder not in (None, "vit") or (encoder and head_only):
+        raise ValueError(encoder)
+    we = None
     if head_only:
         g.add_input("memory", ["B", "S", D])
+    elif encoder == "vit":
+        g.add_input("x", ["B", 1, image_shape[0], image_shape[1]])
+        we = vary_vit_weights(image_shape, D=D, seed=seed, **(vit or {}))
+        _vary_vit(g, "x", we)
     else:
         g.add_input("x", ["B", 1, image_shape[0], image_shape[1]])
         if "bb_w1" not in w:                                                                       # the backbone's weights travel with the head's: the reference runs both
@@ -1344,7 +1353,10 @@ def build_formulanet(D=64, nh=4, F=128, V=300, Ld=2, P=None, M=32, image_shape=(
         g.add_output("memory", ["B", "S", D])
     if read_final_cache:
         g.add_output("K_last_0", ["B", nh, M, dh])
-    return g.model(), {"params": g.n_params, "weights": w, "D": D, "nh": nh, "F": F, "V": V, "Ld": Ld, "M": M, "P": P, "sos": sos}
+    info = {"params": g.n_params, "weights": w, "D": D, "nh": nh, "F": F, "V": V, "Ld": Ld, "M": M, "P": P, "sos": sos}
+    if we is not None:
+        info["encoder"] = we
+    return g.model(), info
 
 
 # ---------------------------------------------------------------------------------------------- formula recognition: UniMERNet
@@ -1547,6 +1559,166 @@ def build_unimernet(image_shape=(192, 672), C=32, heads=(2, 4), depths=(2, 2), w
     g.add_output("memory", ["B", H * W, D])
     info["params"] = g.n_params
     return g.model(), info
+
+
+# ---------------------------------------------------------------------------------------------- formula recognition: the ViT encoder of PP-FormulaNet-L
+def vit_block_weights(C, nh, H, W, ws, hidden, seed=0, prefix=""):
+    """f32 weights of one SAM / Vary ViT block on an H x W token grid (ws = 0: global attention, the key grid is the token grid; ws > 0: ws x ws windows): LN1,
+    the fused qkv Linear wqkv [3 C, C] / bqkv [3 C] (q and k rows x2: an attention that is not uniform), the decomposed relative-position tables rh [h, h, dh]
+    and rw [w, w, dh] -- rh[qy, ky] is the dh-vector a query of row qy is multiplied with for a key of row ky, the table an exporter gathers out of
+    get_rel_pos; 0.5 N(0, 1) per entry, shared by the heads --, the projection, LN2 and the two MLP Linears."""
+    rng = np.random.default_rng(seed)
+    u = lambda *s, k, g=1.0: ((rng.random(s) * 2.0 - 1.0) * (g / np.sqrt(k))).astype(np.float32)
+    ln = lambda n: ((1.0 + 0.1 * (rng.random(n) * 2.0 - 1.0)).astype(np.float32), (0.1 * (rng.random(n) * 2.0 - 1.0)).astype(np.float32))
+    h, wd, dh = (ws, ws, C // nh) if ws else (H, W, C // nh)
+    w = {}
+    w["ln1_g"], w["ln1_b"] = ln(C)
+    gain = np.repeat(np.array([2.0, 2.0, 1.0], np.float32), C)
+    w["wqkv"], w["bqkv"] = u(3 * C, C, k=C) * gain[:, None], u(3 * C, k=C, g=0.1) * gain
+    w["rh"] = (0.5 * rng.standard_normal((h, h, dh))).astype(np.float32)
+    w["rw"] = (0.5 * rng.standard_normal((wd, wd, dh))).astype(np.float32)
+    w["wp"], w["bp"] = u(C, C, k=C), u(C, k=C, g=0.1)
+    w["ln2_g"], w["ln2_b"] = ln(C)
+    w["w1"], w["b1"] = u(hidden, C, k=C), u(hidden, k=C, g=0.1)
+    w["w2"], w["b2"] = u(C, hidden, k=hidden), u(C, k=hidden, g=0.1)
+    return {prefix + k: v for k, v in w.items()}
+
+
+def _vit_attention(g, x, w, p, H, W, C, nh, ws=0, scale="pre", rel_from="q", rh_name=None):
+    """x [B, H W, C] -> x + attention of LN1(x) with the decomposed relative-position bias q . Rh[qy, ky] + q . Rw[qx, kx], in the spelling DESIGN 4.35 fixes (the
+    engine's rewrite pass 3d matches it).  ws = 0: global attention; ws > 0: ws x ws windows on the grid padded with zeros at the bottom / right, in front of
+    the fused qkv Linear, so a padding key carries bqkv; there is no mask.  scale: "pre" Mul(q, dh^-0.5) in front of the score MatMul (SAM), "post" Mul on the
+    scores.  Knobs that write a near miss: rel_from = "scaled" takes the rel term from the scaled q (needs scale = "pre"); rh_name: the name of a graph input
+    that stands in for the RhT initializer."""
+    if H < 1 or W < 1 or C % nh or ws < 0:
+        raise ValueError("H and W must be positive and C a multiple of the heads")
+    if scale not in ("pre", "post") or rel_from not in ("q", "scaled") or (rel_from == "scaled" and scale != "pre"):
+        raise ValueError((scale, rel_from))
+    dh = C // nh
+    hb, wb = (-(-H // ws), -(-W // ws)) if ws else (1, 1)
+    Hp, Wp = (hb * ws, wb * ws) if ws else (H, W)
+    h, wd = (ws, ws) if ws else (H, W)
+    ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    i64 = lambda v, nm: g.init(np.array([v], np.int64), nm)
+    c = lambda nm, a: g.init(np.ascontiguousarray(a), "vit_" + p + nm)
+    lin = lambda t, wn, bn: g.op("Add", [g.op("MatMul", [t, c(wn, w[p + wn].T)]), c(bn, w[p + bn])])
+    tr = lambda t, perm: g.op("Transpose", [t], perm=list(perm))
+    rs = lambda t, shape: g.op("Reshape", [t, ci(shape)])
+    y = g.op("LayerNormalization", [x, c("ln1_g", w[p + "ln1_g"]), c("ln1_b", w[p + "ln1_b"])], axis=-1, epsilon=1e-5)
+    y = rs(y, [0, H, W, C])
+    if ws:
+        if (Hp, Wp) != (H, W):
+            y = g.op("Pad", [y, g.init(np.array([0, 0, 0, 0, 0, Hp - H, Wp - W, 0], np.int64), "pads"), g.init(np.array(0.0, np.float32), "pad_value")], mode="constant")
+        y = rs(tr(rs(y, [0, hb, ws, wb, ws, C]), [0, 1, 3, 2, 4, 5]), [-1, ws, ws, C])
+    qkv = lin(rs(y, [0, h * wd, C]), "wqkv", "bqkv")
+    qkv = rs(tr(rs(qkv, [0, -1, 3, nh, dh]), [2, 0, 3, 1, 4]), [3, -1, h * wd, dh])
+    sq = i64(0, "axes")
+    q, k, v = (g.op("Squeeze", [t, sq]) for t in g.op("Split", [qkv], n_out=3, axis=0))
+    cs = g.init(np.array(dh ** -0.5, np.float32), "c")
+    kt = tr(k, [0, 2, 1])
+    if scale == "pre":
+        qs = g.op("Mul", [q, cs])
+        s = g.op("MatMul", [qs, kt])
+    else:
+        s = g.op("Mul", [g.op("MatMul", [q, kt]), cs])
+    rq = rs(qs if rel_from == "scaled" else q, [0, h, wd, dh])
+    rht = rh_name or c("rhT", w[p + "rh"].transpose(0, 2, 1))                                      # [qy][d][ky]
+    rwt = c("rwT", w[p + "rw"].transpose(0, 2, 1))                                                # [qx][d][kx]
+    rh = tr(rs(g.op("MatMul", [rs(tr(rq, [1, 0, 2, 3]), [h, -1, dh]), rht]), [h, -1, wd, h]), [1, 0, 2, 3])    # [G, h, w, kh]
+    rw = tr(rs(g.op("MatMul", [rs(tr(rq, [2, 0, 1, 3]), [wd, -1, dh]), rwt]), [wd, -1, h, wd]), [1, 2, 0, 3])  # [G, h, w, kw]
+    a = g.op("Add", [g.op("Add", [rs(s, [0, h, wd, h, wd]), g.op("Unsqueeze", [rh, i64(-1, "axes")])]), g.op("Unsqueeze", [rw, i64(-2, "axes")])])
+    a = g.op("Softmax", [rs(a, [0, h * wd, h * wd])], axis=-1)
+    o = rs(tr(rs(g.op("MatMul", [a, v]), [-1, nh, h, wd, dh]), [0, 2, 3, 1, 4]), [0, h * wd, C])
+    o = lin(o, "wp", "bp")
+    if ws:
+        o = rs(tr(rs(o, [-1, hb, wb, ws, ws, C]), [0, 1, 3, 2, 4, 5]), [-1, Hp, Wp, C])
+        if Hp != H:
+            o = g.op("Slice", [o, i64(0, "starts"), i64(H, "ends"), i64(1, "axes")])
+        if Wp != W:
+            o = g.op("Slice", [o, i64(0, "starts"), i64(W, "ends"), i64(2, "axes")])
+    return g.op("Add", [x, rs(o, [0, H * W, C])])
+
+
+def _vit_block(g, x, w, p, H, W, C, nh, ws=0, scale="pre", **knobs):
+    """the attention block and LN2 -> Linear -> GELU -> Linear with its residual"""
+    c = lambda nm, a: g.init(np.ascontiguousarray(a), "vit_" + p + nm)
+    lin = lambda t, wn, bn: g.op("Add", [g.op("MatMul", [t, c(wn, w[p + wn].T)]), c(bn, w[p + bn])])
+    x = _vit_attention(g, x, w, p, H, W, C, nh, ws, scale, **knobs)
+    y = g.op("LayerNormalization", [x, c("ln2_g", w[p + "ln2_g"]), c("ln2_b", w[p + "ln2_b"])], axis=-1, epsilon=1e-5)
+    return g.op("Add", [x, lin(g.op("Gelu", [lin(y, "w1", "b1")], approximate="none"), "w2", "b2")])
+
+
+def build_vit_block(H, W, C, nh, ws=0, seed=0, scale="pre", whole=False, **knobs):
+    """One ViT block as a graph of its own: x [B, H W, C] -> `y` [B, H W, C].  whole = False: the attention part only (LN1 .. the residual Add).  knobs:
+    rel_from = "scaled" (_vit_attention's); rh_input = True declares RhT [h, dh, h] as a second graph input `rhT` in place of the initializer (info["rhT"]
+    holds the array to feed)."""
+    rh_input = bool(knobs.pop("rh_input", False))
+    w = vit_block_weights(C, nh, H, W, ws, 2 * C, seed)
+    g = GraphBuilder("vit_block", 17)
+    g.add_input("x", ["B", H * W, C])
+    if rh_input:
+        hh = ws if ws else H
+        g.add_input("rhT", [hh, C // nh, hh])
+        knobs["rh_name"] = "rhT"
+    y = (_vit_block if whole else _vit_attention)(g, "x", w, "", H, W, C, nh, ws, scale, **knobs)
+    g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
+    g.add_output("y", ["B", H * W, C])
+    info = {"params": g.n_params, "weights": w, "H": H, "W": W, "C": C, "nh": nh, "ws": ws, "scale": scale, "whole": whole, "rel_from": knobs.get("rel_from", "q")}
+    if rh_input:
+        info["rhT"] = np.ascontiguousarray(w["rh"].transpose(0, 2, 1))
+    return g.model(), info
+
+
+def vary_vit_weights(image_shape=(64, 48), C=32, nh=2, depth=2, ws=2, global_blocks=(1,), mlp_ratio=2, neck=16, D=64, seed=0):
+    """the encoder's weights: a 16 x 16 stride-16 patch convolution (one grey channel -> C), the constant position embedding pos [1, h w, C], `depth` ViT
+    blocks (prefix b<i>_; those in global_blocks attend globally, the others in ws x ws windows), and the neck: a 1 x 1 convolution C -> neck, a 3 x 3 stride-2
+    convolution neck -> 2 neck, and the Linear 2 neck -> D on the flattened map"""
+    Hi, Wi = image_shape
+    if Hi % 16 or Wi % 16:
+        raise ValueError("the image sides must be multiples of 16")
+    H, W = Hi // 16, Wi // 16
+    rng = np.random.default_rng(seed + 17)
+    u = lambda *s, k, g=1.0: ((rng.random(s) * 2.0 - 1.0) * (g / np.sqrt(k))).astype(np.float32)
+    w = {"pe_w": u(C, 1, 16, 16, k=256, g=3.0), "pe_b": u(C, k=256, g=0.3), "pos": (0.5 * rng.standard_normal((1, H * W, C))).astype(np.float32)}
+    for i in range(depth):
+        w.update(vit_block_weights(C, nh, H, W, 0 if i in global_blocks else ws, mlp_ratio * C, seed * 1000 + i + 1, f"b{i}_"))
+    w["n1_w"], w["n1_b"] = u(neck, C, 1, 1, k=C, g=2.0), u(neck, k=C, g=0.2)
+    w["n2_w"], w["n2_b"] = u(2 * neck, neck, 3, 3, k=9 * neck, g=2.0), u(2 * neck, k=9 * neck, g=0.2)
+    w["fc_w"], w["fc_b"] = u(D, 2 * neck, k=2 * neck, g=2.0), u(D, k=2 * neck, g=0.2)
+    w.update(image_shape=(Hi, Wi), C=C, nh=nh, depth=depth, ws=ws, global_blocks=tuple(global_blocks), mlp_ratio=mlp_ratio, neck=neck, D=D)
+    return w
+
+
+def _vary_vit(g, x, we, scale="pre", out="memory"):
+    """x [B, 1, Hi, Wi] -> `out` [B, S, D], S = ceil(h / 2) ceil(w / 2) of the h x w token grid: the nodes of build_vary_vit"""
+    Hi, Wi = we["image_shape"]
+    C, nh, ws, D, neck = int(we["C"]), int(we["nh"]), int(we["ws"]), int(we["D"]), int(we["neck"])
+    H, W = Hi // 16, Wi // 16
+    ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    conv = lambda t, nm, k, s, pd: g.op("Conv", [t, g.init(we[nm + "_w"], "vit_" + nm + "_w"), g.init(we[nm + "_b"], "vit_" + nm + "_b")], kernel_shape=[k, k], strides=[s, s],
+                                        pads=[pd, pd, pd, pd], group=1, dilations=[1, 1])
+    t = conv(x, "pe", 16, 16, 0)
+    t = g.op("Transpose", [g.op("Reshape", [t, ci([0, C, -1])])], perm=[0, 2, 1])
+    t = g.op("Add", [t, g.init(we["pos"], "vit_pos")])
+    for i in range(int(we["depth"])):
+        t = _vit_block(g, t, we, f"b{i}_", H, W, C, nh, 0 if i in we["global_blocks"] else ws, scale)
+    t = g.op("Reshape", [g.op("Transpose", [t], perm=[0, 2, 1]), ci([0, C, H, W])])
+    t = conv(conv(t, "n1", 1, 1, 0), "n2", 3, 2, 1)
+    t = g.op("Transpose", [g.op("Reshape", [t, ci([0, 2 * neck, -1])])], perm=[0, 2, 1])
+    t = g.op("MatMul", [t, g.init(np.ascontiguousarray(we["fc_w"].T), "vit_fc_w")])
+    g.nodes.append(node("Add", [t, g.init(we["fc_b"], "vit_fc_b")], [out], name=g.uid("n")))
+    return -(-H // 2) * -(-W // 2)
+
+
+def build_vary_vit(image_shape=(64, 48), C=32, nh=2, depth=2, ws=2, global_blocks=(1,), mlp_ratio=2, neck=16, D=64, seed=0, scale="pre"):
+    """The Vary / SAM ViT-shaped encoder of the larger PP-FormulaNet files, in the spelling DESIGN 4.35 fixes: x [B, 1, Hi, Wi] -> 16 x 16 patches -> + pos ->
+    `depth` blocks (_vit_block) -> neck -> `memory` [B, S, D], the only output.  Returns (onnx_bytes, info) with info["encoder"] = vary_vit_weights(...)."""
+    we = vary_vit_weights(image_shape, C, nh, depth, ws, global_blocks, mlp_ratio, neck, D, seed)
+    g = GraphBuilder("vary_vit", 17)
+    g.add_input("x", ["B", 1, image_shape[0], image_shape[1]])
+    S = _vary_vit(g, "x", we, scale)
+    g.add_output("memory", ["B", S, D])
+    return g.model(), {"encoder": we, "image_shape": tuple(image_shape), "S": S, "D": D, "scale": scale, "params": g.n_params}
 
 
 def formula_tokenizer_spec(V, decoder="ByteLevel"):
