@@ -106,6 +106,9 @@ typedef struct {
  * engine's lock (like the reference's closure under the session lock): it must not call back into the same engine. */
 typedef int32_t (*oar_output_view_fn)(void* user, const int64_t* dims, int32_t rank, const float* data);
 
+/* The environment variable OAR_FUSE_MHA_ATTENTION, read when the graph is loaded: 0 turns off the rewrite of multi-head attention with separate
+ * q / k / v sources (an RT-DETR decoder's self-attention, its hybrid encoder's AIFI layer) into one launch and keeps the op-by-op route; unset or
+ * any other number leaves it on. */
 oar_status oar_engine_create(const uint8_t* onnx, size_t onnx_len, const oar_engine_cfg* cfg, oar_engine** out);
 void oar_engine_destroy(oar_engine* e);
 /* Name of the graph's first non-initializer input (DB/CRNN use "x": models/detection/db.rs:388-390). */

@@ -1712,6 +1712,100 @@ void Engine::rewrite_graph(OnnxModel& m) {
         for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
         nodes.swap(keep);
     }
+    // ---- pass 3e: ordinary multi-head attention with separate q / k / v sources (PaddleDetection's MultiHeadAttention as exported: the self-attention of an
+    //   RT-DETR decoder layer and the AIFI layer of its hybrid encoder), with static Tq, Tk, nh, dh:
+    //   heads(t, T) = Transpose[0,2,1,3](Reshape(t, [0, T, nh, dh]))                                  (t: any tensor, usually a Linear's [N, T, nh dh] output)
+    //   s = Mul(MatMul(heads(q, Tq), Transpose[0,1,3,2](heads(k, Tk))), c)   or   MatMul(Mul(heads(q, Tq), c), Transpose[0,1,3,2](heads(k, Tk)))
+    //   o = Reshape(Transpose[0,2,1,3](MatMul(Softmax(s, -1), heads(v, Tk))), [0, Tq, nh dh])
+    // becomes ONE MultiHeadAttention(q, k, v) node (csrc/mha_attention.hip) under the final Reshape's name: the head split and merge are address arithmetic
+    // and no score tensor exists.  The match is exact, operand order included: a Softmax on another axis, anything between the scale and the Softmax (an
+    // additive mask), no scale or a non-constant one, another permutation or Reshape target, an intermediate with a second reader (or that is a graph output)
+    // and a shape k::mha_attention_supported rejects keep the op-by-op route.  The q / k / v of the SVTR (pass 5), Swin (3b) and ViT (3d) blocks come from
+    // rank-5 splits, not from heads(t), so this pass cannot take them.  OAR_FUSE_MHA_ATTENTION=0, read at load time, keeps the op-by-op route; the default is on
+    // (the fused arm's whole range lies below the op-by-op arm's on the decoder and the AIFI layer at N = 1 and 8).  It runs before pass 4 so that
+    // the block's residual Add folds into the projection behind it.
+    {
+        const char* fe = getenv("OAR_FUSE_MHA_ATTENTION");
+        const bool fuse = !fe || atoi(fe) != 0;
+        auto cons = consumers(nodes);
+        std::map<std::string, int> producer;
+        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
+        std::vector<bool> dead(nodes.size(), false);
+        using V = std::vector<int64_t>;
+        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
+        auto prod1 = [&](const std::string& v, const char* op) -> int {   // the live producer `op` of v, v read by nobody else
+            auto it = producer.find(v);
+            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op || nodes[it->second].act.kind != k::ACT_NONE || !nodes[it->second].residual.empty() || !single_use(v)) return -1;
+            return it->second;
+        };
+        auto reader1 = [&](const std::string& v, const char* op) -> int {   // the single consumer of v, a live `op` reading it first
+            if (!single_use(v)) return -1;
+            const int c = cons[v][0];
+            return !dead[c] && nodes[c].op == op && nodes[c].act.kind == k::ACT_NONE && nodes[c].residual.empty() && nodes[c].in[0] == v ? c : -1;
+        };
+        auto target = [&](int r) -> V {
+            if (nodes[r].in.size() < 2 || nodes[r].ai("allowzero", 0) != 0) return V{};
+            auto it = inits_.find(nodes[r].in[1]);
+            return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
+        };
+        auto perm_is = [&](int t, std::initializer_list<int64_t> want) { return nodes[t].ais("perm") == V(want); };
+        // heads(t, T): -> the Transpose and the Reshape, and (T, nh, dh); false where v is anything else
+        auto heads = [&](const std::string& v, int& tr, int& rs, int64_t& T, int64_t& nh, int64_t& dh) {
+            tr = prod1(v, "Transpose");
+            if (tr < 0 || !perm_is(tr, {0, 2, 1, 3})) return false;
+            rs = prod1(nodes[tr].in[0], "Reshape");
+            if (rs < 0) return false;
+            const V t = target(rs);
+            if (t.size() != 4 || t[0] != 0 || t[1] < 1 || t[2] < 1 || t[3] < 1) return false;
+            T = t[1]; nh = t[2]; dh = t[3];
+            return true;
+        };
+        for (int i = 0; fuse && i < (int)nodes.size(); ++i) {
+            if (nodes[i].op != "Softmax" || dead[i] || nodes[i].act.kind != k::ACT_NONE) continue;
+            const int64_t sax = nodes[i].ai("axis", -1);
+            if (sax != -1 && sax != 3) continue;
+            // the scale: on the product, or on q in front of it
+            const std::string& sv = nodes[i].in[0];
+            int mul = prod1(sv, "Mul"), mm1 = -1, scale_pre = 0;
+            if (mul >= 0) {
+                mm1 = prod1(nodes[mul].in[0], "MatMul");
+            } else {
+                mm1 = prod1(sv, "MatMul");
+                mul = mm1 < 0 ? -1 : prod1(nodes[mm1].in[0], "Mul");
+                scale_pre = 1;
+            }
+            if (mm1 < 0 || mul < 0 || nodes[mul].in.size() != 2 || nodes[mm1].in.size() != 2) continue;
+            auto sit = inits_.find(nodes[mul].in[1]);
+            if (sit == inits_.end() || sit->second.dtype != DType::F32 || sit->second.f.size() != 1) continue;
+            const int tk = prod1(nodes[mm1].in[1], "Transpose");
+            if (tk < 0 || !perm_is(tk, {0, 1, 3, 2})) continue;
+            const int mm2 = reader1(nodes[i].out[0], "MatMul");
+            if (mm2 < 0 || nodes[mm2].in.size() != 2) continue;
+            int qt, qr, kt, kr, vt, vr;
+            int64_t Tq, Tk, Tv, nh, nhk, nhv, dh, dhk, dhv;
+            if (!heads(scale_pre ? nodes[mul].in[0] : nodes[mm1].in[0], qt, qr, Tq, nh, dh) || !heads(nodes[tk].in[0], kt, kr, Tk, nhk, dhk) ||
+                !heads(nodes[mm2].in[1], vt, vr, Tv, nhv, dhv))
+                continue;
+            if (Tv != Tk || nhk != nh || nhv != nh || dhk != dh || dhv != dh || qt == kt || qt == vt || kt == vt) continue;
+            // the merge: Transpose[0,2,1,3] -> Reshape[0, Tq, nh dh]
+            const int o1 = reader1(nodes[mm2].out[0], "Transpose");
+            if (o1 < 0 || !perm_is(o1, {0, 2, 1, 3})) continue;
+            const int o2 = reader1(nodes[o1].out[0], "Reshape");
+            if (o2 < 0 || !k::mha_attention_supported(1, Tq, Tk, nh, dh) || target(o2) != V{0, Tq, nh * dh}) continue;
+            GNode ma;
+            ma.op = "MultiHeadAttention";
+            ma.in = {nodes[qr].in[0], nodes[kr].in[0], nodes[vr].in[0]};
+            ma.out = {nodes[o2].out[0]};
+            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; ma.attrs[k] = a; };
+            iattr("Tq", Tq); iattr("Tk", Tk); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_pos", scale_pre ? 0 : 1);
+            Attr as; as.kind = Attr::F; as.f = sit->second.f[0]; ma.attrs["scale"] = as;
+            for (int d : {i, mul, mm1, tk, mm2, qt, qr, kt, kr, vt, vr, o1}) dead[d] = true;
+            nodes[o2] = std::move(ma);                   // the pattern's last node: every input is computed in front of it
+        }
+        std::vector<GNode> keep;
+        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
+        nodes.swap(keep);
+    }
     // ---- pass 4: Linear / Conv -> Add(residual): fold the residual into the producer's epilogue (no act between);
     // shapes are only known at plan time: op_conv / op_linear fall back to a separate add when they do not match
     {
@@ -4892,6 +4986,28 @@ struct Planner {
         step([=](const RunCtx& c) { k::RelPosAttnP r = p; r.qkv = c.at(xl); r.o = c.mut(yl); k::relpos_attention(c.s, r); },
              sets * N * (4.0 * N * d + 2.0 * (gh + gw) * d), 4.0 * (4.0 * tokens * C + sets * std::ceil(N / k::kRpQueries) * 2.0 * N * d));
     }
+    // fused multi-head attention with separate sources (rewrite pass 3e): q [N, Tq, heads * head_dim], k and v [N, Tk, heads * head_dim] -> [N, Tq, heads * head_dim]
+    void op_mha_attention(const GNode& n) {
+        TInfo q = get(n.in[0]), kk = get(n.in[1]), v = get(n.in[2]);
+        const int64_t Tq = n.ai("Tq", 1), Tk = n.ai("Tk", 1), h = n.ai("heads", 1), d = n.ai("head_dim", 1), D = h * d;
+        OAR_CHECK(k::mha_attention_supported(1, Tq, Tk, h, d), OAR_INTERNAL, "MultiHeadAttention: the rewrite let an unsupported shape through at " + n.out[0]);
+        // (the graph's Reshape [0, T, heads, head_dim] keeps the first dimension and needs the rest to hold T heads head_dim values, whatever the rank)
+        OAR_CHECK(!q.host_int && !kk.host_int && !v.host_int && !q.dims.empty() && q.dims[0] >= 1 && numel(q.dims) == q.dims[0] * Tq * D, OAR_SHAPE_MISMATCH,
+                  "MultiHeadAttention: q must be [N, " + std::to_string(Tq) + ", " + std::to_string(D) + "] at " + n.out[0]);
+        const int64_t N = q.dims[0];
+        OAR_CHECK(!kk.dims.empty() && kk.dims[0] == N && numel(kk.dims) == N * Tk * D && !v.dims.empty() && v.dims[0] == N && numel(v.dims) == N * Tk * D, OAR_SHAPE_MISMATCH,
+                  "MultiHeadAttention: k and v must be [N, " + std::to_string(Tk) + ", " + std::to_string(D) + "] at " + n.out[0]);
+        OAR_CHECK(k::mha_attention_supported(N, Tq, Tk, h, d), OAR_SHAPE_MISMATCH, "MultiHeadAttention: batch out of range at " + n.out[0]);
+        Loc ql = to_native_loc(q), kl = to_native_loc(kk), vl = to_native_loc(v);
+        TInfo& y = new_out(n.out[0], {N, Tq, D}, Layout::NATIVE);
+        Loc yl = y.loc;
+        k::MhaAttnP p{};
+        p.N = (int)N; p.Tq = (int)Tq; p.Tk = (int)Tk; p.nh = (int)h; p.dh = (int)d; p.ldq = p.ldk = p.ldv = (int)D;
+        p.scale = n.af("scale", 1.0f); p.scale_pre = n.ai("scale_pos", 0) == 0;
+        const double sets = (double)N * h;
+        step([=](const RunCtx& c) { k::MhaAttnP r = p; r.q = c.at(ql); r.k = c.at(kl); r.v = c.at(vl); r.o = c.mut(yl); k::mha_attention(c.s, r); },
+             sets * 4.0 * Tq * Tk * d, 4.0 * (2.0 * N * Tq * D + sets * std::ceil((double)Tq / k::kMhaQueries) * 2.0 * Tk * d));
+    }
     // fused multi-scale deformable attention (rewrite pass 3c): value [N, Lv, heads * c], loc [N, Q, heads, L, P, 2], logits or weights [N, Q, heads * L * P]
     // -> [N, Q, heads * c]
     void op_deformable_attention(const GNode& n) {
@@ -5259,6 +5375,7 @@ struct Planner {
         if (op == "WindowAttention") return op_window_attention(n);
         if (op == "DeformableAttention") return op_deformable_attention(n);
         if (op == "RelPosAttention") return op_relpos_attention(n);
+        if (op == "MultiHeadAttention") return op_mha_attention(n);
         if (op == "SLADecode") return op_sla_decode(n);
         if (op == "FormulaDecode") return op_formula_decode(n);
         if (op == "SEGate") return op_se_gate(n);

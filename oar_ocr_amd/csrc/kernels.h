@@ -308,6 +308,28 @@ inline size_t relpos_attention_lds_bytes(int gh, int gw) {
     return ((size_t)4 * kRpKeys * kRpLd + (size_t)2 * kRpKeys + (size_t)kRpQueries * ((size_t)(gh | 1) + (size_t)(gw | 1))) * sizeof(float);
 }
 void relpos_attention(hipStream_t s, const RelPosAttnP& p);
+// mha_attention.hip: multi-head attention with separate q / k / v sources, one launch.  q is viewed as [N][Tq][nh][dh] with a row stride of ldq
+// floats (image b starts at b Tq ldq), k and v as [N][Tk][nh][dh] with ldk / ldv: a q / k pair may live in one [N, T, 2 nh dh] Linear output (ld = 2 nh dh, k's
+// pointer advanced by nh dh).  o [N][Tq][nh dh] is contiguous, in token order.  o = softmax(scaled q k^T) v per (image, head);
+// scale_pre: q is multiplied by `scale` in front of the product (the graph's Mul on q), otherwise the product is (its Mul on the scores).
+// The keys are streamed in blocks of kMhaKeys with a running maximum and sum: no score row exists in memory and Tq, Tk have no upper limit.
+struct MhaAttnP {
+    const float *q, *k, *v;
+    float* o;
+    int N, Tq, Tk, nh, dh;
+    int ldq, ldk, ldv;
+    float scale; int scale_pre;
+};
+constexpr int kMhaThreads = 256, kMhaQueries = 64, kMhaKeys = 32, kMhaLd = 68, kMhaMaxDh = 64;
+// head_dim % 4 == 0 and <= kMhaMaxDh; token and workgroup counts that fit 32 bits (N = 1: the static part of the question)
+bool mha_attention_supported(int64_t N, int64_t Tq, int64_t Tk, int64_t heads, int64_t head_dim);
+// the kernel's LDS, all of it dynamic: K and V blocks [2 stages][kMhaKeys][kMhaLd] each.  The rows are padded for the largest head whatever head_dim is, so
+// the answer does not depend on it (tests/test_mha_attention_cpu.py compiles this)
+inline size_t mha_attention_lds_bytes(int head_dim) {
+    (void)head_dim;
+    return (size_t)4 * kMhaKeys * kMhaLd * sizeof(float);
+}
+void mha_attention(hipStream_t s, const MhaAttnP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

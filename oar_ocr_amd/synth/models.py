@@ -789,7 +789,7 @@ def build_layout(kind="picodet", n_classes=5, seed=11, image_shape=(800, 608), f
 
 
 # ---------------------------------------------------------------------------------------------- table cell detector: a graph that SELECTS
-def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classes=1, seed=21, decoder_layers=0, decoder_heads=4, decoder_points=4):
+def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classes=1, seed=21, decoder_layers=0, decoder_heads=4, decoder_points=4, encoder_layers=0):
     """An RT-DETR-shaped table cell detector with synthetic weights whose query selection really runs in the graph (build_layout's "rtdetr" is
     a CNN head with RT-DETR's column order).  Inputs, bound by name as RTDetrModel::infer binds them (models/detection/rtdetr.rs:160-180):
     "image" [N,3,H,W] (declared first: the engine's primary input), "scale_factor" [N,2] = (ratio_h, ratio_w), "im_shape" [N,2] = resized (h, w).
@@ -800,6 +800,9 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
                 decoder_layers > 0: an RT-DETR decoder of that many layers (_rtdetr_decoder: self-attention over the queries, multi-scale deformable
                 cross-attention into `memory` with decoder_heads heads and decoder_points points per level, FFN, box refinement) sits between the
                 gathers and these heads, which then read its last layer's queries and reference logits.  0 (the default) leaves the graph as it was
+      encoder   encoder_layers > 0: the stride-32 level's projected map goes through that many AIFI layers (_aifi_layer: the hybrid encoder's transformer
+                half, decoder_heads heads, F = 2 D, the 2-D sin-cos position table) before it joins the concat: flattened and transposed to [N, h w, D]
+                in, transposed and reshaped back to [N, D, h, w] out (info["aifi"]: the tensor names and weights).  0 (the default): as it was
       order     TopK(keep) over the per-query best score; a tensor-indexed Gather over the batch-flattened rows assembles
                 output 0 "boxes" [N * keep, 6] = (class, score, x1, y1, x2, y2), sorted by score like the real export's
     Every TopK has its input and its index output declared as further graph outputs (info["topk"]), so a test can check each selection exactly
@@ -832,6 +835,15 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
     for lvl, (ft, cin, stride) in enumerate(((f8, c3, 8), (f16, c4, 16), (f32_, c5, 32))):
         h, w = H // stride, W // stride
         p = n.conv(ft, cin, D, 1, act="hswish")
+        if encoder_layers and stride == 32:
+            t = g.op("Transpose", [g.op("Reshape", [p, i64([0, D, h * w])])], perm=[0, 2, 1])
+            aifi = {"in": t, "H": h, "W": w, "D": D, "nh": decoder_heads, "F": 2 * D, "layers": []}
+            for li in range(encoder_layers):
+                aw = aifi_layer_weights(D, 2 * D, seed=seed + 2 + li)
+                t = _aifi_layer(g, t, aw, f"enc{li}_", h, w, D, decoder_heads)
+                aifi["layers"].append(aw)
+            aifi["out"] = t
+            p = g.op("Reshape", [g.op("Transpose", [t], perm=[0, 2, 1]), i64([0, D, h, w])])
         tokens.append(g.op("Transpose", [g.op("Reshape", [p, i64([0, D, h * w])])], perm=[0, 2, 1]))                    # [N, h * w, D]
         ys, xs = np.mgrid[0:h, 0:w]
         size = 0.12 * 2.0 ** lvl                                                                                        # RT-DETR's anchors: grid centres, a size per level
@@ -885,7 +897,7 @@ def build_table_cell_det(image_shape=(640, 640), queries=300, keep=300, n_classe
         g.add_output(t["input"], ["N", A if cols == "A" else queries])
         g.add_output(t["index"], ["N", t["k"]], elem_type=7)
     return g.model(), {"params": g.n_params, "kind": "rtdetr", "classes": n_classes, "anchors": A, "queries": queries, "keep": keep, "feat": 6, "topk": topk,
-                       **({"decoder_layers": decoder_layers} if decoder_layers else {})}
+                       **({"decoder_layers": decoder_layers} if decoder_layers else {}), **({"encoder_layers": encoder_layers, "aifi": aifi} if encoder_layers else {})}
 
 
 # ---------------------------------------------------------------------------------------------- RT-DETR decoder: multi-scale deformable attention
@@ -1033,6 +1045,116 @@ def build_rtdetr_decoder(D=32, nh=4, levels=((8, 8), (4, 4), (2, 2)), P=4, layer
         names += [f"out{i}", f"ref{i}"]
     return g.model(), {"params": g.n_params, "weights": w, "D": D, "nh": nh, "levels": levels, "P": P, "layers": layers, "Q": Q, "classes": n_classes,
                        "layer_outputs": names}
+
+
+# ---------------------------------------------------------------------------------------------- RT-DETR: multi-head attention with separate q / k / v sources
+def mha_weights(D, seed=0, prefix=""):
+    """f32 weights of one multi-head attention block, every Linear an [in, out] matrix with its bias: q and k (gain 2: an attention that is not uniform), v, o"""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for nm, gain in (("q", 2.0), ("k", 2.0), ("v", 1.0), ("o", 1.0)):
+        w[prefix + nm + "_w"] = ((rng.random((D, D)) * 2.0 - 1.0) * (gain / np.sqrt(D))).astype(np.float32)
+        w[prefix + nm + "_b"] = ((rng.random(D) * 2.0 - 1.0) * 0.1).astype(np.float32)
+    return w
+
+
+def _mha(g, w, p, xq, xk, xv, Tq, Tk, nh, dh, scale="post", mask=None, scores_out=None):
+    """PaddleDetection's MultiHeadAttention as its export spells it (the engine's rewrite pass 3e matches exactly this): three Linears on
+    xq [N, Tq, D], xk and xv [N, Tk, D], each split into heads by Reshape[0, T, nh, dh] -> Transpose[0,2,1,3]; scale = "post": Mul(MatMul(q, k^T), dh^-0.5),
+    "pre": MatMul(Mul(q, dh^-0.5), k^T); Softmax; MatMul with v; Transpose[0,2,1,3] -> Reshape[0, Tq, D]; the output Linear.  Knobs that write a near miss:
+    mask, a constant [Tq, Tk] added in front of the Softmax; scores_out, a name the Softmax's input gets, for the caller to declare as a graph output."""
+    if scale not in ("pre", "post"):
+        raise ValueError(scale)
+    D = nh * dh
+    ci = lambda v: g.init(np.array(v, np.int64), "shape")
+    lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(w[p + nm + "_w"], "mha_" + p + nm + "_w")]), g.init(w[p + nm + "_b"], "mha_" + p + nm + "_b")])
+    heads = lambda t, T: g.op("Transpose", [g.op("Reshape", [t, ci([0, T, nh, dh])])], perm=[0, 2, 1, 3])
+    cs = g.init(np.array(dh ** -0.5, np.float32), "c")
+    q, k, v = heads(lin(xq, "q"), Tq), heads(lin(xk, "k"), Tk), heads(lin(xv, "v"), Tk)
+    kt = g.op("Transpose", [k], perm=[0, 1, 3, 2])
+    last = {} if mask is not None or scores_out is None else {"outputs": [scores_out]}
+    if scale == "pre":
+        s = g.op("MatMul", [g.op("Mul", [q, cs]), kt], **last)
+    else:
+        s = g.op("Mul", [g.op("MatMul", [q, kt]), cs], **last)
+    if mask is not None:
+        s = g.op("Add", [s, g.init(np.ascontiguousarray(mask, np.float32), "mask")], **({} if scores_out is None else {"outputs": [scores_out]}))
+    o = g.op("MatMul", [g.op("Softmax", [s], axis=-1), v])
+    return lin(g.op("Reshape", [g.op("Transpose", [o], perm=[0, 2, 1, 3]), ci([0, Tq, D])]), "o")
+
+
+def build_mha(N, Tq, Tk, nh, dh, seed=0, scale="post", shared_qk=True, pos=True, mask=False, scores_output=False):
+    """The block on its own: x [N, Tq, D] (and mem [N, Tk, D]) -> y [N, Tq, D], D = nh dh.  Tk == Tq and shared_qk: self-attention, q and k read
+    Add(x, posc) and v reads x, as an RT-DETR decoder layer and the AIFI layer do (`mem` is not declared); otherwise cross-attention: q reads x (+ posc), k and
+    v read mem.  posc [1, Tq, D] ~ N(0, 1) is a constant (pos = False: no Add).  Near misses for the engine's fall-back tests: mask = True adds a constant
+    [Tq, Tk] ~ 2 N(0, 1) in front of the Softmax (info["mask"]); scores_output = True declares the Softmax's input as the graph output `scores`.
+    The batch is dynamic; N is recorded in info for the caller's inputs."""
+    D = nh * dh
+    self_attn = bool(Tk == Tq and shared_qk)
+    w = mha_weights(D, seed)
+    rng = np.random.default_rng(seed + 1000)
+    posc = rng.standard_normal((1, Tq, D)).astype(np.float32) if pos else None
+    m = (2.0 * rng.standard_normal((Tq, Tk))).astype(np.float32) if mask else None
+    g = GraphBuilder("mha", 17)
+    g.add_input("x", ["N", Tq, D])
+    if not self_attn:
+        g.add_input("mem", ["N", Tk, D])
+    xq = g.op("Add", ["x", g.init(posc, "mha_pos")]) if pos else "x"
+    y = _mha(g, w, "", xq, xq if self_attn else "mem", "x" if self_attn else "mem", Tq, Tk, nh, dh, scale, m, "scores" if scores_output else None)
+    g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
+    g.add_output("y", ["N", Tq, D])
+    if scores_output:
+        g.add_output("scores", ["N", nh, Tq, Tk])
+    return g.model(), {"params": g.n_params, "weights": w, "N": N, "Tq": Tq, "Tk": Tk, "nh": nh, "dh": dh, "scale": scale, "self": self_attn, "pos": posc, "mask": m}
+
+
+def sincos_2d(H, W, D, temperature=10000.0):
+    """the constant 2-D sin-cos position table of the AIFI layer, [1, H W, D] in f32: with omega_i = temperature^(-i / (D / 4)), i < D / 4, the token at
+    (y, x), row-major, holds [sin(x omega), cos(x omega), sin(y omega), cos(y omega)]"""
+    if D % 4:
+        raise ValueError("D must be a multiple of 4")
+    omega = 1.0 / temperature ** (np.arange(D // 4, dtype=np.float64) / (D // 4))
+    ys, xs = np.mgrid[0:H, 0:W]
+    ox, oy = xs.reshape(-1, 1) * omega[None], ys.reshape(-1, 1) * omega[None]
+    return np.concatenate([np.sin(ox), np.cos(ox), np.sin(oy), np.cos(oy)], 1)[None].astype(np.float32)
+
+
+def aifi_layer_weights(D, F, seed=0):
+    """mha_weights plus the two LayerNorms and the FFN (D -> F -> D) of a post-norm TransformerLayer"""
+    w = mha_weights(D, seed)
+    rng = np.random.default_rng(seed + 500)
+    for nm in ("ln1", "ln2"):
+        w[nm + "_g"] = (1.0 + 0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32)
+        w[nm + "_b"] = (0.1 * (rng.random(D) * 2.0 - 1.0)).astype(np.float32)
+    for nm, cin, cout in (("ffn1", D, F), ("ffn2", F, D)):
+        w[nm + "_w"] = ((rng.random((cin, cout)) * 2.0 - 1.0) / np.sqrt(cin)).astype(np.float32)
+        w[nm + "_b"] = ((rng.random(cout) * 2.0 - 1.0) * 0.1).astype(np.float32)
+    return w
+
+
+def _aifi_layer(g, src, w, p, H, W, D, nh):
+    """PaddleDetection's post-norm TransformerLayer on src [N, H W, D]: q = k = src + pos_embed (sincos_2d, an initializer), v = src; _mha; Add +
+    LayerNormalization; Linear -> Gelu -> Linear; Add + LayerNormalization"""
+    c = lambda nm: g.init(w[nm], "aifi_" + p + nm)
+    lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, c(nm + "_w")]), c(nm + "_b")])
+    lnorm = lambda t, nm: g.op("LayerNormalization", [t, c(nm + "_g"), c(nm + "_b")], axis=-1, epsilon=1e-5)
+    qk = g.op("Add", [src, g.init(sincos_2d(H, W, D), "aifi_" + p + "pos")])
+    src = lnorm(g.op("Add", [src, _mha(g, w, "", qk, qk, src, H * W, H * W, nh, D // nh)]), "ln1")
+    ffn = lin(g.op("Gelu", [lin(src, "ffn1")], approximate="none"), "ffn2")
+    return lnorm(g.op("Add", [src, ffn]), "ln2")
+
+
+def build_aifi_layer(H, W, D, nh, F, seed=0):
+    """The AIFI layer of RT-DETR's hybrid encoder as a graph of its own: src [N, H W, D] -> y [N, H W, D] (_aifi_layer)."""
+    if D % nh:
+        raise ValueError("D must be a multiple of the heads")
+    w = aifi_layer_weights(D, F, seed)
+    g = GraphBuilder("aifi_layer", 17)
+    g.add_input("src", ["N", H * W, D])
+    y = _aifi_layer(g, "src", w, "", H, W, D, nh)
+    g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
+    g.add_output("y", ["N", H * W, D])
+    return g.model(), {"params": g.n_params, "weights": w, "H": H, "W": W, "D": D, "nh": nh, "F": F}
 
 
 # ---------------------------------------------------------------------------------------------- table structure recognition: SLANet
