@@ -1029,6 +1029,53 @@ void Engine::rewrite_graph(OnnxModel& m) {
         }
     }
 
+    // ---- the matcher toolkit of passes 3b - 3e: declared once, by node index throughout.  scan() reads the current `nodes` at the head of a pass (readers,
+    // producers, nobody dead) and sweep() drops what the pass killed.  Every node a helper returns is live and PLAIN: no fused activation (so far pass 3 alone
+    // attaches one, to Conv / ConvTranspose / Linear / Gemm / Add) and no fused residual (pass 4, behind all four passes, is the first to attach one).
+    using V = std::vector<int64_t>;
+    std::map<std::string, std::vector<int>> cons;
+    std::map<std::string, int> producer;
+    std::vector<bool> dead;
+    auto scan = [&] {
+        cons = consumers(nodes);
+        producer.clear();
+        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
+        dead.assign(nodes.size(), false);
+    };
+    auto sweep = [&] {
+        std::vector<GNode> keep;
+        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
+        nodes.swap(keep);
+    };
+    auto plain = [&](int i, const char* op) { return !dead[i] && nodes[i].op == op && nodes[i].act.kind == k::ACT_NONE && nodes[i].residual.empty(); };
+    auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
+    auto prodn = [&](const std::string& v, const char* op) -> int {    // the producer `op` of v (v may have several readers)
+        auto it = producer.find(v);
+        return it != producer.end() && plain(it->second, op) ? it->second : -1;
+    };
+    auto prod1 = [&](const std::string& v, const char* op) -> int { return single_use(v) ? prodn(v, op) : -1; };   // ... and v read by nobody else
+    auto reader1 = [&](const std::string& v, const char* op) -> int {  // the single consumer of v, an `op` reading it first
+        if (!single_use(v)) return -1;
+        const int c = cons[v][0];
+        return plain(c, op) && nodes[c].in[0] == v ? c : -1;
+    };
+    auto ints = [&](const std::string& v) -> V {
+        auto it = inits_.find(v);
+        return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
+    };
+    auto target = [&](int r) -> V { return nodes[r].in.size() < 2 || nodes[r].ai("allowzero", 0) != 0 ? V{} : ints(nodes[r].in[1]); };   // of a Reshape
+    auto perm_is = [&](int t, std::initializer_list<int64_t> want) { return nodes[t].ais("perm") == V(want); };
+    auto axes_are = [&](int n, int64_t a, int64_t rank) {              // opset 13 input or the older attribute; a or a - rank
+        const V ax = nodes[n].in.size() > 1 && !nodes[n].in[1].empty() ? ints(nodes[n].in[1]) : nodes[n].ais("axes");
+        return ax.size() == 1 && (ax[0] == a || ax[0] == a - rank);
+    };
+    auto f32_scalar = [&](const std::string& v) -> const HostTensor* {
+        auto it = inits_.find(v);
+        return it != inits_.end() && it->second.dtype == DType::F32 && it->second.f.size() == 1 ? &it->second : nullptr;
+    };
+    auto iattr = [](GNode& n, const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; n.attrs[k] = a; };
+    auto fattr = [](GNode& n, const char* k, float v) { Attr a; a.kind = Attr::F; a.f = v; n.attrs[k] = a; };
+
     // ---- pass 3b: the attention of a Swin block (UniMERNet's encoder), y [B, H W, C] with static H, W, ws, N = ws^2:
     //   p = Reshape(y, [0, H/ws, ws, W/ws, ws, C]) -> Transpose[0,1,3,2,4,5] -> Reshape[-1, N, C]                     (window partition)
     //   q, k, v = Linear(p);  qh, kh, vh = Transpose[0,2,1,3](Reshape(., [0, N, nh, dh]))
@@ -1052,38 +1099,14 @@ void Engine::rewrite_graph(OnnxModel& m) {
     {
         const char* fe = getenv("OAR_FUSE_WINDOW_ATTENTION");
         const bool fuse = !fe || atoi(fe) != 0;
-        auto cons = consumers(nodes);
-        std::map<std::string, int> producer;
-        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
-        std::vector<bool> dead(nodes.size(), false);
-        auto prod = [&](const std::string& v, const char* op) -> int {
-            auto it = producer.find(v);
-            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op) return -1;
-            return it->second;
-        };
-        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
-        auto only_reader = [&](const std::string& v, const char* op) -> int {   // the single consumer of v, which must be a live `op` reading it first
-            if (!single_use(v)) return -1;
-            const int c = cons[v][0];
-            return !dead[c] && nodes[c].op == op && nodes[c].in[0] == v ? c : -1;
-        };
-        auto target = [&](const GNode& r) -> std::vector<int64_t> {
-            if (r.in.size() < 2 || r.ai("allowzero", 0) != 0) return {};
-            auto it = inits_.find(r.in[1]);
-            return it == inits_.end() || it->second.dtype == DType::F32 ? std::vector<int64_t>{} : it->second.i;
-        };
-        auto perm_is = [&](const GNode& t, std::initializer_list<int64_t> want) { return t.ais("perm") == std::vector<int64_t>(want); };
-        auto ints = [&](const std::string& v) -> std::vector<int64_t> {
-            auto it = inits_.find(v);
-            return it == inits_.end() || it->second.dtype == DType::F32 ? std::vector<int64_t>{} : it->second.i;
-        };
+        scan();
         struct Sl { std::string src; int64_t ax, st, en; };
         auto slice1 = [&](int idx, Sl& o) {   // a single-axis unit-step Slice with constant non-negative operands
             const GNode& sl = nodes[idx];
             if (sl.op != "Slice" || sl.in.size() < 4 || sl.in.size() > 5) return false;
-            const std::vector<int64_t> st = ints(sl.in[1]), en = ints(sl.in[2]), ax = ints(sl.in[3]);
+            const V st = ints(sl.in[1]), en = ints(sl.in[2]), ax = ints(sl.in[3]);
             if (st.size() != 1 || en.size() != 1 || ax.size() != 1 || st[0] < 0 || en[0] < 0 || ax[0] < 0) return false;
-            if (sl.in.size() == 5 && !sl.in[4].empty() && ints(sl.in[4]) != std::vector<int64_t>{1}) return false;
+            if (sl.in.size() == 5 && !sl.in[4].empty() && ints(sl.in[4]) != V{1}) return false;
             o = Sl{sl.in[0], ax[0], st[0], en[0]};
             return true;
         };
@@ -1093,8 +1116,8 @@ void Engine::rewrite_graph(OnnxModel& m) {
             if (cc.op != "Concat" || cc.in.size() != 2 || cc.ai("axis", 0) != axis || cc.act.kind != k::ACT_NONE) return false;
             Sl a[2];
             for (int t = 0; t < 2; ++t) {
-                sl[t] = prod(cc.in[t], "Slice");
-                if (sl[t] < 0 || !single_use(cc.in[t]) || !slice1(sl[t], a[t]) || a[t].ax != axis) return false;
+                sl[t] = prod1(cc.in[t], "Slice");
+                if (sl[t] < 0 || !slice1(sl[t], a[t]) || a[t].ax != axis) return false;
             }
             if (a[0].src != a[1].src || a[1].st != 0 || a[0].st != a[1].en || a[0].st <= 0 || a[0].st >= n || a[0].en < n) return false;
             if (cons[a[0].src].size() != 2 || graph_outs.count(a[0].src)) return false;
@@ -1122,23 +1145,23 @@ void Engine::rewrite_graph(OnnxModel& m) {
             // the per-window mask, where there is one: Reshape[-1, nW, nh, N, N] -> Add(mask [1, nW, 1, N, N]) -> Reshape[-1, nh, N, N]
             std::string sv = sm.in[0], maskn;
             int m1 = -1, m2 = -1;
-            const int m3 = prod(sv, "Reshape");
+            const int m3 = prodn(sv, "Reshape");
             if (m3 >= 0) {
                 if (!single_use(sv)) continue;
-                m2 = prod(nodes[m3].in[0], "Add");
-                if (m2 < 0 || !single_use(nodes[m3].in[0]) || nodes[m2].act.kind != k::ACT_NONE) continue;
+                m2 = prod1(nodes[m3].in[0], "Add");
+                if (m2 < 0) continue;
                 const int mi = is_init(nodes[m2].in[1]) ? 1 : is_init(nodes[m2].in[0]) ? 0 : -1;
                 if (mi < 0) continue;
                 maskn = nodes[m2].in[mi];
                 const HostTensor& mk = inits_[maskn];
                 if (mk.dtype != DType::F32 || mk.dims.size() != 5 || mk.dims[0] != 1 || mk.dims[2] != 1 || mk.dims[3] != mk.dims[4] || (int64_t)mk.f.size() != numel(mk.dims)) continue;
-                m1 = prod(nodes[m2].in[1 - mi], "Reshape");
-                if (m1 < 0 || !single_use(nodes[m2].in[1 - mi])) continue;
+                m1 = prod1(nodes[m2].in[1 - mi], "Reshape");
+                if (m1 < 0) continue;
                 sv = nodes[m1].in[0];
             }
             // scores: Add(scaled, bias) in either order, scaled = Div(MatMul, c) or Mul(MatMul, c) / Mul(c, MatMul)
-            const int ad = prod(sv, "Add");
-            if (ad < 0 || !single_use(sv) || !single_use(sm.out[0]) || nodes[ad].act.kind != k::ACT_NONE) continue;
+            const int ad = prod1(sv, "Add");
+            if (ad < 0 || !single_use(sm.out[0])) continue;
             const int bi = is_init(nodes[ad].in[1]) ? 1 : is_init(nodes[ad].in[0]) ? 0 : -1;
             if (bi < 0) continue;
             const HostTensor& bias = inits_[nodes[ad].in[bi]];
@@ -1148,103 +1171,102 @@ void Engine::rewrite_graph(OnnxModel& m) {
             if (m3 >= 0) {
                 const HostTensor& mk = inits_[maskn];
                 nWm = mk.dims[1];
-                if (mk.dims[3] != N || target(nodes[m3]) != std::vector<int64_t>{-1, nh, N, N} || target(nodes[m1]) != std::vector<int64_t>{-1, nWm, nh, N, N}) continue;
+                if (mk.dims[3] != N || target(m3) != V{-1, nh, N, N} || target(m1) != V{-1, nWm, nh, N, N}) continue;
             }
             const std::string& scaled = nodes[ad].in[1 - bi];
-            if (!single_use(scaled)) continue;
-            int sc = prod(scaled, "Div"), scale_div = 1, ci = 1;
-            if (sc < 0) { sc = prod(scaled, "Mul"); scale_div = 0; if (sc >= 0) ci = is_init(nodes[sc].in[1]) ? 1 : 0; }
-            if (sc < 0 || nodes[sc].act.kind != k::ACT_NONE || !is_init(nodes[sc].in[ci])) continue;
-            const HostTensor& sct = inits_[nodes[sc].in[ci]];
-            if (sct.dtype != DType::F32 || sct.f.size() != 1) continue;
-            const int mm1 = prod(nodes[sc].in[1 - ci], "MatMul");
-            if (mm1 < 0 || !single_use(nodes[sc].in[1 - ci])) continue;
-            const int mm2 = only_reader(sm.out[0], "MatMul");
+            int sc = prod1(scaled, "Div"), scale_div = 1, ci = 1;
+            if (sc < 0) { sc = prod1(scaled, "Mul"); scale_div = 0; if (sc >= 0) ci = is_init(nodes[sc].in[1]) ? 1 : 0; }
+            if (sc < 0) continue;
+            const HostTensor* sct = f32_scalar(nodes[sc].in[ci]);
+            if (!sct) continue;
+            const int mm1 = prod1(nodes[sc].in[1 - ci], "MatMul");
+            if (mm1 < 0) continue;
+            const int mm2 = reader1(sm.out[0], "MatMul");
             if (mm2 < 0) continue;
             // heads: Transpose[0,2,1,3](Reshape(Linear, [0, N, nh, dh])), the keys once more through Transpose[0,1,3,2]
-            const int tk = prod(nodes[mm1].in[1], "Transpose");
-            if (tk < 0 || !single_use(nodes[mm1].in[1]) || !perm_is(nodes[tk], {0, 1, 3, 2})) continue;
+            const int tk = prod1(nodes[mm1].in[1], "Transpose");
+            if (tk < 0 || !perm_is(tk, {0, 1, 3, 2})) continue;
             int64_t dh = 0;
             int tr[3], rs[3], ln[3];
             const std::string* hv[3] = {&nodes[mm1].in[0], &nodes[tk].in[0], &nodes[mm2].in[1]};
             bool ok = true;
             for (int t = 0; t < 3 && ok; ++t) {
-                tr[t] = prod(*hv[t], "Transpose");
-                ok = tr[t] >= 0 && single_use(*hv[t]) && perm_is(nodes[tr[t]], {0, 2, 1, 3});
+                tr[t] = prod1(*hv[t], "Transpose");
+                ok = tr[t] >= 0 && perm_is(tr[t], {0, 2, 1, 3});
                 if (!ok) break;
-                rs[t] = prod(nodes[tr[t]].in[0], "Reshape");
-                ok = rs[t] >= 0 && single_use(nodes[tr[t]].in[0]);
+                rs[t] = prod1(nodes[tr[t]].in[0], "Reshape");
+                ok = rs[t] >= 0;
                 if (!ok) break;
-                const std::vector<int64_t> tg = target(nodes[rs[t]]);
+                const V tg = target(rs[t]);
                 ok = tg.size() == 4 && tg[0] == 0 && tg[1] == N && tg[2] == nh && tg[3] > 0 && (dh == 0 || tg[3] == dh);
                 if (!ok) break;
                 dh = tg[3];
-                ln[t] = prod(nodes[rs[t]].in[0], "Linear");
-                ok = ln[t] >= 0 && single_use(nodes[rs[t]].in[0]) && plain_linear(nodes[ln[t]], nh * dh);
+                ln[t] = prod1(nodes[rs[t]].in[0], "Linear");
+                ok = ln[t] >= 0 && plain_linear(nodes[ln[t]], nh * dh);
             }
             if (!ok || ln[0] == ln[1] || ln[0] == ln[2] || ln[1] == ln[2]) continue;
             const int64_t C = nh * dh;
             // window partition: the three projections are the only readers of p
             const std::string pv = nodes[ln[0]].in[0];
             if (nodes[ln[1]].in[0] != pv || nodes[ln[2]].in[0] != pv || cons[pv].size() != 3 || graph_outs.count(pv)) continue;
-            const int p3 = prod(pv, "Reshape");
-            if (p3 < 0 || target(nodes[p3]) != std::vector<int64_t>{-1, N, C}) continue;
-            const int p2 = prod(nodes[p3].in[0], "Transpose");
-            if (p2 < 0 || !single_use(nodes[p3].in[0]) || !perm_is(nodes[p2], {0, 1, 3, 2, 4, 5})) continue;
-            const int p1 = prod(nodes[p2].in[0], "Reshape");
-            if (p1 < 0 || !single_use(nodes[p2].in[0])) continue;
-            const std::vector<int64_t> pt = target(nodes[p1]);
+            const int p3 = prodn(pv, "Reshape");
+            if (p3 < 0 || target(p3) != V{-1, N, C}) continue;
+            const int p2 = prod1(nodes[p3].in[0], "Transpose");
+            if (p2 < 0 || !perm_is(p2, {0, 1, 3, 2, 4, 5})) continue;
+            const int p1 = prod1(nodes[p2].in[0], "Reshape");
+            if (p1 < 0) continue;
+            const V pt = target(p1);
             if (pt.size() != 6 || pt[0] != 0 || pt[1] <= 0 || pt[2] <= 0 || pt[3] <= 0 || pt[4] != pt[2] || pt[5] != C || pt[2] * pt[2] != N) continue;
             const int64_t hb = pt[1], ws = pt[2], wb = pt[3], Hp = hb * ws, Wp = wb * ws;
             if (!k::window_attention_supported((int)std::min<int64_t>(ws, 1 << 20), (int)std::min<int64_t>(nh, 1 << 20), (int)std::min<int64_t>(dh, 1 << 20))) continue;
             if (Hp >= (int64_t)1 << 30 || Wp >= (int64_t)1 << 30 || (m3 >= 0 && nWm != hb * wb)) continue;
             // output side: Transpose[0,2,1,3] -> Reshape[0, N, C] -> Linear -> window reverse
-            const int t2 = only_reader(nodes[mm2].out[0], "Transpose");
-            if (t2 < 0 || !perm_is(nodes[t2], {0, 2, 1, 3})) continue;
-            const int r2 = only_reader(nodes[t2].out[0], "Reshape");
-            if (r2 < 0 || target(nodes[r2]) != std::vector<int64_t>{0, N, C}) continue;
-            const int pj = only_reader(nodes[r2].out[0], "Linear");
+            const int t2 = reader1(nodes[mm2].out[0], "Transpose");
+            if (t2 < 0 || !perm_is(t2, {0, 2, 1, 3})) continue;
+            const int r2 = reader1(nodes[t2].out[0], "Reshape");
+            if (r2 < 0 || target(r2) != V{0, N, C}) continue;
+            const int pj = reader1(nodes[r2].out[0], "Linear");
             if (pj < 0 || !plain_linear(nodes[pj], C)) continue;
-            const int v1 = only_reader(nodes[pj].out[0], "Reshape");
-            if (v1 < 0 || target(nodes[v1]) != std::vector<int64_t>{-1, hb, wb, ws, ws, C}) continue;
-            const int v2 = only_reader(nodes[v1].out[0], "Transpose");
-            if (v2 < 0 || !perm_is(nodes[v2], {0, 1, 3, 2, 4, 5})) continue;
-            const int v3 = only_reader(nodes[v2].out[0], "Reshape");
+            const int v1 = reader1(nodes[pj].out[0], "Reshape");
+            if (v1 < 0 || target(v1) != V{-1, hb, wb, ws, ws, C}) continue;
+            const int v2 = reader1(nodes[v1].out[0], "Transpose");
+            if (v2 < 0 || !perm_is(v2, {0, 1, 3, 2, 4, 5})) continue;
+            const int v3 = reader1(nodes[v2].out[0], "Reshape");
             if (v3 < 0) continue;
             // the reverse ends in [-1, Hp Wp, C]: the plain block, y feeds the partition.  It ends in [-1, Hp, Wp, C]: the tokens are handled as a grid, with
             // Reshape[0, H, W, C] -> Pad (bottom / right, constant 0) -> roll by -s on axis 1, then on axis 2 in front of the partition, Pad and roll each optional
-            const bool grid = target(nodes[v3]) == std::vector<int64_t>{-1, Hp, Wp, C};
-            if (!grid && target(nodes[v3]) != std::vector<int64_t>{-1, Hp * Wp, C}) continue;
+            const bool grid = target(v3) == V{-1, Hp, Wp, C};
+            if (!grid && target(v3) != V{-1, Hp * Wp, C}) continue;
             std::vector<int> extra;
             std::string cur = nodes[p1].in[0];
             int64_t shift = 0, H = Hp, W = Wp;
             if (grid) {
                 bool counted = false;                // cur's readers are already known to be the two Slices of a roll
-                if (const int c2 = prod(cur, "Concat"); c2 >= 0) {
+                if (const int c2 = prodn(cur, "Concat"); c2 >= 0) {
                     std::string s2, s1;
                     int64_t k2 = 0, k1 = 0;
                     int sa[2], sb[2];
                     if (!single_use(cur) || !roll(c2, 2, Wp, s2, k2, sa)) continue;
-                    const int c1 = prod(s2, "Concat");
+                    const int c1 = prodn(s2, "Concat");
                     if (c1 < 0 || !roll(c1, 1, Hp, s1, k1, sb) || k1 != k2) continue;
                     shift = k1; cur = s1; counted = true;
                     extra.insert(extra.end(), {c2, c1, sa[0], sa[1], sb[0], sb[1]});
                 }
-                if (const int pd = prod(cur, "Pad"); pd >= 0) {
+                if (const int pd = prodn(cur, "Pad"); pd >= 0) {
                     const GNode& pn = nodes[pd];
                     if (!(counted || single_use(cur)) || pn.as("mode", "constant") != "constant" || pn.in.size() < 2 || pn.in.size() > 3) continue;
-                    const std::vector<int64_t> pads = ints(pn.in[1]);
+                    const V pads = ints(pn.in[1]);
                     if (pads.size() != 8 || pads[0] || pads[1] || pads[2] || pads[3] || pads[4] || pads[7] || pads[5] < 0 || pads[6] < 0 || pads[5] >= ws || pads[6] >= ws) continue;
                     if (pn.in.size() == 3 && !pn.in[2].empty()) {
-                        auto it = inits_.find(pn.in[2]);
-                        if (it == inits_.end() || it->second.dtype != DType::F32 || it->second.f.size() != 1 || it->second.f[0] != 0.0f) continue;
+                        const HostTensor* pv0 = f32_scalar(pn.in[2]);
+                        if (!pv0 || pv0->f[0] != 0.0f) continue;
                     }
                     H = Hp - pads[5]; W = Wp - pads[6];
                     cur = pn.in[0]; counted = false;
                     extra.push_back(pd);
                 }
-                const int fr = prod(cur, "Reshape");
-                if (fr < 0 || !(counted || single_use(cur)) || target(nodes[fr]) != std::vector<int64_t>{0, H, W, C}) continue;   // (constants: a dynamic H / W is not matched)
+                const int fr = prodn(cur, "Reshape");
+                if (fr < 0 || !(counted || single_use(cur)) || target(fr) != V{0, H, W, C}) continue;   // (constants: a dynamic H / W is not matched)
                 cur = nodes[fr].in[0];
                 extra.push_back(fr);
             }
@@ -1261,16 +1283,16 @@ void Engine::rewrite_graph(OnnxModel& m) {
                 }
                 for (int ax = 1; ax <= 2 && ok2; ++ax) {
                     if ((ax == 1 ? Hp - H : Wp - W) == 0) continue;
-                    const int cr = only_reader(out, "Slice");
+                    const int cr = reader1(out, "Slice");
                     Sl c;
                     ok2 = cr >= 0 && slice1(cr, c) && c.ax == ax && c.st == 0 && c.en == (ax == 1 ? H : W);
                     if (ok2) { out = nodes[cr].out[0]; extra.push_back(cr); }
                 }
                 if (!ok2) continue;
-                const int fin = only_reader(out, "Reshape");
+                const int fin = reader1(out, "Reshape");
                 if (fin < 0) continue;
-                const std::vector<int64_t> ft = target(nodes[fin]);
-                if (ft != std::vector<int64_t>{0, H * W, C} && ft != std::vector<int64_t>{-1, H * W, C}) continue;
+                const V ft = target(fin);
+                if (ft != V{0, H * W, C} && ft != V{-1, H * W, C}) continue;
                 out = nodes[fin].out[0];
                 extra.push_back(fin);
             }
@@ -1282,9 +1304,8 @@ void Engine::rewrite_graph(OnnxModel& m) {
                 wa.in.insert(wa.in.end(), {maskn, pads ? nodes[ln[1]].bias : std::string(), pads ? nodes[ln[2]].bias : std::string()});
             }
             wa.out = {nodes[r2].out[0]};
-            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; wa.attrs[k] = a; };
-            iattr("ws", ws); iattr("H", H); iattr("W", W); iattr("Hp", Hp); iattr("Wp", Wp); iattr("shift", shift); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_div", scale_div);
-            Attr as; as.kind = Attr::F; as.f = sct.f[0]; wa.attrs["scale"] = as;
+            iattr(wa, "ws", ws); iattr(wa, "H", H); iattr(wa, "W", W); iattr(wa, "Hp", Hp); iattr(wa, "Wp", Wp); iattr(wa, "shift", shift); iattr(wa, "heads", nh); iattr(wa, "head_dim", dh); iattr(wa, "scale_div", scale_div);
+            fattr(wa, "scale", sct->f[0]);
             for (int t = 0; t < 3; ++t) nodes[ln[t]].in[0] = y;
             nodes[pj].out[0] = out;
             for (int d : {p1, p2, p3, rs[0], rs[1], rs[2], tr[0], tr[1], tr[2], tk, mm1, sc, ad, i, mm2, t2, v1, v2, v3}) dead[d] = true;
@@ -1292,9 +1313,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
             for (int d : {m1, m2, m3}) if (d >= 0) dead[d] = true;
             nodes[r2] = std::move(wa);   // behind q, k and v, in front of the projection
         }
-        std::vector<GNode> keep;
-        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
-        nodes.swap(keep);
+        sweep();
     }
     // ---- pass 3d: the attention of a SAM / Vary ViT block with the decomposed relative-position bias (the encoder of the larger PP-FormulaNet files; DESIGN
     //   4.35), y [B, H W, C] with static H, W; (h, w) = (H, W) for global attention, (ws, ws) for windows; N = h w, G = B (windows) nh:
@@ -1317,37 +1336,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
     {
         const char* fe = getenv("OAR_FUSE_RELPOS_ATTENTION");
         const bool fuse = fe && atoi(fe) != 0;           // opt-in until the three-arm speed measurement of DESIGN 4.35 exists: unset or 0 keeps the op-by-op route
-        auto cons = consumers(nodes);
-        std::map<std::string, int> producer;
-        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
-        std::vector<bool> dead(nodes.size(), false);
-        using V = std::vector<int64_t>;
-        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
-        auto prodn = [&](const std::string& v, const char* op) -> int {    // the live producer `op` of v (v may have several readers)
-            auto it = producer.find(v);
-            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op || nodes[it->second].act.kind != k::ACT_NONE || !nodes[it->second].residual.empty()) return -1;
-            return it->second;
-        };
-        auto prod1 = [&](const std::string& v, const char* op) -> int { return single_use(v) ? prodn(v, op) : -1; };   // ... and v read by nobody else
-        auto reader1 = [&](const std::string& v, const char* op) -> int {  // the single consumer of v, a live `op` reading it first
-            if (!single_use(v)) return -1;
-            const int c = cons[v][0];
-            return !dead[c] && nodes[c].op == op && nodes[c].act.kind == k::ACT_NONE && nodes[c].residual.empty() && nodes[c].in[0] == v ? c : -1;
-        };
-        auto ints = [&](const std::string& v) -> V {
-            auto it = inits_.find(v);
-            return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
-        };
-        auto target = [&](int r) -> V { return nodes[r].in.size() < 2 || nodes[r].ai("allowzero", 0) != 0 ? V{} : ints(nodes[r].in[1]); };
-        auto perm_is = [&](int t, std::initializer_list<int64_t> want) { return nodes[t].ais("perm") == V(want); };
-        auto axes_are = [&](const GNode& n, int64_t a, int64_t rank) {   // opset 13 input or the older attribute; a or a - rank
-            const V ax = n.in.size() > 1 && !n.in[1].empty() ? ints(n.in[1]) : n.ais("axes");
-            return ax.size() == 1 && (ax[0] == a || ax[0] == a - rank);
-        };
-        auto f32_scalar = [&](const std::string& v) -> const HostTensor* {
-            auto it = inits_.find(v);
-            return it != inits_.end() && it->second.dtype == DType::F32 && it->second.f.size() == 1 ? &it->second : nullptr;
-        };
+        scan();
         auto table = [&](const std::string& v, int64_t n, int64_t dh) {  // a constant f32 [n, dh, n]
             auto it = inits_.find(v);
             return it != inits_.end() && it->second.dtype == DType::F32 && it->second.dims == V{n, dh, n} && (int64_t)it->second.f.size() == n * dh * n;
@@ -1370,9 +1359,9 @@ void Engine::rewrite_graph(OnnxModel& m) {
             const int a2 = prod1(nodes[ra].in[0], "Add");
             if (a2 < 0 || nodes[a2].in.size() != 2) continue;
             const int a1 = prod1(nodes[a2].in[0], "Add"), uw = prod1(nodes[a2].in[1], "Unsqueeze");
-            if (a1 < 0 || uw < 0 || nodes[a1].in.size() != 2 || !axes_are(nodes[uw], 3, 5)) continue;
+            if (a1 < 0 || uw < 0 || nodes[a1].in.size() != 2 || !axes_are(uw, 3, 5)) continue;
             const int s5 = prod1(nodes[a1].in[0], "Reshape"), uh = prod1(nodes[a1].in[1], "Unsqueeze");
-            if (s5 < 0 || uh < 0 || !axes_are(nodes[uh], 4, 5)) continue;
+            if (s5 < 0 || uh < 0 || !axes_are(uh, 4, 5)) continue;
             const V t5 = target(s5);
             if (t5.size() != 5 || t5[0] != 0 || t5[1] < 1 || t5[2] < 1 || t5[3] != t5[1] || t5[4] != t5[2] || t5[1] > (1 << 20) || t5[2] > (1 << 20) || t5[1] * t5[2] != N) continue;
             const int64_t h = t5[1], w = t5[2];
@@ -1400,7 +1389,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
             bool ok = true;
             for (int t = 0; t < 3 && ok; ++t) {
                 sq[t] = t == 0 ? prodn(*hv[t], "Squeeze") : prod1(*hv[t], "Squeeze");
-                ok = sq[t] >= 0 && axes_are(nodes[sq[t]], 0, 4);
+                ok = sq[t] >= 0 && axes_are(sq[t], 0, 4);
                 if (!ok) break;
                 const int s = prod1(nodes[sq[t]].in[0], "Split");
                 ok = s >= 0 && (sp < 0 || s == sp) && nodes[s].out.size() == 3 && nodes[s].out[(size_t)t] == nodes[sq[t]].in[0];
@@ -1527,18 +1516,15 @@ void Engine::rewrite_graph(OnnxModel& m) {
             ra_node.in = {nodes[lq].out[0], nodes[mh].in[1], nodes[mw].in[1]};
             if (padded) ra_node.in.push_back(nodes[lq].bias);   // what a padding token is behind the Linear (empty: zeros)
             ra_node.out = {nodes[o3].out[0]};
-            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; ra_node.attrs[k] = a; };
-            iattr("H", H); iattr("W", W); iattr("ws", ws); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_pos", scale_pre ? 0 : 1);
-            Attr as; as.kind = Attr::F; as.f = sct->f[0]; ra_node.attrs["scale"] = as;
+            iattr(ra_node, "H", H); iattr(ra_node, "W", W); iattr(ra_node, "ws", ws); iattr(ra_node, "heads", nh); iattr(ra_node, "head_dim", dh); iattr(ra_node, "scale_pos", scale_pre ? 0 : 1);
+            fattr(ra_node, "scale", sct->f[0]);
             nodes[lq].in[0] = y;
             nodes[pj].out[0] = out;
             for (int d : {i, ra, a2, a1, uw, uh, s5, mul, mm1, tk, mm2, sq[0], sq[1], sq[2], sp, h3, h2, h1, rq, th2, tw2, rh2, rw2, mh, mw, rh1, rw1, th1, tw1, o1, o2, r0, f0}) dead[d] = true;
             for (int d : extra) dead[d] = true;
             nodes[o3] = std::move(ra_node);              // behind the fused Linear, in front of the projection
         }
-        std::vector<GNode> keep;
-        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
-        nodes.swap(keep);
+        sweep();
     }
     // ---- pass 3c: multi-scale deformable attention (the cross-attention core of an RT-DETR decoder layer), in the exported spelling, with static
     //   nh, c, Q, P and levels (h_l, w_l), Lv = sum h_l w_l:
@@ -1556,34 +1542,10 @@ void Engine::rewrite_graph(OnnxModel& m) {
     {
         const char* fe = getenv("OAR_FUSE_DEFORMABLE_ATTENTION");
         const bool fuse = !fe || atoi(fe) != 0;
-        auto cons = consumers(nodes);
-        std::map<std::string, int> producer;
-        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
-        std::vector<bool> dead(nodes.size(), false);
-        using V = std::vector<int64_t>;
-        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
-        auto prod1 = [&](const std::string& v, const char* op) -> int {   // the live producer `op` of v, v read by nobody else
-            auto it = producer.find(v);
-            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op || nodes[it->second].act.kind != k::ACT_NONE || !single_use(v)) return -1;
-            return it->second;
-        };
-        auto reader1 = [&](const std::string& v, const char* op) -> int {   // the single consumer of v, a live `op` reading it first
-            if (!single_use(v)) return -1;
-            const int c = cons[v][0];
-            return !dead[c] && nodes[c].op == op && nodes[c].act.kind == k::ACT_NONE && nodes[c].in[0] == v ? c : -1;
-        };
-        auto ints = [&](const std::string& v) -> V {
-            auto it = inits_.find(v);
-            return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
-        };
-        auto target = [&](const GNode& r) -> V { return r.in.size() < 2 || r.ai("allowzero", 0) != 0 ? V{} : ints(r.in[1]); };
-        auto axes_are = [&](const GNode& n, int64_t a, int64_t rank) {   // opset 13 input or the older attribute; a or a - rank
-            const V ax = n.in.size() > 1 && !n.in[1].empty() ? ints(n.in[1]) : n.ais("axes");
-            return ax.size() == 1 && (ax[0] == a || ax[0] == a - rank);
-        };
+        scan();
         auto scalar_is = [&](const std::string& v, float want) {
-            auto it = inits_.find(v);
-            return it != inits_.end() && it->second.dtype == DType::F32 && it->second.f.size() == 1 && it->second.f[0] == want;
+            const HostTensor* t = f32_scalar(v);
+            return t && t->f[0] == want;
         };
         for (int i = 0; fuse && i < (int)nodes.size(); ++i) {
             const GNode& cc = nodes[i];
@@ -1598,7 +1560,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
             for (int64_t l = 0; l < L && ok; ++l) {
                 ok = false;
                 const int us = prod1(cc.in[l], "Unsqueeze");
-                if (us < 0 || !axes_are(nodes[us], 3, 5)) break;
+                if (us < 0 || !axes_are(us, 3, 5)) break;
                 const int gs = prod1(nodes[us].in[0], "GridSample");
                 if (gs < 0 || nodes[gs].in.size() != 2) break;
                 const std::string mode = nodes[gs].as("mode", "linear");
@@ -1606,16 +1568,16 @@ void Engine::rewrite_graph(OnnxModel& m) {
                 // value side
                 const int r2 = prod1(nodes[gs].in[0], "Reshape");
                 if (r2 < 0) break;
-                const V t2 = target(nodes[r2]);
+                const V t2 = target(r2);
                 if (t2.size() != 4 || t2[0] != -1 || t2[1] < 1 || t2[2] < 1 || t2[3] < 1 || (c && t2[1] != c)) break;
                 c = t2[1];
                 const int64_t h = t2[2], w = t2[3];
                 if (h >= (int64_t)1 << 30 || w >= (int64_t)1 << 30) break;
                 const int t1 = prod1(nodes[r2].in[0], "Transpose");
-                if (t1 < 0 || nodes[t1].ais("perm") != V{0, 2, 1}) break;
+                if (t1 < 0 || !perm_is(t1, {0, 2, 1})) break;
                 const int r1 = prod1(nodes[t1].in[0], "Reshape");
                 if (r1 < 0) break;
-                const V tg1 = target(nodes[r1]);
+                const V tg1 = target(r1);
                 if (tg1.size() != 3 || tg1[0] != 0 || tg1[1] != h * w || tg1[2] < c || tg1[2] % c || (nh && tg1[2] != nh * c)) break;
                 nh = tg1[2] / c;
                 const int s = prod1(nodes[r1].in[0], "Split");
@@ -1624,13 +1586,13 @@ void Engine::rewrite_graph(OnnxModel& m) {
                 // grid side
                 const int r3 = prod1(nodes[gs].in[1], "Reshape");
                 if (r3 < 0) break;
-                const V t3 = target(nodes[r3]);
+                const V t3 = target(r3);
                 if (t3.size() != 4 || t3[0] != -1 || t3[1] < 1 || t3[2] < 1 || t3[3] != 2 || (Q && (t3[1] != Q || t3[2] != P))) break;
                 Q = t3[1]; P = t3[2];
                 const int tg = prod1(nodes[r3].in[0], "Transpose");
-                if (tg < 0 || nodes[tg].ais("perm") != V{0, 2, 1, 3, 4}) break;
+                if (tg < 0 || !perm_is(tg, {0, 2, 1, 3, 4})) break;
                 const int sq = prod1(nodes[tg].in[0], "Squeeze");
-                if (sq < 0 || !axes_are(nodes[sq], 3, 6)) break;
+                if (sq < 0 || !axes_are(sq, 3, 6)) break;
                 const int sl = prod1(nodes[sq].in[0], "Slice");
                 if (sl < 0 || nodes[sl].in.size() < 4 || nodes[sl].in.size() > 5) break;
                 if (ints(nodes[sl].in[1]) != V{l} || ints(nodes[sl].in[2]) != V{l + 1} || ints(nodes[sl].in[3]) != V{3}) break;
@@ -1651,13 +1613,11 @@ void Engine::rewrite_graph(OnnxModel& m) {
             for (int64_t l = 0; l < L; ++l) parts_ok = parts_ok && parts[(size_t)l] == lv[(size_t)(2 * l)] * lv[(size_t)(2 * l + 1)];
             if (!parts_ok) continue;
             const int rv = prod1(spn.in[0], "Reshape");
-            if (rv < 0 || target(nodes[rv]) != V{0, Lv, nh, c}) continue;
+            if (rv < 0 || target(rv) != V{0, Lv, nh, c}) continue;
             // the grid: Sub(Mul(loc, 2), 1), read by the L Slices alone
             if ((int64_t)cons[gridn].size() != L || graph_outs.count(gridn)) continue;
-            auto git = producer.find(gridn);
-            if (git == producer.end() || dead[git->second]) continue;
-            const int sb = git->second;
-            if (nodes[sb].op != "Sub" || nodes[sb].act.kind != k::ACT_NONE || nodes[sb].in.size() != 2 || !scalar_is(nodes[sb].in[1], 1.0f)) continue;
+            const int sb = prodn(gridn, "Sub");
+            if (sb < 0 || nodes[sb].in.size() != 2 || !scalar_is(nodes[sb].in[1], 1.0f)) continue;
             const int ml = prod1(nodes[sb].in[0], "Mul");
             if (ml < 0 || nodes[ml].in.size() != 2) continue;
             const int ci = scalar_is(nodes[ml].in[1], 2.0f) ? 1 : scalar_is(nodes[ml].in[0], 2.0f) ? 0 : -1;
@@ -1665,42 +1625,41 @@ void Engine::rewrite_graph(OnnxModel& m) {
             const std::string locn = nodes[ml].in[1 - ci];
             // combine
             const int rc = reader1(cc.out[0], "Reshape");
-            if (rc < 0 || target(nodes[rc]) != V{0, c, Q, L * P}) continue;
+            if (rc < 0 || target(rc) != V{0, c, Q, L * P}) continue;
             const int mu = reader1(nodes[rc].out[0], "Mul");
             if (mu < 0 || nodes[mu].in.size() != 2) continue;
             const int rw = prod1(nodes[mu].in[1], "Reshape");
-            if (rw < 0 || target(nodes[rw]) != V{-1, 1, Q, L * P}) continue;
+            if (rw < 0 || target(rw) != V{-1, 1, Q, L * P}) continue;
             const int tw = prod1(nodes[rw].in[0], "Transpose");
-            if (tw < 0 || nodes[tw].ais("perm") != V{0, 2, 1, 3, 4}) continue;
+            if (tw < 0 || !perm_is(tw, {0, 2, 1, 3, 4})) continue;
             const int r5 = prod1(nodes[tw].in[0], "Reshape");
-            if (r5 < 0 || target(nodes[r5]) != V{0, Q, nh, L, P}) continue;
+            if (r5 < 0 || target(r5) != V{0, Q, nh, L, P}) continue;
             int sm = prod1(nodes[r5].in[0], "Softmax"), r4 = -1;
             std::string wn = nodes[r5].in[0];
             if (sm >= 0) {
                 const int64_t ax = nodes[sm].ai("axis", -1);
                 if (ax != -1 && ax != 3) continue;
                 r4 = prod1(nodes[sm].in[0], "Reshape");
-                if (r4 < 0 || target(nodes[r4]) != V{0, Q, nh, L * P}) continue;
+                if (r4 < 0 || target(r4) != V{0, Q, nh, L * P}) continue;
                 wn = nodes[r4].in[0];
             } else if (producer.count(wn) && nodes[producer[wn]].op == "Softmax") {
                 continue;                            // a Softmax that did not fit (a second reader, another axis): not ours
-            } else if (const int r = prod1(wn, "Reshape"); r >= 0 && target(nodes[r]) == V{0, Q, nh, L * P}) {
+            } else if (const int r = prod1(wn, "Reshape"); r >= 0 && target(r) == V{0, Q, nh, L * P}) {
                 r4 = r;                              // the weights as an input: the same two Reshapes without the Softmax between them
                 wn = nodes[r4].in[0];
             }
             const int rd = reader1(nodes[mu].out[0], "ReduceSum");
-            if (rd < 0 || !axes_are(nodes[rd], 3, 4) || nodes[rd].ai("keepdims", 1) != 0) continue;
+            if (rd < 0 || !axes_are(rd, 3, 4) || nodes[rd].ai("keepdims", 1) != 0) continue;
             const int ro = reader1(nodes[rd].out[0], "Reshape");
-            if (ro < 0 || target(nodes[ro]) != V{-1, nh * c, Q}) continue;
+            if (ro < 0 || target(ro) != V{-1, nh * c, Q}) continue;
             const int tf = reader1(nodes[ro].out[0], "Transpose");
-            if (tf < 0 || nodes[tf].ais("perm") != V{0, 2, 1}) continue;
+            if (tf < 0 || !perm_is(tf, {0, 2, 1})) continue;
             if (!k::deformable_attention_supported(1, Q, nh, c, L, P, Lv)) continue;
             GNode da;
             da.op = "DeformableAttention";
             da.in = {nodes[rv].in[0], locn, wn};
             da.out = {nodes[tf].out[0]};
-            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; da.attrs[k] = a; };
-            iattr("heads", nh); iattr("points", P); iattr("softmax", sm >= 0 ? 1 : 0);
+            iattr(da, "heads", nh); iattr(da, "points", P); iattr(da, "softmax", sm >= 0 ? 1 : 0);
             Attr la; la.kind = Attr::IS; la.is = lv; da.attrs["levels"] = la;
             for (int d : kill) dead[d] = true;
             for (int d : {i, sp, rv, sb, ml, rc, mu, rw, tw, r5, rd, ro}) dead[d] = true;
@@ -1708,9 +1667,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
             if (r4 >= 0) dead[r4] = true;
             nodes[tf] = std::move(da);               // the pattern's last node: every input is computed in front of it
         }
-        std::vector<GNode> keep;
-        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
-        nodes.swap(keep);
+        sweep();
     }
     // ---- pass 3e: ordinary multi-head attention with separate q / k / v sources (PaddleDetection's MultiHeadAttention as exported: the self-attention of an
     //   RT-DETR decoder layer and the AIFI layer of its hybrid encoder), with static Tq, Tk, nh, dh:
@@ -1727,28 +1684,7 @@ void Engine::rewrite_graph(OnnxModel& m) {
     {
         const char* fe = getenv("OAR_FUSE_MHA_ATTENTION");
         const bool fuse = !fe || atoi(fe) != 0;
-        auto cons = consumers(nodes);
-        std::map<std::string, int> producer;
-        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
-        std::vector<bool> dead(nodes.size(), false);
-        using V = std::vector<int64_t>;
-        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
-        auto prod1 = [&](const std::string& v, const char* op) -> int {   // the live producer `op` of v, v read by nobody else
-            auto it = producer.find(v);
-            if (it == producer.end() || dead[it->second] || nodes[it->second].op != op || nodes[it->second].act.kind != k::ACT_NONE || !nodes[it->second].residual.empty() || !single_use(v)) return -1;
-            return it->second;
-        };
-        auto reader1 = [&](const std::string& v, const char* op) -> int {   // the single consumer of v, a live `op` reading it first
-            if (!single_use(v)) return -1;
-            const int c = cons[v][0];
-            return !dead[c] && nodes[c].op == op && nodes[c].act.kind == k::ACT_NONE && nodes[c].residual.empty() && nodes[c].in[0] == v ? c : -1;
-        };
-        auto target = [&](int r) -> V {
-            if (nodes[r].in.size() < 2 || nodes[r].ai("allowzero", 0) != 0) return V{};
-            auto it = inits_.find(nodes[r].in[1]);
-            return it == inits_.end() || it->second.dtype == DType::F32 ? V{} : it->second.i;
-        };
-        auto perm_is = [&](int t, std::initializer_list<int64_t> want) { return nodes[t].ais("perm") == V(want); };
+        scan();
         // heads(t, T): -> the Transpose and the Reshape, and (T, nh, dh); false where v is anything else
         auto heads = [&](const std::string& v, int& tr, int& rs, int64_t& T, int64_t& nh, int64_t& dh) {
             tr = prod1(v, "Transpose");
@@ -1775,8 +1711,8 @@ void Engine::rewrite_graph(OnnxModel& m) {
                 scale_pre = 1;
             }
             if (mm1 < 0 || mul < 0 || nodes[mul].in.size() != 2 || nodes[mm1].in.size() != 2) continue;
-            auto sit = inits_.find(nodes[mul].in[1]);
-            if (sit == inits_.end() || sit->second.dtype != DType::F32 || sit->second.f.size() != 1) continue;
+            const HostTensor* sct = f32_scalar(nodes[mul].in[1]);
+            if (!sct) continue;
             const int tk = prod1(nodes[mm1].in[1], "Transpose");
             if (tk < 0 || !perm_is(tk, {0, 1, 3, 2})) continue;
             const int mm2 = reader1(nodes[i].out[0], "MatMul");
@@ -1796,15 +1732,12 @@ void Engine::rewrite_graph(OnnxModel& m) {
             ma.op = "MultiHeadAttention";
             ma.in = {nodes[qr].in[0], nodes[kr].in[0], nodes[vr].in[0]};
             ma.out = {nodes[o2].out[0]};
-            auto iattr = [&](const char* k, int64_t v) { Attr a; a.kind = Attr::I; a.i = v; ma.attrs[k] = a; };
-            iattr("Tq", Tq); iattr("Tk", Tk); iattr("heads", nh); iattr("head_dim", dh); iattr("scale_pos", scale_pre ? 0 : 1);
-            Attr as; as.kind = Attr::F; as.f = sit->second.f[0]; ma.attrs["scale"] = as;
+            iattr(ma, "Tq", Tq); iattr(ma, "Tk", Tk); iattr(ma, "heads", nh); iattr(ma, "head_dim", dh); iattr(ma, "scale_pos", scale_pre ? 0 : 1);
+            fattr(ma, "scale", sct->f[0]);
             for (int d : {i, mul, mm1, tk, mm2, qt, qr, kt, kr, vt, vr, o1}) dead[d] = true;
             nodes[o2] = std::move(ma);                   // the pattern's last node: every input is computed in front of it
         }
-        std::vector<GNode> keep;
-        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
-        nodes.swap(keep);
+        sweep();
     }
     // ---- pass 4: Linear / Conv -> Add(residual): fold the residual into the producer's epilogue (no act between);
     // shapes are only known at plan time: op_conv / op_linear fall back to a separate add when they do not match

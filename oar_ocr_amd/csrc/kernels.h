@@ -284,6 +284,11 @@ struct DeformAttnP {
 // c % 4 == 0, c <= kDefMaxC, L <= kDefMaxLevels, L P <= kDefMaxSamples, and token / thread counts that fit 32 bits (N = Q = 1: the static part of the question)
 bool deformable_attention_supported(int64_t N, int64_t Q, int64_t nh, int64_t c, int64_t L, int64_t P, int64_t Lv);
 void deformable_attention(hipStream_t s, const DeformAttnP& p);
+// flash_f32_dev.h: the flash-attention core relpos_attention.hip and mha_attention.hip share -- ONE layout: a workgroup of kFlashThreads owns kFlashQueries
+// queries, K and V stream through LDS in blocks of kFlashKeys keys, rows padded to kFlashLd floats, head_dim <= kFlashMaxDh.
+constexpr int kFlashThreads = 256, kFlashQueries = 64, kFlashKeys = 32, kFlashLd = 68, kFlashMaxDh = 64;
+// the K and V blocks [2 stages][kFlashKeys][kFlashLd] each, in front of whatever else a kernel keeps in its dynamic LDS
+inline size_t flash_kv_lds_bytes() { return (size_t)4 * kFlashKeys * kFlashLd * sizeof(float); }
 // relpos_attention.hip: the attention of one SAM / Vary ViT block with the decomposed relative-position bias, one launch.
 // qkv [B H W][3][nh][dh]: the fused projection of the UNPADDED tokens in IMAGE order (token (b, y, x) is row (b H + y) W + x); o [B H W][nh dh] in image order.
 // ws = 0: every query attends to the whole H x W grid; ws > 0: inside ws x ws windows of the grid padded at the bottom / right to multiples of ws.  A padding
@@ -291,28 +296,28 @@ void deformable_attention(hipStream_t s, const DeformAttnP& p);
 // query it is skipped.  With (gh, gw) = (ws, ws) or (H, W) the key grid: rh [gh][dh][gh], rw [gw][dh][gw] (query row / column, component, key row / column), and
 //   score[(qy, qx), (ky, kx)] = scaled q . k + q . rh[qy][:][ky] + q . rw[qx][:][kx]   with the UNSCALED q in both rel terms;
 // scale_pre: q is multiplied by `scale` in front of the product (the graph's Mul on q), otherwise the product is (its Mul on the scores).
-// The key set is streamed in blocks of kRpKeys with a running maximum and sum: no score row exists in memory and gh gw has no upper limit.
+// The key set is streamed in blocks of kFlashKeys with a running maximum and sum: no score row exists in memory and gh gw has no upper limit.
 struct RelPosAttnP {
     const float *qkv, *rh, *rw, *bqkv;
     float* o;
     int B, H, W, ws, nh, dh;
     float scale; int scale_pre;
 };
-constexpr int kRpThreads = 256, kRpQueries = 64, kRpKeys = 32, kRpLd = 68, kRpMaxDh = 64, kRpMaxGrid = 64;
+constexpr int kRpQueries = kFlashQueries, kRpMaxDh = kFlashMaxDh, kRpMaxGrid = 64;
 // head_dim % 4 == 0 and <= kRpMaxDh; key grid sides <= kRpMaxGrid (ws <= 64, or H, W <= 64 when ws = 0); token and workgroup counts that fit 32 bits (B = 1: the
 // static part of the question)
 bool relpos_attention_supported(int64_t B, int64_t H, int64_t W, int64_t ws, int64_t heads, int64_t head_dim);
-// the kernel's LDS, all of it dynamic: K and V blocks [2 stages][kRpKeys][kRpLd] each, the blocks' key coordinates [2][kRpKeys], and rh / rw of the workgroup's
-// queries [kRpQueries][gh | 1], [kRpQueries][gw | 1] (tests/test_vit_relpos_cpu.py compiles this)
+// the kernel's LDS, all of it dynamic: the K and V blocks, the blocks' key coordinates [2][kFlashKeys], and rh / rw of the workgroup's queries
+// [kRpQueries][gh | 1], [kRpQueries][gw | 1] (tests/test_vit_relpos_cpu.py compiles this)
 inline size_t relpos_attention_lds_bytes(int gh, int gw) {
-    return ((size_t)4 * kRpKeys * kRpLd + (size_t)2 * kRpKeys + (size_t)kRpQueries * ((size_t)(gh | 1) + (size_t)(gw | 1))) * sizeof(float);
+    return flash_kv_lds_bytes() + ((size_t)2 * kFlashKeys + (size_t)kRpQueries * ((size_t)(gh | 1) + (size_t)(gw | 1))) * sizeof(float);
 }
 void relpos_attention(hipStream_t s, const RelPosAttnP& p);
 // mha_attention.hip: multi-head attention with separate q / k / v sources, one launch.  q is viewed as [N][Tq][nh][dh] with a row stride of ldq
 // floats (image b starts at b Tq ldq), k and v as [N][Tk][nh][dh] with ldk / ldv: a q / k pair may live in one [N, T, 2 nh dh] Linear output (ld = 2 nh dh, k's
 // pointer advanced by nh dh).  o [N][Tq][nh dh] is contiguous, in token order.  o = softmax(scaled q k^T) v per (image, head);
 // scale_pre: q is multiplied by `scale` in front of the product (the graph's Mul on q), otherwise the product is (its Mul on the scores).
-// The keys are streamed in blocks of kMhaKeys with a running maximum and sum: no score row exists in memory and Tq, Tk have no upper limit.
+// The keys are streamed in blocks of kFlashKeys with a running maximum and sum: no score row exists in memory and Tq, Tk have no upper limit.
 struct MhaAttnP {
     const float *q, *k, *v;
     float* o;
@@ -320,14 +325,14 @@ struct MhaAttnP {
     int ldq, ldk, ldv;
     float scale; int scale_pre;
 };
-constexpr int kMhaThreads = 256, kMhaQueries = 64, kMhaKeys = 32, kMhaLd = 68, kMhaMaxDh = 64;
+constexpr int kMhaQueries = kFlashQueries, kMhaMaxDh = kFlashMaxDh;
 // head_dim % 4 == 0 and <= kMhaMaxDh; token and workgroup counts that fit 32 bits (N = 1: the static part of the question)
 bool mha_attention_supported(int64_t N, int64_t Tq, int64_t Tk, int64_t heads, int64_t head_dim);
-// the kernel's LDS, all of it dynamic: K and V blocks [2 stages][kMhaKeys][kMhaLd] each.  The rows are padded for the largest head whatever head_dim is, so
-// the answer does not depend on it (tests/test_mha_attention_cpu.py compiles this)
+// the kernel's LDS, all of it dynamic: the K and V blocks.  The rows are padded for the largest head whatever head_dim is, so the answer does not depend
+// on it (tests/test_mha_attention_cpu.py compiles this)
 inline size_t mha_attention_lds_bytes(int head_dim) {
     (void)head_dim;
-    return (size_t)4 * kMhaKeys * kMhaLd * sizeof(float);
+    return flash_kv_lds_bytes();
 }
 void mha_attention(hipStream_t s, const MhaAttnP& p);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }

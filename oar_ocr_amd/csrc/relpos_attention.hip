@@ -4,25 +4,18 @@
 // -> crop]:  a Linear is per token, so the fused projection reads the unpadded tokens in image order and this kernel gathers a key set's rows by address
 // (a window, or the whole grid); a padding token is a key carrying bqkv's k / v rows and is skipped as a query.
 //
-// Flash-style, exact f32 on the matrix pipe (v_mfma_f32_16x16x4_f32 is bitwise an fmaf chain):
-//   * a workgroup (4 waves) owns kRpQueries = 64 queries of one (image, window, head), a wave 16 of them: lane (ql = lane & 15, g = lane >> 4) holds
-//     components 16 c + 4 g + j of query ql (B operand of S^T = K Q^T; MFMA j of chunk c contracts component 16 c + 4 g + j of both sides);
+// The key loop is the shared flash core (flash_f32_dev.h, where the lane layout is described); a workgroup owns kFlashQueries queries of one (image,
+// window, head).  What is this kernel's own:
 //   * before the key loop the workgroup stages its queries in LDS once and computes rh[q][ky] = q . Rh[qy][:][ky] and rw[q][kx] from the UNSCALED q
 //     ((gh + gw) dh fmas per query, ascending d), kept in LDS for the whole loop;
-//   * K and V stream through LDS in blocks of kRpKeys = 32 keys, double-buffered, every global load unconditional (a key past the end reads the last key and
-//     is masked with -inf; a padding key reads bqkv), rows padded to kRpLd = 68 floats: the K fragment is one 16-byte read per 4 MFMAs, the V fragment reads
-//     (key 4 g + r, component i) hit 64 different banks;
-//   * the accumulator lane (ql, g) of a 16-key tile holds the scores of query ql against keys 4 g + r: each gets the scale where the graph has it, then
-//     + rh[q][ky] + rw[q][kx] (the key's coordinates come from a table the staging threads write next to the block), then the running maximum (two
-//     cross-lane maxima per block) and expf;
-//   * these 4 probabilities ARE the lane's B operands of O^T = V^T P^T when MFMA r contracts key 4 g + r, so P never crosses lanes; the running sum stays
-//     per lane and is reduced once, in the epilogue, in a fixed order: run-to-run identical.
-// The head size is rounded up to DH16 * 16 components with zeros (template: registers stay statically indexed, no scratch).
+//   * a key past the end reads the last key and is masked with -inf; a padding key reads bqkv;
+//   * each score gets the scale where the graph has it, then + rh[q][ky] + rw[q][kx]: the key's coordinates come from a table the staging threads write
+//     next to the block.
 // LDS (dynamic, k::relpos_attention_lds_bytes): 34,816 + 256 + 256 ((gh | 1) + (gw | 1)) bytes, 68,352 at gh = gw = 64: two workgroups per CU, so one wave's
 // soft-max overlaps the other's MFMAs.
 #include "common.h"
 #include "kernels.h"
-#include "kernels_dev.h"
+#include "flash_f32_dev.h"
 
 namespace oar {
 namespace k {
@@ -30,16 +23,16 @@ namespace k {
 namespace {
 
 template <int DH16>
-__global__ __launch_bounds__(kRpThreads) void relpos_attention_kernel(RelPosAttnP p, int q_tiles) {
+__global__ __launch_bounds__(kFlashThreads) void relpos_attention_kernel(RelPosAttnP p, int q_tiles) {
     extern __shared__ float4 rp_lds4[];
     constexpr int F4 = 4 * DH16;                       // float4 groups per staged row
     const int gw = p.ws ? p.ws : p.W, gh = p.ws ? p.ws : p.H, N = gh * gw;
     const int ghs = gh | 1, gws = gw | 1;
-    float* Ks = reinterpret_cast<float*>(rp_lds4);     // [2][kRpKeys][kRpLd]; before the key loop: the workgroup's queries [kRpQueries][kRpLd]
-    float* Vs = Ks + 2 * kRpKeys * kRpLd;              // [2][kRpKeys][kRpLd]
-    int* tab = reinterpret_cast<int*>(Vs + 2 * kRpKeys * kRpLd);   // [2][kRpKeys]: ky << 8 | kx, negative past the key set's end
-    float* rhs = reinterpret_cast<float*>(tab + 2 * kRpKeys);      // [kRpQueries][ghs]
-    float* rws = rhs + kRpQueries * ghs;               // [kRpQueries][gws]
+    float* Ks = reinterpret_cast<float*>(rp_lds4);     // [2][kFlashKeys][kFlashLd]; before the key loop: the workgroup's queries [kFlashQueries][kFlashLd]
+    float* Vs = Ks + 2 * kFlashKeys * kFlashLd;        // [2][kFlashKeys][kFlashLd]
+    int* tab = reinterpret_cast<int*>(Vs + 2 * kFlashKeys * kFlashLd);   // [2][kFlashKeys]: ky << 8 | kx, negative past the key set's end
+    float* rhs = reinterpret_cast<float*>(tab + 2 * kFlashKeys);        // [kFlashQueries][ghs]
+    float* rws = rhs + kFlashQueries * ghs;            // [kFlashQueries][gws]
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ql = lane & 15, g = lane >> 4;
     const int wbn = p.ws ? (p.W + p.ws - 1) / p.ws : 1, hbn = p.ws ? (p.H + p.ws - 1) / p.ws : 1, nW = hbn * wbn;
@@ -55,29 +48,29 @@ __global__ __launch_bounds__(kRpThreads) void relpos_attention_kernel(RelPosAttn
         const int r = n / gw, c = n - r * gw, y = oy + r, x = ox + c;
         return y < p.H && x < p.W ? y * p.W + x : -1;
     };
-    const int q0 = qt * kRpQueries;
+    const int q0 = qt * kFlashQueries;
 
     // ---- the workgroup's queries -> LDS (unscaled), then rh / rw
     for (int i = 0; i < DH16; ++i) {
-        const int idx = tid + kRpThreads * i, qi = idx / F4, f = idx - qi * F4;
+        const int idx = tid + kFlashThreads * i, qi = idx / F4, f = idx - qi * F4;
         const int row = max(token(min(q0 + qi, N - 1)), 0);        // (a padding query and a query past the end compute values nobody stores)
         float4 v = *reinterpret_cast<const float4*>(img + (size_t)row * ld + min(4 * f, dh - 4));
         if (4 * f >= dh) v = make_float4(0.f, 0.f, 0.f, 0.f);
-        *reinterpret_cast<float4*>(Ks + qi * kRpLd + 4 * f) = v;
+        *reinterpret_cast<float4*>(Ks + qi * kFlashLd + 4 * f) = v;
     }
     __syncthreads();
-    for (int idx = tid; idx < kRpQueries * gh; idx += kRpThreads) {
+    for (int idx = tid; idx < kFlashQueries * gh; idx += kFlashThreads) {
         const int qi = idx / gh, ky = idx - qi * gh, qy = min(q0 + qi, N - 1) / gw;
         const float* r = p.rh + (size_t)qy * dh * gh + ky;
         float a = 0.f;
-        for (int d = 0; d < dh; ++d) a = fmaf(Ks[qi * kRpLd + d], r[(size_t)d * gh], a);
+        for (int d = 0; d < dh; ++d) a = fmaf(Ks[qi * kFlashLd + d], r[(size_t)d * gh], a);
         rhs[qi * ghs + ky] = a;
     }
-    for (int idx = tid; idx < kRpQueries * gw; idx += kRpThreads) {
+    for (int idx = tid; idx < kFlashQueries * gw; idx += kFlashThreads) {
         const int qi = idx / gw, kx = idx - qi * gw, n = min(q0 + qi, N - 1), qx = n - (n / gw) * gw;
         const float* r = p.rw + (size_t)qx * dh * gw + kx;
         float a = 0.f;
-        for (int d = 0; d < dh; ++d) a = fmaf(Ks[qi * kRpLd + d], r[(size_t)d * gw], a);
+        for (int d = 0; d < dh; ++d) a = fmaf(Ks[qi * kFlashLd + d], r[(size_t)d * gw], a);
         rws[qi * gws + kx] = a;
     }
 
@@ -85,17 +78,10 @@ __global__ __launch_bounds__(kRpThreads) void relpos_attention_kernel(RelPosAttn
     const int qn = q0 + wave * 16 + ql;
     const int qrow = token(min(qn, N - 1));
     float4 qf[DH16];
-#pragma clang loop unroll(full)
-    for (int c = 0; c < DH16; ++c) {
-        const int col = 16 * c + 4 * g;
-        float4 v = *reinterpret_cast<const float4*>(img + (size_t)max(qrow, 0) * ld + min(col, dh - 4));
-        if (col >= dh) v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p.scale_pre) { v.x *= p.scale; v.y *= p.scale; v.z *= p.scale; v.w *= p.scale; }
-        qf[c] = v;
-    }
+    flash_load_q<DH16>(qf, img + (size_t)max(qrow, 0) * ld, g, dh, p.scale_pre, p.scale);
     const float post = p.scale_pre ? 1.0f : p.scale;   // (x * 1.0f is exact)
 
-    // ---- staging: waves 0, 1 take K and waves 2, 3 take V; thread slot = tid & 127 takes float4 group (idx % F4) of key (idx / F4), idx = slot + 128 i
+    // ---- staging: waves 0, 1 take K and waves 2, 3 take V; threads 0 .. kFlashKeys - 1 also take the block's key coordinates
     float4 stg[DH16];
     int tst = 0;
     const bool is_v = tid >= 128;
@@ -103,37 +89,27 @@ __global__ __launch_bounds__(kRpThreads) void relpos_attention_kernel(RelPosAttn
     const float* bpad = p.bqkv ? p.bqkv + part + head * dh : nullptr;   // what a padding token is behind the Linear
     float* dst = is_v ? Vs : Ks;
     auto stage_load = [&](int kb) {
-#pragma clang loop unroll(full)
-        for (int i = 0; i < DH16; ++i) {
-            const int idx = slot + 128 * i, kl = idx / F4, f = idx - kl * F4;
-            const int row = token(min(kb * kRpKeys + kl, N - 1));
-            const float* src = row >= 0 ? img + (size_t)row * ld + part : bpad ? bpad : img + part;   // (always a valid address: the load is unconditional)
-            float4 v = *reinterpret_cast<const float4*>(src + min(4 * f, dh - 4));
-            if (4 * f >= dh || (row < 0 && !bpad)) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            stg[i] = v;
-        }
-        if (tid < kRpKeys) {
-            const int n = kb * kRpKeys + tid, r = n / gw;
+        flash_stage_load<DH16>(stg, slot, kb, N, dh, [&](int n, bool& zero) {
+            const int row = token(n);
+            zero = row < 0 && !bpad;
+            return row >= 0 ? img + (size_t)row * ld + part : bpad ? bpad : img + part;
+        });
+        if (tid < kFlashKeys) {
+            const int n = kb * kFlashKeys + tid, r = n / gw;
             tst = n < N ? (r << 8) | (n - r * gw) : (int)0x80000000;
         }
     };
     auto stage_commit = [&](int st) {
-#pragma clang loop unroll(full)
-        for (int i = 0; i < DH16; ++i) {
-            const int idx = slot + 128 * i, kl = idx / F4, f = idx - kl * F4;
-            *reinterpret_cast<float4*>(dst + (st * kRpKeys + kl) * kRpLd + 4 * f) = stg[i];
-        }
-        if (tid < kRpKeys) tab[st * kRpKeys + tid] = tst;
+        flash_stage_commit<DH16>(stg, dst, slot, st);
+        if (tid < kFlashKeys) tab[st * kFlashKeys + tid] = tst;
     };
 
-    f32x4 o[DH16];                                     // lane (ql, g): components 16 dt + 4 g + r of query ql
-#pragma clang loop unroll(full)
-    for (int dt = 0; dt < DH16; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
+    FlashAcc<DH16> acc;
+    acc.init();
     const float* rhq = rhs + (wave * 16 + ql) * ghs;
     const float* rwq = rws + (wave * 16 + ql) * gws;
 
-    const int n_blocks = (N + kRpKeys - 1) / kRpKeys;
+    const int n_blocks = (N + kFlashKeys - 1) / kFlashKeys;
     stage_load(0);
     __syncthreads();                                   // rh / rw are written and the staged queries read: the K buffer may be overwritten
     stage_commit(0);
@@ -142,77 +118,29 @@ __global__ __launch_bounds__(kRpThreads) void relpos_attention_kernel(RelPosAttn
         const int st = kb & 1;
         const bool more = kb + 1 < n_blocks;
         if (more) stage_load(kb + 1);
-        // ---- S^T = K Q^T: two 16-key tiles, two independent accumulators
-        f32x4 s[2];
-        s[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; s[1] = s[0];
+        flash_block<DH16>(Ks, Vs, st, ql, g, qf, acc, [&](const f32x4 (&s)[2], float (&sc)[8]) {   // scale, rel terms, tail mask
 #pragma clang loop unroll(full)
-        for (int c = 0; c < DH16; ++c) {
-            float4 ka[2];
+            for (int t = 0; t < 2; ++t) {
+                const int4 tv = *reinterpret_cast<const int4*>(tab + st * kFlashKeys + 16 * t + 4 * g);
+                const int tk[4] = {tv.x, tv.y, tv.z, tv.w};
 #pragma clang loop unroll(full)
-            for (int t = 0; t < 2; ++t) ka[t] = *reinterpret_cast<const float4*>(Ks + (st * kRpKeys + 16 * t + ql) * kRpLd + 16 * c + 4 * g);
-#pragma clang loop unroll(full)
-            for (int t = 0; t < 2; ++t) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[t].x, qf[c].x, s[t], 0, 0, 0);
-#pragma clang loop unroll(full)
-            for (int t = 0; t < 2; ++t) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[t].y, qf[c].y, s[t], 0, 0, 0);
-#pragma clang loop unroll(full)
-            for (int t = 0; t < 2; ++t) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[t].z, qf[c].z, s[t], 0, 0, 0);
-#pragma clang loop unroll(full)
-            for (int t = 0; t < 2; ++t) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[t].w, qf[c].w, s[t], 0, 0, 0);
-        }
-        // ---- scale, rel terms, tail mask
-        float sc[8];
-#pragma clang loop unroll(full)
-        for (int t = 0; t < 2; ++t) {
-            const int4 tv = *reinterpret_cast<const int4*>(tab + st * kRpKeys + 16 * t + 4 * g);
-            const int tk[4] = {tv.x, tv.y, tv.z, tv.w};
-#pragma clang loop unroll(full)
-            for (int r = 0; r < 4; ++r) {
-                const int ky = (tk[r] >> 8) & 0xff, kx = tk[r] & 0xff;
-                float x = s[t][r] * post;
-                x = x + rhq[ky];
-                x = x + rwq[kx];
-                sc[4 * t + r] = tk[r] < 0 ? -INFINITY : x;
+                for (int r = 0; r < 4; ++r) {
+                    const int ky = (tk[r] >> 8) & 0xff, kx = tk[r] & 0xff;
+                    float x = s[t][r] * post;
+                    x = x + rhq[ky];
+                    x = x + rwq[kx];
+                    sc[4 * t + r] = tk[r] < 0 ? -INFINITY : x;
+                }
             }
-        }
-        // ---- online soft-max (the first block holds key 0, so the maximum is finite from there on)
-        float mx = fmaxf(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3])), fmaxf(fmaxf(sc[4], sc[5]), fmaxf(sc[6], sc[7])));
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = expf(m_run - m_new);       // first block: expf(-inf) = 0
-        m_run = m_new;
-        float ls = 0.f;
-#pragma clang loop unroll(full)
-        for (int j = 0; j < 8; ++j) { sc[j] = expf(sc[j] - m_new); ls += sc[j]; }
-        l_run = l_run * alpha + ls;
-#pragma clang loop unroll(full)
-        for (int dt = 0; dt < DH16; ++dt)
-#pragma clang loop unroll(full)
-            for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-        // ---- O^T += V^T P^T: MFMA (t, r) contracts key 16 t + 4 g + r
-#pragma clang loop unroll(full)
-        for (int t = 0; t < 2; ++t)
-#pragma clang loop unroll(full)
-            for (int r = 0; r < 4; ++r) {
-                const float* vr = Vs + (st * kRpKeys + 16 * t + 4 * g + r) * kRpLd + ql;
-#pragma clang loop unroll(full)
-                for (int dt = 0; dt < DH16; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[16 * dt], sc[4 * t + r], o[dt], 0, 0, 0);
-            }
+        });
         if (more) {
             stage_commit(st ^ 1);                      // (stage st ^ 1 was last read in iteration kb - 1, before that iteration's barrier)
             __syncthreads();
         }
     }
-    // ---- epilogue: the sum over the four lane groups in a fixed order, one float4 store per (query, 16-component tile)
-    float l = l_run;
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    if (qn < N && qrow >= 0) {
-        float* y = p.o + ((size_t)b * p.H * p.W + qrow) * C + head * dh + 4 * g;
-#pragma clang loop unroll(full)
-        for (int dt = 0; dt < DH16; ++dt)
-            if (16 * dt + 4 * g < dh) *reinterpret_cast<float4*>(y + 16 * dt) = make_float4(o[dt][0] / l, o[dt][1] / l, o[dt][2] / l, o[dt][3] / l);
-    }
+    // ---- one float4 store per (query, 16-component tile)
+    const float l = flash_sum(acc);
+    if (qn < N && qrow >= 0) flash_store(acc, l, p.o + ((size_t)b * p.H * p.W + qrow) * C + head * dh + 4 * g, g, dh);
 }
 
 }  // namespace
@@ -222,7 +150,7 @@ bool relpos_attention_supported(int64_t B, int64_t H, int64_t W, int64_t ws, int
     if (ws ? ws > kRpMaxGrid : (H > kRpMaxGrid || W > kRpMaxGrid)) return false;
     const int64_t lim = (int64_t)1 << 31;
     if (B >= lim || H >= lim || W >= lim || heads >= lim || H * W >= lim || B * H * W >= lim) return false;   // (each product of two factors below 2^31)
-    const int64_t N = ws ? ws * ws : H * W, nW = ws ? ((H + ws - 1) / ws) * ((W + ws - 1) / ws) : 1, q_tiles = (N + kRpQueries - 1) / kRpQueries;
+    const int64_t N = ws ? ws * ws : H * W, nW = ws ? ((H + ws - 1) / ws) * ((W + ws - 1) / ws) : 1, q_tiles = (N + kFlashQueries - 1) / kFlashQueries;
     if (B * nW >= lim || B * nW * heads >= lim) return false;
     return B * nW * heads * q_tiles < lim;               // one workgroup per (image, key set, head, query tile)
 }
@@ -231,23 +159,17 @@ void relpos_attention(hipStream_t s, const RelPosAttnP& p) {
     OAR_CHECK(relpos_attention_supported(p.B, p.H, p.W, p.ws, p.nh, p.dh), OAR_UNSUPPORTED_OP, "RelPosAttention: shape outside the kernel's limits");
     OAR_CHECK(p.qkv && p.rh && p.rw && p.o && ((uintptr_t)p.qkv & 15) == 0 && ((uintptr_t)p.o & 15) == 0 && ((uintptr_t)p.bqkv & 15) == 0, OAR_INTERNAL,
               "RelPosAttention: bad or misaligned arguments");
-    const int gh = p.ws ? p.ws : p.H, gw = p.ws ? p.ws : p.W, N = gh * gw, q_tiles = (N + kRpQueries - 1) / kRpQueries;
+    const int gh = p.ws ? p.ws : p.H, gw = p.ws ? p.ws : p.W, N = gh * gw, q_tiles = (N + kFlashQueries - 1) / kFlashQueries;
     const int nW = p.ws ? ((p.H + p.ws - 1) / p.ws) * ((p.W + p.ws - 1) / p.ws) : 1;
     const int64_t grid = (int64_t)p.B * nW * p.nh * q_tiles;
     const size_t lds = relpos_attention_lds_bytes(gh, gw);   // (the kernel carves its five arrays in the order of that sum)
-    const int dh16 = (p.dh + 15) / 16;
-    auto launch = [&](auto kern) {
-        if (lds > 64 * 1024) OAR_MAX_LDS_ONCE(kern, (int)relpos_attention_lds_bytes(kRpMaxGrid, kRpMaxGrid));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kRpThreads), lds, s, p, q_tiles);
-    };
     const double tokens = (double)p.B * p.H * p.W, sets = (double)p.B * nW * p.nh, C = (double)p.nh * p.dh;
     ProfScope ps(s, "relpos_attention", 4.0 * (4.0 * tokens * C + sets * q_tiles * 2.0 * N * p.dh), sets * N * (4.0 * N * p.dh + 2.0 * (gh + gw) * p.dh));
-    switch (dh16) {
-        case 1: launch(relpos_attention_kernel<1>); break;
-        case 2: launch(relpos_attention_kernel<2>); break;
-        case 3: launch(relpos_attention_kernel<3>); break;
-        default: launch(relpos_attention_kernel<4>); break;
-    }
+    flash_dispatch(p.dh, [&](auto n) {
+        auto kern = relpos_attention_kernel<decltype(n)::value>;
+        if (lds > 64 * 1024) OAR_MAX_LDS_ONCE(kern, (int)relpos_attention_lds_bytes(kRpMaxGrid, kRpMaxGrid));
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kFlashThreads), lds, s, p, q_tiles);
+    });
 }
 
 }  // namespace k

@@ -132,7 +132,7 @@ def test_default_bytes_are_those_of_the_parent():
 
 
 # ------------------------------------------------------------------------------------------------ the kernel's resources
-VGPRS = {1: 67, 2: 86, 3: 103, 4: 120}                                                             # per DH16 = ceil(head_dim / 16), as DESIGN 4.35 records them
+VGPRS = {1: 59, 2: 77, 3: 102, 4: 119}                                                             # per DH16 = ceil(head_dim / 16), as DESIGN 4.35 records them
 
 
 def test_relpos_attention_kernel_resources(tmp_path):

@@ -10,7 +10,7 @@ Everything outside the block is common to the arms, so  (op-by-op total) - (fuse
 are paired.  Prints one JSON line per (graph, batch): medians and the min .. max spread over the repetitions, launches per infer of each arm, whether the fused
 arm's range lies entirely below the op-by-op arm's (the rule that decides the knob's default), the largest |difference| of the two arms' outputs, and the
 kernel's achieved TFLOP/s against the 155 TF f32-matrix peak, for information.
-Usage: python tools/mha_attention_bench.py [--batch 1 8] [--reps 30] [--warmup 5] [--graphs mha300 mha400 decoder aifi20 aifi25]"""
+Usage: python tools/mha_attention_bench.py [--batch 1 8] [--reps 30] [--warmup 5] [--graphs mha300 mha400 decoder aifi20 aifi25] [--lib other.so]"""
 import argparse
 import json
 import os
@@ -95,7 +95,10 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graphs", nargs="+", default=["mha300", "mha400", "decoder", "aifi20", "aifi25"])
+    ap.add_argument("--lib", default=None, help="time this build of the library instead of the tree's own")
     a = ap.parse_args()
+    if a.lib:
+        api.LIB_PATH = Path(a.lib).resolve()
     Lv = sum(h * w for h, w in LEVELS)
     core = lambda n, T: 4.0 * n * NH * T * T * (D // NH)                  # the two products of one block, multiply and add counted apart
     for n in a.batch:
