@@ -562,6 +562,28 @@ oar_status oar_k_box_scores(const float* pred, uint32_t height, uint32_t width, 
  * out must hold at least cap bytes. */
 oar_status oar_k_rotate_crop(const uint8_t* rgb, uint32_t w, uint32_t h, const float box[8], uint8_t* out,
                              size_t cap, uint32_t* out_w, uint32_t* out_h);
+/* The flash-attention kernels on caller-chosen layouts (no reference counterpart: the engine's fused attention launches).
+ * o = softmax(scaled q k^T) v per (image, head).  q, k and v are views into ONE buffer of buf_floats floats: q is [n][tq][heads][head_dim]
+ * from float q_off on with a row stride of ldq floats (image i starts at i tq ldq), k and v are [n][tk][heads][head_dim] with ldk / ldv, so
+ * dense, interleaved (one [n, t, 2 D] or [n, t, 3 D] tensor) and padded layouts are all expressible.  scale_pre != 0: q is multiplied by
+ * `scale` in front of the product, otherwise the scores are.  o_io (o_floats floats) is uploaded, the kernel writes [n][tq][heads head_dim]
+ * contiguous floats from float o_off on, and the WHOLE of o_io is downloaded again: what surrounds the output comes back as it went in.
+ * Nothing is launched unless every view lies inside its buffer: OAR_UNSUPPORTED_OP for a shape outside the kernel's limits (head_dim a
+ * multiple of 4 in 4..64); OAR_INVALID_INPUT for a null buffer, an offset or stride that is no multiple of 4 floats, a stride below
+ * heads head_dim, off + (n t - 1) ld + heads head_dim > buf_floats, or o_off + n tq heads head_dim > o_floats. */
+oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off, size_t k_off, size_t v_off, int32_t ldq, int32_t ldk, int32_t ldv,
+                               int32_t n, int32_t tq, int32_t tk, int32_t heads, int32_t head_dim, float scale, int32_t scale_pre,
+                               float* o_io, size_t o_floats, size_t o_off);
+/* The same for the ViT attention with the decomposed relative-position bias: qkv [b h w][3][heads][head_dim] in image order, ws = 0 for
+ * one h x w key grid or the window side (the grid is padded at the bottom / right; a padding token is a key carrying bqkv's k / v rows,
+ * zeros when bqkv is NULL, and gives no output row); with (gh, gw) the key grid, rh is [gh][head_dim][gh] and rw [gw][head_dim][gw]
+ * (query row / column, component, key row / column), bqkv [3][heads][head_dim] or NULL;
+ * score = scaled q . k + q . rh[qy][:][ky] + q . rw[qx][:][kx] with the unscaled q in both bias terms.  o_io / o_floats / o_off as above,
+ * the output being [b h w][heads head_dim].  OAR_UNSUPPORTED_OP: head_dim as above, key grid sides above 64; OAR_INVALID_INPUT: a null
+ * qkv / rh / rw / o_io, o_off no multiple of 4 floats, or an output that does not fit o_floats. */
+oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_t w, int32_t ws, int32_t heads, int32_t head_dim,
+                                  const float* rh, const float* rw, const float* bqkv, float scale, int32_t scale_pre,
+                                  float* o_io, size_t o_floats, size_t o_off);
 
 /* ------------------------------------------------------------------------------------------------ image decode
  * load_image_from_memory (oar-ocr-core/src/utils/image.rs:65-68: image::load_from_memory + DynamicImage::to_rgb8) for the

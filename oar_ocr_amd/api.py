@@ -153,7 +153,7 @@ EXPORTS = [
     "oar_engine_cache_stats", "oar_onnx_inspect", "oar_host_contours", "oar_ctc_dict_create", "oar_ctc_dict_destroy", "oar_ctc_dict_classes",
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
-    "oar_engine_set_decode_stop", "oar_engine_decode_stats",
+    "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention",
 ]
 
 
@@ -231,6 +231,10 @@ def lib():
     L.oar_k_ctc_argmax.argtypes = [vp, C.c_size_t, C.c_size_t, vp, vp]
     L.oar_k_box_scores.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
     L.oar_k_unclip.argtypes = [vp, C.c_uint32, C.c_float, vp, vp, C.c_uint32]
+    L.oar_k_mha_attention.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t]
+    L.oar_k_relpos_attention.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, C.c_int32, vp, C.c_size_t,
+                                         C.c_size_t]
     L.oar_image_decode.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.oar_image_free.argtypes = [C.POINTER(C.c_uint8)]
     L.oar_layout_create.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_void_p)]
@@ -1657,6 +1661,37 @@ def k_ctc_argmax(probs):
     p = np.zeros(rows, np.float32)
     _check(lib().oar_k_ctc_argmax(_p(probs), rows, v, _p(idx), _p(p)))
     return idx, p
+
+
+def k_mha_attention(buf, q_off, k_off, v_off, ldq, ldk, ldv, n, tq, tk, heads, head_dim, scale, scale_pre, o_io, o_off):
+    """mha_attention.hip on views into ONE flat f32 buffer (offsets and row strides in floats).  o_io is uploaded, the kernel writes
+    [n][tq][heads head_dim] floats from o_off on, and all of o_io comes back: -> the new o_io (the argument is left alone)."""
+    buf = np.ascontiguousarray(buf, np.float32).reshape(-1)
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    _check(lib().oar_k_mha_attention(_p(buf), buf.size, q_off, k_off, v_off, ldq, ldk, ldv, n, tq, tk, heads, head_dim, scale, int(bool(scale_pre)),
+                                     _p(out), out.size, o_off))
+    return out
+
+
+def k_relpos_attention(qkv, b, h, w, ws, heads, head_dim, rh, rw, bqkv, scale, scale_pre, o_io, o_off):
+    """relpos_attention.hip: qkv [b h w][3][heads][head_dim], rh [gh][head_dim][gh], rw [gw][head_dim][gw] with (gh, gw) = (ws, ws) or (h, w),
+    bqkv [3 heads head_dim] or None; o_io as in k_mha_attention, the output being [b h w][heads head_dim].  The library cannot see the lengths of
+    qkv and the tables, so they are checked here (ValueError); rh / rw = None reaches the library as a null pointer."""
+    gh, gw = (ws, ws) if ws else (h, w)
+    c = heads * head_dim
+
+    def arr(a, want, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        if a.size != want:
+            raise ValueError(f"k_relpos_attention: {name} has {a.size} floats, the shape needs {want}")
+        return a
+    qkv, rh, rw, bqkv = arr(qkv, b * h * w * 3 * c, "qkv"), arr(rh, gh * head_dim * gh, "rh"), arr(rw, gw * head_dim * gw, "rw"), arr(bqkv, 3 * c, "bqkv")
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    ptr = lambda a: None if a is None else _p(a)
+    _check(lib().oar_k_relpos_attention(ptr(qkv), b, h, w, ws, heads, head_dim, ptr(rh), ptr(rw), ptr(bqkv), scale, int(bool(scale_pre)), _p(out), out.size, o_off))
+    return out
 
 
 def k_box_scores(pred, boxes):

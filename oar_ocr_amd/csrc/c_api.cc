@@ -1207,6 +1207,75 @@ oar_status oar_k_rotate_crop(const uint8_t* rgb, uint32_t w, uint32_t h, const f
     });
 }
 
+// The two flash-attention kernels on caller-chosen layouts.  Every argument is checked before the device is asked for, so a bad call launches nothing (and
+// answers the same with or without a GPU): null pointers, then the kernel's own shape limits, then alignment and that each view lies inside its buffer.
+// off + (rows - 1) ld + width <= total, with rows, ld, width below 2^31 (the *_supported limits): no product or sum can wrap
+static bool view_fits(size_t off, int64_t rows, int64_t ld, int64_t width, size_t total) {
+    const uint64_t need = (uint64_t)(rows - 1) * (uint64_t)ld + (uint64_t)width;
+    return off <= total && need <= total - off;
+}
+
+oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off, size_t k_off, size_t v_off, int32_t ldq, int32_t ldk, int32_t ldv, int32_t n,
+                               int32_t tq, int32_t tk, int32_t heads, int32_t head_dim, float scale, int32_t scale_pre, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(buf && o_io, OAR_INVALID_INPUT, "oar_k_mha_attention: null buffer");
+        OAR_CHECK(k::mha_attention_supported(n, tq, tk, heads, head_dim), OAR_UNSUPPORTED_OP, "oar_k_mha_attention: shape outside the kernel's limits");
+        const int64_t D = (int64_t)heads * head_dim;
+        OAR_CHECK(ldq >= D && ldk >= D && ldv >= D && ((ldq | ldk | ldv) & 3) == 0, OAR_INVALID_INPUT, "oar_k_mha_attention: a row stride is below heads * head_dim or no multiple of 4");
+        OAR_CHECK(((q_off | k_off | v_off | o_off) & 3) == 0, OAR_INVALID_INPUT, "oar_k_mha_attention: an offset is no multiple of 4 floats");
+        OAR_CHECK(view_fits(q_off, (int64_t)n * tq, ldq, D, buf_floats) && view_fits(k_off, (int64_t)n * tk, ldk, D, buf_floats) &&
+                      view_fits(v_off, (int64_t)n * tk, ldv, D, buf_floats),
+                  OAR_INVALID_INPUT, "oar_k_mha_attention: a q / k / v view does not fit buf_floats");
+        OAR_CHECK(view_fits(o_off, (int64_t)n * tq, D, D, o_floats), OAR_INVALID_INPUT, "oar_k_mha_attention: the output does not fit o_floats");
+        require_device();
+        DevBuf din, dout;
+        din.reserve(buf_floats * 4); dout.reserve(o_floats * 4);
+        OAR_HIP(hipMemcpy(din.p, buf, buf_floats * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        k::MhaAttnP p{};
+        p.q = din.as<float>() + q_off; p.k = din.as<float>() + k_off; p.v = din.as<float>() + v_off;
+        p.o = dout.as<float>() + o_off;
+        p.N = n; p.Tq = tq; p.Tk = tk; p.nh = heads; p.dh = head_dim;
+        p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
+        p.scale = scale; p.scale_pre = scale_pre ? 1 : 0;
+        k::mha_attention(nullptr, p);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_t w, int32_t ws, int32_t heads, int32_t head_dim, const float* rh, const float* rw,
+                                  const float* bqkv, float scale, int32_t scale_pre, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(qkv && rh && rw && o_io, OAR_INVALID_INPUT, "oar_k_relpos_attention: null buffer or table");
+        OAR_CHECK(k::relpos_attention_supported(b, h, w, ws, heads, head_dim), OAR_UNSUPPORTED_OP, "oar_k_relpos_attention: shape outside the kernel's limits");
+        const int64_t C = (int64_t)heads * head_dim, tokens = (int64_t)b * h * w;
+        OAR_CHECK((o_off & 3) == 0, OAR_INVALID_INPUT, "oar_k_relpos_attention: o_off is no multiple of 4 floats");
+        OAR_CHECK(view_fits(o_off, tokens, C, C, o_floats), OAR_INVALID_INPUT, "oar_k_relpos_attention: the output does not fit o_floats");
+        require_device();
+        const size_t gh = ws ? ws : h, gw = ws ? ws : w;
+        const size_t n_qkv = (size_t)tokens * 3 * (size_t)C, n_rh = gh * head_dim * gh, n_rw = gw * head_dim * gw;
+        DevBuf dqkv, drh, drw, db, dout;
+        dqkv.reserve(n_qkv * 4); drh.reserve(n_rh * 4); drw.reserve(n_rw * 4); dout.reserve(o_floats * 4);
+        OAR_HIP(hipMemcpy(dqkv.p, qkv, n_qkv * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(drh.p, rh, n_rh * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(drw.p, rw, n_rw * 4, hipMemcpyHostToDevice));
+        if (bqkv) {
+            db.reserve((size_t)3 * C * 4);
+            OAR_HIP(hipMemcpy(db.p, bqkv, (size_t)3 * C * 4, hipMemcpyHostToDevice));
+        }
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        k::RelPosAttnP p{};
+        p.qkv = dqkv.as<float>(); p.rh = drh.as<float>(); p.rw = drw.as<float>(); p.bqkv = bqkv ? db.as<float>() : nullptr;
+        p.o = dout.as<float>() + o_off;
+        p.B = b; p.H = h; p.W = w; p.ws = ws; p.nh = heads; p.dh = head_dim;
+        p.scale = scale; p.scale_pre = scale_pre ? 1 : 0;
+        k::relpos_attention(nullptr, p);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 // ---------------------------------------------------------------------------------------------- host hooks (no GPU)
 int32_t oar_host_candidates(const uint8_t* mask, uint32_t width, uint32_t height, uint32_t max_candidates, int32_t max_bands,
                             float* boxes8, int32_t cap) {
