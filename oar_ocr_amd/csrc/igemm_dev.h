@@ -174,7 +174,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmP& p, f32x4 (&acc)[NT]
     };
     switch (p.act) {
         case ACT_NONE: break;
-        case ACT_RELU: act_all([](float v) { return v > 0.f ? v : 0.f; }); break;
+        case ACT_RELU: act_all([](float v) { return !(v <= 0.f) ? v : 0.f; }); break;   // (NaN stays NaN, as max(0, x) of the ONNX operator does: `v > 0 ? v : 0` made 0 of it)
         case ACT_HSWISH: act_all([](float v) { float t = fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.f), 1.f); return v * t; }); break;
         default: { const int kind = p.act; const float al = p.alpha, be = p.beta; act_all([=](float v) { return apply_act(v, kind, al, be); }); } break;
     }

@@ -8,6 +8,10 @@
 namespace oar {
 namespace k {
 
+// ACT_RELU and NaN: the implicit-GEMM epilogue (igemm_dev.h) and apply_act (kernels_dev.h: element-wise kernel, row-streaming 3x3, large-kernel and direct
+// convolutions) keep a NaN, as max(0, x) of the ONNX operator does -- tests/test_gpu_x6_accuracy.py pins that.  The fused dsblock kernels (dsblock*.inc) and the
+// sample-local chain (chain.hip) apply their own `x > 0 ? x : 0` / fmaxf(x, 0), which make 0 of a NaN: whether a graph's Relu passes a NaN on therefore depends on
+// the kernel the planner picks for its layer.  No result on finite values differs.
 enum ActKind : int { ACT_NONE = 0, ACT_RELU, ACT_HSWISH, ACT_HSIGMOID, ACT_SIGMOID, ACT_SWISH, ACT_LEAKY, ACT_CLIP, ACT_TANH, ACT_GELU_ERF,
                      // element-wise math (decomposed GELU / LayerNorm exports, UVDoc)
                      ACT_ERF, ACT_SQRT, ACT_EXP, ACT_ABS, ACT_NEG, ACT_RECIP, ACT_LOG, ACT_GELU_TANH, ACT_SOFTPLUS, ACT_FLOOR, ACT_CEIL, ACT_ROUND, ACT_NOT };

@@ -35,7 +35,7 @@ __device__ __forceinline__ float erf_rational(float x) {
 __device__ __forceinline__ float apply_act(float v, int kind, float alpha, float beta) {
     switch (kind) {
         case ACT_NONE: return v;
-        case ACT_RELU: return v > 0.f ? v : 0.f;
+        case ACT_RELU: return !(v <= 0.f) ? v : 0.f;   // (NaN stays NaN; every other value as `v > 0 ? v : 0`, -0 included)
         case ACT_HSWISH: {
             float t = fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.f), 1.f);
             return v * t;
