@@ -574,6 +574,14 @@ oar_status oar_k_rotate_crop(const uint8_t* rgb, uint32_t w, uint32_t h, const f
 oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off, size_t k_off, size_t v_off, int32_t ldq, int32_t ldk, int32_t ldv,
                                int32_t n, int32_t tq, int32_t tk, int32_t heads, int32_t head_dim, float scale, int32_t scale_pre,
                                float* o_io, size_t o_floats, size_t o_off);
+/* Residual add + LayerNorm over the last axis as the engine's one launch (add_layernorm.hip): s = a + b in f32, y = LN(s) gamma + beta.
+ * a is [rows][C]; row r of b is b[(r % b_rows) C ...] with b_rows dividing rows (b_rows = rows: the same shape; = T: a [1, T, C] table; = 1: a [C]
+ * vector); gamma and beta are [C] or NULL.  o_io / o_floats as above: uploaded whole, y written as [rows][C] from float y_off on and, when
+ * write_sum != 0, s from float s_off on (nothing is written there otherwise), and the WHOLE of o_io downloaded again.  Offsets need not be multiples
+ * of 4 floats: such a call takes the kernel's 4-byte form.  Nothing is launched unless every view fits: OAR_INVALID_INPUT for a null a, b or
+ * o_io, rows, C or b_rows <= 0, b_rows not dividing rows, eps <= 0, or outputs that do not fit o_floats or overlap each other. */
+oar_status oar_k_add_layernorm(const float* a, const float* b, int64_t b_rows, const float* gamma, const float* beta, int64_t rows, int32_t C, float eps,
+                               int32_t write_sum, float* o_io, size_t o_floats, size_t y_off, size_t s_off);
 /* The same for the ViT attention with the decomposed relative-position bias: qkv [b h w][3][heads][head_dim] in image order, ws = 0 for
  * one h x w key grid or the window side (the grid is padded at the bottom / right; a padding token is a key carrying bqkv's k / v rows,
  * zeros when bqkv is NULL, and gives no output row); with (gh, gw) the key grid, rh is [gh][head_dim][gh] and rw [gw][head_dim][gw]

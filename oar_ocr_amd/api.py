@@ -153,7 +153,7 @@ EXPORTS = [
     "oar_engine_cache_stats", "oar_onnx_inspect", "oar_host_contours", "oar_ctc_dict_create", "oar_ctc_dict_destroy", "oar_ctc_dict_classes",
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
-    "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention",
+    "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm",
 ]
 
 
@@ -235,6 +235,7 @@ def lib():
                                       C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_relpos_attention.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, C.c_int32, vp, C.c_size_t,
                                          C.c_size_t]
+    L.oar_k_add_layernorm.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t, C.c_size_t]
     L.oar_image_decode.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.oar_image_free.argtypes = [C.POINTER(C.c_uint8)]
     L.oar_layout_create.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_void_p)]
@@ -1670,6 +1671,27 @@ def k_mha_attention(buf, q_off, k_off, v_off, ldq, ldk, ldv, n, tq, tk, heads, h
     out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
     _check(lib().oar_k_mha_attention(_p(buf), buf.size, q_off, k_off, v_off, ldq, ldk, ldv, n, tq, tk, heads, head_dim, scale, int(bool(scale_pre)),
                                      _p(out), out.size, o_off))
+    return out
+
+
+def k_add_layernorm(a, b, gamma, beta, eps, write_sum, o_io, y_off, s_off=0, b_rows=None):
+    """add_layernorm.hip: a [rows, C] and b [b_rows, C] (b_rows divides rows; taken from b's size unless given), gamma / beta [C] or None.
+    o_io as in k_mha_attention: y is written as [rows][C] from y_off on, the f32 sum a + b from s_off on when write_sum is set, and all of
+    o_io comes back.  a = None or b = None reaches the library as a null pointer."""
+    C_ = 0 if a is None else int(np.shape(a)[-1])
+    arr = lambda x: None if x is None else np.ascontiguousarray(x, np.float32).reshape(-1)
+    a, b, gamma, beta = arr(a), arr(b), arr(gamma), arr(beta)
+    rows = 0 if a is None or C_ == 0 else a.size // C_
+    if b_rows is None:
+        b_rows = 0 if b is None or C_ == 0 else b.size // C_
+    for v, name in ((gamma, "gamma"), (beta, "beta")):
+        if v is not None and v.size != C_:
+            raise ValueError(f"k_add_layernorm: {name} has {v.size} floats, the rows have {C_}")
+    if b is not None and b_rows > 0 and b.size < b_rows * C_:
+        raise ValueError(f"k_add_layernorm: b has {b.size} floats, b_rows = {b_rows} needs {b_rows * C_}")
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    ptr = lambda x: None if x is None else _p(x)
+    _check(lib().oar_k_add_layernorm(ptr(a), ptr(b), b_rows, ptr(gamma), ptr(beta), rows, C_, eps, int(bool(write_sum)), _p(out), out.size, y_off, s_off))
     return out
 
 

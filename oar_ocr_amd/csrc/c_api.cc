@@ -1244,6 +1244,36 @@ oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off
     });
 }
 
+// Residual add + LayerNorm (add_layernorm.hip) on host arrays: a [rows][C], b [b_rows][C], gamma / beta [C] or NULL.  The same order of checks: arguments first,
+// the device afterwards.  Offsets need no alignment: an output that does not start on 16 bytes makes the kernel take its 4-byte form.
+oar_status oar_k_add_layernorm(const float* a, const float* b, int64_t b_rows, const float* gamma, const float* beta, int64_t rows, int32_t C, float eps,
+                               int32_t write_sum, float* o_io, size_t o_floats, size_t y_off, size_t s_off) {
+    return guard([&] {
+        OAR_CHECK(a && b && o_io, OAR_INVALID_INPUT, "oar_k_add_layernorm: null a, b or o_io");
+        OAR_CHECK(rows > 0 && C > 0 && b_rows > 0, OAR_INVALID_INPUT, "oar_k_add_layernorm: rows, C and b_rows must be positive");
+        OAR_CHECK(rows < (1ll << 31) && rows % b_rows == 0, OAR_INVALID_INPUT, "oar_k_add_layernorm: b_rows must divide rows (below 2^31)");
+        OAR_CHECK(eps > 0.0f, OAR_INVALID_INPUT, "oar_k_add_layernorm: eps must be positive");   // (false for a NaN too)
+        OAR_CHECK(view_fits(y_off, rows, C, C, o_floats), OAR_INVALID_INPUT, "oar_k_add_layernorm: y does not fit o_floats");
+        const size_t cnt = (size_t)rows * (size_t)C;
+        if (write_sum) {
+            OAR_CHECK(view_fits(s_off, rows, C, C, o_floats), OAR_INVALID_INPUT, "oar_k_add_layernorm: the sum does not fit o_floats");
+            OAR_CHECK(y_off + cnt <= s_off || s_off + cnt <= y_off, OAR_INVALID_INPUT, "oar_k_add_layernorm: y and the sum overlap");
+        }
+        require_device();
+        DevBuf da, db, dg, dbe, dout;
+        da.reserve(cnt * 4); db.reserve((size_t)b_rows * C * 4); dout.reserve(o_floats * 4);
+        OAR_HIP(hipMemcpy(da.p, a, cnt * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(db.p, b, (size_t)b_rows * C * 4, hipMemcpyHostToDevice));
+        if (gamma) { dg.reserve((size_t)C * 4); OAR_HIP(hipMemcpy(dg.p, gamma, (size_t)C * 4, hipMemcpyHostToDevice)); }
+        if (beta) { dbe.reserve((size_t)C * 4); OAR_HIP(hipMemcpy(dbe.p, beta, (size_t)C * 4, hipMemcpyHostToDevice)); }
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        k::add_layernorm(nullptr, da.as<float>(), db.as<float>(), b_rows, gamma ? dg.as<float>() : nullptr, beta ? dbe.as<float>() : nullptr,
+                         write_sum ? dout.as<float>() + s_off : nullptr, dout.as<float>() + y_off, rows, C, eps);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_t w, int32_t ws, int32_t heads, int32_t head_dim, const float* rh, const float* rw,
                                   const float* bqkv, float scale, int32_t scale_pre, float* o_io, size_t o_floats, size_t o_off) {
     return guard([&] {

@@ -976,6 +976,140 @@ void Engine::rewrite_graph(OnnxModel& m) {
         nodes.swap(keep);
     }
 
+    // ---- pass 2c: LayerNorm over the last axis as exporters below opset 17 spell it:
+    //   m = ReduceMean(x, [a], keepdims 1);  d = Sub(x, m);  v = ReduceMean(Pow(d, 2) | Mul(d, d), [a], keepdims 1);  r = Sqrt(Add(v, eps))
+    //   y = Div(d, r)  |  Mul(d, Reciprocal(r))  |  Mul(d, Div(1, r))        [-> Mul(y, gamma [C]) [-> Add(., beta [C])]]
+    // becomes ONE LayerNormalization node (nine launches that pass the tensor through HBM about seven times -> one), so that an opset-13 and an opset-17 export
+    // of the same block meet the same later passes.  Axes as an attribute or a constant input; Add and the Muls in either order; eps a positive f32 constant of
+    // one element; gamma / beta f32 initializers of [C] or [1, .., 1, C], each folded only when the value in front of it has that single reader.  m, v, the
+    // squares, the Add and the Sqrt must have one reader each, d exactly the square and the quotient, none a graph output.  a = -1 or a >= 0: the rank of x
+    // is unknown here, so the replaced nodes are kept (ln_spelled_) and op_layernorm plans them instead when a turns out not to be the last axis (or x has
+    // rank 1, or gamma / beta do not have x's last extent).  Anything else stays as it is.  OAR_FUSE_LAYERNORM=0 keeps the op-by-op route.
+    {
+        const char* fe = getenv("OAR_FUSE_LAYERNORM");
+        const bool fuse = !fe || atoi(fe) != 0;
+        auto cons = consumers(nodes);
+        std::map<std::string, int> producer;
+        for (int i = 0; i < (int)nodes.size(); ++i) for (auto& o : nodes[i].out) producer[o] = i;
+        std::vector<bool> dead(nodes.size(), false);
+        auto single_use = [&](const std::string& v) { return cons[v].size() == 1 && !graph_outs.count(v); };
+        auto reader = [&](const std::string& v, const char* op) -> int {   // the only reader of v, a live two-input `op` (or -1)
+            if (!single_use(v)) return -1;
+            const int c = cons[v][0];
+            return !dead[c] && nodes[c].op == op ? c : -1;
+        };
+        auto scalar_is = [&](const std::string& v, float want) {
+            auto it = inits_.find(v);
+            if (it == inits_.end()) return false;
+            const HostTensor& t = it->second;
+            return t.dtype == DType::F32 ? (t.f.size() == 1 && t.f[0] == want) : (t.i.size() == 1 && (float)t.i[0] == want);
+        };
+        auto mean_axis = [&](const GNode& q, int64_t& ax) {   // ReduceMean over ONE axis, keepdims 1
+            if (q.op != "ReduceMean" || q.in.empty() || q.ai("keepdims", 1) != 1) return false;
+            std::vector<int64_t> a;
+            if (q.in.size() > 1 && !q.in[1].empty()) {
+                auto it = inits_.find(q.in[1]);
+                if (it == inits_.end() || it->second.dtype == DType::F32) return false;
+                a = it->second.i;
+            } else {
+                a = q.ais("axes");
+            }
+            if (a.size() != 1 || a[0] < -1) return false;
+            ax = a[0];
+            return true;
+        };
+        auto affine_vec = [&](const std::string& v) -> int64_t {   // elements of an f32 initializer shaped [C] or [1, .., 1, C]; 0: not one
+            auto it = inits_.find(v);
+            if (it == inits_.end() || it->second.dtype != DType::F32 || it->second.dims.empty()) return 0;
+            const int64_t c = it->second.dims.back();
+            return c > 0 && numel(it->second.dims) == c && (int64_t)it->second.f.size() == c ? c : 0;
+        };
+        for (int i = 0; fuse && i < (int)nodes.size(); ++i) {
+            const GNode& sub = nodes[i];
+            if (sub.op != "Sub" || dead[i] || sub.in.size() != 2) continue;
+            const std::string x = sub.in[0], m = sub.in[1], d = sub.out[0];
+            auto mp = producer.find(m);
+            if (mp == producer.end() || dead[mp->second] || !single_use(m)) continue;
+            const int rm1 = mp->second;
+            int64_t ax1 = 0, ax2 = 0;
+            if (!mean_axis(nodes[rm1], ax1) || nodes[rm1].in[0] != x) continue;
+            // d: read by the square and by the quotient, by nothing else
+            if (graph_outs.count(d)) continue;
+            std::set<int> dr(cons[d].begin(), cons[d].end());
+            if (dr.size() != 2) continue;
+            int sq = -1, fin = -1;
+            for (int c : dr) {
+                const GNode& q = nodes[c];
+                if (dead[c] || q.in.size() != 2) continue;
+                if ((q.op == "Pow" && q.in[0] == d && scalar_is(q.in[1], 2.0f)) || (q.op == "Mul" && q.in[0] == d && q.in[1] == d)) sq = c;
+            }
+            if (sq < 0) continue;
+            for (int c : dr) if (c != sq) fin = c;
+            if ((int)cons[d].size() != (nodes[sq].op == "Mul" ? 3 : 2) || dead[fin]) continue;
+            const int rm2 = reader(nodes[sq].out[0], "ReduceMean");
+            if (rm2 < 0 || !mean_axis(nodes[rm2], ax2)) continue;
+            // the same axis: written the same way, or -1 on one ReduceMean and a number k >= 0 on the other -- then k is kept, and op_layernorm, which knows the
+            // rank, takes the node only where k is the last axis (which is what -1 says)
+            if (ax2 != ax1) {
+                if (std::min(ax1, ax2) != -1 || std::max(ax1, ax2) < 0) continue;
+                ax1 = std::max(ax1, ax2);
+            }
+            const std::string& v = nodes[rm2].out[0];
+            const int add = reader(v, "Add");
+            if (add < 0 || nodes[add].in.size() != 2) continue;
+            const std::string& epsn = nodes[add].in[0] == v ? nodes[add].in[1] : nodes[add].in[0];
+            auto ei = inits_.find(epsn);
+            if (ei == inits_.end() || ei->second.dtype != DType::F32 || ei->second.f.size() != 1 || ei->second.dims.size() > 1 || !(ei->second.f[0] > 0.0f)) continue;
+            const float eps = ei->second.f[0];
+            const int sqr = reader(nodes[add].out[0], "Sqrt");
+            if (sqr < 0) continue;
+            const std::string& r = nodes[sqr].out[0];
+            if (!single_use(r) || dead[cons[r][0]]) continue;
+            int inv = -1;   // Reciprocal(r) or Div(1, r) between the root and the product
+            const GNode& f = nodes[fin];
+            if (f.in.size() != 2) continue;
+            if (cons[r][0] == fin) {
+                if (!(f.op == "Div" && f.in[0] == d && f.in[1] == r)) continue;
+            } else {
+                inv = cons[r][0];
+                const GNode& q = nodes[inv];
+                const bool recip = (q.op == "Reciprocal" && q.in.size() == 1) || (q.op == "Div" && q.in.size() == 2 && q.in[1] == r && scalar_is(q.in[0], 1.0f));
+                if (!recip || !single_use(q.out[0]) || cons[q.out[0]][0] != fin || f.op != "Mul") continue;
+                if (!((f.in[0] == d && f.in[1] == q.out[0]) || (f.in[1] == d && f.in[0] == q.out[0]))) continue;
+            }
+            std::vector<int> parts = {rm1, i, sq, rm2, add, sqr, fin};
+            if (inv >= 0) parts.push_back(inv);
+            int last = fin;
+            std::string gamma, beta;
+            int64_t cg = 0;
+            if (const int mu = reader(nodes[last].out[0], "Mul"); mu >= 0 && nodes[mu].in.size() == 2) {
+                const std::string& o = nodes[mu].in[0] == nodes[last].out[0] ? nodes[mu].in[1] : nodes[mu].in[0];
+                if ((cg = affine_vec(o)) > 0) { gamma = o; parts.push_back(mu); last = mu; }
+            }
+            if (const int ad = reader(nodes[last].out[0], "Add"); ad >= 0 && nodes[ad].in.size() == 2) {
+                const std::string& o = nodes[ad].in[0] == nodes[last].out[0] ? nodes[ad].in[1] : nodes[ad].in[0];
+                const int64_t cb = affine_vec(o);
+                if (cb > 0 && (gamma.empty() || cb == cg)) { beta = o; parts.push_back(ad); last = ad; }
+            }
+            std::sort(parts.begin(), parts.end());
+            GNode ln;
+            ln.op = "LayerNormalization";
+            ln.in = {x};
+            if (!gamma.empty() || !beta.empty()) ln.in.push_back(gamma);
+            if (!beta.empty()) ln.in.push_back(beta);
+            ln.out = {nodes[last].out[0]};
+            { Attr a; a.kind = Attr::I; a.i = ax1; ln.attrs["axis"] = a; }
+            { Attr a; a.kind = Attr::F; a.f = eps; ln.attrs["epsilon"] = a; }
+            std::vector<GNode>& spelled = ln_spelled_[ln.out[0]];
+            for (int p : parts) { spelled.push_back(nodes[p]); dead[p] = true; }
+            dead[last] = false;
+            nodes[last] = std::move(ln);   // the last node of the pattern: x is computed in front of it and every reader comes after it
+        }
+        std::vector<GNode> keep;
+        for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
+        nodes.swap(keep);
+    }
+
     // ---- pass 3: fuse activations into Conv / ConvTranspose / Linear / Gemm / Add
     {
         bool changed = true;
@@ -2022,6 +2156,26 @@ void Engine::rewrite_graph(OnnxModel& m) {
         for (int i = 0; i < (int)nodes.size(); ++i) if (!dead[i]) keep.push_back(std::move(nodes[i]));
         nodes.swap(keep);
     }
+    // ---- pass 10: residual Add -> LayerNormalization.  Behind every pass above: an Add that pass 4 folded into its Linear is that Linear's
+    // residual by now (one folded into a Conv stays there), one that pass 3 gave an activation is not plain.  Layouts, shapes and whether the sample-local chain takes the LayerNorm are known at plan time only, so this pass
+    // just marks the pair: a LayerNormalization directly behind the plain Add it reads (where every exporter puts it), its scale and bias initializers or absent;
+    // Planner::fuse_chains then replaces the two launches by ONE k::add_layernorm where the pair qualifies.  OAR_FUSE_ADD_LAYERNORM=0 keeps both.
+    {
+        const char* fe = getenv("OAR_FUSE_ADD_LAYERNORM");
+        fuse_add_ln_ = !fe || atoi(fe) != 0;
+        for (int j = 1; fuse_add_ln_ && j < (int)nodes.size(); ++j) {
+            GNode& ln = nodes[j];
+            const GNode& ad = nodes[j - 1];
+            if (ln.op != "LayerNormalization" || ln.in.empty() || ad.out.empty() || ad.out[0] != ln.in[0]) continue;
+            // the Add itself, or the Linear that pass 4 folded it into (Linear(x) + residual, no activation: op_linear hands the residual back where that pays)
+            const bool add = ad.op == "Add" && ad.in.size() == 2 && ad.residual.empty(), lin = ad.op == "Linear" && !ad.residual.empty();
+            if ((!add && !lin) || ad.act.kind != k::ACT_NONE) continue;
+            bool consts = true;
+            for (size_t q = 1; q < ln.in.size(); ++q) consts = consts && (ln.in[q].empty() || is_init(ln.in[q]));
+            if (!consts) continue;
+            Attr a; a.kind = Attr::I; a.i = 1; ln.attrs["after_add"] = a;
+        }
+    }
     for (int i = 0; i < (int)nodes.size(); ++i) nodes[i].id = i;
     nodes_ = std::move(nodes);
 }
@@ -2416,14 +2570,37 @@ struct Planner {
         return peak;
     }
     void fuse_chains() {
-        if (!chain_on || chain_recs.empty()) return;
+        if ((!chain_on || chain_recs.empty()) && add_ln_at.empty()) return;
         const int ns = (int)P.steps.size();
         std::vector<std::function<void(const RunCtx&)>> out;
         int fused_away = 0;
         int a = 0;
         std::vector<std::string> out_ops;
         const bool names = P.step_ops.size() == P.steps.size();
-        auto keep = [&](int i) { out.push_back(std::move(P.steps[(size_t)i])); if (names) out_ops.push_back(P.step_ops[(size_t)i]); };
+        // Add + LayerNorm: a step that stays a launch of its own goes through keep().  A LayerNorm that does (no chain took it) and whose marked Add was
+        // kept right in front of it becomes ONE add_layernorm launch in the Add's place (same operands, same arithmetic: bit-identical to the pair).  Where the
+        // step in front is a Linear that carries the residual (op_linear), the pair stays two launches: the Linear alone, then add_layernorm
+        int last_kept = -2;
+        auto keep = [&](int i) {
+            auto al = add_ln_at.find(i);
+            if (al != add_ln_at.end() && last_kept == i - 1 && !out.empty() && al->second.lin) {
+                // behind a Linear that carries the residual: the Linear writes its product alone, and add_layernorm takes the LayerNorm's place
+                out.back() = std::move(al->second.lin);
+                out.push_back(std::move(al->second.run)); if (names) out_ops.push_back(al->second.label);
+                last_kept = i;
+                return;
+            }
+            if (al != add_ln_at.end() && last_kept == i - 1 && !out.empty()) {
+                out.back() = std::move(al->second.run);
+                if (names) out_ops.back() = al->second.label;
+                P.bytes -= al->second.bytes_saved;
+                ++fused_away;
+                last_kept = i;
+                return;
+            }
+            out.push_back(std::move(P.steps[(size_t)i])); if (names) out_ops.push_back(P.step_ops[(size_t)i]);
+            last_kept = i;
+        };
         while (a < ns) {
             if (step_chain[(size_t)a] < 0) { keep(a++); continue; }
             int b = a;
@@ -3472,6 +3649,7 @@ struct Planner {
         }
         TInfo a = get(n.in[0]), b = get(n.in[1]);
         const bool ints_in = (a.host_int ? !a.host_f : a.is_int) && (b.host_int ? !b.host_f : b.is_int);
+        const bool f32_native = !a.host_int && !b.host_int && !a.is_int && !b.is_int && a.layout == Layout::NATIVE && b.layout == Layout::NATIVE;
         // a plan-time value meeting a device tensor (e.g. a scale computed from Shape): materialise it as an f32 constant
         if (a.host_int) { a.loc = host_to_device(n.in[0], a); a.host_int = false; a.layout = Layout::NATIVE; }
         if (b.host_int) { b.loc = host_to_device(n.in[1], b); b.host_int = false; b.layout = Layout::NATIVE; }
@@ -3520,7 +3698,32 @@ struct Planner {
         Act post = n.act;
         int64_t cnt = numel(od);
         step([=](const RunCtx& c) { k::binary(c.s, c.at(al), c.at(bl), c.mut(yl), op, r, pod.data(), sa.data(), sb.data(), post); }, (double)cnt, 12.0 * cnt);
+        // a plain Add of two f32 device tensors in NATIVE layout, the second one the same shape or [1, .., 1, d_k, .., C] (its rows repeat with period b_rows):
+        // what k::add_layernorm can take over when a marked LayerNormalization is the next step (op_layernorm, fuse_chains)
+        last_add = AddRec();
+        if (op == 0 && E.fuse_add_ln_ && post.kind == k::ACT_NONE && f32_native && !clast && r >= 1 && od[(size_t)r - 1] > 0) {
+            const bool swapped = numel(ad) < numel(bd);
+            const std::vector<int64_t>& full = swapped ? bd : ad;
+            const std::vector<int64_t>& part = swapped ? ad : bd;
+            int lead = 0;
+            while (lead < r - 1 && part[(size_t)lead] == 1) ++lead;
+            bool ok = full == od;
+            for (int i = lead; i < r; ++i) ok = ok && part[(size_t)i] == od[(size_t)i];
+            // (an operand that starts off a 16-byte boundary -- a view into a larger tensor -- would put the fused launch on its one-wave form where the pair's
+            // LayerNorm, reading the aligned sum, takes the half-wave form: within tolerance of each other but not the same bits.  Such a pair stays a pair.)
+            if (ok && loc_on_16(al) && loc_on_16(bl)) {
+                last_add.node = cur; last_add.step = (int)P.steps.size() - 1; last_add.out = n.out[0]; last_add.a = al; last_add.b = bl; last_add.sum = yl;
+                last_add.C = od[(size_t)r - 1]; last_add.rows = cnt / last_add.C; last_add.b_rows = numel(part) / last_add.C;
+            }
+        }
     }
+    // the newest plain Add (see op_binary) and the Add + LayerNormalization pairs that fuse_chains turns into one launch
+    // provably on a 16-byte boundary at run time: the arena and the graph inputs are device allocations, so the byte offset decides
+    static bool loc_on_16(const Loc& l) { return l.kind == Loc::CONST ? (reinterpret_cast<uintptr_t>(l.cptr) & 15) == 0 : l.kind != Loc::NONE && (l.off & 15) == 0; }
+    struct AddRec { int node = -2, step = -1; std::string out; Loc a, b, sum; int64_t rows = 0, C = 0, b_rows = 0; std::function<void(const RunCtx&)> lin; };
+    AddRec last_add;
+    struct AddLnRec { std::function<void(const RunCtx&)> run, lin; double bytes_saved = 0; std::string label; };   // lin: the step in front is a Linear; this is it without its residual
+    std::map<int, AddLnRec> add_ln_at;   // by the step index of the LayerNorm; its Add is the step in front of it
 
     // ReduceMean / ReduceSum / ReduceMax / ReduceMin / ReduceProd over the trailing axes (decomposed LayerNorm / softmax
     // exports), or ReduceMean over the spatial axes of an NCHW tensor (= GlobalAveragePool).  mode: k::reduce_lastdim's.
@@ -4728,6 +4931,14 @@ struct Planner {
         Loc yl = y.loc;
         Act act = n.act;
         double flops = 2.0 * M * N * K, bytes = 4.0 * (M * K + M * N * (has_res ? 2 : 1) + K * N);
+        // A residual that rewrite pass 4 folded into this Linear, with a marked LayerNormalization as the next node (pass 10): where nobody else reads the sum,
+        // the Linear can write its product alone and k::add_layernorm add the residual in registers -- the same two launches and the same bytes as the epilogue
+        // route, and the sum never reaches HBM.  A sum that is read again stays in the epilogue, which has to store it anyway.  fuse_chains decides (a chain
+        // that takes either step keeps both as they are); last_add.lin is this Linear without its residual.
+        last_add = AddRec();
+        const bool give_back = has_res && E.fuse_add_ln_ && act.kind == k::ACT_NONE && N > 0 && yl.kind == Loc::ARENA && cur + 1 < (int)E.nodes_.size() &&
+                               E.nodes_[(size_t)cur + 1].op == "LayerNormalization" && E.nodes_[(size_t)cur + 1].ai("after_add", 0) != 0 &&
+                               E.nodes_[(size_t)cur + 1].in[0] == n.out[0] && read_after(n.out[0]) <= cur + 1 && loc_on_16(yl) && loc_on_16(res);
         if (K % 4 == 0 && alpha == 1.0f) {
             // (a CTC head with a short K runs on the output-stationary bf16x6 kernel, ctc_head_x6.hip: bf16x6 fragments whatever igemm_weight_format says)
             const bool ctc_head = P.logits_valid > 0 && od.back() == Np && n.act.kind == k::ACT_NONE && !has_res && k::ctc_head_x6_supported((long)M, (int)K, (int)Np) &&
@@ -4766,11 +4977,18 @@ struct Planner {
             } else {
                 step(run, flops, bytes);
             }
+            if (give_back) last_add.lin = [=](const RunCtx& c) { k::ConvP q = p; q.x = c.at(ain); q.y = c.mut(yl); q.residual = nullptr; k::conv_igemm(c.s, q); };
         } else {
             const float* w = bt.loc.cptr;
             k::GemmP g{};
             g.batch = 1; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.transB = transB; g.alpha = alpha; g.B = w; g.bias = bias; g.act = act;
             step([=](const RunCtx& c) { k::GemmP q = g; q.A = c.at(ain); q.C = c.mut(yl); q.residual = has_res ? c.at(res) : nullptr; k::gemm_batched(c.s, q); }, flops, bytes);
+            if (give_back) last_add.lin = [=](const RunCtx& c) { k::GemmP q = g; q.A = c.at(ain); q.C = c.mut(yl); q.residual = nullptr; k::gemm_batched(c.s, q); };
+        }
+        // (the Linear is this node's last step: op_layernorm asks for exactly that)
+        if (give_back) {
+            last_add.node = cur; last_add.step = (int)P.steps.size() - 1; last_add.out = n.out[0]; last_add.a = yl; last_add.b = res; last_add.sum = yl;
+            last_add.C = N; last_add.rows = M; last_add.b_rows = M;
         }
     }
 
@@ -4974,6 +5192,20 @@ struct Planner {
         int r = (int)x.dims.size();
         int64_t axis = n.ai("axis", -1);
         if (axis < 0) axis += r;
+        // a LayerNormalization that rewrite pass 2c put together without knowing x's rank: where it turns out not to be one over the last axis of a rank >= 2
+        // tensor with [C] scale and bias, the exporter's own nodes are planned instead (their intermediates are per-node temporaries of this node)
+        if (auto sp = E.ln_spelled_.find(n.out[0]); sp != E.ln_spelled_.end()) {
+            bool fits = r >= 2 && axis == r - 1;
+            // (scale / bias of another extent broadcast differently, and a [1, .., 1, C] one of a higher rank than x gives the exporter's result that rank)
+            for (size_t q = 1; fits && q < 3; ++q) fits = !has_input(n, q) || (numel(get(n.in[q]).dims) == x.dims.back() && (int)get(n.in[q]).dims.size() <= r);
+            // The kept nodes run inside this node: their intermediates are allocations of node `cur` like any node's temporaries, none is read after it (pass 2c
+            // took the pattern only where every intermediate had its readers inside it and none was a graph output), and only the last one writes n.out[0].
+            // Passes 3 and later never saw them, so they are planned exactly as the exporter wrote them.
+            if (!fits) {
+                for (const GNode& g : sp->second) dispatch(g);
+                return;
+            }
+        }
         OAR_CHECK(axis == r - 1, OAR_UNSUPPORTED_OP, "LayerNormalization: only the last axis is supported");
         Loc xin = to_native_loc(x);
         const float* g = has_input(n, 1) ? get(n.in[1]).loc.cptr : nullptr;
@@ -4983,6 +5215,19 @@ struct Planner {
         TInfo& y = new_out(n.out[0], x.dims, Layout::NATIVE);
         Loc yl = y.loc;
         auto run = [=](const RunCtx& c) { k::layernorm(c.s, c.at(xin), g, b, c.mut(yl), rows, (int)C, eps); };
+        // the residual Add in front of it (rewrite pass 10): both steps are planned as they are, and fuse_chains replaces them by one launch unless
+        // the sample-local chain takes this LayerNorm.  The sum is stored only when somebody reads it after this node (or it is a graph output).
+        if (n.ai("after_add", 0) != 0 && last_add.node == cur - 1 && last_add.step == (int)P.steps.size() - 1 && last_add.out == n.in[0] && last_add.rows == rows && last_add.C == C &&
+            xin.kind == Loc::ARENA && xin.off == last_add.sum.off && C > 0 && C < (1ll << 31)) {
+            const AddRec ad = last_add;
+            const bool keep_sum = read_after(n.in[0]) > cur;
+            AddLnRec rec;
+            rec.run = [=](const RunCtx& c) { k::add_layernorm(c.s, c.at(ad.a), c.at(ad.b), ad.b_rows, g, b, keep_sum ? c.mut(ad.sum) : nullptr, c.mut(yl), rows, (int)C, eps); };
+            rec.bytes_saved = ad.lin ? 0.0 : 4.0 * rows * C * (keep_sum ? 1.0 : 3.0);   // behind a Linear the residual's read only moves from one launch to the other
+            rec.lin = ad.lin;
+            rec.label = "AddLayerNormalization -> " + n.out[0];
+            add_ln_at[(int)P.steps.size()] = std::move(rec);
+        }
         if (chain_loc_ok(xin) && C > 0) {
             ChainRec r;
             r.d.type = k::CH_LN; r.d.N = (int)C; r.d.in_ld = (int)C; r.d.out_ld = (int)C; r.d.eps = eps; r.dev_gamma = g; r.dev_bias = b;
@@ -5055,6 +5300,13 @@ struct Planner {
                 concat_consumer[n.out[0]] = u->second.second;
                 for (auto& sname : n.in) { int& l = lu[sname]; l = std::max(l, u->second.second); }   // the sources live until the convolution that reads them
             }
+        }
+        // an Add whose LayerNormalization may take it over (rewrite pass 10): the fused launch reads the Add's operands while it writes the LayerNorm's output,
+        // so they stay allocated through the LayerNormalization node -- its output can never be placed in their bytes
+        for (int i = 1; i < (int)E.nodes_.size(); ++i) {
+            if (E.nodes_[i].op != "LayerNormalization" || E.nodes_[i].ai("after_add", 0) == 0) continue;
+            if (E.nodes_[i - 1].residual.empty()) for (auto& s : E.nodes_[i - 1].in) if (!s.empty()) { int& l = lu[s]; l = std::max(l, i); }
+            if (!E.nodes_[i - 1].residual.empty()) { int& l = lu[E.nodes_[i - 1].residual]; l = std::max(l, i); }
         }
         for (int i = (int)E.nodes_.size() - 1; i >= 0; --i) {
             const GNode& n = E.nodes_[i];
@@ -5136,6 +5388,7 @@ struct Planner {
         for (int i = 0; i < (int)E.nodes_.size(); ++i) {
             const GNode& n = E.nodes_[i];
             cur = i;
+            if (last_add.node != i - 1) last_add = AddRec();   // only the node directly in front may hand its Add to a LayerNormalization: nothing older survives
             if (fused_into_prev.count(i)) { release_dead(i); continue; }   // planned together with the node before it (op_dsblock: two blocks, one launch)
             if (skip_final_softmax && n.op == "Softmax" && !n.out.empty() && n.out[0] == E.output_names_[0]) {
                 TInfo x = get(n.in[0]);

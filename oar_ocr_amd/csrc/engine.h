@@ -154,6 +154,10 @@ class Engine {
     bool stem_fusable_ = false;
     std::map<std::string, HostTensor> inits_;
     std::vector<GNode> nodes_;
+    // rewrite pass 2c (decomposed LayerNorm -> LayerNormalization): the nodes each rewritten LayerNormalization replaced, by its output name.  The rank of x is
+    // only known at plan time: where the normalised axis then is not the last one, or x has rank 1, op_layernorm plans these instead.
+    std::map<std::string, std::vector<GNode>> ln_spelled_;
+    bool fuse_add_ln_ = true;            // OAR_FUSE_ADD_LAYERNORM, read at load: Add + LayerNormalization as one add_layernorm launch (Planner::fuse_chains)
     std::map<std::string, const float*> dev_consts_;
     std::vector<void*> dev_allocs_;
     std::map<std::string, std::unique_ptr<Plan>> plans_;

@@ -154,6 +154,9 @@ struct GemmP {
 void gemm_batched(hipStream_t s, const GemmP& p);
 
 void layernorm(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps);
+// add_layernorm.hip: s = a + b (row r of b is b[(r % b_rows) * C ...], b_rows | rows), y = LN(s) * gamma + beta; s is stored only when sum_out != null.
+// Bit-identical to binary (Add) followed by layernorm.  gamma / beta may be null; y and sum_out must not overlap a, b or each other.
+void add_layernorm(hipStream_t s, const float* a, const float* b, int64_t b_rows, const float* gamma, const float* beta, float* sum_out, float* y, int64_t rows, int C, float eps);
 void softmax_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C);
 // squeeze-excite gate on a pooled vector: y[n] = act2(W2 act1(W1 x[n] + b1) + b2); w1 = W1 [Cmid][C], w2 = W2 TRANSPOSED [Cmid][Cout]
 // tiles > 0: x is not the pooled vector but the per-tile channel sums a pooling depthwise conv left ([N][tiles][C], conv_dw with gap_part);

@@ -145,6 +145,181 @@ class _Net:
                          strides=[2, 2], pads=[0, 0, 0, 0], group=1, dilations=[1, 1])
 
 
+LN_SPELLINGS = ("op", "decomposed")
+LN_OUTPUT_MISSES = ("m_output", "d_output", "v_output", "r_output")
+LN_AUX_OUTPUT = "aux"
+
+
+def decomposed_layernorm(g, x, gamma=None, beta=None, eps=1e-5, axis=-1, axes="attr", square="pow", eps_first=False, eps_shape=(), inverse="div",
+                         inverse_first=False, affine_first=False, affine_rank=1, axis2=None, miss=None):
+    """LayerNorm over the last axis of `x` as exporters below opset 17 write it (the engine's rewrite pass 2c matches it):
+    ReduceMean -> Sub -> Pow | Mul -> ReduceMean -> Add(eps) -> Sqrt -> Div [-> Mul(gamma) [-> Add(beta)]].  gamma / beta: names of [C] initializers or None.
+    The accepted variants: axes "attr" | "input" (the opset-18 constant input), axis -1 or rank - 1 (given as a number; axis2: what the second ReduceMean
+    writes when that differs, -1 on one and rank - 1 on the other being the same LayerNorm), square "pow" | "mul",
+    eps_first (Add(eps, v)), eps_shape () | (1,), inverse "div" | "reciprocal" (Mul(d, Reciprocal(r))) | "div1" (Mul(d, Div(1, r))), inverse_first and
+    affine_first (the constant operand of those Muls / of the affine Mul and Add first), affine_rank (gamma / beta reshaped to [1, .., 1, C] of that rank;
+    they are then given as arrays).  miss: one near miss that the pass must leave alone --
+      "two_axes" (axes [-2, -1]), "axis_mid" (axes [-2]), "keepdims0" (the mean through keepdims = 0 + Unsqueeze), "power4" (exponent 4),
+      "numerator" (Div(x, r)), "m_reader" / "d_reader" / "v_reader" / "r_reader" (that intermediate read once more, added to the result times 0.125),
+      "m_output" / "d_output" / "v_output" / "r_output" (that intermediate, read by nobody else, carries the fixed name LN_AUX_OUTPUT: the caller declares it
+      as a graph output), "eps_dynamic" (eps computed from x), "eps_zero", "eps_negative".
+    Returns the output name (with a *_reader miss: of the sum that reads the intermediate)."""
+    f32 = np.float32
+    c = lambda v, nm="c": g.init(np.asarray(v, f32), nm)
+    ax = [-2, -1] if miss == "two_axes" else [-2] if miss == "axis_mid" else [axis]
+    aux = lambda which: {"outputs": [LN_AUX_OUTPUT]} if miss == which + "_output" else {}
+
+    def mean(t, keep=1, ax=ax, **named):
+        if axes == "input":
+            return g.op("ReduceMean", [t, g.init(np.array(ax, np.int64), "axes")], keepdims=keep, **named)
+        if axes != "attr":
+            raise ValueError(axes)
+        return g.op("ReduceMean", [t], axes=ax, keepdims=keep, **named)
+
+    if miss == "keepdims0":
+        m = g.op("Unsqueeze", [mean(x, 0), g.init(np.array([-1], np.int64), "axes")])
+    else:
+        m = mean(x, **aux("m"))
+    d = g.op("Sub", [x, m], **aux("d"))
+    if square == "pow":
+        sq = g.op("Pow", [d, c(4.0 if miss == "power4" else 2.0)])
+    elif square == "mul":
+        sq = g.op("Mul", [d, d])
+        if miss == "power4":
+            sq = g.op("Mul", [sq, sq])
+    else:
+        raise ValueError(square)
+    v = mean(sq, ax=ax if axis2 is None else [axis2], **aux("v"))
+    if miss == "eps_dynamic":
+        e = g.op("Add", [g.op("Mul", [g.op("Abs", [mean(x)]), c(0.0)]), c(eps)])
+    else:
+        e = c(np.full(eps_shape, 0.0 if miss == "eps_zero" else -eps if miss == "eps_negative" else eps, f32), "eps")
+    r = g.op("Sqrt", [g.op("Add", [e, v] if eps_first else [v, e])], **aux("r"))
+    num = x if miss == "numerator" else d
+    if inverse == "div":
+        y = g.op("Div", [num, r])
+    elif inverse in ("reciprocal", "div1"):
+        i = g.op("Reciprocal", [r]) if inverse == "reciprocal" else g.op("Div", [c(1.0), r])
+        y = g.op("Mul", [i, num] if inverse_first else [num, i])
+    else:
+        raise ValueError(inverse)
+    if miss == "numerator":         # d keeps a second reader, so that only the numerator differs from the accepted form
+        y = g.op("Add", [y, g.op("Mul", [d, c(0.0)])])
+
+    def shaped(a):
+        if affine_rank == 1:
+            return a
+        if isinstance(a, str):
+            raise ValueError("affine_rank > 1 needs gamma / beta as arrays")
+        return np.asarray(a, f32).reshape((1,) * (affine_rank - 1) + (-1,))
+    name = lambda a, nm: a if isinstance(a, str) else g.init(shaped(a), nm)
+    if gamma is not None:
+        gn = name(gamma, "ln_g")
+        y = g.op("Mul", [gn, y] if affine_first else [y, gn])
+    if beta is not None:
+        bn = name(beta, "ln_b")
+        y = g.op("Add", [bn, y] if affine_first else [y, bn])
+    extra = {"m_reader": m, "d_reader": d, "v_reader": v, "r_reader": r}.get(miss)
+    if extra is not None:
+        y = g.op("Add", [y, g.op("Mul", [extra, c(0.125)])])
+    elif miss not in (None, "two_axes", "axis_mid", "keepdims0", "power4", "numerator", "eps_dynamic", "eps_zero", "eps_negative") + LN_OUTPUT_MISSES:
+        raise ValueError(miss)
+    return y
+
+
+def _layernorm(g, x, gamma, beta, eps, spelling="op", **variant):
+    """LayerNorm over the last axis with gamma / beta already initializers (names): the opset-17 node, or decomposed_layernorm"""
+    if spelling == "op":
+        return g.op("LayerNormalization", [x, gamma, beta], axis=-1, epsilon=eps)
+    if spelling != "decomposed":
+        raise ValueError(spelling)
+    return decomposed_layernorm(g, x, gamma, beta, eps, **variant)
+
+
+def layernorm_case_weights(C, seed=0):
+    rng = np.random.default_rng(seed)
+    return {"g": (1.0 + 0.3 * rng.standard_normal(C)).astype(np.float32), "b": (0.2 * rng.standard_normal(C)).astype(np.float32)}
+
+
+def build_layernorm_case(shape=(2, 5, 32), spelling="decomposed", affine="both", eps=1e-5, seed=0, affine_extent=None, **variant):
+    """x `shape` (the first extent dynamic when the rank is above 1) -> one LayerNorm over the last axis -> y: the opset-17 node (spelling "op") or
+    decomposed_layernorm with its variants and near misses (`variant`; an *_output miss declares that intermediate as the second graph output `aux`).  affine: "both" | "scale" | "none" ("op" always carries both: the node
+    needs its scale).  The same seed gives the same gamma / beta in every spelling.  affine_extent = 1 (decomposed only): gamma and beta are the [1] heads
+    of those vectors, which broadcast over the channels -- a spelling the LayerNorm kernel does not take.  An affine_rank above x's rank gives y that rank."""
+    C = int(shape[-1])
+    w = layernorm_case_weights(C, seed)
+    dims = (["N"] if len(shape) > 1 else []) + [int(d) for d in shape[1 if len(shape) > 1 else 0:]]
+    g = GraphBuilder("layernorm_case", 17 if spelling == "op" else 13)
+    g.add_input("x", dims)
+    gamma, beta = (w["g"] if affine in ("both", "scale") else None), (w["b"] if affine == "both" else None)
+    if affine_extent is not None:
+        if spelling != "decomposed" or affine_extent != 1:
+            raise ValueError("affine_extent")
+        gamma, beta = (None if gamma is None else gamma[:1]), (None if beta is None else beta[:1])
+    if affine not in ("both", "scale", "none"):
+        raise ValueError(affine)
+    if spelling == "op":
+        one = np.ones(C, np.float32)
+        y = g.op("LayerNormalization", ["x", g.init(one if gamma is None else gamma, "ln_g"), g.init(0 * one if beta is None else beta, "ln_b")], axis=-1, epsilon=float(eps))
+    elif spelling == "decomposed":
+        y = decomposed_layernorm(g, "x", gamma, beta, float(eps), **variant)
+    else:
+        raise ValueError(spelling)
+    g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
+    lifted = variant.get("affine_rank", 1) - len(dims) if spelling == "decomposed" and affine != "none" else 0
+    g.add_output("y", [1] * max(lifted, 0) + dims)
+    if spelling == "decomposed" and variant.get("miss") in LN_OUTPUT_MISSES:
+        g.add_output(LN_AUX_OUTPUT, dims if variant["miss"] == "d_output" else dims[:-1] + [1])
+    return g.model(), {"params": g.n_params, "weights": w, "shape": tuple(shape), "affine": affine, "eps": float(eps)}
+
+
+ADD_LAYERNORM_FORMS = ("post", "pre", "sum_output", "table", "vector", "per_sample", "relu", "offset_view")
+
+
+def build_add_layernorm_case(N, T, C, form="post", layernorm="op", eps=1e-5, seed=0):
+    """x [N, T, C] (+ r) -> s = Add(x, b) -> LayerNorm(s) -> y, the residual add in front of a LayerNorm in the forms the engine's add_layernorm launch takes
+    and the ones it must leave alone.  form:
+      "post"        b = the second input r [N, T, C];  y = LN(s)
+      "pre"         the same, and the sum is read again:  y = s + 0.5 LN(s)
+      "sum_output"  the same as "post", with s declared as the second graph output `s`
+      "table"       b = a constant [1, T, C] (info["b"]);  "vector"  b = a constant [C]
+      "per_sample"  b = r [N, 1, C]: rows that do not repeat with a period -- not fused
+      "relu"        LN(Relu(Add(x, r))): the Add carries an activation -- not fused
+      "offset_view" b = Reshape(Slice(Relu(r), 1:), [N, T, C]) of a flat r [N T C + 1]: a view of a computed tensor that starts one float off a 16-byte
+                    boundary -- not fused
+    layernorm: "op" | "decomposed"."""
+    if form not in ADD_LAYERNORM_FORMS:
+        raise ValueError(form)
+    w = layernorm_case_weights(C, seed)
+    rng = np.random.default_rng(seed + 77)
+    info = {"weights": w, "N": N, "T": T, "C": C, "form": form, "eps": float(eps), "r_shape": None, "b": None}
+    g = GraphBuilder("add_layernorm_case", 17 if layernorm == "op" else 13)
+    g.add_input("x", ["N", T, C])
+    if form in ("table", "vector"):
+        info["b"] = rng.standard_normal((1, T, C) if form == "table" else (C,)).astype(np.float32)
+        b = g.init(info["b"], "addend")
+    elif form == "offset_view":
+        info["r_shape"] = (N * T * C + 1,)
+        g.add_input("r", [N * T * C + 1])
+        i64 = lambda v, nm: g.init(np.array(v, np.int64), nm)
+        b = g.op("Reshape", [g.op("Slice", [g.op("Relu", ["r"]), i64([1], "starts"), i64([N * T * C + 1], "ends"), i64([0], "axes")]), i64([N, T, C], "shape")])
+    else:
+        info["r_shape"] = (N, 1, C) if form == "per_sample" else (N, T, C)
+        g.add_input("r", ["N", info["r_shape"][1], C])
+        b = "r"
+    s = g.op("Add", ["x", b], **({"outputs": ["s"]} if form == "sum_output" else {}))
+    t = g.op("Relu", [s]) if form == "relu" else s
+    y = _layernorm(g, t, g.init(w["g"], "ln_g"), g.init(w["b"], "ln_b"), float(eps), layernorm)
+    if form == "pre":
+        y = g.op("Add", [s, g.op("Mul", [y, g.init(np.array(0.5, np.float32), "c")])])
+    g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
+    g.add_output("y", ["N", T, C])
+    if form == "sum_output":
+        g.add_output("s", ["N", T, C])
+    info["params"] = g.n_params
+    return g.model(), info
+
+
 def build_det(size="tiny", seed=0, soft=False):
     """DB text detector.  Returns (onnx_bytes, info).  soft: a shallow final gain and 30x the weight on the random channels -- the probability
     map is no longer near-binary (thousands of pixels within 0.05 of the 0.3 threshold, blob borders that depend on the random-weight
@@ -451,8 +626,9 @@ _SVTRV2_CFG = {
 }
 
 
-def build_rec_svtrv2(size="svtrv2", vocab=6625, seed=1):
-    """SVTRv2-class CTC recognizer: in [n,3,48,W] (W % 4 == 0) -> out [n, W/4, vocab] softmax probabilities (see the comment above)."""
+def build_rec_svtrv2(size="svtrv2", vocab=6625, seed=1, layernorm="op"):
+    """SVTRv2-class CTC recognizer: in [n,3,48,W] (W % 4 == 0) -> out [n, W/4, vocab] softmax probabilities (see the comment above).
+    layernorm: "op" (the opset-17 node) or "decomposed" (decomposed_layernorm: what an exporter below opset 17 writes; same weights)."""
     dims, depths, heads, mixers = _SVTRV2_CFG[size]
     n = _Net(f"synth_rec_{size}", seed, decomposed_hswish=False)
     g = n.g
@@ -466,10 +642,10 @@ def build_rec_svtrv2(size="svtrv2", vocab=6625, seed=1):
         t = g.op("MatMul", [t, g.init(w)])
         return g.op("Add", [t, g.init(n._b(cout), "b")])
 
-    def layernorm(t, c):
+    def lnorm(t, c):
         gamma = (1.0 + 0.1 * n.rng.standard_normal(c)).astype(np.float32)
         beta = (0.05 * n.rng.standard_normal(c)).astype(np.float32)
-        return g.op("LayerNormalization", [t, g.init(gamma), g.init(beta)], axis=-1, epsilon=1e-6)
+        return _layernorm(g, t, g.init(gamma), g.init(beta), 1e-6, layernorm)
 
     def to_tokens(m, c):      # [n, c, h, w] -> [n, h*w, c]
         t = g.op("Reshape", [m, g.init(np.array([0, c, -1], i64), "shape")])
@@ -486,8 +662,8 @@ def build_rec_svtrv2(size="svtrv2", vocab=6625, seed=1):
 
     def conv_block(t, c, h, nh):
         m = n.conv(to_map(t, c, h), c, c, 5, 1, groups=nh)
-        t = layernorm(g.op("Add", [t, to_tokens(m, c)]), c)
-        return layernorm(g.op("Add", [t, mlp(t, c)]), c)
+        t = lnorm(g.op("Add", [t, to_tokens(m, c)]), c)
+        return lnorm(g.op("Add", [t, mlp(t, c)]), c)
 
     def global_block(t, c, nh):
         hd = c // nh
@@ -506,8 +682,8 @@ def build_rec_svtrv2(size="svtrv2", vocab=6625, seed=1):
         o = g.op("Transpose", [o], perm=[0, 2, 1, 3])
         o = g.op("Reshape", [o, g.init(np.array([0, -1, c], i64), "shape")])
         o = linear(o, c, c, gain=0.5)
-        t = layernorm(g.op("Add", [t, o]), c)
-        return layernorm(g.op("Add", [t, mlp(t, c)]), c)
+        t = lnorm(g.op("Add", [t, o]), c)
+        return lnorm(g.op("Add", [t, mlp(t, c)]), c)
 
     h = 12
     t = to_tokens(x, dims[0])
@@ -518,7 +694,7 @@ def build_rec_svtrv2(size="svtrv2", vocab=6625, seed=1):
         if si < 2:   # sub-sampling: 3x3 convolution, stride (2, 1), then LayerNorm over the channels
             m = n.conv(to_map(t, c, h), c, dims[si + 1], 3, (2, 1))
             h //= 2
-            t = layernorm(to_tokens(m, dims[si + 1]), dims[si + 1])
+            t = lnorm(to_tokens(m, dims[si + 1]), dims[si + 1])
     c = dims[2]
     m = to_map(t, c, h)                                                          # [n, c, 3, W/4]
     m = g.op("ReduceMean", [m], axes=[2], keepdims=0)                            # [n, c, W/4]
@@ -1132,26 +1308,27 @@ def aifi_layer_weights(D, F, seed=0):
     return w
 
 
-def _aifi_layer(g, src, w, p, H, W, D, nh):
+def _aifi_layer(g, src, w, p, H, W, D, nh, layernorm="op"):
     """PaddleDetection's post-norm TransformerLayer on src [N, H W, D]: q = k = src + pos_embed (sincos_2d, an initializer), v = src; _mha; Add +
     LayerNormalization; Linear -> Gelu -> Linear; Add + LayerNormalization"""
     c = lambda nm: g.init(w[nm], "aifi_" + p + nm)
     lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, c(nm + "_w")]), c(nm + "_b")])
-    lnorm = lambda t, nm: g.op("LayerNormalization", [t, c(nm + "_g"), c(nm + "_b")], axis=-1, epsilon=1e-5)
+    lnorm = lambda t, nm: _layernorm(g, t, c(nm + "_g"), c(nm + "_b"), 1e-5, layernorm)
     qk = g.op("Add", [src, g.init(sincos_2d(H, W, D), "aifi_" + p + "pos")])
     src = lnorm(g.op("Add", [src, _mha(g, w, "", qk, qk, src, H * W, H * W, nh, D // nh)]), "ln1")
     ffn = lin(g.op("Gelu", [lin(src, "ffn1")], approximate="none"), "ffn2")
     return lnorm(g.op("Add", [src, ffn]), "ln2")
 
 
-def build_aifi_layer(H, W, D, nh, F, seed=0):
-    """The AIFI layer of RT-DETR's hybrid encoder as a graph of its own: src [N, H W, D] -> y [N, H W, D] (_aifi_layer)."""
+def build_aifi_layer(H, W, D, nh, F, seed=0, layernorm="op"):
+    """The AIFI layer of RT-DETR's hybrid encoder as a graph of its own: src [N, H W, D] -> y [N, H W, D] (_aifi_layer).  layernorm: "op" | "decomposed"
+    (both LayerNorms as decomposed_layernorm writes them)."""
     if D % nh:
         raise ValueError("D must be a multiple of the heads")
     w = aifi_layer_weights(D, F, seed)
     g = GraphBuilder("aifi_layer", 17)
     g.add_input("src", ["N", H * W, D])
-    y = _aifi_layer(g, "src", w, "", H, W, D, nh)
+    y = _aifi_layer(g, "src", w, "", H, W, D, nh, layernorm)
     g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
     g.add_output("y", ["N", H * W, D])
     return g.model(), {"params": g.n_params, "weights": w, "H": H, "W": W, "D": D, "nh": nh, "F": F}
@@ -1519,7 +1696,7 @@ def _roll(g, t, axis, k, n):
     return g.op("Concat", [g.op("Slice", [t, i64(k, "starts"), i64(n, "ends"), ax]), g.op("Slice", [t, i64(0, "starts"), i64(k, "ends"), ax])], axis=axis)
 
 
-def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None, pad_value=0.0, unroll=None):
+def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None, pad_value=0.0, unroll=None, layernorm="op"):
     """x [B, H W, C] -> x + window attention of LN1(x), in the spelling DESIGN 4.33 fixes (the engine's rewrite pass 3b matches it).  scale: "div" writes
     Div(s, sqrt(dh)), "mul" Mul(s, dh^-0.5).  H or W no multiple of ws: LN1's output is padded at the bottom / right with pad_value (Pad) and the result
     cropped (Slice).  shift > 0: the padded grid is rolled by -shift on both axes in front of the partition and by +`unroll` (default: shift) behind the
@@ -1540,7 +1717,7 @@ def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None
     ci = lambda v: g.init(np.array(v, np.int64), "shape")
     i64 = lambda v, nm: g.init(np.array([v], np.int64), nm)
     lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(np.ascontiguousarray(w[p + "w" + nm].T), "sw_" + p + "w" + nm)]), g.init(w[p + "b" + nm], "sw_" + p + "b" + nm)])
-    y = g.op("LayerNormalization", [x, g.init(w[p + "ln1_g"], "sw_" + p + "ln1_g"), g.init(w[p + "ln1_b"], "sw_" + p + "ln1_b")], axis=-1, epsilon=1e-5)
+    y = _layernorm(g, x, g.init(w[p + "ln1_g"], "sw_" + p + "ln1_g"), g.init(w[p + "ln1_b"], "sw_" + p + "ln1_b"), 1e-5, layernorm)
     if grid:
         y = g.op("Reshape", [y, ci([0, H, W, C])])
     if (Hp, Wp) != (H, W):
@@ -1581,22 +1758,22 @@ def _swin_attention(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None
     return g.op("Add", [x, g.op("Reshape", [r, ci([0, H * W, C])])])
 
 
-def _swin_block(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None, pad_value=0.0, unroll=None):
+def _swin_block(g, x, w, p, H, W, C, nh, ws, scale="div", shift=0, mask=None, pad_value=0.0, unroll=None, layernorm="op"):
     """the attention block, the depthwise 3 x 3 "conv enhance" residual on the tokens viewed as an image, and LN2 -> Linear -> GELU -> Linear with its residual"""
     ci = lambda v: g.init(np.array(v, np.int64), "shape")
     lin = lambda t, nm: g.op("Add", [g.op("MatMul", [t, g.init(np.ascontiguousarray(w[p + "w" + nm].T), "sw_" + p + "w" + nm)]), g.init(w[p + "b" + nm], "sw_" + p + "b" + nm)])
-    x = _swin_attention(g, x, w, p, H, W, C, nh, ws, scale, shift, mask, pad_value, unroll)
+    x = _swin_attention(g, x, w, p, H, W, C, nh, ws, scale, shift, mask, pad_value, unroll, layernorm)
     img = g.op("Reshape", [g.op("Transpose", [x], perm=[0, 2, 1]), ci([0, C, H, W])])
     img = g.op("Conv", [img, g.init(w[p + "ce_w"], "sw_" + p + "ce_w"), g.init(w[p + "ce_b"], "sw_" + p + "ce_b")], kernel_shape=[3, 3], strides=[1, 1], pads=[1, 1, 1, 1], group=C, dilations=[1, 1])
     x = g.op("Add", [x, g.op("Transpose", [g.op("Reshape", [img, ci([0, C, -1])])], perm=[0, 2, 1])])
-    y = g.op("LayerNormalization", [x, g.init(w[p + "ln2_g"], "sw_" + p + "ln2_g"), g.init(w[p + "ln2_b"], "sw_" + p + "ln2_b")], axis=-1, epsilon=1e-5)
+    y = _layernorm(g, x, g.init(w[p + "ln2_g"], "sw_" + p + "ln2_g"), g.init(w[p + "ln2_b"], "sw_" + p + "ln2_b"), 1e-5, layernorm)
     return g.op("Add", [x, lin(g.op("Gelu", [lin(y, "1")], approximate="none"), "2")])
 
 
-def build_swin_block(H, W, C, nh, ws, seed=0, scale="div", whole=False, shift=0, mask=None, pad_value=None, unroll=None):
+def build_swin_block(H, W, C, nh, ws, seed=0, scale="div", whole=False, shift=0, mask=None, pad_value=None, unroll=None, layernorm="op"):
     """One Swin block as a graph of its own: x [B, H W, C] -> `y` [B, H W, C].  whole = False: the attention part only (LN1 .. the residual Add).
     shift, mask, pad_value, unroll: _swin_attention's.  A grid that is no multiple of ws is written padded only when pad_value is given (0.0 is the Swin
-    spelling); with pad_value = None such a grid is refused, as it always was."""
+    spelling); with pad_value = None such a grid is refused, as it always was.  layernorm: "op" | "decomposed" (decomposed_layernorm, same weights)."""
     if pad_value is None:
         if H % ws or W % ws:
             raise ValueError("H and W must be multiples of ws unless pad_value is given")
@@ -1604,7 +1781,7 @@ def build_swin_block(H, W, C, nh, ws, seed=0, scale="div", whole=False, shift=0,
     w = swin_block_weights(C, nh, ws, 2 * C, seed)
     g = GraphBuilder("swin_block", 17)
     g.add_input("x", ["B", H * W, C])
-    y = (_swin_block if whole else _swin_attention)(g, "x", w, "", H, W, C, nh, ws, scale, shift, mask, pad_value, unroll)
+    y = (_swin_block if whole else _swin_attention)(g, "x", w, "", H, W, C, nh, ws, scale, shift, mask, pad_value, unroll, layernorm)
     g.nodes.append(node("Identity", [y], ["y"], name=g.uid("n")))
     g.add_output("y", ["B", H * W, C])
     info = {"params": g.n_params, "weights": w, "H": H, "W": W, "C": C, "nh": nh, "ws": ws, "scale": scale, "whole": whole}
@@ -1706,7 +1883,7 @@ def vit_block_weights(C, nh, H, W, ws, hidden, seed=0, prefix=""):
     return {prefix + k: v for k, v in w.items()}
 
 
-def _vit_attention(g, x, w, p, H, W, C, nh, ws=0, scale="pre", rel_from="q", rh_name=None):
+def _vit_attention(g, x, w, p, H, W, C, nh, ws=0, scale="pre", rel_from="q", rh_name=None, layernorm="op"):
     """x [B, H W, C] -> x + attention of LN1(x) with the decomposed relative-position bias q . Rh[qy, ky] + q . Rw[qx, kx], in the spelling DESIGN 4.35 fixes (the
     engine's rewrite pass 3d matches it).  ws = 0: global attention; ws > 0: ws x ws windows on the grid padded with zeros at the bottom / right, in front of
     the fused qkv Linear, so a padding key carries bqkv; there is no mask.  scale: "pre" Mul(q, dh^-0.5) in front of the score MatMul (SAM), "post" Mul on the
@@ -1726,7 +1903,7 @@ def _vit_attention(g, x, w, p, H, W, C, nh, ws=0, scale="pre", rel_from="q", rh_
     lin = lambda t, wn, bn: g.op("Add", [g.op("MatMul", [t, c(wn, w[p + wn].T)]), c(bn, w[p + bn])])
     tr = lambda t, perm: g.op("Transpose", [t], perm=list(perm))
     rs = lambda t, shape: g.op("Reshape", [t, ci(shape)])
-    y = g.op("LayerNormalization", [x, c("ln1_g", w[p + "ln1_g"]), c("ln1_b", w[p + "ln1_b"])], axis=-1, epsilon=1e-5)
+    y = _layernorm(g, x, c("ln1_g", w[p + "ln1_g"]), c("ln1_b", w[p + "ln1_b"]), 1e-5, layernorm)
     y = rs(y, [0, H, W, C])
     if ws:
         if (Hp, Wp) != (H, W):
@@ -1766,14 +1943,14 @@ def _vit_block(g, x, w, p, H, W, C, nh, ws=0, scale="pre", **knobs):
     c = lambda nm, a: g.init(np.ascontiguousarray(a), "vit_" + p + nm)
     lin = lambda t, wn, bn: g.op("Add", [g.op("MatMul", [t, c(wn, w[p + wn].T)]), c(bn, w[p + bn])])
     x = _vit_attention(g, x, w, p, H, W, C, nh, ws, scale, **knobs)
-    y = g.op("LayerNormalization", [x, c("ln2_g", w[p + "ln2_g"]), c("ln2_b", w[p + "ln2_b"])], axis=-1, epsilon=1e-5)
+    y = _layernorm(g, x, c("ln2_g", w[p + "ln2_g"]), c("ln2_b", w[p + "ln2_b"]), 1e-5, knobs.get("layernorm", "op"))
     return g.op("Add", [x, lin(g.op("Gelu", [lin(y, "w1", "b1")], approximate="none"), "w2", "b2")])
 
 
 def build_vit_block(H, W, C, nh, ws=0, seed=0, scale="pre", whole=False, **knobs):
     """One ViT block as a graph of its own: x [B, H W, C] -> `y` [B, H W, C].  whole = False: the attention part only (LN1 .. the residual Add).  knobs:
     rel_from = "scaled" (_vit_attention's); rh_input = True declares RhT [h, dh, h] as a second graph input `rhT` in place of the initializer (info["rhT"]
-    holds the array to feed)."""
+    holds the array to feed); layernorm = "op" | "decomposed" (decomposed_layernorm, same weights)."""
     rh_input = bool(knobs.pop("rh_input", False))
     w = vit_block_weights(C, nh, H, W, ws, 2 * C, seed)
     g = GraphBuilder("vit_block", 17)

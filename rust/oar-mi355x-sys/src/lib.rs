@@ -421,6 +421,7 @@ unsafe extern "C" {
     /// fixed-length arrays: box_: [f32; 8]
     pub fn oar_k_rotate_crop(rgb: *const u8, w: u32, h: u32, box_: *const f32, out: *mut u8, cap: usize, out_w: *mut u32, out_h: *mut u32) -> oar_status;
     pub fn oar_k_mha_attention(buf: *const f32, buf_floats: usize, q_off: usize, k_off: usize, v_off: usize, ldq: i32, ldk: i32, ldv: i32, n: i32, tq: i32, tk: i32, heads: i32, head_dim: i32, scale: f32, scale_pre: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_k_add_layernorm(a: *const f32, b: *const f32, b_rows: i64, gamma: *const f32, beta: *const f32, rows: i64, C: i32, eps: f32, write_sum: i32, o_io: *mut f32, o_floats: usize, y_off: usize, s_off: usize) -> oar_status;
     pub fn oar_k_relpos_attention(qkv: *const f32, b: i32, h: i32, w: i32, ws: i32, heads: i32, head_dim: i32, rh: *const f32, rw: *const f32, bqkv: *const f32, scale: f32, scale_pre: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_image_decode(bytes: *const u8, len: usize, rgb: *mut *mut u8, width: *mut u32, height: *mut u32) -> oar_status;
     pub fn oar_image_free(rgb: *mut u8);
