@@ -593,6 +593,60 @@ oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_
                                   const float* rh, const float* rw, const float* bqkv, float scale, int32_t scale_pre,
                                   float* o_io, size_t o_floats, size_t o_off);
 
+/* ------------------------------------------------------------------------------------------------ VL: the text decoder
+ * The decoder-only language model of the oar-ocr-vl crate (PaddleOCR-VL's ERNIE-4.5 text decoder, oar-ocr-vl/src/models/paddleocr_vl/ernie.rs; the
+ * Qwen2-VL family differs in configuration only): RMSNorm, M-RoPE (runtime/attention.rs select_rope_sections), grouped-query attention over a
+ * key / value cache, SwiGLU MLP, greedy argmax (lowest index among equal maxima).  Prefill and decode run the same chain of 5 layers + 2 HIP launches
+ * per step of <= 16 rows (lm_decode.hip).  Not built: the vision encoder, the projector, the tokenizer, sampling.                        */
+typedef struct oar_lm oar_lm;
+typedef enum { OAR_LM_F32 = 1, OAR_LM_BF16 = 16 } oar_lm_dtype;
+typedef struct {
+    int32_t hidden, layers, heads, kv_heads, head_dim, intermediate, vocab;
+    float rms_eps, rope_theta;
+    int32_t mrope_section[3];    /* sums to head_dim / 2; {head_dim / 2, 0, 0} = plain 1-D RoPE                                  */
+    int32_t qkv_bias;            /* 1: q_proj / k_proj / v_proj carry a bias                                                     */
+    int32_t tie_embeddings;      /* 1: the lm-head is embed_tokens (no lm_head.weight in the table)                               */
+    int32_t max_positions;       /* cache length per sequence                                                                     */
+    int32_t max_sequences;       /* 1 .. 16                                                                                       */
+} oar_lm_cfg;
+/* One named tensor of a checkpoint: row-major host memory; bf16 as its 16-bit patterns. */
+typedef struct {
+    const char* name;
+    int32_t dtype;               /* oar_lm_dtype                                                                                  */
+    int32_t rank;
+    int64_t dims[4];
+    const void* data;
+} oar_lm_tensor;
+/* tensors: the checkpoint's own names (the reference's loader, ernie.rs / model.rs): "model.embed_tokens.weight" [vocab, hidden],
+ * "model.layers.{i}.input_layernorm.weight" [hidden], "model.layers.{i}.self_attn.{q,k,v}_proj.weight" [heads or kv_heads x head_dim, hidden]
+ * (+ ".bias" with qkv_bias), "model.layers.{i}.self_attn.o_proj.weight" [hidden, heads x head_dim], "model.layers.{i}.post_attention_layernorm.weight",
+ * "model.layers.{i}.mlp.{gate,up}_proj.weight" [intermediate, hidden], "model.layers.{i}.mlp.down_proj.weight" [hidden, intermediate],
+ * "model.norm.weight" and, untied, "lm_head.weight" [vocab, hidden].  The matrices share one dtype (bf16 stays bf16 in HBM); norm weights and biases
+ * are widened to f32.  Other names are ignored.  OAR_INVALID_INPUT: a configuration that is inconsistent (heads % kv_heads, mrope_section, sizes
+ * <= 0, max_sequences outside 1..16), a missing tensor, a wrong shape or dtype; OAR_UNSUPPORTED_OP: head_dim outside 8..128 or no multiple of 4.
+ * All of that is reported before the device is touched. */
+oar_status oar_lm_create(const oar_lm_cfg* cfg, const oar_lm_tensor* tensors, int32_t n_tensors, int32_t device_id, oar_lm** out);
+void oar_lm_destroy(oar_lm* lm);
+typedef struct {
+    int32_t n_seq;                          /* 1 .. cfg.max_sequences                                                            */
+    const int32_t* lengths;                 /* [n_seq] prompt lengths T_i >= 1                                                   */
+    const float* const* inputs_embeds;      /* [n_seq] -> [T_i][hidden], or NULL: input_ids                                      */
+    const int32_t* const* input_ids;        /* [n_seq] -> [T_i]                                                                  */
+    const int32_t* const* position_ids;     /* NULL, or [n_seq] -> [3][T_i] (an entry may be NULL): default 0 .. T_i - 1 on all axes */
+    int32_t max_new_tokens;                 /* T_i + max_new_tokens <= cfg.max_positions                                         */
+    int32_t eos_token_id;                   /* -1: none                                                                          */
+    const int32_t* forced_tokens;           /* NULL, or [n_seq][max_new_tokens]: entry >= 0 is fed as the next input instead of the argmax */
+    float* logits;                          /* NULL, or [n_seq][max_new_tokens][vocab] (rows after a sequence's eos are unspecified) */
+    int32_t* tokens;                        /* out [n_seq][max_new_tokens]: the argmax tokens; eos from a sequence's first eos on */
+    int32_t* counts;                        /* out [n_seq]: tokens up to and including the first eos, else max_new_tokens          */
+} oar_lm_request;
+/* Generated token i of a sequence gets the position max(position_ids) + 1 + i on all three axes.  The prompt is prefilled in steps of at most 16
+ * positions through the same chain.  Every argument is checked before anything is launched (OAR_INVALID_INPUT). */
+oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req);
+/* Analytic cost of ONE step of n_rows rows (1 .. 16) whose sequences hold cache_len positions: bytes = every weight once (in its stored dtype) +
+ * the cache rows read + the row buffers; flops = 2 x MACs; n_kernels = 5 layers + 2. */
+oar_status oar_lm_cost(const oar_lm* lm, int32_t n_rows, int32_t cache_len, double* flops, double* bytes, int32_t* n_kernels);
+
 /* ------------------------------------------------------------------------------------------------ image decode
  * load_image_from_memory (oar-ocr-core/src/utils/image.rs:65-68: image::load_from_memory + DynamicImage::to_rgb8) for the
  * formats this library decodes itself.  PNG: every colour type / bit depth / interlace mode, to the bytes the image crate

@@ -154,6 +154,7 @@ EXPORTS = [
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
     "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm",
+    "oar_lm_create", "oar_lm_destroy", "oar_lm_generate", "oar_lm_cost",
 ]
 
 

@@ -1,0 +1,61 @@
+// lm_decode.h -- the decoder-only language-model chain (lm_decode.hip): shapes, the per-step row table and the launchers.
+// Plain C++ (no HIP header): the LDS sizes below are also compiled by the host-only resource test.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+struct ihipStream_t;
+
+namespace oar {
+namespace k {
+
+constexpr int kLmRows = 16;          // rows ((sequence, position) pairs) of one step
+constexpr int kLmThreads = 256;      // rows / lm-head / combine kernels
+constexpr int kLmKC = 1024;          // columns of the row inputs staged in LDS at a time
+constexpr int kLmAttnThreads = 512;  // attention: 8 waves, each takes every 8th group of keys
+constexpr int kLmAttnWaves = kLmAttnThreads / 64;
+constexpr int kLmMaxDh = 128, kLmMinDh = 8;
+constexpr int kLmMaxGT = 8;          // query heads of one kv head that a workgroup serves at once (a larger group takes several workgroups)
+
+// One row of a step.  xrow: the row's hidden vector in the arena ([arena rows][D]); gen >= 0: the row's logits give generated token `gen` of its sequence.
+struct LmRow { int32_t seq, pos, rp[3], xrow, gen, pad; };
+struct LmStep { int32_t nrows, nhead, pad[2]; LmRow rows[kLmRows]; int32_t head[kLmRows]; };   // head[i]: slot of the i-th row that needs a token
+struct LmState { int32_t done[kLmRows]; int32_t alive; int32_t pad[3]; };
+
+struct LmLayerW { const void *w_qkv, *w_o, *w_gu, *w_down; const float *b_qkv, *ln1, *ln2; };
+
+struct LmDecodeP {
+    int D, L, H, KVH, dh, F, V, maxpos, sec0, sec1, bf16;   // sec0 / sec1: frequencies below sec0 take axis 0, below sec0 + sec1 axis 1, the rest axis 2
+    float eps;
+    const LmLayerW* layers;      // host array [L] of device pointers
+    const float* lnf;
+    const void *w_lm, *embed;    // [V][pad4(D)] each (the same table when tied)
+    const float* inv_freq;       // [dh / 2]
+    float *kcache, *vcache;      // [L][sequences][KVH][maxpos][dh] each
+    size_t cache_layer;          // floats of one layer's K (or V) cache
+    float* arena;                // [arena rows][D]: prompt rows, then one decode row per sequence from xdec0 on
+    int xdec0;
+    float *q, *o, *h;            // [16][H dh], [16][H dh], [16][F]
+    void* part;                  // float2 [16][lm workgroups]
+    LmState* state;
+    int32_t* tokens;             // [sequences][max_new]
+    const int32_t* forced;       // [sequences][max_new] or null; < 0: not forced
+    float* logits;               // [sequences][max_new][V] or null
+    int max_new, eos;
+};
+
+inline int lm_pad4(int n) { return (n + 3) & ~3; }
+inline int lm_nb(int rows) { int nb = 1; while (nb < rows) nb <<= 1; return nb; }
+// dynamic LDS of a rows / lm-head launch with `rows` rows over K input columns; static LDS of the attention kernel at its widest instantiation
+inline size_t lm_rows_lds_bytes(int rows, int K) { const int kp = lm_pad4(K); return (size_t)lm_nb(rows) * (size_t)(kp < kLmKC ? kp : kLmKC) * 4; }
+inline size_t lm_rows_static_lds_bytes() { return 16 * 4 + 4 * 16 * 4 * 2; }
+inline size_t lm_attn_lds_bytes() { return (size_t)kLmAttnWaves * kLmMaxGT * (kLmMaxDh + 2) * 4; }
+inline bool lm_head_dim_supported(int dh) { return dh >= kLmMinDh && dh <= kLmMaxDh && dh % 4 == 0; }
+inline int lm_launches_per_step(int L) { return 5 * L + 2; }
+int lm_head_workgroups(int V);
+
+void lm_embed(ihipStream_t* s, const LmDecodeP& p, const int32_t* ids, const int32_t* xrows, int n);   // arena[xrows[i]] = E[ids[i]]
+void lm_step(ihipStream_t* s, const LmDecodeP& p, const LmStep* dev_step, int nrows, int nhead, int max_pos_in_step);
+
+}  // namespace k
+}  // namespace oar

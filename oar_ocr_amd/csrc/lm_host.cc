@@ -1,0 +1,393 @@
+// lm_host.cc -- host side of the decoder-only language model (lm_decode.hip): checks a checkpoint's tensor table, stacks / permutes / pads the matrices,
+// uploads them, and drives prefill and decode as one schedule of <= 16-row steps.  C ABI: oar_lm_create / oar_lm_generate / oar_lm_cost / oar_lm_destroy.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "lm_decode.h"
+
+using namespace oar;
+
+namespace {
+
+template <typename F>
+oar_status guard(F&& f) {
+    try {
+        f();
+        return OAR_OK;
+    } catch (const Error& e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        set_last_error("host allocation failed");
+        return OAR_OOM;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return OAR_INTERNAL;
+    } catch (...) {
+        set_last_error("unknown error");
+        return OAR_INTERNAL;
+    }
+}
+
+float bf16_to_f32(uint16_t v) {
+    const uint32_t u = (uint32_t)v << 16;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+struct DevMem {   // one allocation, freed with the model
+    void* p = nullptr;
+    ~DevMem() { if (p) { (void)hipFree(p); (void)hipGetLastError(); } }
+    void alloc(size_t bytes) { OAR_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
+    void upload(const void* src, size_t bytes) { alloc(bytes); OAR_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)); }
+};
+
+void check_cfg(const oar_lm_cfg& c) {
+    OAR_CHECK(c.hidden > 0 && c.layers > 0 && c.heads > 0 && c.kv_heads > 0 && c.head_dim > 0 && c.intermediate > 0 && c.vocab >= 2, OAR_INVALID_INPUT,
+              "oar_lm_create: hidden, layers, heads, kv_heads, head_dim, intermediate must be positive and vocab >= 2");
+    OAR_CHECK(c.heads % c.kv_heads == 0, OAR_INVALID_INPUT, "oar_lm_create: heads is no multiple of kv_heads");
+    OAR_CHECK(k::lm_head_dim_supported(c.head_dim), OAR_UNSUPPORTED_OP, "oar_lm_create: head_dim must be a multiple of 4 in 8..128");
+    OAR_CHECK(c.hidden % 4 == 0 && c.intermediate % 4 == 0, OAR_UNSUPPORTED_OP, "oar_lm_create: hidden and intermediate must be multiples of 4 (rows are read 16 bytes at a time)");
+    OAR_CHECK(c.mrope_section[0] >= 0 && c.mrope_section[1] >= 0 && c.mrope_section[2] >= 0 &&
+                  (int64_t)c.mrope_section[0] + c.mrope_section[1] + c.mrope_section[2] == c.head_dim / 2,
+              OAR_INVALID_INPUT, "oar_lm_create: mrope_section must sum to head_dim / 2");
+    OAR_CHECK(c.rms_eps > 0.0f && c.rope_theta > 0.0f, OAR_INVALID_INPUT, "oar_lm_create: rms_eps and rope_theta must be positive");
+    OAR_CHECK(c.max_sequences >= 1 && c.max_sequences <= k::kLmRows, OAR_INVALID_INPUT, "oar_lm_create: max_sequences must be in 1..16");
+    OAR_CHECK(c.max_positions >= 2 && c.max_positions <= (1 << 20), OAR_INVALID_INPUT, "oar_lm_create: max_positions must be in 2..2^20");
+    OAR_CHECK((int64_t)c.heads * c.head_dim < (1 << 24) && c.hidden < (1 << 24) && c.intermediate < (1 << 24) && c.vocab < (1 << 24), OAR_INVALID_INPUT,
+              "oar_lm_create: a dimension of 2^24 or more");
+}
+
+struct Table {
+    std::map<std::string, const oar_lm_tensor*> by_name;
+    const oar_lm_tensor& need(const std::string& name, int64_t d0, int64_t d1) const {
+        auto it = by_name.find(name);
+        OAR_CHECK(it != by_name.end(), OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' is missing");
+        const oar_lm_tensor& t = *it->second;
+        OAR_CHECK(t.data != nullptr, OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' has no data");
+        OAR_CHECK(t.dtype == OAR_LM_F32 || t.dtype == OAR_LM_BF16, OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' is neither f32 nor bf16");
+        const bool ok = d1 < 0 ? (t.rank == 1 && t.dims[0] == d0) : (t.rank == 2 && t.dims[0] == d0 && t.dims[1] == d1);
+        OAR_CHECK(ok, OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' has the wrong shape");
+        return t;
+    }
+};
+
+std::vector<float> widen(const oar_lm_tensor& t, size_t n) {
+    std::vector<float> v(n);
+    if (t.dtype == OAR_LM_F32) std::memcpy(v.data(), t.data, n * 4);
+    else
+        for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(static_cast<const uint16_t*>(t.data)[i]);
+    return v;
+}
+
+// Copies row `src_row` of t ([rows][K]) to row `dst_row` of a [.][Kp] matrix of t's own element size (the padding stays zero).
+void put_row(std::vector<uint8_t>& dst, size_t dst_row, const oar_lm_tensor& t, size_t src_row, int K, int Kp) {
+    const size_t es = t.dtype == OAR_LM_BF16 ? 2 : 4;
+    std::memcpy(dst.data() + dst_row * Kp * es, static_cast<const uint8_t*>(t.data) + src_row * K * es, (size_t)K * es);
+}
+
+// Row order that puts the rotary pair (d, d + dh / 2) of every head side by side: new row head dh + 2 i + s holds old row head dh + i + s dh / 2.
+size_t rope_src(size_t n, int dh) {
+    const size_t head = n / dh, r = n % dh, i = r >> 1, s = r & 1;
+    return head * dh + i + s * (dh / 2);
+}
+
+}  // namespace
+
+struct oar_lm {
+    oar_lm_cfg cfg{};
+    int device = 0;
+    int bf16 = 0;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    std::vector<std::unique_ptr<DevMem>> mem;
+    std::vector<k::LmLayerW> layers;
+    k::LmDecodeP P{};
+    DevMem work;     // arena | tokens | forced | logits | steps | ids, sized per call
+    size_t work_cap = 0;
+    double weight_bytes = 0;
+    ~oar_lm() {
+        if (stream) {
+            Profiler::get().drop_events();
+            (void)hipStreamDestroy(stream);
+        }
+    }
+    void* up(const void* src, size_t bytes) {
+        mem.emplace_back(new DevMem());
+        mem.back()->upload(src, bytes);
+        return mem.back()->p;
+    }
+    void* raw(size_t bytes) {
+        mem.emplace_back(new DevMem());
+        mem.back()->alloc(bytes);
+        return mem.back()->p;
+    }
+};
+
+oar_status oar_lm_create(const oar_lm_cfg* cfg, const oar_lm_tensor* tensors, int32_t n_tensors, int32_t device_id, oar_lm** out) {
+    return guard([&] {
+        OAR_CHECK(cfg && out && (tensors || n_tensors == 0) && n_tensors >= 0, OAR_INVALID_INPUT, "oar_lm_create: null argument");
+        *out = nullptr;
+        const oar_lm_cfg c = *cfg;
+        check_cfg(c);
+        Table T;
+        for (int32_t i = 0; i < n_tensors; ++i)
+            if (tensors[i].name) T.by_name[tensors[i].name] = &tensors[i];
+        const int D = c.hidden, L = c.layers, H = c.heads, KVH = c.kv_heads, dh = c.head_dim, F = c.intermediate, V = c.vocab;
+        const int Hd = H * dh, Kd = KVH * dh, Dp = k::lm_pad4(D), Hdp = k::lm_pad4(Hd), Fp = k::lm_pad4(F);
+        // every tensor is looked up and checked before the device is touched
+        const oar_lm_tensor& emb = T.need("model.embed_tokens.weight", V, D);
+        const oar_lm_tensor& lmw = c.tie_embeddings ? emb : T.need("lm_head.weight", V, D);
+        const oar_lm_tensor& nf = T.need("model.norm.weight", D, -1);
+        const int wdt = emb.dtype;
+        struct LayerT { const oar_lm_tensor *ln1, *ln2, *q, *k, *v, *o, *g, *u, *d, *bq, *bk, *bv; };
+        std::vector<LayerT> lt((size_t)L);
+        for (int l = 0; l < L; ++l) {
+            const std::string pre = "model.layers." + std::to_string(l) + ".";
+            LayerT& t = lt[(size_t)l];
+            t.ln1 = &T.need(pre + "input_layernorm.weight", D, -1);
+            t.ln2 = &T.need(pre + "post_attention_layernorm.weight", D, -1);
+            t.q = &T.need(pre + "self_attn.q_proj.weight", Hd, D);
+            t.k = &T.need(pre + "self_attn.k_proj.weight", Kd, D);
+            t.v = &T.need(pre + "self_attn.v_proj.weight", Kd, D);
+            t.o = &T.need(pre + "self_attn.o_proj.weight", D, Hd);
+            t.g = &T.need(pre + "mlp.gate_proj.weight", F, D);
+            t.u = &T.need(pre + "mlp.up_proj.weight", F, D);
+            t.d = &T.need(pre + "mlp.down_proj.weight", D, F);
+            t.bq = t.bk = t.bv = nullptr;
+            if (c.qkv_bias) {
+                t.bq = &T.need(pre + "self_attn.q_proj.bias", Hd, -1);
+                t.bk = &T.need(pre + "self_attn.k_proj.bias", Kd, -1);
+                t.bv = &T.need(pre + "self_attn.v_proj.bias", Kd, -1);
+            }
+            for (const oar_lm_tensor* m : {t.q, t.k, t.v, t.o, t.g, t.u, t.d})
+                OAR_CHECK(m->dtype == wdt, OAR_INVALID_INPUT, "oar_lm_create: the weight matrices do not share one dtype (layer " + std::to_string(l) + ")");
+        }
+        OAR_CHECK(lmw.dtype == wdt, OAR_INVALID_INPUT, "oar_lm_create: lm_head.weight and embed_tokens do not share one dtype");
+
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        OAR_CHECK(device_id >= 0 && device_id < ndev, OAR_DEVICE, "oar_lm_create: no such device");
+        OAR_HIP(hipSetDevice(device_id));
+        std::unique_ptr<oar_lm> M(new oar_lm());
+        M->cfg = c; M->device = device_id; M->bf16 = wdt == OAR_LM_BF16;
+        OAR_HIP(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
+        const size_t es = M->bf16 ? 2 : 4;
+        M->layers.resize((size_t)L);
+        for (int l = 0; l < L; ++l) {
+            const LayerT& t = lt[(size_t)l];
+            k::LmLayerW& W = M->layers[(size_t)l];
+            const int Nqkv = Hd + 2 * Kd;
+            std::vector<uint8_t> m((size_t)Nqkv * Dp * es, 0);
+            for (int n = 0; n < Hd; ++n) put_row(m, (size_t)n, *t.q, rope_src((size_t)n, dh), D, Dp);
+            for (int n = 0; n < Kd; ++n) put_row(m, (size_t)Hd + n, *t.k, rope_src((size_t)n, dh), D, Dp);
+            for (int n = 0; n < Kd; ++n) put_row(m, (size_t)Hd + Kd + n, *t.v, (size_t)n, D, Dp);
+            W.w_qkv = M->up(m.data(), m.size());
+            W.b_qkv = nullptr;
+            if (c.qkv_bias) {
+                const std::vector<float> bq = widen(*t.bq, (size_t)Hd), bk = widen(*t.bk, (size_t)Kd), bv = widen(*t.bv, (size_t)Kd);
+                std::vector<float> b((size_t)Nqkv);
+                for (int n = 0; n < Hd; ++n) b[(size_t)n] = bq[rope_src((size_t)n, dh)];
+                for (int n = 0; n < Kd; ++n) b[(size_t)Hd + n] = bk[rope_src((size_t)n, dh)];
+                for (int n = 0; n < Kd; ++n) b[(size_t)Hd + Kd + n] = bv[(size_t)n];
+                W.b_qkv = static_cast<const float*>(M->up(b.data(), b.size() * 4));
+            }
+            m.assign((size_t)D * Hdp * es, 0);
+            for (int n = 0; n < D; ++n) put_row(m, (size_t)n, *t.o, (size_t)n, Hd, Hdp);
+            W.w_o = M->up(m.data(), m.size());
+            m.assign((size_t)2 * F * Dp * es, 0);
+            for (int n = 0; n < F; ++n) { put_row(m, (size_t)2 * n, *t.g, (size_t)n, D, Dp); put_row(m, (size_t)2 * n + 1, *t.u, (size_t)n, D, Dp); }
+            W.w_gu = M->up(m.data(), m.size());
+            m.assign((size_t)D * Fp * es, 0);
+            for (int n = 0; n < D; ++n) put_row(m, (size_t)n, *t.d, (size_t)n, F, Fp);
+            W.w_down = M->up(m.data(), m.size());
+            const std::vector<float> g1 = widen(*t.ln1, (size_t)D), g2 = widen(*t.ln2, (size_t)D);
+            W.ln1 = static_cast<const float*>(M->up(g1.data(), g1.size() * 4));
+            W.ln2 = static_cast<const float*>(M->up(g2.data(), g2.size() * 4));
+            M->weight_bytes += (double)es * ((double)Nqkv * Dp + (double)D * Hdp + 2.0 * F * Dp + (double)D * Fp) + 4.0 * (2.0 * D + (c.qkv_bias ? Nqkv : 0));
+        }
+        k::LmDecodeP& P = M->P;
+        {
+            std::vector<uint8_t> m((size_t)V * Dp * es, 0);
+            for (int n = 0; n < V; ++n) put_row(m, (size_t)n, emb, (size_t)n, D, Dp);
+            P.embed = M->up(m.data(), m.size());
+            P.w_lm = P.embed;
+            if (!c.tie_embeddings) {
+                m.assign((size_t)V * Dp * es, 0);
+                for (int n = 0; n < V; ++n) put_row(m, (size_t)n, lmw, (size_t)n, D, Dp);
+                P.w_lm = M->up(m.data(), m.size());
+            }
+            M->weight_bytes += (double)es * V * Dp + 4.0 * D;
+            const std::vector<float> g = widen(nf, (size_t)D);
+            P.lnf = static_cast<const float*>(M->up(g.data(), g.size() * 4));
+            std::vector<float> inv((size_t)dh / 2);
+            for (int i = 0; i < dh / 2; ++i) inv[(size_t)i] = (float)std::pow((double)c.rope_theta, -2.0 * i / dh);
+            P.inv_freq = static_cast<const float*>(M->up(inv.data(), inv.size() * 4));
+        }
+        P.D = D; P.L = L; P.H = H; P.KVH = KVH; P.dh = dh; P.F = F; P.V = V; P.maxpos = c.max_positions; P.sec0 = c.mrope_section[0]; P.sec1 = c.mrope_section[1];
+        P.bf16 = M->bf16; P.eps = c.rms_eps; P.layers = M->layers.data();
+        P.cache_layer = (size_t)c.max_sequences * KVH * c.max_positions * dh;
+        P.kcache = static_cast<float*>(M->raw(P.cache_layer * L * 4));
+        P.vcache = static_cast<float*>(M->raw(P.cache_layer * L * 4));
+        P.q = static_cast<float*>(M->raw((size_t)k::kLmRows * Hd * 4));
+        P.o = static_cast<float*>(M->raw((size_t)k::kLmRows * Hd * 4));
+        P.h = static_cast<float*>(M->raw((size_t)k::kLmRows * F * 4));
+        P.part = M->raw((size_t)k::kLmRows * k::lm_head_workgroups(V) * 8);
+        P.state = static_cast<k::LmState*>(M->raw(sizeof(k::LmState)));
+        *out = M.release();
+    });
+}
+
+void oar_lm_destroy(oar_lm* lm) {
+    if (!lm) return;
+    (void)hipSetDevice(lm->device);
+    delete lm;
+}
+
+oar_status oar_lm_cost(const oar_lm* lm, int32_t n_rows, int32_t cache_len, double* flops, double* bytes, int32_t* n_kernels) {
+    return guard([&] {
+        OAR_CHECK(lm && n_rows >= 1 && n_rows <= k::kLmRows && cache_len >= 0 && cache_len <= lm->cfg.max_positions, OAR_INVALID_INPUT,
+                  "oar_lm_cost: null model, n_rows outside 1..16 or cache_len outside the cache");
+        const oar_lm_cfg& c = lm->cfg;
+        const double D = c.hidden, Hd = (double)c.heads * c.head_dim, Kd = (double)c.kv_heads * c.head_dim, F = c.intermediate, V = c.vocab, L = c.layers, B = n_rows, n = cache_len;
+        const double macs = L * (D * (Hd + 2 * Kd) + Hd * D + 3.0 * F * D + 2.0 * n * Hd) + V * D;
+        const double acts = 4.0 * B * (L * (2 * D + 2 * (Hd + 2 * Kd) + 2 * Hd + 3 * D + 2 * F + 2 * D) + D + 2.0 * k::lm_head_workgroups(c.vocab) + D);
+        if (flops) *flops = 2.0 * macs * B;
+        if (bytes) *bytes = lm->weight_bytes + 4.0 * B * L * 2.0 * n * Kd + acts;
+        if (n_kernels) *n_kernels = k::lm_launches_per_step(c.layers);
+    });
+}
+
+oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
+    return guard([&] {
+        OAR_CHECK(lm && req, OAR_INVALID_INPUT, "oar_lm_generate: null argument");
+        const oar_lm_cfg& c = lm->cfg;
+        const int S = req->n_seq, MN = req->max_new_tokens, D = c.hidden, V = c.vocab;
+        OAR_CHECK(S >= 1 && S <= c.max_sequences, OAR_INVALID_INPUT, "oar_lm_generate: n_seq outside 1..max_sequences");
+        OAR_CHECK(MN >= 1, OAR_INVALID_INPUT, "oar_lm_generate: max_new_tokens must be positive");
+        OAR_CHECK(req->lengths && req->tokens && req->counts && (req->inputs_embeds || req->input_ids), OAR_INVALID_INPUT, "oar_lm_generate: null lengths, outputs or inputs");
+        OAR_CHECK(req->eos_token_id >= -1 && req->eos_token_id < V, OAR_INVALID_INPUT, "oar_lm_generate: eos_token_id outside the vocabulary");
+        int64_t total = 0;
+        for (int s = 0; s < S; ++s) {
+            const int T = req->lengths[s];
+            OAR_CHECK(T >= 1 && (int64_t)T + MN <= c.max_positions, OAR_INVALID_INPUT, "oar_lm_generate: prompt length + max_new_tokens exceeds max_positions (sequence " + std::to_string(s) + ")");
+            if (req->inputs_embeds) OAR_CHECK(req->inputs_embeds[s] != nullptr, OAR_INVALID_INPUT, "oar_lm_generate: null inputs_embeds entry");
+            else {
+                OAR_CHECK(req->input_ids[s] != nullptr, OAR_INVALID_INPUT, "oar_lm_generate: null input_ids entry");
+                for (int t = 0; t < T; ++t) OAR_CHECK(req->input_ids[s][t] >= 0 && req->input_ids[s][t] < V, OAR_INVALID_INPUT, "oar_lm_generate: token id outside the vocabulary");
+            }
+            total += T;
+        }
+        OAR_CHECK(total < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: prompts too long");
+        // the schedule: prompt rows of all sequences in order, 16 to a step; then one step per generated token
+        std::vector<k::LmStep> steps;
+        std::vector<int> step_maxpos;
+        std::vector<int32_t> next_pos((size_t)S);
+        {
+            k::LmStep cur{};
+            int mp = 0, xrow = 0;
+            for (int s = 0; s < S; ++s) {
+                const int T = req->lengths[s];
+                const int32_t* pid = req->position_ids ? req->position_ids[s] : nullptr;
+                int64_t mx = pid ? INT64_MIN : T - 1;
+                for (int t = 0; t < T; ++t) {
+                    k::LmRow& R = cur.rows[cur.nrows];
+                    R.seq = s; R.pos = t; R.xrow = xrow++; R.gen = t == T - 1 ? 0 : -1; R.pad = 0;
+                    for (int a = 0; a < 3; ++a) {
+                        R.rp[a] = pid ? pid[(size_t)a * T + t] : t;
+                        OAR_CHECK(R.rp[a] >= 0 && R.rp[a] < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: position id outside 0..2^24");
+                        if (pid) mx = std::max<int64_t>(mx, R.rp[a]);
+                    }
+                    if (R.gen >= 0) cur.head[cur.nhead++] = cur.nrows;
+                    mp = std::max(mp, t);
+                    if (++cur.nrows == k::kLmRows) { steps.push_back(cur); step_maxpos.push_back(mp); cur = k::LmStep{}; mp = 0; }
+                }
+                OAR_CHECK(mx + MN < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: position id outside 0..2^24");
+                next_pos[(size_t)s] = (int32_t)(mx + 1);
+            }
+            if (cur.nrows) { steps.push_back(cur); step_maxpos.push_back(mp); }
+        }
+        const int xdec0 = (int)total;
+        for (int g = 1; g < MN; ++g) {   // the step that consumes token g - 1 and produces token g
+            k::LmStep st{};
+            int mp = 0;
+            for (int s = 0; s < S; ++s) {
+                k::LmRow& R = st.rows[st.nrows];
+                R.seq = s; R.pos = req->lengths[s] + g - 1; R.xrow = xdec0 + s; R.gen = g; R.pad = 0;
+                R.rp[0] = R.rp[1] = R.rp[2] = next_pos[(size_t)s] + g - 1;
+                st.head[st.nhead++] = st.nrows++;
+                mp = std::max(mp, R.pos);
+            }
+            steps.push_back(st); step_maxpos.push_back(mp);
+        }
+
+        std::lock_guard<std::mutex> lk(lm->mu);
+        OAR_HIP(hipSetDevice(lm->device));
+        hipStream_t s = lm->stream;
+        // per-call device memory: arena | tokens | forced | steps | ids + xrows | logits
+        auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        const size_t arena_b = align(((size_t)total + S) * D * 4), tok_b = align((size_t)S * MN * 4), steps_b = align(steps.size() * sizeof(k::LmStep)), ids_b = align((size_t)total * 4);
+        const size_t logits_b = req->logits ? align((size_t)S * MN * V * 4) : 0;
+        const size_t need = arena_b + 2 * tok_b + steps_b + 2 * ids_b + logits_b;
+        if (need > lm->work_cap) {
+            if (lm->work.p) { OAR_HIP(hipFree(lm->work.p)); lm->work.p = nullptr; lm->work_cap = 0; }
+            lm->work.alloc(need);
+            lm->work_cap = need;
+        }
+        uint8_t* w = static_cast<uint8_t*>(lm->work.p);
+        k::LmDecodeP P = lm->P;
+        P.layers = lm->layers.data();
+        P.arena = reinterpret_cast<float*>(w); P.xdec0 = xdec0;
+        P.tokens = reinterpret_cast<int32_t*>(w + arena_b);
+        int32_t* d_forced = reinterpret_cast<int32_t*>(w + arena_b + tok_b);
+        k::LmStep* d_steps = reinterpret_cast<k::LmStep*>(w + arena_b + 2 * tok_b);
+        int32_t* d_ids = reinterpret_cast<int32_t*>(w + arena_b + 2 * tok_b + steps_b);
+        int32_t* d_xrows = reinterpret_cast<int32_t*>(w + arena_b + 2 * tok_b + steps_b + ids_b);
+        P.logits = req->logits ? reinterpret_cast<float*>(w + arena_b + 2 * tok_b + steps_b + 2 * ids_b) : nullptr;
+        P.forced = req->forced_tokens ? d_forced : nullptr;
+        P.max_new = MN; P.eos = req->eos_token_id;
+        OAR_HIP(hipMemsetAsync(P.tokens, 0, (size_t)S * MN * 4, s));
+        if (P.logits) OAR_HIP(hipMemsetAsync(P.logits, 0, (size_t)S * MN * V * 4, s));
+        if (req->forced_tokens) OAR_HIP(hipMemcpyAsync(d_forced, req->forced_tokens, (size_t)S * MN * 4, hipMemcpyHostToDevice, s));
+        OAR_HIP(hipMemcpyAsync(d_steps, steps.data(), steps.size() * sizeof(k::LmStep), hipMemcpyHostToDevice, s));
+        k::LmState st0{};
+        st0.alive = S;
+        OAR_HIP(hipMemcpyAsync(P.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
+        if (req->inputs_embeds) {
+            size_t row = 0;
+            for (int q = 0; q < S; ++q) {
+                OAR_HIP(hipMemcpyAsync(P.arena + row * D, req->inputs_embeds[q], (size_t)req->lengths[q] * D * 4, hipMemcpyHostToDevice, s));
+                row += (size_t)req->lengths[q];
+            }
+        } else {
+            std::vector<int32_t> ids, xr;
+            for (int q = 0; q < S; ++q)
+                for (int t = 0; t < req->lengths[q]; ++t) { xr.push_back((int32_t)ids.size()); ids.push_back(req->input_ids[q][t]); }
+            OAR_HIP(hipMemcpyAsync(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
+            OAR_HIP(hipMemcpyAsync(d_xrows, xr.data(), xr.size() * 4, hipMemcpyHostToDevice, s));
+            OAR_HIP(hipStreamSynchronize(s));   // (the two host vectors are pageable and end with this block)
+            k::lm_embed(s, P, d_ids, d_xrows, (int)ids.size());
+        }
+        OAR_HIP(hipStreamSynchronize(s));       // (pageable sources: steps, st0)
+        for (size_t i = 0; i < steps.size(); ++i) k::lm_step(s, P, d_steps + i, steps[i].nrows, steps[i].nhead, step_maxpos[i]);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpyAsync(req->tokens, P.tokens, (size_t)S * MN * 4, hipMemcpyDeviceToHost, s));
+        if (P.logits) OAR_HIP(hipMemcpyAsync(req->logits, P.logits, (size_t)S * MN * V * 4, hipMemcpyDeviceToHost, s));
+        OAR_HIP(hipStreamSynchronize(s));
+        if (Profiler::get().enabled) Profiler::get().flush();
+        for (int q = 0; q < S; ++q) {
+            int n = MN;
+            if (req->eos_token_id >= 0)
+                for (int g = 0; g < MN; ++g)
+                    if (req->tokens[(size_t)q * MN + g] == req->eos_token_id) { n = g + 1; break; }
+            req->counts[q] = n;
+        }
+    });
+}

@@ -26,6 +26,10 @@ pub type oar_dtype = c_int;
 pub const OAR_DTYPE_F32: oar_dtype = 1;
 pub const OAR_DTYPE_I64: oar_dtype = 7;
 
+pub type oar_lm_dtype = c_int;
+pub const OAR_LM_F32: oar_lm_dtype = 1;
+pub const OAR_LM_BF16: oar_lm_dtype = 16;
+
 pub const OAR_RECT_NATIVE_SIZE: u32 = 0xFFFFFFFF;
 
 #[repr(C)]
@@ -72,6 +76,12 @@ pub struct oar_rect {
 
 #[repr(C)]
 pub struct oar_layout {
+    _private: [u8; 0],
+    _marker: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)>,
+}
+
+#[repr(C)]
+pub struct oar_lm {
     _private: [u8; 0],
     _marker: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)>,
 }
@@ -321,6 +331,51 @@ pub struct oar_ppdoc_cfg {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
+pub struct oar_lm_cfg {
+    pub hidden: i32,
+    pub layers: i32,
+    pub heads: i32,
+    pub kv_heads: i32,
+    pub head_dim: i32,
+    pub intermediate: i32,
+    pub vocab: i32,
+    pub rms_eps: f32,
+    pub rope_theta: f32,
+    pub mrope_section: [i32; 3],
+    pub qkv_bias: i32,
+    pub tie_embeddings: i32,
+    pub max_positions: i32,
+    pub max_sequences: i32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct oar_lm_tensor {
+    pub name: *const c_char,
+    pub dtype: i32,
+    pub rank: i32,
+    pub dims: [i64; 4],
+    pub data: *const c_void,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct oar_lm_request {
+    pub n_seq: i32,
+    pub lengths: *const i32,
+    pub inputs_embeds: *const *const f32,
+    pub input_ids: *const *const i32,
+    pub position_ids: *const *const i32,
+    pub max_new_tokens: i32,
+    pub eos_token_id: i32,
+    pub forced_tokens: *const i32,
+    pub logits: *mut f32,
+    pub tokens: *mut i32,
+    pub counts: *mut i32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
 pub struct oar_prof_entry {
     pub name: [c_char; 48],
     pub launches: u64,
@@ -423,6 +478,10 @@ unsafe extern "C" {
     pub fn oar_k_mha_attention(buf: *const f32, buf_floats: usize, q_off: usize, k_off: usize, v_off: usize, ldq: i32, ldk: i32, ldv: i32, n: i32, tq: i32, tk: i32, heads: i32, head_dim: i32, scale: f32, scale_pre: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_k_add_layernorm(a: *const f32, b: *const f32, b_rows: i64, gamma: *const f32, beta: *const f32, rows: i64, C: i32, eps: f32, write_sum: i32, o_io: *mut f32, o_floats: usize, y_off: usize, s_off: usize) -> oar_status;
     pub fn oar_k_relpos_attention(qkv: *const f32, b: i32, h: i32, w: i32, ws: i32, heads: i32, head_dim: i32, rh: *const f32, rw: *const f32, bqkv: *const f32, scale: f32, scale_pre: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_lm_create(cfg: *const oar_lm_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_lm) -> oar_status;
+    pub fn oar_lm_destroy(lm: *mut oar_lm);
+    pub fn oar_lm_generate(lm: *mut oar_lm, req: *const oar_lm_request) -> oar_status;
+    pub fn oar_lm_cost(lm: *const oar_lm, n_rows: i32, cache_len: i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
     pub fn oar_image_decode(bytes: *const u8, len: usize, rgb: *mut *mut u8, width: *mut u32, height: *mut u32) -> oar_status;
     pub fn oar_image_free(rgb: *mut u8);
     pub fn oar_image_decode_device(bytes: *const u8, len: usize, device_id: i32, dev_rgb: *mut *mut c_void, width: *mut u32, height: *mut u32) -> oar_status;
