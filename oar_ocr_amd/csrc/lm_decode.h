@@ -14,6 +14,10 @@ constexpr int kLmThreads = 256;      // rows / lm-head / combine kernels
 constexpr int kLmKC = 1024;          // columns of the row inputs staged in LDS at a time
 constexpr int kLmAttnThreads = 512;  // attention: 8 waves, each takes every 8th group of keys
 constexpr int kLmAttnWaves = kLmAttnThreads / 64;
+constexpr int kLmAttnUnroll = 4;     // attention: turns of a wave whose keys and values are loaded before the first is used
+constexpr int kLmWaves = kLmThreads / 64;
+constexpr int kLmR = 2;              // matrix rows a wave of the rows kernels owns at a time (a rotary or gate / up pair)
+constexpr int kLmTargetWgs = 512;    // rows kernels: a workgroup takes as many row groups (kLmWaves x kLmR rows each) as keep the grid at about this size
 constexpr int kLmMaxDh = 128, kLmMinDh = 8;
 constexpr int kLmMaxGT = 8;          // query heads of one kv head that a workgroup serves at once (a larger group takes several workgroups)
 
@@ -52,6 +56,12 @@ inline size_t lm_rows_static_lds_bytes() { return 16 * 4 + 4 * 16 * 4 * 2; }
 inline size_t lm_attn_lds_bytes() { return (size_t)kLmAttnWaves * kLmMaxGT * (kLmMaxDh + 2) * 4; }
 inline bool lm_head_dim_supported(int dh) { return dh >= kLmMinDh && dh <= kLmMaxDh && dh % 4 == 0; }
 inline int lm_launches_per_step(int L) { return 5 * L + 2; }
+// rows kernels over an [N][K] matrix: row groups per workgroup, and workgroups
+inline int lm_groups_for(int N) { const int per = kLmWaves * kLmR; const int g = (N + per * kLmTargetWgs - 1) / (per * kLmTargetWgs); return g > 1 ? g : 1; }
+inline int lm_wgs_for(int N) { const int rows = lm_groups_for(N) * kLmWaves * kLmR; return (N + rows - 1) / rows; }
+// attention: lanes that hold one key (the power of two >= dh / 4, at least 2), and keys a wave takes per turn
+constexpr int lm_attn_lanes_per_key(int dh) { int lpk = 2; while (lpk * 4 < dh) lpk <<= 1; return lpk; }   // (constexpr: the kernel calls it too)
+constexpr int lm_attn_keys_per_wave(int dh) { return 64 / lm_attn_lanes_per_key(dh); }
 int lm_head_workgroups(int V);
 
 void lm_embed(ihipStream_t* s, const LmDecodeP& p, const int32_t* ids, const int32_t* xrows, int n);   // arena[xrows[i]] = E[ids[i]]

@@ -29,8 +29,6 @@ namespace k {
 
 namespace {
 
-constexpr int kLmWaves = kLmThreads / 64, kLmR = 2, kLmTargetWgs = 512;
-
 enum : int { LM_PLAIN = 0, LM_QKV = 1, LM_GATE = 2, LM_HEAD = 3 };
 
 struct LmRowsP {
@@ -269,8 +267,7 @@ __global__ __launch_bounds__(kLmAttnThreads) void lm_attn_kernel(LmAttnP p) {
     const int kvh = (int)blockIdx.x, b = (int)blockIdx.y, g0 = (int)blockIdx.z * GT;
     const LmRow& R = p.st->rows[b];
     const int dh = p.dh, G = p.H / p.KVH, n = R.pos + 1;
-    int lpk = 2;
-    while (lpk * 4 < dh) lpk <<= 1;
+    const int lpk = lm_attn_lanes_per_key(dh);
     const int kpw = 64 / lpk, d4 = lane & (lpk - 1), grp = lane / lpk;
     const bool din = d4 * 4 < dh;
     float4 qv[GT], acc[GT];
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(kLmAttnThreads) void lm_attn_kernel(LmAttnP p) {
     const size_t base = ((size_t)R.seq * p.KVH + kvh) * p.maxpos * dh;
     const float* kb = p.kc + base;
     const float* vb = p.vc + base;
-    constexpr int U = 4;   // turns whose keys and values are loaded before the first is used (the same order of keys as one turn at a time)
+    constexpr int U = kLmAttnUnroll;   // turns whose keys and values are loaded before the first is used (the same order of keys as one turn at a time)
     const int turn = kLmAttnWaves * kpw;
     for (int j0 = wave * kpw; j0 < n; j0 += U * turn) {   // (uniform over the wave)
         float4 kk[U], vv[U];
@@ -435,11 +432,8 @@ __global__ __launch_bounds__(kLmThreads) void lm_embed_kernel(const void* embed,
     for (int i = (int)threadIdx.x; i < D; i += kLmThreads) x[i] = embed_at(embed, bf16, (size_t)tok * Kp + i);
 }
 
-int groups_for(int N) {   // row groups per workgroup: about kLmTargetWgs workgroups
-    const int per = kLmWaves * kLmR;
-    return std::max(1, (N + per * kLmTargetWgs - 1) / (per * kLmTargetWgs));
-}
-int wgs_for(int N) { const int rows = groups_for(N) * kLmWaves * kLmR; return (N + rows - 1) / rows; }
+int groups_for(int N) { return lm_groups_for(N); }   // row groups per workgroup: about kLmTargetWgs workgroups
+int wgs_for(int N) { return lm_wgs_for(N); }
 
 template <int MODE, typename WT, int NB>
 void launch_rows_nb(hipStream_t s, const LmRowsP& p, int wgs, size_t lds) {

@@ -1,7 +1,8 @@
 """vl.CausalLM (lm_decode.hip) against the f64 torch reference (synth/lm_reference.py): teacher-forced logits within the reference's own f32 noise, exact greedy tokens
 on greedy-safe seeds, and the two properties the kernels promise -- a row's result does not depend on the rows it shares a step with, and two runs give the same bytes.
 
-Cases A-D and why they are what they are: synth/lm_reference.py CASES.  Case D runs as specified: the rows kernels stage 1024 columns at a time (not 768), and D = 1544 /
+Cases A-D, E-H (3, 7, 8 and 12 query heads per kv head, idle lanes), V and W (several row groups per workgroup) and why they are what they are: synth/lm_reference.py
+CASES; long caches, equal maxima and the end of generation: tests/test_gpu_lm_paths.py.  Case D runs as specified: the rows kernels stage 1024 columns at a time (not 768), and D = 1544 /
 F = 1540 are still above one staging chunk and no multiples of it."""
 import ctypes as C
 

@@ -58,7 +58,15 @@ def _full_forward(case, weights, x, pos3):
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_cached_forward_equals_the_full_recomputation(name):
     """The step-by-step forward with its cache (prompt chunk, then one position at a time) against the uncached full-sequence forward over prompt + generated tokens."""
-    ref = R.reference_for(name)
+    _cached_equals_full(name, R.reference_for(name))
+
+
+@pytest.mark.parametrize("name", list(R.LONG_CASES))
+def test_cached_forward_equals_the_full_recomputation_on_long_caches(name):
+    _cached_equals_full(name, R.long_reference_for(name))
+
+
+def _cached_equals_full(name, ref):
     case, weights = ref["case"], ref["weights"]
     for (emb, pos, _), (toks, logits) in zip(ref["prompts"], ref["runs"]):
         T, n = emb.shape[0], 8
@@ -128,6 +136,120 @@ def test_seeds_are_greedy_safe(name):
     toks = ref["runs"][1][0]
     if name == "A":
         assert toks[5] not in toks[:5]
+
+
+@pytest.mark.parametrize("name", list(R.LONG_CASES))
+def test_long_cache_seeds_are_greedy_safe(name):
+    """The same condition for the long-cache cases: both sequences (T positions and its one-position step mate), every one of the LONG_STEPS steps."""
+    ref = R.long_reference_for(name)
+    assert [p[0].shape[0] for p in ref["prompts"]] == [ref["T"], 1]
+    for (emb, pos, _), (toks, logits) in zip(ref["prompts"], ref["runs"]):
+        m = R.greedy_margins(logits)
+        print(f"case {name} T={emb.shape[0]}: noise {ref['noise']:.3e} tol {ref['tol']:.3e} least margin {m.min():.3e} = {m.min() / ref['tol']:.1f} x tol")
+        assert len(toks) == R.LONG_STEPS and m.min() > 4 * ref["tol"]
+    assert ref["tol"] >= 2.0 ** -19 and ref["noise"] > 0
+    emb, pos, _ = ref["prompts"][0]
+    T = ref["T"]
+    pre = (T - 12) // 2
+    assert 0 < pre and pre + 12 < T and len(set(pos[:, pre + 5].tolist())) > 1          # the image block sits in the middle
+
+
+@pytest.mark.parametrize("name", list(R.LONG_CASES))
+def test_a_dropped_key_at_any_loop_boundary_moves_the_long_cache_logits(name):
+    """A condition on the inputs: an attention loop that lost one key -- the last of a wave's first turn, the first of the next wave, of the next unrolled turn, of the next
+    outer iteration, or the newest prompt key -- must be visible.  For every such key j the skip_key variant moves the teacher-forced f64 logits by more than 20 tol."""
+    ref = R.long_reference_for(name)
+    case, T, tol = ref["case"], ref["T"], ref["tol"]
+    (kpw, turn, ut), js = R.attn_boundaries(case.head_dim, T)
+    assert {kpw - 1, kpw, turn - 1, turn, T - 1} <= set(js) or turn >= T
+    emb, pos, _ = ref["prompts"][0]
+    toks, logits = ref["runs"][0]
+    least = None
+    for j in js:
+        _, bad = R.RefLM(case, ref["weights"], torch.float64, skip_key=j).generate(inputs_embeds=emb, position_ids=pos, max_new_tokens=R.LONG_STEPS, forced_tokens=toks)
+        moved = float((bad - logits).abs().max())
+        least = (moved, j) if least is None or moved < least[0] else least
+        assert moved > 20 * tol, (name, j, moved / tol)
+    print(f"case {name} head size {case.head_dim} T={T}: kpw {kpw} turn {turn} U x turn {ut}, keys {js}: least skip_key movement {least[0] / tol:.0f} x tol at j = {least[1]}")
+
+
+def test_skip_key_changes_only_rows_beyond_the_key():
+    ref = R.reference_for("A")
+    emb, pos, _ = ref["prompts"][2]
+    x, p3 = torch.from_numpy(emb).double(), torch.from_numpy(pos).long()
+    good = R.RefLM(ref["case"], ref["weights"]).forward_chunk(x, p3, [None] * ref["case"].L)
+    bad = R.RefLM(ref["case"], ref["weights"], skip_key=20).forward_chunk(x, p3, [None] * ref["case"].L)
+    assert torch.equal(good[:21], bad[:21]) and all(float((good[t] - bad[t]).abs().max()) > 0 for t in range(21, 37))
+
+
+def test_the_new_cases_take_the_kernel_paths_their_comments_name():
+    """The arithmetic of lm_decode.hip's grids and loops, from its own header (compiled for the host), at the shapes of the cases."""
+    cs = R.CASES
+    V, W = cs["V"], cs["W"]
+    g = R.kernel_geometry((V.vocab, 2 * W.F, W.D, 8192 // 2, 3080))
+    per = g["waves"] * g["rows_per_wave"]
+    # query heads per kv head: 1 / 2 run <1> / <2>, 3 .. 7 run <4>, 8 and more <8>, ceil(G / GT) chunks along gridDim.z
+    G = {n: c.heads // c.kv_heads for n, c in cs.items()}
+    assert (G["E"], G["F"], G["G"], G["H"]) == (8, 7, 3, 12) and g["max_gt"] == 8
+    assert G["F"] % 4 == 3 and G["G"] < 4 and G["H"] % 8 == 4                 # a partial chunk of heads in F (the second), G (the only one) and H (the second of <8>)
+    assert max(G[n] for n in "ABCD") == 2                                     # what the first four cases left out
+    idle = lambda dh: 64 // g["kpw"][dh] - dh // 4                              # noqa: E731  lanes of a key's lane group beyond the head size
+    assert idle(cs["G"].head_dim) == 3 and 64 // g["kpw"][20] == 8 and [idle(c.head_dim) for c in (cs["A"], cs["B"], cs["C"], cs["D"], cs["E"], cs["F"])] == [0] * 6
+    assert idle(R.LONG_CASES["LB"][0].head_dim) == 12 and idle(R.LONG_CASES["LE"][0].head_dim) == 1 and idle(R.LONG_CASES["LC"][0].head_dim) == 3
+    # rows kernels: one row group up to N = per x 512; the largest N of the first four cases (2 F of D) stays below
+    assert g["rows"][8192 // 2] == (1, 512) and g["rows"][3080][0] == 1 and per == 8
+    # V: the lm-head has 3 row groups per workgroup, 417 workgroups, so lm_combine's 256 threads stride over the partials; K = 32 is staged once
+    assert g["rows"][V.vocab] == (3, 417) and 417 > g["threads"] and V.D <= g["kc"] and not V.tie
+    # W: gate / up has 2 row groups and K = D = 1028 is two staging chunks (1024 + 4), restaged per group; the down projection's K = F = 2052 ends in 4 columns as well
+    assert g["rows"][2 * W.F] == (2, 257)
+    assert g["kc"] < W.D < 2 * g["kc"] and W.D % g["kc"] == 4 and W.F % g["kc"] == 4 and g["rows"][W.D][0] == 1
+    # equal maxima: the five places of a pair
+    d = R.tie_distances()
+    assert [d[k] for k in R.TIE_PLACES] == [1, 2, 8, 24, 4992, 16, 48, 9984]
+    # far: workgroup w and w + 208 hold a pair, which two different threads of lm_combine read; 9984 pairs the last workgroup (416) with the first
+    assert d["far_workgroup"] % (3 * per) == 0 and 0 < (d["far_workgroup"] // (3 * per)) % g["threads"] and d["d9984"] == 416 * 3 * per < V.vocab
+
+
+@pytest.mark.parametrize("name", list(R.LONG_CASES))
+def test_the_long_cases_cross_the_boundaries_of_the_key_loop(name):
+    """Row r of a step attends n = p_r + 1 keys; the forced steps take n from T to T + LONG_STEPS - 1.  That range crosses a multiple of U x turn, or of turn where
+    U x turn lies beyond what a test can pin; the one-position mate has n = 1 .. LONG_STEPS in the same steps."""
+    case, T = R.LONG_CASES[name]
+    (kpw, turn, ut), _ = R.attn_boundaries(case.head_dim, T)
+    lo, hi = T, T + R.LONG_STEPS - 1
+    b = ut if ut <= hi else turn
+    assert any(lo <= m < hi for m in range(b, hi + 1, b)), (name, kpw, turn, ut, T)
+    assert hi > turn                                                               # all eight waves hold keys
+    if name in ("LA", "LB", "LC"):
+        assert hi > 2 * ut                                                         # a second and a third outer iteration
+    else:
+        assert turn < hi <= ut and hi > (hi // turn) * turn                        # one outer iteration whose unroll is used in part: the `break`
+    print(f"case {name}: head size {case.head_dim} kpw {kpw} turn {turn} U x turn {ut}; n = {lo} .. {hi} crosses {[m for m in range(b, hi + 1, b) if lo <= m < hi]}")
+
+
+@pytest.mark.parametrize("place", R.TIE_PLACES)
+def test_equal_maxima_models_keep_the_winning_pair_clear_of_the_rest(place):
+    """A condition on the inputs of the equal-maxima GPU test: with lm-head rows paired d apart, the f64 margin between the winning pair and the best other row exceeds
+    4 tol at every forced step, and the forced tokens are the lower row of their pair."""
+    d = R.tie_distances()[place]
+    ref = R.tie_reference_for(d)
+    canon, w = ref["canon"], ref["weights"]["lm_head.weight"]
+    assert np.array_equal(w, w[canon]) and (canon <= np.arange(len(canon))).all() and int((canon != np.arange(len(canon))).sum()) >= (len(canon) - d) // 2
+    least = min(float(R.pair_margins(l64, canon).min()) for _, l64 in ref["runs"])
+    print(f"equal maxima {place} d={d}: noise {ref['noise']:.3e} tol {ref['tol']:.3e} least pair margin {least / ref['tol']:.1f} x tol")
+    assert least > 4 * ref["tol"] and ref["tol"] >= 2.0 ** -19 and ref["noise"] > 0
+    for t64, _ in ref["runs"]:
+        assert np.array_equal(canon[t64], t64)
+    if place != "d9984":      # (9984 pairs 23 rows only: its winners are single rows, and the test pins the pairs' logits)
+        assert any((t64 + d < len(canon)).any() for t64, _ in ref["runs"])          # winners that do have a copy, d rows up
+
+
+def test_an_eos_exists_that_ends_every_sequence_early():
+    pick = R.all_end_choice(R.reference_for("A"))
+    assert pick is not None
+    i, j, eos, nj = pick
+    ti, tj = R.reference_for("A")["runs"][i][0], R.reference_for("A")["runs"][j][0]
+    assert ti[0] == eos and tj[nj - 1] == eos and eos not in tj[:nj - 1] and 1 < nj < R.FREE_STEPS
 
 
 def test_position_ids_have_three_different_axes_and_end_below_T():
