@@ -574,6 +574,22 @@ oar_status oar_k_rotate_crop(const uint8_t* rgb, uint32_t w, uint32_t h, const f
 oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off, size_t k_off, size_t v_off, int32_t ldq, int32_t ldk, int32_t ldv,
                                int32_t n, int32_t tq, int32_t tk, int32_t heads, int32_t head_dim, float scale, int32_t scale_pre,
                                float* o_io, size_t o_floats, size_t o_off);
+/* The attention of one layer of the PaddleOCR-VL vision encoder (vis_attention.hip) on a packed sequence: n_segs images back to back,
+ * image i being seg_lens[i] rows, t = sum of seg_lens.  Row r of the fused projection is buf[qkv_off + r ld ...]: q [heads][head_dim], then k, then v
+ * (ld >= 3 heads head_dim).  cos_tab / sin_tab are [t][head_dim / 2]: q and k are rotated as
+ * x'[c] = x[c] cos[c] - x[c + head_dim/2] sin[c], x'[c + head_dim/2] = x[c + head_dim/2] cos[c] + x[c] sin[c], and
+ * o = softmax(head_dim^-0.5 q' k'^T) v with the keys of the query's own image only.  o_io / o_floats / o_off as for oar_k_mha_attention, the output
+ * being [t][heads head_dim] in token order.  Nothing is launched unless every check passes: OAR_UNSUPPORTED_OP for a head_dim that is no multiple
+ * of 8 in 8..80; OAR_INVALID_INPUT for a null buffer, heads < 1, n_segs < 1, an empty segment, an offset or ld that is no multiple of 4 floats, ld below
+ * 3 heads head_dim, or a view that does not fit its buffer. */
+oar_status oar_k_vis_attention(const float* buf, size_t buf_floats, size_t qkv_off, int32_t ld, const int32_t* seg_lens, int32_t n_segs, int32_t heads,
+                               int32_t head_dim, const float* cos_tab, const float* sin_tab, float* o_io, size_t o_floats, size_t o_off);
+/* The learned position table of that encoder resampled to every image's grid (vis_misc.hip): table [pos_grid^2][hidden], grids [n_images][2] = (h, w);
+ * bilinear with align_corners = false, the source coordinate ((o + 0.5) pos_grid / out - 0.5) formed in f32 and clamped to [0, pos_grid - 1], the four
+ * weights wy wx, the sum in the order 00, 01, 10, 11.  h = w = pos_grid returns the table itself.  o_io / o_floats / o_off as above, the output being
+ * [sum h w][hidden].  OAR_INVALID_INPUT: a null pointer, pos_grid outside 1..1024, hidden no multiple of 4, n_images outside 1..16, a grid side < 1,
+ * o_off no multiple of 4 floats, or an output that does not fit o_floats. */
+oar_status oar_k_vis_pos_embed(const float* table, int32_t pos_grid, int32_t hidden, const int32_t* grids, int32_t n_images, float* o_io, size_t o_floats, size_t o_off);
 /* Residual add + LayerNorm over the last axis as the engine's one launch (add_layernorm.hip): s = a + b in f32, y = LN(s) gamma + beta.
  * a is [rows][C]; row r of b is b[(r % b_rows) C ...] with b_rows dividing rows (b_rows = rows: the same shape; = T: a [1, T, C] table; = 1: a [C]
  * vector); gamma and beta are [C] or NULL.  o_io / o_floats as above: uploaded whole, y written as [rows][C] from float y_off on and, when
@@ -597,7 +613,7 @@ oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_
  * The decoder-only language model of the oar-ocr-vl crate (PaddleOCR-VL's ERNIE-4.5 text decoder, oar-ocr-vl/src/models/paddleocr_vl/ernie.rs; the
  * Qwen2-VL family differs in configuration only): RMSNorm, M-RoPE (runtime/attention.rs select_rope_sections), grouped-query attention over a
  * key / value cache, SwiGLU MLP, greedy argmax (lowest index among equal maxima).  Prefill and decode run the same chain of 5 layers + 2 HIP launches
- * per step of <= 16 rows (lm_decode.hip).  Not built: the vision encoder, the projector, the tokenizer, sampling.                        */
+ * per step of <= 16 rows (lm_decode.hip).  Not built: the tokenizer, sampling (the vision stage: below).                                    */
 typedef struct oar_lm oar_lm;
 typedef enum { OAR_LM_F32 = 1, OAR_LM_BF16 = 16 } oar_lm_dtype;
 typedef struct {
@@ -646,6 +662,45 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req);
 /* Analytic cost of ONE step of n_rows rows (1 .. 16) whose sequences hold cache_len positions: bytes = every weight once (in its stored dtype) +
  * the cache rows read + the row buffers; flops = 2 x MACs; n_kernels = 5 layers + 2. */
 oar_status oar_lm_cost(const oar_lm* lm, int32_t n_rows, int32_t cache_len, double* flops, double* bytes, int32_t* n_kernels);
+
+/* ------------------------------------------------------------------------------------------------ VL: the vision stage
+ * The vision encoder and projector of the oar-ocr-vl crate's PaddleOCR-VL (vision.rs, projector.rs): a SigLIP-style pre-LN ViT over the patches of an
+ * image (patch Linear + bilinearly resampled position table; per layer LayerNorm, fused q / k / v Linear, attention with 2-D rotary embedding, out_proj +
+ * residual, LayerNorm, fc1 + GELU, fc2 + residual; post_layernorm), then mlp_AR: LayerNorm (eps 1e-5), merge x merge blocks of patches concatenated in
+ * the order (hb, wb, mi, mj, d), linear_1 + erf-GELU, linear_2.  All images of a call are packed back to back; they do not see each other.
+ * Not built: the tokenizer, the chat template, sampling.                                                                                              */
+typedef struct oar_vis oar_vis;
+typedef enum { OAR_VIS_GELU_TANH = 0, OAR_VIS_GELU_ERF = 1 } oar_vis_act;
+typedef struct {
+    int32_t hidden, layers, heads, intermediate, patch, channels, pos_grid, merge, text_hidden;
+    float ln_eps;
+    int32_t act;                 /* oar_vis_act: the encoder MLP's activation (the projector's is always the erf GELU)                */
+    float rope_theta;            /* 10000                                                                                            */
+    int32_t max_tokens;          /* patches per call: the device buffers are allocated once, at create                               */
+    int32_t max_images;          /* 1 .. 16                                                                                          */
+} oar_vis_cfg;
+/* tensors: the checkpoint's own names, "visual.vision_model.embeddings.patch_embedding.{weight [hidden, channels, patch, patch], bias}",
+ * "visual.vision_model.embeddings.position_embedding.weight" [pos_grid^2, hidden], "visual.vision_model.encoder.layers.{i}.layer_norm{1,2}.{weight,bias}",
+ * ".self_attn.{q,k,v,out}_proj.{weight,bias}", ".mlp.fc{1,2}.{weight,bias}", "visual.vision_model.post_layernorm.{weight,bias}",
+ * "mlp_AR.pre_norm.{weight,bias}", "mlp_AR.linear_{1,2}.{weight,bias}".  f32 or bf16; bf16 is widened to f32 at upload (the matrix formats are built
+ * from f32), so a bf16 checkpoint computes exactly what the same values given as f32 compute.  Other names are ignored.  Each Linear's weight format
+ * is chosen once, from (max_tokens, K, N).  OAR_INVALID_INPUT: an inconsistent configuration (sizes <= 0, hidden % heads, channels patch^2, hidden or
+ * intermediate no multiple of 4, max_images outside 1..16), a missing tensor, a wrong shape or dtype; OAR_UNSUPPORTED_OP: a head size that is no
+ * multiple of 8 in 8..80.  All of that is reported before the device is touched. */
+oar_status oar_vis_create(const oar_vis_cfg* cfg, const oar_lm_tensor* tensors, int32_t n_tensors, int32_t device_id, oar_vis** out);
+void oar_vis_destroy(oar_vis* vis);
+typedef struct {
+    int32_t n_images;            /* 1 .. cfg.max_images                                                                               */
+    const int32_t* grids;        /* [n_images][2] = (h, w) in patches, each a multiple of cfg.merge; sum h w <= cfg.max_tokens         */
+    const float* pixel_values;   /* [sum h w][channels patch patch], a patch in (c, dy, dx) order                                     */
+    float* embeds;               /* out [sum h w / merge^2][text_hidden]                                                              */
+    float* features;             /* NULL, or out [sum h w][hidden]: post_layernorm's output, in front of the projector                */
+} oar_vis_request;
+/* Every argument is checked before anything is launched (OAR_INVALID_INPUT). */
+oar_status oar_vis_encode(oar_vis* vis, const oar_vis_request* req);
+/* Analytic cost of one call over these grids: flops = 2 x MACs of the Linears and the attention, bytes = every weight once + the activations each
+ * launch reads and writes, n_kernels = 7 per layer (8 with the tanh GELU, which is a launch of its own) + 2 (embedding) + 1 (post_layernorm) + 4 (projector). */
+oar_status oar_vis_cost(const oar_vis* vis, int32_t n_images, const int32_t* grids_hw, double* flops, double* bytes, int32_t* n_kernels);
 
 /* ------------------------------------------------------------------------------------------------ image decode
  * load_image_from_memory (oar-ocr-core/src/utils/image.rs:65-68: image::load_from_memory + DynamicImage::to_rgb8) for the

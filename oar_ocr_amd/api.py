@@ -153,8 +153,9 @@ EXPORTS = [
     "oar_engine_cache_stats", "oar_onnx_inspect", "oar_host_contours", "oar_ctc_dict_create", "oar_ctc_dict_destroy", "oar_ctc_dict_classes",
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
-    "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm",
+    "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm", "oar_k_vis_attention", "oar_k_vis_pos_embed",
     "oar_lm_create", "oar_lm_destroy", "oar_lm_generate", "oar_lm_cost",
+    "oar_vis_create", "oar_vis_destroy", "oar_vis_encode", "oar_vis_cost",
 ]
 
 
@@ -236,6 +237,8 @@ def lib():
                                       C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_relpos_attention.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, C.c_int32, vp, C.c_size_t,
                                          C.c_size_t]
+    L.oar_k_vis_attention.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_size_t, C.c_size_t]
+    L.oar_k_vis_pos_embed.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_add_layernorm.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t, C.c_size_t]
     L.oar_image_decode.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.oar_image_free.argtypes = [C.POINTER(C.c_uint8)]
@@ -1672,6 +1675,40 @@ def k_mha_attention(buf, q_off, k_off, v_off, ldq, ldk, ldv, n, tq, tk, heads, h
     out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
     _check(lib().oar_k_mha_attention(_p(buf), buf.size, q_off, k_off, v_off, ldq, ldk, ldv, n, tq, tk, heads, head_dim, scale, int(bool(scale_pre)),
                                      _p(out), out.size, o_off))
+    return out
+
+
+def k_vis_attention(buf, qkv_off, ld, seg_lens, heads, head_dim, cos, sin, o_io, o_off):
+    """vis_attention.hip on a packed sequence: row r of the fused projection is buf[qkv_off + r ld ...] (q, k, v of all heads), seg_lens the images'
+    token counts, cos / sin [sum(seg_lens), head_dim / 2].  o_io as in k_mha_attention, the output being [sum(seg_lens)][heads head_dim] from o_off on.
+    The library cannot see the lengths of seg_lens and the tables, so the tables are checked here (ValueError); None reaches it as a null pointer."""
+    buf = None if buf is None else np.ascontiguousarray(buf, np.float32).reshape(-1)
+    lens = None if seg_lens is None else np.ascontiguousarray(seg_lens, np.int32).reshape(-1)
+    want = 0 if lens is None else int(np.maximum(lens, 0).sum()) * (head_dim // 2)
+
+    def tab(a, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        if a.size != want:
+            raise ValueError(f"k_vis_attention: {name} has {a.size} floats, the segments need {want}")
+        return a
+    cos, sin = tab(cos, "cos"), tab(sin, "sin")
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    ptr = lambda a: None if a is None else _p(a)
+    _check(lib().oar_k_vis_attention(ptr(buf), 0 if buf is None else buf.size, qkv_off, ld, ptr(lens), 0 if lens is None else lens.size, heads, head_dim,
+                                     ptr(cos), ptr(sin), _p(out), out.size, o_off))
+    return out
+
+
+def k_vis_pos_embed(table, pos_grid, grids, o_io, o_off):
+    """vis_misc.hip: table [pos_grid^2, hidden] resampled to grids [n, 2] = (h, w); o_io as in k_mha_attention, the output being [sum h w][hidden] from o_off on."""
+    table = np.ascontiguousarray(table, np.float32)
+    if table.ndim != 2 or table.shape[0] != pos_grid * pos_grid:
+        raise ValueError(f"k_vis_pos_embed: the table has shape {table.shape}, pos_grid {pos_grid} needs [{pos_grid * pos_grid}, hidden]")
+    g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    _check(lib().oar_k_vis_pos_embed(_p(table), pos_grid, table.shape[1], _p(g) if g.size else None, g.shape[0], _p(out), out.size, o_off))
     return out
 
 

@@ -1244,6 +1244,85 @@ oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off
     });
 }
 
+// The vision encoder's attention (vis_attention.hip) on a packed sequence: the same order of checks, and the segment and tile tables are built here.
+oar_status oar_k_vis_attention(const float* buf, size_t buf_floats, size_t qkv_off, int32_t ld, const int32_t* seg_lens, int32_t n_segs, int32_t heads,
+                               int32_t head_dim, const float* cos_tab, const float* sin_tab, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(buf && o_io && seg_lens && cos_tab && sin_tab, OAR_INVALID_INPUT, "oar_k_vis_attention: null buffer");
+        OAR_CHECK(heads >= 1 && heads < (1 << 20), OAR_INVALID_INPUT, "oar_k_vis_attention: heads outside 1..2^20");
+        OAR_CHECK(k::vis_attention_supported(heads, head_dim), OAR_UNSUPPORTED_OP, "oar_k_vis_attention: head_dim must be a multiple of 8 in 8..80");
+        OAR_CHECK(n_segs >= 1 && n_segs <= (1 << 16), OAR_INVALID_INPUT, "oar_k_vis_attention: n_segs outside 1..65536");
+        const int64_t D = (int64_t)heads * head_dim, lim = (int64_t)1 << 31;
+        int64_t T = 0;
+        for (int32_t i = 0; i < n_segs; ++i) {
+            OAR_CHECK(seg_lens[i] >= 1, OAR_INVALID_INPUT, "oar_k_vis_attention: an empty segment");
+            T += seg_lens[i];
+        }
+        OAR_CHECK(T < lim && k::vis_attention_tile_count(seg_lens, n_segs, heads) < lim, OAR_INVALID_INPUT, "oar_k_vis_attention: token or workgroup count above 2^31");
+        OAR_CHECK(ld >= 3 * D && (ld & 3) == 0, OAR_INVALID_INPUT, "oar_k_vis_attention: the row stride is below 3 heads head_dim or no multiple of 4");
+        OAR_CHECK(((qkv_off | o_off) & 3) == 0, OAR_INVALID_INPUT, "oar_k_vis_attention: an offset is no multiple of 4 floats");
+        OAR_CHECK(view_fits(qkv_off, T, ld, 3 * D, buf_floats), OAR_INVALID_INPUT, "oar_k_vis_attention: the qkv view does not fit buf_floats");
+        OAR_CHECK(view_fits(o_off, T, D, D, o_floats), OAR_INVALID_INPUT, "oar_k_vis_attention: the output does not fit o_floats");
+        const int n_tiles = (int)k::vis_attention_tile_count(seg_lens, n_segs, heads);
+        std::vector<k::VisSeg> segs((size_t)n_segs);
+        std::vector<k::VisTile> tiles((size_t)n_tiles);
+        k::vis_attention_tables(seg_lens, n_segs, heads, segs.data(), tiles.data());
+        const size_t tab = (size_t)T * (head_dim / 2) * 4;
+        require_device();
+        DevBuf din, dout, dcos, dsin, dsegs, dtiles;
+        din.reserve(buf_floats * 4); dout.reserve(o_floats * 4); dcos.reserve(tab); dsin.reserve(tab);
+        dsegs.reserve(segs.size() * sizeof(k::VisSeg)); dtiles.reserve(tiles.size() * sizeof(k::VisTile));
+        OAR_HIP(hipMemcpy(din.p, buf, buf_floats * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dcos.p, cos_tab, tab, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dsin.p, sin_tab, tab, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dsegs.p, segs.data(), segs.size() * sizeof(k::VisSeg), hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dtiles.p, tiles.data(), tiles.size() * sizeof(k::VisTile), hipMemcpyHostToDevice));
+        k::VisAttnP p{};
+        p.qkv = din.as<float>() + qkv_off; p.cos = dcos.as<float>(); p.sin = dsin.as<float>();
+        p.o = dout.as<float>() + o_off;
+        p.segs = dsegs.as<k::VisSeg>(); p.tiles = dtiles.as<k::VisTile>();
+        p.n_tiles = n_tiles; p.nh = heads; p.dh = head_dim; p.ld = ld;
+        p.scale = (float)std::pow((double)head_dim, -0.5);
+        double bytes = 0.0, flops = 0.0;
+        k::vis_attention_cost(seg_lens, n_segs, heads, head_dim, &bytes, &flops);
+        k::vis_attention(nullptr, p, bytes, flops);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// The position table of the vision encoder resampled to every image's grid (vis_misc.hip): table [pos_grid^2][hidden], grids [n_images][2] = (h, w).
+oar_status oar_k_vis_pos_embed(const float* table, int32_t pos_grid, int32_t hidden, const int32_t* grids, int32_t n_images, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(table && grids && o_io, OAR_INVALID_INPUT, "oar_k_vis_pos_embed: null table, grids or o_io");
+        OAR_CHECK(pos_grid >= 1 && pos_grid <= 1024 && hidden >= 4 && hidden % 4 == 0 && hidden < (1 << 20), OAR_INVALID_INPUT, "oar_k_vis_pos_embed: pos_grid outside 1..1024 or hidden no multiple of 4");
+        OAR_CHECK(n_images >= 1 && n_images <= k::kVisMaxImages, OAR_INVALID_INPUT, "oar_k_vis_pos_embed: n_images outside 1..16");
+        OAR_CHECK((o_off & 3) == 0, OAR_INVALID_INPUT, "oar_k_vis_pos_embed: o_off is no multiple of 4 floats");
+        k::VisGrids g{};
+        g.n = n_images;
+        int64_t total = 0;
+        for (int32_t i = 0; i < n_images; ++i) {
+            const int64_t h = grids[2 * i], w = grids[2 * i + 1];
+            OAR_CHECK(h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), OAR_INVALID_INPUT, "oar_k_vis_pos_embed: a grid side outside 1..32768");
+            g.start[i] = (int)total; g.h[i] = (int)h; g.w[i] = (int)w;
+            total += h * w;
+            OAR_CHECK(total * (hidden / 4) < ((int64_t)1 << 31), OAR_INVALID_INPUT, "oar_k_vis_pos_embed: too many elements");
+        }
+        g.start[n_images] = (int)total;
+        OAR_CHECK(view_fits(o_off, total, hidden, hidden, o_floats), OAR_INVALID_INPUT, "oar_k_vis_pos_embed: the output does not fit o_floats");
+        const size_t tab = (size_t)pos_grid * pos_grid * hidden * 4;
+        require_device();
+        DevBuf dt, dout;
+        dt.reserve(tab); dout.reserve(o_floats * 4);
+        OAR_HIP(hipMemcpy(dt.p, table, tab, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        k::vis_pos_embed(nullptr, dt.as<float>(), dout.as<float>() + o_off, g, pos_grid, hidden);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 // Residual add + LayerNorm (add_layernorm.hip) on host arrays: a [rows][C], b [b_rows][C], gamma / beta [C] or NULL.  The same order of checks: arguments first,
 // the device afterwards.  Offsets need no alignment: an output that does not start on 16 bytes makes the kernel take its 4-byte form.
 oar_status oar_k_add_layernorm(const float* a, const float* b, int64_t b_rows, const float* gamma, const float* beta, int64_t rows, int32_t C, float eps,

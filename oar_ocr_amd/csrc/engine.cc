@@ -5594,6 +5594,8 @@ struct Planner {
     }
 };
 
+std::vector<float> igemm_to_fragments(int fmt, const std::vector<float>& w, int64_t rows, int64_t K) { return Planner::to_fragments(fmt, w, rows, K); }
+
 // Host-only structural checks of the initializers the load-time rewrites and the planner index by their DECLARED dims
 // (a malformed file must end in OAR_MODEL_LOAD, not in an out-of-bounds read).
 void Engine::validate_model(const OnnxModel& m) {

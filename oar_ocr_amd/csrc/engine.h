@@ -188,4 +188,8 @@ class Engine {
     void end_run(const Plan& p, bool replayed);
 };
 
+// [rows][K] row-major GEMM weights in the fragment order k::conv_igemm reads for weight format `fmt` (k::igemm_weight_format): the planner's own packing, for
+// hosts that drive conv_igemm without a graph (vis_host.cc)
+std::vector<float> igemm_to_fragments(int fmt, const std::vector<float>& w, int64_t rows, int64_t K);
+
 }  // namespace oar

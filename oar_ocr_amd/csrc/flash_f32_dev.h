@@ -63,19 +63,20 @@ __device__ __forceinline__ void flash_stage_load(float4 (&stg)[DH16], int slot, 
         stg[i] = v;
     }
 }
-template <int DH16>
+// LD: the row stride of Ks / Vs in floats, kFlashLd unless a kernel with a larger head says otherwise (vis_attention.hip: 84 at DH16 = 5)
+template <int DH16, int LD = kFlashLd>
 __device__ __forceinline__ void flash_stage_commit(const float4 (&stg)[DH16], float* dst, int slot, int st) {   // dst: Ks or Vs, as the thread's half has it
     constexpr int F4 = 4 * DH16;
 #pragma clang loop unroll(full)
     for (int i = 0; i < DH16; ++i) {
         const int idx = slot + 128 * i, kl = idx / F4, f = idx - kl * F4;
-        *reinterpret_cast<float4*>(dst + (st * kFlashKeys + kl) * kFlashLd + 4 * f) = stg[i];
+        *reinterpret_cast<float4*>(dst + (st * kFlashKeys + kl) * LD + 4 * f) = stg[i];
     }
 }
 
-// one block of kFlashKeys keys from stage st of Ks / Vs ([2][kFlashKeys][kFlashLd] each).  score(s, sc): the two raw accumulators (tile t, s[t][r]: key
+// one block of kFlashKeys keys from stage st of Ks / Vs ([2][kFlashKeys][LD] each).  score(s, sc): the two raw accumulators (tile t, s[t][r]: key
 // 16 t + 4 g + r of the block) -> the eight finished scores sc[4 t + r], -inf for a key that does not exist.
-template <int DH16, class Score>
+template <int DH16, int LD = kFlashLd, class Score>
 __device__ __forceinline__ void flash_block(const float* Ks, const float* Vs, int st, int ql, int g, const float4 (&qf)[DH16], FlashAcc<DH16>& a, Score&& score) {
     // ---- S^T = K Q^T: two 16-key tiles, two independent accumulators
     f32x4 s[2];
@@ -84,7 +85,7 @@ __device__ __forceinline__ void flash_block(const float* Ks, const float* Vs, in
     for (int c = 0; c < DH16; ++c) {
         float4 ka[2];
 #pragma clang loop unroll(full)
-        for (int t = 0; t < 2; ++t) ka[t] = *reinterpret_cast<const float4*>(Ks + (st * kFlashKeys + 16 * t + ql) * kFlashLd + 16 * c + 4 * g);
+        for (int t = 0; t < 2; ++t) ka[t] = *reinterpret_cast<const float4*>(Ks + (st * kFlashKeys + 16 * t + ql) * LD + 16 * c + 4 * g);
 #pragma clang loop unroll(full)
         for (int t = 0; t < 2; ++t) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[t].x, qf[c].x, s[t], 0, 0, 0);
 #pragma clang loop unroll(full)
@@ -116,7 +117,7 @@ __device__ __forceinline__ void flash_block(const float* Ks, const float* Vs, in
     for (int t = 0; t < 2; ++t)
 #pragma clang loop unroll(full)
         for (int r = 0; r < 4; ++r) {
-            const float* vr = Vs + (st * kFlashKeys + 16 * t + 4 * g + r) * kFlashLd + ql;
+            const float* vr = Vs + (st * kFlashKeys + 16 * t + 4 * g + r) * LD + ql;
 #pragma clang loop unroll(full)
             for (int dt = 0; dt < DH16; ++dt) a.o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vr[16 * dt], sc[4 * t + r], a.o[dt], 0, 0, 0);
         }

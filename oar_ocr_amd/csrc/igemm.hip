@@ -296,7 +296,9 @@ bool conv_igemm_se_ok(long M, int K, int N, int hw) {
     return lds <= 160 * 1024;
 }
 
-void conv_igemm(hipStream_t s, const ConvP& c) {
+bool igemm_x6_serves_any_rows(int K, int N) { return K % 8 == 0 && (N & 3) == 0 && ws_x6_tile(K, (N + 15) / 16) > 0; }
+
+void conv_igemm(hipStream_t s, const ConvP& c, const char* prof_class) {
     IgemmP p;
     p.x = c.x; p.w = c.w; p.bias = c.bias; p.res = c.residual; p.y = c.y;
     p.H = c.H; p.W = c.W; p.Cin = c.Cin; p.kh = c.kh; p.kw = c.kw; p.sh = c.sh; p.sw = c.sw;
@@ -393,6 +395,7 @@ void conv_igemm(hipStream_t s, const ConvP& c) {
     const bool lk = x6 && !c.ctc_part && !c.se && !c.convt2x2 && !is1x1 &&
                     conv_lk_x6_eligible(c.kh, c.kw, c.sh, c.sw, c.pt, c.pl, c.dh, c.dw, c.H, c.W, c.Ho, c.Wo, c.Cin, c.Cout, c.y_ld, p.M);
     const char* cls = lk ? "conv_lk_x6" : rs3_cls ? "conv_rs3_x6" : x6_os ? "conv_igemm_os_x6" : x6 ? "conv_igemm_ws_x6" : ws ? "conv_igemm_ws" : "conv_igemm";   // one profiler class per kernel
+    if (prof_class) cls = prof_class;
     if (Profiler::get().detail) {
         snprintf(pname, sizeof pname, "conv_igemm%s M=%ld K=%d N=%d k%dx%d s%d%s", lk ? "_lk_x6" : rs3_cls ? "_rs3_x6" : x6_os ? "_os_x6" : x6 ? "_x6" : ws ? "_ws" : "", p.M, p.K, p.gemm_cout, c.kh, c.kw, c.sh, c.convt2x2 ? " convT" : "");
         cls = pname;

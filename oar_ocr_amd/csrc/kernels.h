@@ -55,11 +55,15 @@ enum : int { IGEMM_W_K16 = 0, IGEMM_W_X6 = 1, IGEMM_W_X6RS = 2, IGEMM_W_X6CS = 3
 //   X6 : bf16x6 fragments Wx[cout/16][K/32][3 planes][lane][8 bf16] -> v_mfma_f32_16x16x32_bf16 x 6 (f32-equivalent),
 //        weight-stationary kernel only (wide 1x1 / Linear layers)
 // Rows are padded to 64 couts, K to the chunk size, with zeros.
-void conv_igemm(hipStream_t s, const ConvP& p);
+// prof_class: the profiler class of this launch instead of the kernel's own (null: `conv_igemm*` by kernel, as ever) -- a host that is not the engine names its Linears
+void conv_igemm(hipStream_t s, const ConvP& p, const char* prof_class = nullptr);
 // chosen per layer AND input shape at plan time: M = GEMM rows (pixels), N = couts
 // same3x3_px: pixels of ONE image when the layer is a 3x3 / stride 1 / pad 1 / dilation 1 convolution without residual (0 otherwise): the row-streaming
 // bf16x6 kernel of igemm_rs3_x6.hip takes such layers with <= 16 output channels
 int igemm_weight_format(long M, int K, int N, bool is1x1, int Cin = 0, long same3x3_px = 0, bool lk_ok = false);
+// may a 1x1 layer keep bf16x6 (IGEMM_W_X6) weights and still be launched with ANY row count?  Only where the weight-stationary bf16x6 kernel takes it (its LDS tile fits this K):
+// the output-stationary kernel, which igemm_weight_format also answers IGEMM_W_X6 for, refuses small row counts
+bool igemm_x6_serves_any_rows(int K, int N);
 // lk_ok: conv_lk_x6_eligible said yes for this layer (large-kernel same convolution from an LDS-staged halo tile, igemm_lk_x6.hip)
 bool conv_lk_x6_eligible(int kh, int kw, int sh, int sw, int pt, int pl, int dh, int dw, int H, int W, int Ho, int Wo, int Cin, int Cout, int y_ld, long M);
 // one group of a grouped k x k convolution (ConvP::x_ld) as its own implicit GEMM on the output-stationary bf16x6 kernel: M pixels, K = kh * kw * Cin_g, N = Cout_g >= 32
@@ -130,7 +134,7 @@ void resize(hipStream_t s, const float* x, float* y, int N, int H, int W, int C,
 struct ConcatGatherP { const float* x[8]; int c[8], off[8], fh[8], fw[8]; int n_src, N, Ho, Wo, C; };
 void concat_gather(hipStream_t s, const ConcatGatherP& p, float* y);
 
-void unary(hipStream_t s, const float* x, float* y, int64_t n, Act act);
+void unary(hipStream_t s, const float* x, float* y, int64_t n, Act act, const char* prof_class = nullptr);   // prof_class: as for conv_igemm
 // y = op(a, b) with numpy broadcasting over up to 6 dims. op: 0 add, 1 sub, 2 mul, 3 div, 4 pow, 5 prelu, 6 max, 7 min,
 // 8 equal, 9 less, 10 greater, 11 and, 12 or (comparisons / logic give 1.0f or 0.0f: bool tensors live as f32 on the device). Strides in elements
 // (0 for broadcast dims); output is contiguous with dims `dims`.
@@ -153,7 +157,7 @@ struct GemmP {
 };
 void gemm_batched(hipStream_t s, const GemmP& p);
 
-void layernorm(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps);
+void layernorm(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps, const char* prof_class = nullptr);   // prof_class: as for conv_igemm
 // add_layernorm.hip: s = a + b (row r of b is b[(r % b_rows) * C ...], b_rows | rows), y = LN(s) * gamma + beta; s is stored only when sum_out != null.
 // Bit-identical to binary (Add) followed by layernorm.  gamma / beta may be null; y and sum_out must not overlap a, b or each other.
 void add_layernorm(hipStream_t s, const float* a, const float* b, int64_t b_rows, const float* gamma, const float* beta, float* sum_out, float* y, int64_t rows, int C, float eps);
@@ -342,6 +346,66 @@ inline size_t mha_attention_lds_bytes(int head_dim) {
     return flash_kv_lds_bytes();
 }
 void mha_attention(hipStream_t s, const MhaAttnP& p);
+// vis_attention.hip: the attention of one layer of the PaddleOCR-VL vision encoder, one launch.  The patches of several images are packed back
+// to back as T rows; qkv [T][ld] is the fused projection (row t: q [nh][dh] at column 0, k at nh dh, v at 2 nh dh; ld >= 3 nh dh), cos / sin [T][dh / 2]
+// the rotary tables, o [T][nh dh] in token order.  Segment i is rows [start, start + len) and a query attends exactly to the keys of its own segment:
+//   q'[c] = q[c] cos[c] - q[c + dh/2] sin[c],  q'[c + dh/2] = q[c + dh/2] cos[c] + q[c] sin[c]   (c < dh/2; the same for k),  o = softmax(scale q' k'^T) v.
+// The rotation happens in registers when the q fragments are loaded and when a key block is staged; the scores are scaled after the product.
+// tiles: one (segment, head, query tile of kFlashQueries) entry per workgroup, built on the host, so the grid is flat over segments of different lengths.
+struct VisSeg { int start, len; };
+struct VisTile { int seg, head, qt, pad; };
+struct VisAttnP {
+    const float *qkv, *cos, *sin;
+    float* o;
+    const VisSeg* segs;
+    const VisTile* tiles;
+    int n_tiles, nh, dh, ld;
+    float scale;
+};
+constexpr int kVisMinDh = 8, kVisMaxDh = 80, kVisLd5 = 84;   // head_dim % 8 == 0 (the rotary partner of a float4 group is a float4 group); the LDS row stride at DH16 = 5
+inline bool vis_attention_supported(int64_t heads, int64_t head_dim) {
+    return heads >= 1 && heads < ((int64_t)1 << 20) && head_dim >= kVisMinDh && head_dim <= kVisMaxDh && head_dim % 8 == 0;
+}
+// the kernel's LDS, all of it dynamic: the K and V blocks [2][kFlashKeys][ld] each with ld = kFlashLd up to head size 64 and kVisLd5 above
+// (tests/test_vision_resources_cpu.py compiles this)
+inline size_t vis_attention_lds_bytes(int head_dim) {
+    return (size_t)4 * kFlashKeys * (head_dim > kFlashMaxDh ? kVisLd5 : kFlashLd) * sizeof(float);
+}
+inline int64_t vis_attention_tile_count(const int32_t* lens, int n_segs, int heads) {
+    int64_t n = 0;
+    for (int i = 0; i < n_segs; ++i) n += (int64_t)heads * ((lens[i] + kFlashQueries - 1) / kFlashQueries);
+    return n;
+}
+// segs [n_segs] and tiles [vis_attention_tile_count] in the order (segment, head, query tile)
+inline void vis_attention_tables(const int32_t* lens, int n_segs, int heads, VisSeg* segs, VisTile* tiles) {
+    int start = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        segs[i] = VisSeg{start, lens[i]};
+        start += lens[i];
+        for (int h = 0; h < heads; ++h)
+            for (int qt = 0; qt < (lens[i] + kFlashQueries - 1) / kFlashQueries; ++qt) *tiles++ = VisTile{i, h, qt, 0};
+    }
+}
+// what one launch moves and computes: q, o and the tables once, k and v once per query tile; 4 len^2 dh flops per (segment, head)
+inline void vis_attention_cost(const int32_t* lens, int n_segs, int heads, int head_dim, double* bytes, double* flops) {
+    double b = 0.0, f = 0.0;
+    for (int i = 0; i < n_segs; ++i) {
+        const double len = lens[i], tiles = (lens[i] + kFlashQueries - 1) / kFlashQueries;
+        b += 4.0 * heads * head_dim * len * (2.0 + 2.0 * tiles) + 4.0 * len * head_dim * (1.0 + tiles);
+        f += 4.0 * heads * len * len * head_dim;
+    }
+    *bytes = b; *flops = f;
+}
+void vis_attention(hipStream_t s, const VisAttnP& p, double bytes, double flops);
+// vis_misc.hip: the small steps of the vision encoder.  Up to kVisMaxImages images of one call, image i being rows [start[i], start[i + 1]) with an
+// h[i] x w[i] grid of patches.
+constexpr int kVisMaxImages = 16;
+struct VisGrids { int n; int start[kVisMaxImages + 1]; int h[kVisMaxImages], w[kVisMaxImages]; };
+// out [T][D]: the learned position table [G G][D] resampled bilinearly to every image's grid (align_corners = false: source coordinate
+// ((o + 0.5) G / out - 0.5) in f32, clamped to [0, G - 1]; weights wy wx, sum in the order 00, 01, 10, 11).  h = w = G gives the table itself.  D % 4 == 0
+void vis_pos_embed(hipStream_t s, const float* table, float* out, const VisGrids& g, int G, int D);
+// out [T / m^2][m^2 D]: row (image, hb, wb) is the concatenation over (mi, mj) of x's rows (image, hb m + mi, wb m + mj).  D % 4 == 0, m | h, w
+void vis_merge_gather(hipStream_t s, const float* x, float* out, const VisGrids& g, int m, int D);
 inline void reduce_mean_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) { reduce_lastdim(s, x, y, rows, C, 0); }
 // y = cond != 0 ? a : b with numpy broadcasting over up to 6 dims (strides in elements, 0 = broadcast)
 void where(hipStream_t s, const float* cond, const float* a, const float* b, float* y, int rank, const int64_t* dims, const int64_t* sc, const int64_t* sa, const int64_t* sb);

@@ -780,9 +780,9 @@ __global__ __launch_bounds__(256) void unary_kernel(const float* x, float* y, lo
     for (long i = n4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
         y[i] = apply_unary(x[i], kind, alpha, beta);
 }
-void unary(hipStream_t s, const float* x, float* y, int64_t n, Act act) {
+void unary(hipStream_t s, const float* x, float* y, int64_t n, Act act, const char* prof_class) {
     if (n == 0) return;
-    ProfScope ps(s, "unary", 8.0 * (double)n, 0.0);
+    ProfScope ps(s, prof_class ? prof_class : "unary", 8.0 * (double)n, 0.0);
     hipLaunchKernelGGL(unary_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, x, y, (long)n, act.kind, act.alpha, act.beta);
 }
 
@@ -1143,9 +1143,9 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float4* __restr
         yr[j] = t;
     }
 }
-void layernorm(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps) {
+void layernorm(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps, const char* prof_class) {
     if (rows == 0) return;
-    ProfScope ps(s, "layernorm", 8.0 * (double)rows * C, 8.0 * (double)rows * C);
+    ProfScope ps(s, prof_class ? prof_class : "layernorm", 8.0 * (double)rows * C, 8.0 * (double)rows * C);
     static const bool v4 = [] { const char* e = getenv("OAR_LN_V4"); return !e || atoi(e) != 0; }();
     const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0;
     if (v4 && (C & 3) == 0 && C <= 1024 && aligned) {

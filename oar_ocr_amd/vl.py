@@ -1,12 +1,15 @@
-"""VL support, first stage: the decoder-only text model of the oar-ocr-vl crate on HIP (lm_decode.hip).
+"""VL support: the decoder-only text model of the oar-ocr-vl crate on HIP (lm_decode.hip) and, second stage, PaddleOCR-VL's vision
+encoder and projector in front of it (vis_attention.hip, vis_host.cc).
 
 `CausalLM` is PaddleOCR-VL's ERNIE-4.5 text decoder (oar-ocr-vl/src/models/paddleocr_vl/ernie.rs) and, by configuration, the Qwen2-VL
-family's: RMSNorm, M-RoPE, grouped-query attention over a key / value cache, SwiGLU, greedy decoding.  The vision encoder, the projector,
-image preprocessing, the tokenizer and the chat template are not built: `generate` takes token ids or ready `inputs_embeds`."""
+family's: RMSNorm, M-RoPE, grouped-query attention over a key / value cache, SwiGLU, greedy decoding.  `VisionEncoder` turns patches into
+the decoder's input rows, `preprocess_images` RGB images into patches, `PaddleOCRVL.generate_tokens` images into generated token ids.
+The tokenizer and the chat template are not built: prompts are token ids."""
 from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import struct
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -318,3 +321,372 @@ class CausalLM:
         if single:
             return LMOutput(tokens[0], counts, None if logits is None else logits[0])
         return LMOutput(tokens, counts, logits)
+
+
+# ================================================================================== the vision stage
+MAX_IMAGES = 16
+OAR_VIS_GELU_TANH, OAR_VIS_GELU_ERF = 0, 1
+
+
+class VisCfg(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("intermediate", C.c_int32), ("patch", C.c_int32), ("channels", C.c_int32),
+                ("pos_grid", C.c_int32), ("merge", C.c_int32), ("text_hidden", C.c_int32), ("ln_eps", C.c_float), ("act", C.c_int32), ("rope_theta", C.c_float),
+                ("max_tokens", C.c_int32), ("max_images", C.c_int32)]
+
+
+class VisRequest(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("grids", C.c_void_p), ("pixel_values", C.c_void_p), ("embeds", C.c_void_p), ("features", C.c_void_p)]
+
+
+_vis_bound = False
+
+
+def _vis_lib():
+    global _vis_bound
+    L = api.lib()
+    if not _vis_bound:
+        L.oar_vis_create.restype = C.c_int
+        L.oar_vis_create.argtypes = [C.POINTER(VisCfg), C.POINTER(LmTensor), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.oar_vis_destroy.restype = None
+        L.oar_vis_destroy.argtypes = [C.c_void_p]
+        L.oar_vis_encode.restype = C.c_int
+        L.oar_vis_encode.argtypes = [C.c_void_p, C.POINTER(VisRequest)]
+        L.oar_vis_cost.restype = C.c_int
+        L.oar_vis_cost.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        _vis_bound = True
+    return L
+
+
+@dataclass
+class VisionConfig:
+    hidden_size: int
+    num_hidden_layers: int
+    num_attention_heads: int
+    intermediate_size: int
+    patch_size: int
+    text_hidden: int
+    num_channels: int = 3
+    pos_grid: int = 27                 # side of the learned position table (image_size // patch_size)
+    spatial_merge_size: int = 2
+    layer_norm_eps: float = 1e-6
+    hidden_act: str = "gelu_pytorch_tanh"
+    rope_theta: float = 10000.0
+    max_tokens: int = 5120             # patches per call
+    max_images: int = MAX_IMAGES
+
+    @classmethod
+    def from_hf_json(cls, d: dict, text_hidden: int, **overrides) -> "VisionConfig":
+        """`config["vision_config"]` of a PaddleOCR-VL checkpoint (the reference's PaddleOcrVlVisionConfig)."""
+        patch = int(d["patch_size"])
+        kw = dict(hidden_size=int(d["hidden_size"]), num_hidden_layers=int(d["num_hidden_layers"]), num_attention_heads=int(d["num_attention_heads"]),
+                  intermediate_size=int(d["intermediate_size"]), patch_size=patch, text_hidden=int(text_hidden), num_channels=int(d.get("num_channels", 3)),
+                  pos_grid=int(d.get("image_size", 27 * patch)) // patch, spatial_merge_size=int(d.get("spatial_merge_size", 2)),
+                  layer_norm_eps=float(d.get("layer_norm_eps", 1e-6)), hidden_act=str(d.get("hidden_act", "gelu_pytorch_tanh")))
+        kw.update(overrides)
+        return cls(**kw)
+
+    def act_code(self) -> int:
+        if self.hidden_act in ("gelu_pytorch_tanh", "gelu_new", "gelu_tanh"):
+            return OAR_VIS_GELU_TANH
+        if self.hidden_act == "gelu":
+            return OAR_VIS_GELU_ERF
+        raise api.OCRError(api.OAR_UNSUPPORTED_OP, f"vision hidden_act {self.hidden_act!r} is neither the tanh nor the erf GELU")
+
+    def to_c(self) -> VisCfg:
+        c = VisCfg()
+        c.hidden, c.layers, c.heads, c.intermediate, c.patch, c.channels = self.hidden_size, self.num_hidden_layers, self.num_attention_heads, self.intermediate_size, self.patch_size, self.num_channels
+        c.pos_grid, c.merge, c.text_hidden, c.ln_eps, c.act, c.rope_theta = self.pos_grid, self.spatial_merge_size, self.text_hidden, self.layer_norm_eps, self.act_code(), self.rope_theta
+        c.max_tokens, c.max_images = self.max_tokens, self.max_images
+        return c
+
+
+@dataclass
+class ImageProcessorConfig:
+    patch_size: int = 14
+    merge_size: int = 2
+    min_pixels: int = 28 * 28 * 130
+    max_pixels: int = 28 * 28 * 1280
+    do_resize: bool = True
+    do_rescale: bool = True
+    do_normalize: bool = True
+    rescale_factor: float = 1.0 / 255.0
+    image_mean: Sequence[float] = (0.5, 0.5, 0.5)
+    image_std: Sequence[float] = (0.5, 0.5, 0.5)
+    resample: Optional[int] = None     # PIL's code; None: CatmullRom
+
+    @classmethod
+    def from_json(cls, d: dict) -> "ImageProcessorConfig":
+        """a `preprocessor_config.json` (the reference's PaddleOcrVlImageProcessorConfig)"""
+        names = ("patch_size", "merge_size", "min_pixels", "max_pixels", "do_resize", "do_rescale", "do_normalize", "rescale_factor", "image_mean", "image_std", "resample")
+        cfg = cls(**{k: d[k] for k in names if k in d and d[k] is not None})
+        if len(cfg.image_mean) != 3 or len(cfg.image_std) != 3 or any(float(v) == 0.0 for v in cfg.image_std):
+            raise api.OCRError(api.OAR_INVALID_INPUT, "image_mean / image_std must have 3 entries and no zero std")
+        if cfg.patch_size <= 0 or cfg.merge_size <= 0:
+            raise api.OCRError(api.OAR_INVALID_INPUT, "patch_size and merge_size must be positive")
+        return cfg
+
+
+_PIL_RESAMPLE = {1: "lanczos3", 2: "triangle", 3: "catmullrom", 4: "triangle", 5: "catmullrom"}   # (box and hamming: the reference's stand-ins)
+
+
+def smart_resize(height: int, width: int, factor: int, min_pixels: int, max_pixels: int):
+    """-> (h, w), multiples of `factor` with min_pixels <= h w <= max_pixels where possible, in the reference's f64 arithmetic: round both sides to the factor
+    (half away from zero); above max_pixels divide by beta = sqrt(h w / max_pixels) and floor, below min_pixels multiply by beta = sqrt(min_pixels / (h w)) and
+    ceil; never below one factor."""
+    if factor <= 0:
+        raise api.OCRError(api.OAR_INVALID_INPUT, "smart_resize: factor must be > 0")
+    h, w, f = float(height), float(width), float(factor)
+    lo, hi = min(h, w), max(h, w)
+    if lo > 0.0 and hi / lo > 200.0:
+        raise api.OCRError(api.OAR_INVALID_INPUT, f"smart_resize: absolute aspect ratio must be <= 200, got {hi / lo:.3f}")
+    rnd = lambda v: math.floor(v + 0.5)   # noqa: E731  (v >= 0)
+    hb, wb = rnd(h / f) * f, rnd(w / f) * f
+    if hb * wb > float(max_pixels):
+        beta = math.sqrt((h * w) / float(max_pixels))
+        hb, wb = max(math.floor((h / beta) / f) * f, f), max(math.floor((w / beta) / f) * f, f)
+        if hb * wb < float(min_pixels):
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"smart_resize: cannot satisfy both min_pixels={min_pixels} and max_pixels={max_pixels} constraints after quantization")
+    elif hb * wb < float(min_pixels):
+        beta = math.sqrt(float(min_pixels) / (h * w))
+        hb, wb = max(math.ceil((h * beta) / f) * f, f), max(math.ceil((w * beta) / f) * f, f)
+        if hb * wb > float(max_pixels):
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"smart_resize: cannot satisfy both min_pixels={min_pixels} and max_pixels={max_pixels} constraints after quantization")
+    return int(hb), int(wb)
+
+
+def patchify(img_f32: np.ndarray, patch: int) -> np.ndarray:
+    """[H, W, 3] -> [H/p W/p, 3 p p]: patch (gy, gx) in row-major order, its values in (c, dy, dx) order"""
+    H, W, Cn = img_f32.shape
+    gh, gw = H // patch, W // patch
+    return np.ascontiguousarray(img_f32.reshape(gh, patch, gw, patch, Cn).transpose(0, 2, 4, 1, 3)).reshape(gh * gw, Cn * patch * patch)
+
+
+def preprocess_images(images, cfg: ImageProcessorConfig, max_pixels: Optional[int] = None):
+    """images: [H, W, 3] uint8 RGB arrays -> (pixel_values [sum h w, 3 p p] float32, grids [n, 2] int32 = (h, w) in patches).  Resize (smart_resize, through the
+    library's exact resize kernel), then v * rescale_factor, then (v - mean) / std, each in f32 and in that order."""
+    if len(images) == 0:
+        raise api.OCRError(api.OAR_INVALID_INPUT, "preprocess_images: no images")
+    p, factor = int(cfg.patch_size), int(cfg.patch_size) * int(cfg.merge_size)
+    if cfg.resample is None:
+        filt = "catmullrom"
+    else:
+        filt = _PIL_RESAMPLE.get(int(cfg.resample))
+        if filt is None:
+            raise api.OCRError(api.OAR_UNSUPPORTED_OP, f"preprocess_images: resample code {cfg.resample} has no resize filter here")
+    mean, std = np.asarray(cfg.image_mean, np.float32), np.asarray(cfg.image_std, np.float32)
+    rows, grids = [], []
+    for im in images:
+        im = np.ascontiguousarray(im, np.uint8)
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"preprocess_images: an image has shape {im.shape}, expected [H, W, 3]")
+        h, w = im.shape[:2]
+        rh, rw = smart_resize(h, w, factor, cfg.min_pixels, cfg.max_pixels if max_pixels is None else max_pixels) if cfg.do_resize else (h, w)
+        if (rh, rw) != (h, w):
+            im = api.k_resize_filter(im, rw, rh, filt)
+        if rh % p or rw % p:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"preprocess_images: {rh}x{rw} is not divisible by patch_size={p}")
+        v = im.astype(np.float32)
+        if cfg.do_rescale:
+            v = v * np.float32(cfg.rescale_factor)
+        if cfg.do_normalize:
+            v = (v - mean) / std
+        rows.append(patchify(v, p))
+        grids.append((rh // p, rw // p))
+    return np.concatenate(rows), np.asarray(grids, np.int32).reshape(-1, 2)
+
+
+def rope_index(input_ids, grids, image_token_id: int, vision_start_token_id: int, merge: int):
+    """-> (positions [3, T] int32, delta): text runs count up on all three axes from the largest position so far + 1; the image tokens of a grid (h, w) get
+    (base, base + hh, base + ww) over the merged grid (h / merge, w / merge); delta = largest position + 1 - T."""
+    ids = [int(v) for v in np.asarray(input_ids).reshape(-1)]
+    grids = [(int(h), int(w)) for h, w in np.asarray(grids, np.int64).reshape(-1, 2)]
+    count = sum(1 for i in range(len(ids) - 1) if ids[i] == vision_start_token_id and ids[i + 1] == image_token_id)
+    if count != len(grids):
+        raise api.OCRError(api.OAR_INVALID_INPUT, f"rope_index: image count mismatch between prompt ({count}) and grids ({len(grids)})")
+    pos, st, cur = [], 0, -1
+    for n, (h, w) in enumerate(grids):
+        try:
+            ed = ids.index(image_token_id, st)
+        except ValueError:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"rope_index: expected an image token for image {n} but none found")
+        base0 = cur + 1
+        for i in range(ed - st):
+            pos.append((base0 + i,) * 3)
+        cur = max(cur, base0 + ed - st - 1) if ed > st else cur
+        base, lh, lw = base0 + ed - st, h // merge, w // merge
+        for hh in range(lh):
+            for ww in range(lw):
+                pos.append((base, base + hh, base + ww))
+        if lh * lw:
+            cur = max(cur, base + max(lh, lw) - 1)
+        st = ed + lh * lw
+    base0 = cur + 1
+    for i in range(st, len(ids)):
+        pos.append((base0 + i - st,) * 3)
+        cur = base0 + i - st
+    if len(pos) != len(ids):
+        raise api.OCRError(api.OAR_INVALID_INPUT, f"rope_index: position ids length mismatch: got {len(pos)}, expected {len(ids)}")
+    return np.ascontiguousarray(np.asarray(pos, np.int32).reshape(-1, 3).T), cur + 1 - len(ids)
+
+
+class VisionEncoder:
+    def __init__(self, cfg: VisionConfig, handle):
+        self.cfg, self._h = cfg, handle
+
+    @classmethod
+    def from_state_dict(cls, cfg: VisionConfig, tensors: dict, device_id: int = 0) -> "VisionEncoder":
+        """tensors: checkpoint name -> float array, uint16 array (bf16 bits) or torch tensor; the `visual.` and `mlp_AR.` names are taken."""
+        keep, table = [], []
+        for name, t in tensors.items():
+            if not (name.startswith("visual.") or name.startswith("mlp_AR.")):
+                continue
+            a, code = _as_table_entry(name, t)
+            if a.ndim > 4:
+                continue
+            e = LmTensor()
+            e.name, e.dtype, e.rank, e.data = name.encode(), code, a.ndim, a.ctypes.data
+            for i, v in enumerate(a.shape):
+                e.dims[i] = v
+            keep.append(a)
+            table.append(e)
+        arr = (LmTensor * max(len(table), 1))(*table)
+        h = C.c_void_p()
+        api._check(_vis_lib().oar_vis_create(C.byref(cfg.to_c()), arr, len(table), device_id, C.byref(h)))
+        return cls(cfg, h)
+
+    @classmethod
+    def from_dir(cls, path, device_id: int = 0, **cfg_overrides) -> "VisionEncoder":
+        path = Path(path)
+        d = json.loads((path / "config.json").read_text())
+        text_hidden = int((d.get("text_config") or {}).get("hidden_size", d.get("hidden_size")))
+        cfg = VisionConfig.from_hf_json(d["vision_config"], text_hidden=text_hidden, **cfg_overrides)
+        files = sorted(path.glob("*.safetensors"))
+        if not files:
+            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
+        tensors = {}
+        for f in files:
+            tensors.update(read_safetensors(f, names=lambda n: n.startswith("visual.") or n.startswith("mlp_AR.")))
+        return cls.from_state_dict(cfg, tensors, device_id=device_id)
+
+    def close(self):
+        if self._h:
+            _vis_lib().oar_vis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def cost(self, grids):
+        """(flops, bytes, launches) of one call over these grids."""
+        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+        f, b, n = C.c_double(), C.c_double(), C.c_int32()
+        api._check(_vis_lib().oar_vis_cost(self._h, g.shape[0], g.ctypes.data, C.byref(f), C.byref(b), C.byref(n)))
+        return f.value, b.value, n.value
+
+    def encode(self, pixel_values, grids, return_features: bool = False):
+        """pixel_values [sum h w, 3 p p], grids [n, 2] -> embeds [sum h w / merge^2, text_hidden] (and features [sum h w, hidden] when asked for); all
+        images run in ONE call, packed back to back."""
+        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+        px = np.ascontiguousarray(pixel_values, np.float32)
+        T = int((g[:, 0].astype(np.int64) * g[:, 1]).sum()) if g.size else 0
+        kp = self.cfg.num_channels * self.cfg.patch_size ** 2
+        if px.size != T * kp:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"encode: pixel_values hold {px.size} floats, the grids need {T} x {kp}")
+        m2 = self.cfg.spatial_merge_size ** 2
+        emb = np.empty((max(T // m2, 0), self.cfg.text_hidden), np.float32)
+        feat = np.empty((T, self.cfg.hidden_size), np.float32) if return_features else None
+        req = VisRequest()
+        req.n_images, req.grids, req.pixel_values, req.embeds = g.shape[0], g.ctypes.data, px.ctypes.data, emb.ctypes.data
+        req.features = feat.ctypes.data if return_features else None
+        api._check(_vis_lib().oar_vis_encode(self._h, C.byref(req)))
+        return (emb, feat) if return_features else emb
+
+
+def _widen_rows(table: np.ndarray, ids) -> np.ndarray:
+    rows = table[np.asarray(ids, np.int64)]
+    if rows.dtype == np.uint16:   # bf16 bits
+        return (rows.astype(np.uint32) << 16).view(np.float32)
+    return np.ascontiguousarray(rows, np.float32)
+
+
+class PaddleOCRVL:
+    """Vision encoder + projector + text decoder: images and token-id prompts in, generated token ids out."""
+
+    def __init__(self, vision: VisionEncoder, lm: CausalLM, embed_table: np.ndarray, preproc: ImageProcessorConfig, image_token_id: int, vision_start_token_id: int):
+        self.vision, self.lm, self.embed_table, self.preproc = vision, lm, embed_table, preproc
+        self.image_token_id, self.vision_start_token_id = int(image_token_id), int(vision_start_token_id)
+
+    @classmethod
+    def from_state_dict(cls, cfg_json: dict, preproc_json: dict, tensors: dict, device_id: int = 0, lm_overrides: Optional[dict] = None,
+                        vision_overrides: Optional[dict] = None) -> "PaddleOCRVL":
+        lm_cfg = CausalLMConfig.from_hf_json(cfg_json, **(lm_overrides or {}))
+        vis_cfg = VisionConfig.from_hf_json(cfg_json["vision_config"], text_hidden=lm_cfg.hidden_size, **(vision_overrides or {}))
+        table, _ = _as_table_entry("model.embed_tokens.weight", tensors["model.embed_tokens.weight"])
+        vision = VisionEncoder.from_state_dict(vis_cfg, tensors, device_id=device_id)
+        try:
+            lm = CausalLM.from_state_dict(lm_cfg, tensors, device_id=device_id)
+        except Exception:
+            vision.close()
+            raise
+        return cls(vision, lm, table, ImageProcessorConfig.from_json(preproc_json), cfg_json["image_token_id"], cfg_json["vision_start_token_id"])
+
+    @classmethod
+    def from_dir(cls, path, device_id: int = 0, **kw) -> "PaddleOCRVL":
+        path = Path(path)
+        files = sorted(path.glob("*.safetensors"))
+        if not files:
+            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
+        tensors = {}
+        for f in files:
+            tensors.update(read_safetensors(f))
+        return cls.from_state_dict(json.loads((path / "config.json").read_text()), json.loads((path / "preprocessor_config.json").read_text()), tensors, device_id=device_id, **kw)
+
+    def close(self):
+        self.vision.close()
+        self.lm.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None) -> LMOutput:
+        """One sequence per image: ids = prefix + [image_token_id] x (h w / merge^2) + suffix; its embeddings are the table rows with the image span replaced
+        by the projector's rows, its positions come from rope_index.  The images are encoded in calls of at most 16 (and at most max_tokens patches)."""
+        m = self.vision.cfg.spatial_merge_size
+        px, grids = preprocess_images(images, self.preproc)
+        kp = px.shape[1]
+        counts = grids[:, 0].astype(np.int64) * grids[:, 1]
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        embeds = [None] * len(images)
+        i = 0
+        while i < len(images):                                   # greedy groups: <= 16 images and <= max_tokens patches (a single larger image is refused by the library)
+            j = i + 1
+            while j < len(images) and j - i < self.vision.cfg.max_images and starts[j + 1] - starts[i] <= self.vision.cfg.max_tokens:
+                j += 1
+            e = self.vision.encode(px[starts[i]:starts[j]].reshape(-1, kp), grids[i:j])
+            off = 0
+            for n in range(i, j):
+                embeds[n] = e[off:off + counts[n] // (m * m)]
+                off += counts[n] // (m * m)
+            i = j
+        seqs, pos = [], []
+        for n in range(len(images)):
+            n_img = int(counts[n]) // (m * m)
+            ids = list(prefix_ids) + [self.image_token_id] * n_img + list(suffix_ids)
+            x = _widen_rows(self.embed_table, ids)
+            x[len(prefix_ids):len(prefix_ids) + n_img] = embeds[n]
+            seqs.append(x)
+            pos.append(rope_index(ids, grids[n:n + 1], self.image_token_id, self.vision_start_token_id, m)[0])
+        return self.lm.generate(inputs_embeds=seqs, position_ids=pos, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
+                                forced_tokens=forced_tokens)

@@ -30,6 +30,10 @@ pub type oar_lm_dtype = c_int;
 pub const OAR_LM_F32: oar_lm_dtype = 1;
 pub const OAR_LM_BF16: oar_lm_dtype = 16;
 
+pub type oar_vis_act = c_int;
+pub const OAR_VIS_GELU_TANH: oar_vis_act = 0;
+pub const OAR_VIS_GELU_ERF: oar_vis_act = 1;
+
 pub const OAR_RECT_NATIVE_SIZE: u32 = 0xFFFFFFFF;
 
 #[repr(C)]
@@ -82,6 +86,12 @@ pub struct oar_layout {
 
 #[repr(C)]
 pub struct oar_lm {
+    _private: [u8; 0],
+    _marker: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)>,
+}
+
+#[repr(C)]
+pub struct oar_vis {
     _private: [u8; 0],
     _marker: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)>,
 }
@@ -376,6 +386,35 @@ pub struct oar_lm_request {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
+pub struct oar_vis_cfg {
+    pub hidden: i32,
+    pub layers: i32,
+    pub heads: i32,
+    pub intermediate: i32,
+    pub patch: i32,
+    pub channels: i32,
+    pub pos_grid: i32,
+    pub merge: i32,
+    pub text_hidden: i32,
+    pub ln_eps: f32,
+    pub act: i32,
+    pub rope_theta: f32,
+    pub max_tokens: i32,
+    pub max_images: i32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct oar_vis_request {
+    pub n_images: i32,
+    pub grids: *const i32,
+    pub pixel_values: *const f32,
+    pub embeds: *mut f32,
+    pub features: *mut f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
 pub struct oar_prof_entry {
     pub name: [c_char; 48],
     pub launches: u64,
@@ -476,12 +515,18 @@ unsafe extern "C" {
     /// fixed-length arrays: box_: [f32; 8]
     pub fn oar_k_rotate_crop(rgb: *const u8, w: u32, h: u32, box_: *const f32, out: *mut u8, cap: usize, out_w: *mut u32, out_h: *mut u32) -> oar_status;
     pub fn oar_k_mha_attention(buf: *const f32, buf_floats: usize, q_off: usize, k_off: usize, v_off: usize, ldq: i32, ldk: i32, ldv: i32, n: i32, tq: i32, tk: i32, heads: i32, head_dim: i32, scale: f32, scale_pre: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_k_vis_attention(buf: *const f32, buf_floats: usize, qkv_off: usize, ld: i32, seg_lens: *const i32, n_segs: i32, heads: i32, head_dim: i32, cos_tab: *const f32, sin_tab: *const f32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_k_vis_pos_embed(table: *const f32, pos_grid: i32, hidden: i32, grids: *const i32, n_images: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_k_add_layernorm(a: *const f32, b: *const f32, b_rows: i64, gamma: *const f32, beta: *const f32, rows: i64, C: i32, eps: f32, write_sum: i32, o_io: *mut f32, o_floats: usize, y_off: usize, s_off: usize) -> oar_status;
     pub fn oar_k_relpos_attention(qkv: *const f32, b: i32, h: i32, w: i32, ws: i32, heads: i32, head_dim: i32, rh: *const f32, rw: *const f32, bqkv: *const f32, scale: f32, scale_pre: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_lm_create(cfg: *const oar_lm_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_lm) -> oar_status;
     pub fn oar_lm_destroy(lm: *mut oar_lm);
     pub fn oar_lm_generate(lm: *mut oar_lm, req: *const oar_lm_request) -> oar_status;
     pub fn oar_lm_cost(lm: *const oar_lm, n_rows: i32, cache_len: i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
+    pub fn oar_vis_create(cfg: *const oar_vis_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_vis) -> oar_status;
+    pub fn oar_vis_destroy(vis: *mut oar_vis);
+    pub fn oar_vis_encode(vis: *mut oar_vis, req: *const oar_vis_request) -> oar_status;
+    pub fn oar_vis_cost(vis: *const oar_vis, n_images: i32, grids_hw: *const i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
     pub fn oar_image_decode(bytes: *const u8, len: usize, rgb: *mut *mut u8, width: *mut u32, height: *mut u32) -> oar_status;
     pub fn oar_image_free(rgb: *mut u8);
     pub fn oar_image_decode_device(bytes: *const u8, len: usize, device_id: i32, dev_rgb: *mut *mut c_void, width: *mut u32, height: *mut u32) -> oar_status;
