@@ -663,6 +663,32 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req);
  * the cache rows read + the row buffers; flops = 2 x MACs; n_kernels = 5 layers + 2. */
 oar_status oar_lm_cost(const oar_lm* lm, int32_t n_rows, int32_t cache_len, double* flops, double* bytes, int32_t* n_kernels);
 
+/* ------------------------------------------------------------------------------------------------ VL: GEMM-based prefill
+ * A second way to prefill, opt-in per model.  OAR_LM_PREFILL_ROWS (the default) prefills through the chain above.  OAR_LM_PREFILL_GEMM runs every prompt
+ * position except each prompt's last as token-major GEMMs on the exact-f32 matrix instructions plus one causal flash-attention launch per layer, in chunks
+ * of chunk_rows packed rows (0: the default, 2048; else 1 .. 65536), writes K and V into the same cache, and hands over to the chain: one step with the
+ * last position of every sequence, then the decode steps as before.  Logits do not depend on chunk_rows or on the other sequences of the call, and two runs
+ * give the same bytes; they differ from the rows prefill's in the last bits (another sum order), except that prompts of length 1 take the same path.
+ * oar_lm_set_prefill takes the model's mutex; OAR_INVALID_INPUT for another mode or chunk_rows. */
+typedef enum { OAR_LM_PREFILL_ROWS = 0, OAR_LM_PREFILL_GEMM = 1 } oar_lm_prefill_mode;
+oar_status oar_lm_set_prefill(oar_lm* lm, int32_t mode, int32_t chunk_rows);
+/* Analytic cost of the GEMM phase of a call with these prompt lengths at the model's current chunk_rows: flops = 2 x MACs, bytes = per chunk every
+ * layer's weights once + the rows in and out + the cache rows the attention streams, n_kernels = chunks x (5 (layers - 1) + 1): the last layer stops
+ * after its q/k/v launch.  All zero when every prompt has length 1. */
+oar_status oar_lm_prefill_cost(oar_lm* lm, int32_t n_seq, const int32_t* lengths, double* flops, double* bytes, int32_t* n_kernels);
+/* The GEMM of that phase alone (lm_prefill_gemm.hip): y [m][n] = x [m][k] w [n][k]^T, w in f32 or as bf16 bit patterns (w_dtype: oar_lm_dtype), widened
+ * exactly.  o_io / o_floats / o_off as for oar_k_mha_attention (o_off need not be a multiple of 4).  Nothing is launched unless every check passes:
+ * OAR_UNSUPPORTED_OP for a k that is no multiple of 4; OAR_INVALID_INPUT for a null buffer, another w_dtype, m outside 1..2^21, n or k outside 1..2^24,
+ * or an output that does not fit o_floats. */
+oar_status oar_k_lm_gemm(const float* x, int32_t m, int32_t k, const void* w, int32_t w_dtype, int32_t n, float* o_io, size_t o_floats, size_t o_off);
+/* The causal grouped-query attention of that phase alone (lm_prefill_attn.hip): kcache / vcache are [n_seq][kv_heads][max_positions][head_dim]; the
+ * queries of sequence i are its positions starts[i] .. starts[i] + lens[i] - 1, packed in order as rows of q [sum lens][heads head_dim]; the query at
+ * position p sees keys 0 .. p of its own sequence, scale head_dim^-0.5.  The output is [sum lens][heads head_dim] from float o_off on.
+ * OAR_UNSUPPORTED_OP for a head_dim that is no multiple of 4 in 8..128; OAR_INVALID_INPUT for a null buffer, heads no multiple of kv_heads, n_seq < 1,
+ * an empty sequence, positions outside the cache, o_off no multiple of 4 floats, or an output that does not fit o_floats. */
+oar_status oar_k_lm_prefill_attention(const float* q, const float* kcache, const float* vcache, int32_t n_seq, int32_t max_positions, const int32_t* starts,
+                                      const int32_t* lens, int32_t heads, int32_t kv_heads, int32_t head_dim, float* o_io, size_t o_floats, size_t o_off);
+
 /* ------------------------------------------------------------------------------------------------ VL: the vision stage
  * The vision encoder and projector of the oar-ocr-vl crate's PaddleOCR-VL (vision.rs, projector.rs): a SigLIP-style pre-LN ViT over the patches of an
  * image (patch Linear + bilinearly resampled position table; per layer LayerNorm, fused q / k / v Linear, attention with 2-D rotary embedding, out_proj +

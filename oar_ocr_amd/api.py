@@ -154,7 +154,7 @@ EXPORTS = [
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
     "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm", "oar_k_vis_attention", "oar_k_vis_pos_embed",
-    "oar_lm_create", "oar_lm_destroy", "oar_lm_generate", "oar_lm_cost",
+    "oar_lm_create", "oar_lm_destroy", "oar_lm_generate", "oar_lm_cost", "oar_lm_set_prefill", "oar_lm_prefill_cost", "oar_k_lm_gemm", "oar_k_lm_prefill_attention",
     "oar_vis_create", "oar_vis_destroy", "oar_vis_encode", "oar_vis_cost",
 ]
 
@@ -239,6 +239,8 @@ def lib():
                                          C.c_size_t]
     L.oar_k_vis_attention.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_size_t, C.c_size_t]
     L.oar_k_vis_pos_embed.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_size_t, C.c_size_t]
+    L.oar_k_lm_gemm.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
+    L.oar_k_lm_prefill_attention.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_add_layernorm.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t, C.c_size_t]
     L.oar_image_decode.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.oar_image_free.argtypes = [C.POINTER(C.c_uint8)]
@@ -1698,6 +1700,46 @@ def k_vis_attention(buf, qkv_off, ld, seg_lens, heads, head_dim, cos, sin, o_io,
     ptr = lambda a: None if a is None else _p(a)
     _check(lib().oar_k_vis_attention(ptr(buf), 0 if buf is None else buf.size, qkv_off, ld, ptr(lens), 0 if lens is None else lens.size, heads, head_dim,
                                      ptr(cos), ptr(sin), _p(out), out.size, o_off))
+    return out
+
+
+def k_lm_gemm(x, w, o_io, o_off, m=None, k=None, n=None):
+    """lm_prefill_gemm.hip with the plain epilogue: x [m, k] f32, w [n, k] as float32 or as uint16 bf16 bit patterns (widened exactly); o_io as in
+    k_mha_attention, the output being [m][n] from o_off on.  m / k / n default to the arrays' shapes; None for x or w reaches the library as a null pointer."""
+    x = None if x is None else np.ascontiguousarray(x, np.float32)
+    bf16 = w is not None and np.asarray(w).dtype == np.uint16
+    w = None if w is None else np.ascontiguousarray(w, np.uint16 if bf16 else np.float32)
+    m = (0 if x is None else x.shape[0]) if m is None else m
+    k = (0 if x is None else x.shape[-1]) if k is None else k
+    n = (0 if w is None else w.shape[0]) if n is None else n
+    for a, name, want in ((x, "x", m * k), (w, "w", n * k)):
+        if a is not None and m > 0 and n > 0 and k > 0 and a.size != want:
+            raise ValueError(f"k_lm_gemm: {name} has {a.size} elements, the shape needs {want}")
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    ptr = lambda a: None if a is None else _p(a)
+    _check(lib().oar_k_lm_gemm(ptr(x), m, k, ptr(w), 16 if bf16 else 1, n, _p(out), out.size, o_off))
+    return out
+
+
+def k_lm_prefill_attention(q, kcache, vcache, starts, lens, heads, o_io, o_off):
+    """lm_prefill_attn.hip: kcache / vcache [n_seq, kv_heads, max_positions, head_dim]; the queries of sequence i are its positions starts[i] ..
+    starts[i] + lens[i] - 1, packed as rows of q [sum(lens), heads head_dim]; position p sees keys 0 .. p.  o_io as in k_mha_attention, the output
+    being [sum(lens)][heads head_dim] from o_off on.  The library cannot see the arrays' lengths, so they are checked here (ValueError)."""
+    kc = np.ascontiguousarray(kcache, np.float32)
+    vc = np.ascontiguousarray(vcache, np.float32)
+    if kc.ndim != 4 or kc.shape != vc.shape:
+        raise ValueError(f"k_lm_prefill_attention: kcache {kc.shape} and vcache {vc.shape} must be one [n_seq, kv_heads, max_positions, head_dim] shape")
+    n_seq, kvh, maxpos, dh = kc.shape
+    st = np.ascontiguousarray(starts, np.int32).reshape(-1)
+    ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+    if st.size != n_seq or ln.size != n_seq:
+        raise ValueError(f"k_lm_prefill_attention: {st.size} starts and {ln.size} lens for {n_seq} sequences")
+    q = None if q is None else np.ascontiguousarray(q, np.float32).reshape(-1)
+    want = int(np.maximum(ln, 0).sum()) * heads * dh
+    if q is not None and q.size != want:
+        raise ValueError(f"k_lm_prefill_attention: q has {q.size} floats, the sequences need {want}")
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    _check(lib().oar_k_lm_prefill_attention(None if q is None else _p(q), _p(kc), _p(vc), n_seq, maxpos, _p(st), _p(ln), heads, kvh, dh, _p(out), out.size, o_off))
     return out
 
 

@@ -1,5 +1,7 @@
 // lm_host.cc -- host side of the decoder-only language model (lm_decode.hip): checks a checkpoint's tensor table, stacks / permutes / pads the matrices,
 // uploads them, and drives prefill and decode as one schedule of <= 16-row steps.  C ABI: oar_lm_create / oar_lm_generate / oar_lm_cost / oar_lm_destroy.
+// Opt-in (oar_lm_set_prefill): the prompt positions before each prompt's last run as token-major GEMMs and one causal flash-attention launch per layer
+// (lm_prefill_gemm.hip, lm_prefill_attn.hip) into the same cache, then the chain above takes over with the last positions.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,6 +12,7 @@
 
 #include "common.h"
 #include "lm_decode.h"
+#include "lm_prefill.h"
 
 using namespace oar;
 
@@ -113,6 +116,8 @@ struct oar_lm {
     DevMem work;     // arena | tokens | forced | logits | steps | ids, sized per call
     size_t work_cap = 0;
     double weight_bytes = 0;
+    int prefill_mode = OAR_LM_PREFILL_ROWS;
+    int chunk_rows = k::kLmPrefillDefaultChunk;
     ~oar_lm() {
         if (stream) {
             Profiler::get().drop_events();
@@ -286,10 +291,14 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
             total += T;
         }
         OAR_CHECK(total < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: prompts too long");
-        // the schedule: prompt rows of all sequences in order, 16 to a step; then one step per generated token
+        std::lock_guard<std::mutex> lk(lm->mu);
+        const bool gemm = lm->prefill_mode == OAR_LM_PREFILL_GEMM;
+        // the schedule: prompt rows of all sequences in order, 16 to a step; then one step per generated token.  GEMM prefill: the prompt rows before each
+        // prompt's last go to the GEMM phase's row table instead, and the first step holds the last rows alone.
         std::vector<k::LmStep> steps;
         std::vector<int> step_maxpos;
         std::vector<int32_t> next_pos((size_t)S);
+        std::vector<k::LmPfRow> pf_rows;
         {
             k::LmStep cur{};
             int mp = 0, xrow = 0;
@@ -304,6 +313,10 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                         R.rp[a] = pid ? pid[(size_t)a * T + t] : t;
                         OAR_CHECK(R.rp[a] >= 0 && R.rp[a] < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: position id outside 0..2^24");
                         if (pid) mx = std::max<int64_t>(mx, R.rp[a]);
+                    }
+                    if (gemm && R.gen < 0) {   // (the slot is filled again by the next row)
+                        pf_rows.push_back(k::LmPfRow{R.seq, R.pos, {R.rp[0], R.rp[1], R.rp[2]}, R.xrow, {0, 0}});
+                        continue;
                     }
                     if (R.gen >= 0) cur.head[cur.nhead++] = cur.nrows;
                     mp = std::max(mp, t);
@@ -328,14 +341,33 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
             steps.push_back(st); step_maxpos.push_back(mp);
         }
 
-        std::lock_guard<std::mutex> lk(lm->mu);
+        // the GEMM phase: chunks of the packed rows, and every chunk's attention tiles (row_lo counts from the chunk's first row)
+        std::vector<k::LmPfSpan> pf_spans;
+        std::vector<int> pf_first, pf_chunk;
+        std::vector<k::LmPfTile> pf_tiles;
+        std::vector<size_t> pf_tile0;
+        int pf_cap = 0;
+        if (!pf_rows.empty()) {
+            k::lm_pf_chunks(req->lengths, S, lm->chunk_rows, pf_spans, pf_first, pf_chunk);
+            for (size_t ci = 0; ci < pf_chunk.size(); ++ci) {
+                pf_tile0.push_back(pf_tiles.size());
+                k::lm_pf_tiles(pf_spans.data() + pf_first[ci], pf_first[ci + 1] - pf_first[ci], c.heads, pf_tiles);
+                pf_cap = std::max(pf_cap, pf_chunk[ci]);
+            }
+            pf_tile0.push_back(pf_tiles.size());
+            OAR_CHECK(pf_tiles.size() < ((size_t)1 << 31), OAR_INVALID_INPUT, "oar_lm_generate: prompts too long");
+        }
+        const size_t Hd_ = (size_t)c.heads * c.head_dim;
+
         OAR_HIP(hipSetDevice(lm->device));
         hipStream_t s = lm->stream;
-        // per-call device memory: arena | tokens | forced | steps | ids + xrows | logits
+        // per-call device memory: arena | tokens | forced | steps | ids + xrows | logits | GEMM prefill: rows | tiles | q | o | h
         auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
         const size_t arena_b = align(((size_t)total + S) * D * 4), tok_b = align((size_t)S * MN * 4), steps_b = align(steps.size() * sizeof(k::LmStep)), ids_b = align((size_t)total * 4);
         const size_t logits_b = req->logits ? align((size_t)S * MN * V * 4) : 0;
-        const size_t need = arena_b + 2 * tok_b + steps_b + 2 * ids_b + logits_b;
+        const size_t pfr_b = align(pf_rows.size() * sizeof(k::LmPfRow)), pft_b = align(pf_tiles.size() * sizeof(k::LmPfTile));
+        const size_t pfq_b = align((size_t)pf_cap * Hd_ * 4), pfh_b = align((size_t)pf_cap * c.intermediate * 4);
+        const size_t need = arena_b + 2 * tok_b + steps_b + 2 * ids_b + logits_b + pfr_b + pft_b + 2 * pfq_b + pfh_b;
         if (need > lm->work_cap) {
             if (lm->work.p) { OAR_HIP(hipFree(lm->work.p)); lm->work.p = nullptr; lm->work_cap = 0; }
             lm->work.alloc(need);
@@ -375,7 +407,59 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
             OAR_HIP(hipStreamSynchronize(s));   // (the two host vectors are pageable and end with this block)
             k::lm_embed(s, P, d_ids, d_xrows, (int)ids.size());
         }
-        OAR_HIP(hipStreamSynchronize(s));       // (pageable sources: steps, st0)
+        uint8_t* wpf = w + arena_b + 2 * tok_b + steps_b + 2 * ids_b + logits_b;
+        k::LmPfRow* d_pfrows = reinterpret_cast<k::LmPfRow*>(wpf);
+        k::LmPfTile* d_pftiles = reinterpret_cast<k::LmPfTile*>(wpf + pfr_b);
+        float* pf_q = reinterpret_cast<float*>(wpf + pfr_b + pft_b);
+        float* pf_o = reinterpret_cast<float*>(wpf + pfr_b + pft_b + pfq_b);
+        float* pf_h = reinterpret_cast<float*>(wpf + pfr_b + pft_b + 2 * pfq_b);
+        if (!pf_rows.empty()) {
+            OAR_HIP(hipMemcpyAsync(d_pfrows, pf_rows.data(), pf_rows.size() * sizeof(k::LmPfRow), hipMemcpyHostToDevice, s));
+            OAR_HIP(hipMemcpyAsync(d_pftiles, pf_tiles.data(), pf_tiles.size() * sizeof(k::LmPfTile), hipMemcpyHostToDevice, s));
+        }
+        OAR_HIP(hipStreamSynchronize(s));       // (pageable sources: steps, st0, the GEMM phase's tables)
+        {
+            // GEMM prefill: per chunk and layer q/k/v GEMM (RMSNorm in front, bias, M-RoPE, k / v into the cache), causal attention, o GEMM +
+            // residual, gate / up GEMM (RMSNorm in front, silu(g) u), down GEMM + residual; the last layer stops after its q/k/v launch
+            const int Hd = (int)Hd_, Kd = c.kv_heads * c.head_dim, F = c.intermediate;
+            size_t row0 = 0;
+            for (size_t ci = 0; ci < pf_chunk.size(); ++ci) {
+                const int M = pf_chunk[ci];
+                const k::LmPfRow* rows = d_pfrows + row0;
+                const k::LmPfTile* tiles = d_pftiles + pf_tile0[ci];
+                const int n_tiles = (int)(pf_tile0[ci + 1] - pf_tile0[ci]);
+                double abytes = 0.0, aflops = 0.0;
+                k::lm_pf_attn_cost(pf_tiles.data() + pf_tile0[ci], n_tiles, c.head_dim, &abytes, &aflops);
+                for (int l = 0; l < c.layers; ++l) {
+                    const k::LmLayerW& Lw = lm->layers[(size_t)l];
+                    float* kc = P.kcache + (size_t)l * P.cache_layer;
+                    float* vc = P.vcache + (size_t)l * P.cache_layer;
+                    k::LmGemmP g{};
+                    g.mode = k::LM_GEMM_QKV; g.bf16 = P.bf16; g.M = M; g.N = Hd + 2 * Kd; g.K = D; g.Kp = k::lm_pad4(D); g.x = P.arena; g.x_ld = D; g.x_gather = 1; g.rows = rows;
+                    g.w = Lw.w_qkv; g.bias = Lw.b_qkv; g.rms_g = Lw.ln1; g.eps = P.eps; g.q = pf_q; g.q_ld = Hd; g.kc = kc; g.vc = vc; g.nq = Hd; g.nk = Kd; g.dh = c.head_dim;
+                    g.kvh = c.kv_heads; g.maxpos = P.maxpos; g.sec0 = P.sec0; g.sec1 = P.sec1; g.inv_freq = P.inv_freq;
+                    k::lm_gemm(s, g);
+                    if (l == c.layers - 1) break;   // nothing reads these rows' hidden state after the last layer's keys and values
+                    k::LmPfAttnP a{};
+                    a.q = pf_q; a.q_ld = Hd; a.kc = kc; a.vc = vc; a.H = c.heads; a.KVH = c.kv_heads; a.dh = c.head_dim; a.maxpos = P.maxpos;
+                    a.scale = 1.0f / sqrtf((float)c.head_dim); a.o = pf_o; a.o_ld = Hd; a.tiles = tiles; a.n_tiles = n_tiles;
+                    k::lm_prefill_attention(s, a, abytes, aflops);
+                    g = k::LmGemmP{};
+                    g.mode = k::LM_GEMM_RESID; g.bf16 = P.bf16; g.M = M; g.N = D; g.K = Hd; g.Kp = k::lm_pad4(Hd); g.x = pf_o; g.x_ld = Hd; g.rows = rows; g.w = Lw.w_o;
+                    g.y = P.arena; g.y_ld = D; g.y_scatter = 1;
+                    k::lm_gemm(s, g);
+                    g = k::LmGemmP{};
+                    g.mode = k::LM_GEMM_GATE; g.bf16 = P.bf16; g.M = M; g.N = 2 * F; g.K = D; g.Kp = k::lm_pad4(D); g.x = P.arena; g.x_ld = D; g.x_gather = 1; g.rows = rows;
+                    g.w = Lw.w_gu; g.rms_g = Lw.ln2; g.eps = P.eps; g.y = pf_h; g.y_ld = F;
+                    k::lm_gemm(s, g);
+                    g = k::LmGemmP{};
+                    g.mode = k::LM_GEMM_RESID; g.bf16 = P.bf16; g.M = M; g.N = D; g.K = F; g.Kp = k::lm_pad4(F); g.x = pf_h; g.x_ld = F; g.rows = rows; g.w = Lw.w_down;
+                    g.y = P.arena; g.y_ld = D; g.y_scatter = 1;
+                    k::lm_gemm(s, g);
+                }
+                row0 += (size_t)M;
+            }
+        }
         for (size_t i = 0; i < steps.size(); ++i) k::lm_step(s, P, d_steps + i, steps[i].nrows, steps[i].nhead, step_maxpos[i]);
         OAR_HIP(hipGetLastError());
         OAR_HIP(hipMemcpyAsync(req->tokens, P.tokens, (size_t)S * MN * 4, hipMemcpyDeviceToHost, s));
@@ -389,5 +473,119 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                     if (req->tokens[(size_t)q * MN + g] == req->eos_token_id) { n = g + 1; break; }
             req->counts[q] = n;
         }
+    });
+}
+
+oar_status oar_lm_set_prefill(oar_lm* lm, int32_t mode, int32_t chunk_rows) {
+    return guard([&] {
+        OAR_CHECK(lm, OAR_INVALID_INPUT, "oar_lm_set_prefill: null model");
+        OAR_CHECK(mode == OAR_LM_PREFILL_ROWS || mode == OAR_LM_PREFILL_GEMM, OAR_INVALID_INPUT, "oar_lm_set_prefill: mode is neither OAR_LM_PREFILL_ROWS nor OAR_LM_PREFILL_GEMM");
+        OAR_CHECK(chunk_rows >= 0 && chunk_rows <= k::kLmPrefillMaxChunk, OAR_INVALID_INPUT, "oar_lm_set_prefill: chunk_rows outside 0..65536");
+        std::lock_guard<std::mutex> lk(lm->mu);
+        lm->prefill_mode = mode;
+        lm->chunk_rows = chunk_rows == 0 ? k::kLmPrefillDefaultChunk : chunk_rows;
+    });
+}
+
+oar_status oar_lm_prefill_cost(oar_lm* lm, int32_t n_seq, const int32_t* lengths, double* flops, double* bytes, int32_t* n_kernels) {
+    return guard([&] {
+        OAR_CHECK(lm && lengths && n_seq >= 1 && n_seq <= lm->cfg.max_sequences, OAR_INVALID_INPUT, "oar_lm_prefill_cost: null argument or n_seq outside 1..max_sequences");
+        int64_t total = 0;
+        for (int s = 0; s < n_seq; ++s) {
+            OAR_CHECK(lengths[s] >= 1 && lengths[s] <= lm->cfg.max_positions, OAR_INVALID_INPUT, "oar_lm_prefill_cost: a length outside 1..max_positions");
+            total += lengths[s];
+        }
+        OAR_CHECK(total < (1 << 24), OAR_INVALID_INPUT, "oar_lm_prefill_cost: prompts too long");
+        int chunk_rows;
+        { std::lock_guard<std::mutex> lk(lm->mu); chunk_rows = lm->chunk_rows; }
+        const oar_lm_cfg& c = lm->cfg;
+        std::vector<k::LmPfSpan> spans;
+        std::vector<int> first, chunk;
+        k::lm_pf_chunks(lengths, n_seq, chunk_rows, spans, first, chunk);
+        const double es = lm->bf16 ? 2.0 : 4.0, D = c.hidden, Hd = (double)c.heads * c.head_dim, Kd = (double)c.kv_heads * c.head_dim, F = c.intermediate, L = c.layers;
+        const double Nqkv = Hd + 2 * Kd;
+        double f = 0.0, b = 0.0;
+        for (size_t ci = 0; ci < chunk.size(); ++ci) {
+            const double M = chunk[ci];
+            std::vector<k::LmPfTile> tiles;
+            k::lm_pf_tiles(spans.data() + first[ci], first[ci + 1] - first[ci], c.heads, tiles);
+            double ab = 0.0, af = 0.0;
+            k::lm_pf_attn_cost(tiles.data(), (int64_t)tiles.size(), c.head_dim, &ab, &af);
+            // every launch: its weights once, its input and output rows
+            f += L * 2.0 * M * Nqkv * D + (L - 1) * (af + 2.0 * M * (D * Hd + 2.0 * F * D + D * F));
+            b += L * (es * Nqkv * D + 4.0 * M * (D + Nqkv)) + (L - 1) * (ab + es * (D * Hd + 2.0 * F * D + D * F) + 4.0 * M * ((Hd + 2 * D) + (D + F) + (F + 2 * D)));
+        }
+        if (flops) *flops = f;
+        if (bytes) *bytes = b;
+        if (n_kernels) *n_kernels = k::lm_pf_launches((int)chunk.size(), c.layers);
+    });
+}
+
+// The two kernels of the GEMM prefill on caller-chosen shapes.  Every argument is checked before the device is asked for, so a bad call launches nothing (and
+// answers the same with or without a GPU).
+oar_status oar_k_lm_gemm(const float* x, int32_t m, int32_t k_, const void* w, int32_t w_dtype, int32_t n, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(x && w && o_io, OAR_INVALID_INPUT, "oar_k_lm_gemm: null buffer");
+        OAR_CHECK(w_dtype == OAR_LM_F32 || w_dtype == OAR_LM_BF16, OAR_INVALID_INPUT, "oar_k_lm_gemm: w_dtype is neither OAR_LM_F32 nor OAR_LM_BF16");
+        OAR_CHECK(m >= 1 && m <= (1 << 21) && n >= 1 && n < (1 << 24) && k_ >= 4 && k_ < (1 << 24), OAR_INVALID_INPUT, "oar_k_lm_gemm: m outside 1..2^21, or n or k outside the limits");
+        OAR_CHECK(k_ % 4 == 0, OAR_UNSUPPORTED_OP, "oar_k_lm_gemm: k must be a multiple of 4 (rows are read 16 bytes at a time)");
+        const uint64_t out = (uint64_t)m * (uint64_t)n;
+        OAR_CHECK(o_off <= o_floats && out <= o_floats - o_off, OAR_INVALID_INPUT, "oar_k_lm_gemm: the output does not fit o_floats");
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        const size_t es = w_dtype == OAR_LM_BF16 ? 2 : 4;
+        DevBuf dx, dw, dout;
+        dx.reserve((size_t)m * k_ * 4); dw.reserve((size_t)n * k_ * es); dout.reserve(o_floats * 4);
+        OAR_HIP(hipMemcpy(dx.p, x, (size_t)m * k_ * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dw.p, w, (size_t)n * k_ * es, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        k::LmGemmP p{};
+        p.mode = k::LM_GEMM_PLAIN; p.bf16 = w_dtype == OAR_LM_BF16; p.M = m; p.N = n; p.K = k_; p.Kp = k_; p.x = dx.as<float>(); p.x_ld = k_; p.w = dw.p;
+        p.y = dout.as<float>() + o_off; p.y_ld = n;
+        k::lm_gemm(nullptr, p);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+oar_status oar_k_lm_prefill_attention(const float* q, const float* kcache, const float* vcache, int32_t n_seq, int32_t max_positions, const int32_t* starts,
+                                      const int32_t* lens, int32_t heads, int32_t kv_heads, int32_t head_dim, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(q && kcache && vcache && starts && lens && o_io, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: null buffer");
+        OAR_CHECK(heads >= 1 && heads < (1 << 16) && kv_heads >= 1 && heads % kv_heads == 0, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: heads outside 1..65535 or no multiple of kv_heads");
+        OAR_CHECK(k::lm_pf_head_dim_supported(head_dim), OAR_UNSUPPORTED_OP, "oar_k_lm_prefill_attention: head_dim must be a multiple of 4 in 8..128");
+        OAR_CHECK(n_seq >= 1 && n_seq <= (1 << 16) && max_positions >= 1 && max_positions <= (1 << 20), OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: n_seq outside 1..65536 or max_positions outside 1..2^20");
+        std::vector<k::LmPfSpan> spans((size_t)n_seq);
+        int64_t rows = 0;
+        for (int32_t i = 0; i < n_seq; ++i) {
+            OAR_CHECK(lens[i] >= 1 && starts[i] >= 0 && (int64_t)starts[i] + lens[i] <= max_positions, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: an empty sequence or positions outside the cache");
+            spans[(size_t)i] = k::LmPfSpan{i, starts[i], lens[i], (int32_t)rows};
+            rows += lens[i];
+            OAR_CHECK(rows < (1 << 24), OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: more than 2^24 query rows");
+        }
+        const int64_t Hd = (int64_t)heads * head_dim, n_tiles = k::lm_pf_tile_count(spans.data(), n_seq, heads);
+        OAR_CHECK(n_tiles < ((int64_t)1 << 31), OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: workgroup count above 2^31");
+        OAR_CHECK((o_off & 3) == 0, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: o_off is no multiple of 4 floats");
+        OAR_CHECK(o_off <= o_floats && (uint64_t)rows * (uint64_t)Hd <= o_floats - o_off, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: the output does not fit o_floats");
+        std::vector<k::LmPfTile> tiles;
+        k::lm_pf_tiles(spans.data(), n_seq, heads, tiles);
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        const size_t qb = (size_t)rows * Hd * 4, cb = (size_t)n_seq * kv_heads * max_positions * head_dim * 4;
+        DevBuf dq, dk, dv, dout, dt;
+        dq.reserve(qb); dk.reserve(cb); dv.reserve(cb); dout.reserve(o_floats * 4); dt.reserve(tiles.size() * sizeof(k::LmPfTile));
+        OAR_HIP(hipMemcpy(dq.p, q, qb, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dk.p, kcache, cb, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dv.p, vcache, cb, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dt.p, tiles.data(), tiles.size() * sizeof(k::LmPfTile), hipMemcpyHostToDevice));
+        k::LmPfAttnP p{};
+        p.q = dq.as<float>(); p.q_ld = (int)Hd; p.kc = dk.as<float>(); p.vc = dv.as<float>(); p.H = heads; p.KVH = kv_heads; p.dh = head_dim; p.maxpos = max_positions;
+        p.scale = 1.0f / sqrtf((float)head_dim); p.o = dout.as<float>() + o_off; p.o_ld = (int)Hd; p.tiles = dt.as<k::LmPfTile>(); p.n_tiles = (int)tiles.size();
+        double bytes = 0.0, flops = 0.0;
+        k::lm_pf_attn_cost(tiles.data(), (int64_t)tiles.size(), head_dim, &bytes, &flops);
+        k::lm_prefill_attention(nullptr, p, bytes, flops);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
     });
 }

@@ -40,6 +40,7 @@ class LmRequest(C.Structure):
 
 
 _bound = False
+PREFILL_MODES = {"rows": 0, "gemm": 1}          # OAR_LM_PREFILL_ROWS / OAR_LM_PREFILL_GEMM
 
 
 def _lib():
@@ -54,6 +55,10 @@ def _lib():
         L.oar_lm_generate.argtypes = [C.c_void_p, C.POINTER(LmRequest)]
         L.oar_lm_cost.restype = C.c_int
         L.oar_lm_cost.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.oar_lm_set_prefill.restype = C.c_int
+        L.oar_lm_set_prefill.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.oar_lm_prefill_cost.restype = C.c_int
+        L.oar_lm_prefill_cost.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         _bound = True
     return L
 
@@ -237,11 +242,29 @@ class CausalLM:
         api._check(_lib().oar_lm_cost(self._h, n_rows, cache_len, C.byref(f), C.byref(b), C.byref(n)))
         return f.value, b.value, n.value
 
+    def set_prefill(self, mode="rows", chunk_rows: Optional[int] = None):
+        """How the following generate calls prefill: "rows" (the decode chain, 16 rows a step) or "gemm"  in chunks of chunk_rows packed
+        rows (None: the default, 2048).  Integers reach the library as they are (it refuses what it does not know)."""
+        code = PREFILL_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(code, str):
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"prefill must be 'rows' or 'gemm', got {mode!r}")
+        api._check(_lib().oar_lm_set_prefill(self._h, int(code), 0 if chunk_rows is None else int(chunk_rows)))
+
+    def prefill_cost(self, lengths):
+        """(flops, bytes, launches) of the GEMM phase of a call with these prompt lengths, at the chunk size set last."""
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        f, b, n = C.c_double(), C.c_double(), C.c_int32()
+        api._check(_lib().oar_lm_prefill_cost(self._h, ln.size, ln.ctypes.data if ln.size else None, C.byref(f), C.byref(b), C.byref(n)))
+        return f.value, b.value, n.value
+
     def generate(self, input_ids=None, inputs_embeds=None, position_ids=None, max_new_tokens: int = 16, eos_token_id: Optional[int] = None,
-                 return_logits: bool = False, forced_tokens=None, logits_out: Optional[np.ndarray] = None) -> LMOutput:
+                 return_logits: bool = False, forced_tokens=None, logits_out: Optional[np.ndarray] = None, prefill: str = "rows",
+                 prefill_chunk: Optional[int] = None) -> LMOutput:
         """Greedy generation for one sequence or a list of sequences (more than 16 run in groups of 16).  input_ids: [T] ints, or inputs_embeds: [T, hidden]
         floats; position_ids: [3, T] (default 0 .. T - 1 on all axes); forced_tokens: [max_new_tokens] per sequence, entries >= 0 are fed instead of the
-        argmax.  logits_out: a flat float32 buffer of at least n_seq x max_new_tokens x vocab that receives the logits in place of a fresh array."""
+        argmax.  logits_out: a flat float32 buffer of at least n_seq x max_new_tokens x vocab that receives the logits in place of a fresh array.
+        prefill: "rows" or "gemm" with prefill_chunk packed rows a chunk (set_prefill); the model keeps the setting of its last call."""
+        self.set_prefill(prefill, prefill_chunk)
         if (input_ids is None) == (inputs_embeds is None):
             raise api.OCRError(api.OAR_INVALID_INPUT, "generate: give exactly one of input_ids and inputs_embeds")
         src = input_ids if input_ids is not None else inputs_embeds
@@ -259,7 +282,8 @@ class CausalLM:
                 sl = slice(i, i + MAX_SEQUENCES)
                 kw = {"input_ids" if input_ids is not None else "inputs_embeds": seqs[sl]}
                 outs.append(self.generate(position_ids=None if pos is None else pos[sl], max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                                          return_logits=return_logits, forced_tokens=None if forced is None else forced[sl], **kw))
+                                          return_logits=return_logits, forced_tokens=None if forced is None else forced[sl], prefill=prefill,
+                                          prefill_chunk=prefill_chunk, **kw))
             return LMOutput(np.concatenate([o.tokens for o in outs]), np.concatenate([o.counts for o in outs]),
                             np.concatenate([o.logits for o in outs]) if return_logits else None)
         V, D = self.cfg.vocab_size, self.cfg.hidden_size
@@ -660,7 +684,8 @@ class PaddleOCRVL:
     def __exit__(self, *a):
         self.close()
 
-    def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None) -> LMOutput:
+    def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None,
+                        prefill: str = "rows", prefill_chunk: Optional[int] = None) -> LMOutput:
         """One sequence per image: ids = prefix + [image_token_id] x (h w / merge^2) + suffix; its embeddings are the table rows with the image span replaced
         by the projector's rows, its positions come from rope_index.  The images are encoded in calls of at most 16 (and at most max_tokens patches)."""
         m = self.vision.cfg.spatial_merge_size
@@ -689,4 +714,4 @@ class PaddleOCRVL:
             seqs.append(x)
             pos.append(rope_index(ids, grids[n:n + 1], self.image_token_id, self.vision_start_token_id, m)[0])
         return self.lm.generate(inputs_embeds=seqs, position_ids=pos, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
-                                forced_tokens=forced_tokens)
+                                forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk)

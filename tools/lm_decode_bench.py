@@ -7,7 +7,11 @@ time, no gaps; the prefill line also has the host wall clock of the whole call w
 (the measured copy rate of the part) + (5 L + 2) kernel boundaries of 1.2 us (the measured gap between a decode layer's short GEMV launches); and the same step in
 torch-ROCm eager, f32 and bf16, as the only outside yardstick.  `--processes 3` runs three fresh processes and prints medians with min .. max.
 
-Usage: python tools/lm_decode_bench.py [--processes 3] [--seqs 1 4 16] [--cache 256 2048] [--steps 8] [--prefill 1024] [--no-torch]"""
+`--prefill-mode rows|gemm|both` chooses how the prefill lines prefill; `both` measures the two arms in the same process, one after the other, for every
+length of `--prefill`.  A GEMM line sums the `lm_gemm_*` classes plus the handover step (the decode classes of a call with one new token), and carries the floor of
+oar_lm_prefill_cost: flops / 157.3 TFLOP/s (the exact-f32 matrix peak) or bytes / 6.29 TB/s, whichever is larger.  `--no-decode` leaves the decode lines out.
+
+Usage: python tools/lm_decode_bench.py [--processes 3] [--seqs 1 4 16] [--cache 256 2048] [--steps 8] [--prefill 64 256 1024 4096] [--prefill-mode both] [--no-decode] [--no-torch]"""
 import argparse
 import json
 import subprocess
@@ -22,9 +26,10 @@ from oar_ocr_amd import api, vl                      # noqa: E402
 
 CFG = dict(hidden_size=1024, num_hidden_layers=18, num_attention_heads=16, num_key_value_heads=2, head_dim=128, intermediate_size=3072, vocab_size=103424,
            rms_norm_eps=1e-5, rope_theta=500000.0, mrope_section=[16, 24, 24], qkv_bias=False, tie_word_embeddings=False)
-COPY_RATE, BOUNDARY_US = 6.29e12, 1.2
+COPY_RATE, BOUNDARY_US, F32_MATRIX_PEAK = 6.29e12, 1.2, 157.3e12
 CLASSES = ("lm_rows", "lm_attn", "lm_head", "lm_combine")
 PREFILL_CLASSES = ("lm_prefill_rows", "lm_prefill_attn", "lm_prefill_head", "lm_prefill_combine")   # steps with prompt positions that give no token
+GEMM_CLASSES = ("lm_gemm_linear", "lm_gemm_attn")                                                    # the GEMM phase; its handover step runs under CLASSES
 
 
 def weights(cfg, rng):
@@ -44,21 +49,21 @@ def bf16_bits(a):
     return ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
 
 
-def profiled(lm, ids, max_new, classes):
+def profiled(lm, ids, max_new, classes, prefill="rows"):
     api.prof_reset()
     api.prof_filter(",".join(classes))                # (only these are bracketed with events: a long prefill in front of the decode steps runs as it is)
     api.prof_enable(True)
     try:
-        lm.generate(input_ids=ids, max_new_tokens=max_new)
+        lm.generate(input_ids=ids, max_new_tokens=max_new, prefill=prefill)
         return {e["name"]: e["total_ms"] * 1e3 for e in api.prof_snapshot() if e["name"].startswith("lm_")}
     finally:
         api.prof_enable(False)
         api.prof_filter("")
 
 
-def wall(lm, ids, max_new):
+def wall(lm, ids, max_new, prefill="rows"):
     t = time.perf_counter()
-    lm.generate(input_ids=ids, max_new_tokens=max_new)
+    lm.generate(input_ids=ids, max_new_tokens=max_new, prefill=prefill)
     return (time.perf_counter() - t) * 1e6
 
 
@@ -105,7 +110,7 @@ def torch_step_us(cfg, n, C, dtype, steps):
 
 
 def child(a):
-    cfg = vl.CausalLMConfig(max_positions=max(max(a.cache), a.prefill) + a.steps + 2, max_sequences=max(a.seqs), **CFG)
+    cfg = vl.CausalLMConfig(max_positions=max(max(a.cache), max(a.prefill)) + a.steps + 2, max_sequences=max(a.seqs), **CFG)
     rng = np.random.default_rng(0)
     w32 = weights(cfg, rng)
     for dtype in a.dtypes:
@@ -113,7 +118,7 @@ def child(a):
         with vl.CausalLM.from_state_dict(cfg, w) as lm:
             del w
             lm.generate(input_ids=[1, 2, 3], max_new_tokens=3)                      # warm-up: code objects, LDS opt-in
-            for C in a.cache:
+            for C in ([] if a.no_decode else a.cache):
                 for n in a.seqs:
                     ids = [rng.integers(0, cfg.vocab_size, C).astype(np.int32) for _ in range(n)]
                     pk = profiled(lm, ids, 1 + a.steps, CLASSES)
@@ -121,10 +126,19 @@ def child(a):
                     flops, nbytes, launches = lm.cost(n, C + a.steps // 2)
                     print(json.dumps({"kind": "decode", "weights": dtype, "seqs": n, "cache": C, "kernel_us": sum(per.values()), "by_class_us": per,
                                       "floor_us": nbytes / COPY_RATE * 1e6 + launches * BOUNDARY_US, "cost_bytes": nbytes, "launches": launches}), flush=True)
-            ids = rng.integers(0, cfg.vocab_size, a.prefill).astype(np.int32)
-            p = profiled(lm, ids, 1, PREFILL_CLASSES)
-            print(json.dumps({"kind": "prefill", "weights": dtype, "positions": a.prefill, "kernel_us": sum(p.get(c, 0.0) for c in PREFILL_CLASSES), "wall_us": wall(lm, ids, 1),
-                              "by_class_us": {c.replace("_prefill", ""): p.get(c, 0.0) for c in PREFILL_CLASSES}}), flush=True)
+            for T in a.prefill:
+                ids = rng.integers(0, cfg.vocab_size, T).astype(np.int32)
+                if a.prefill_mode in ("rows", "both"):
+                    p = profiled(lm, ids, 1, PREFILL_CLASSES)
+                    print(json.dumps({"kind": "prefill", "weights": dtype, "positions": T, "kernel_us": sum(p.get(c, 0.0) for c in PREFILL_CLASSES), "wall_us": wall(lm, ids, 1),
+                                      "by_class_us": {c.replace("_prefill", ""): p.get(c, 0.0) for c in PREFILL_CLASSES}}), flush=True)
+                if a.prefill_mode in ("gemm", "both"):
+                    lm.generate(input_ids=ids[:70], max_new_tokens=1, prefill="gemm")        # warm-up of this arm's code objects
+                    p = profiled(lm, ids, 1, GEMM_CLASSES + CLASSES, prefill="gemm")
+                    flops, nbytes, launches = lm.prefill_cost([T])
+                    print(json.dumps({"kind": "prefill_gemm", "weights": dtype, "positions": T, "kernel_us": sum(p.get(c, 0.0) for c in GEMM_CLASSES + CLASSES),
+                                      "wall_us": wall(lm, ids, 1, "gemm"), "by_class_us": {c: p.get(c, 0.0) for c in GEMM_CLASSES + CLASSES},
+                                      "floor_us": max(flops / F32_MATRIX_PEAK, nbytes / COPY_RATE) * 1e6, "cost_flops": flops, "cost_bytes": nbytes, "launches": launches}), flush=True)
 
 
 def torch_child(a):
@@ -144,7 +158,9 @@ def main():
     ap.add_argument("--cache", type=int, nargs="+", default=[256, 2048])
     ap.add_argument("--dtypes", nargs="+", default=["f32", "bf16"])
     ap.add_argument("--steps", type=int, default=8)
-    ap.add_argument("--prefill", type=int, default=1024)
+    ap.add_argument("--prefill", type=int, nargs="+", default=[1024])
+    ap.add_argument("--prefill-mode", choices=["rows", "gemm", "both"], default="rows")
+    ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--torch-child", action="store_true")
@@ -178,7 +194,7 @@ def main():
             if f in ds[0]:
                 out[f] = stat([d[f] for d in ds])
         if "by_class_us" in ds[0]:
-            out["by_class_us"] = {c: round(float(np.median([d["by_class_us"][c] for d in ds])), 1) for c in CLASSES}
+            out["by_class_us"] = {c: round(float(np.median([d["by_class_us"][c] for d in ds])), 1) for c in ds[0]["by_class_us"]}
         if "floor_us" in ds[0]:
             out["floor_us"] = round(ds[0]["floor_us"], 1)
         print(json.dumps(out), flush=True)
