@@ -689,6 +689,35 @@ oar_status oar_k_lm_gemm(const float* x, int32_t m, int32_t k, const void* w, in
 oar_status oar_k_lm_prefill_attention(const float* q, const float* kcache, const float* vcache, int32_t n_seq, int32_t max_positions, const int32_t* starts,
                                       const int32_t* lens, int32_t heads, int32_t kv_heads, int32_t head_dim, float* o_io, size_t o_floats, size_t o_off);
 
+/* ------------------------------------------------------------------------------------------------ VL: split-key decode attention, stop at eos
+ * Two opt-in properties of a model's following oar_lm_generate calls; the defaults (OAR_LM_ATTN_SERIAL, stop_at_eos 0) are the chain as described above.
+ * OAR_LM_ATTN_SPLIT: the attention of every step (rows prefill, the GEMM prefill's handover step, decode) runs as two launches, 6 layers + 2 per step: the keys
+ * 0 .. p of a row are cut into spans of split_keys keys (0: the default, 64; else a multiple of 64 in 64..4096), one workgroup per (row, kv head, chunk of <= 8
+ * query heads, span) writes a partial per head, and a second launch merges a row's partials in span order.  A row's output depends on (p, head_dim, split_keys)
+ * and the data only -- not on its slot, the other rows of the step, the kind of step or earlier calls -- and two runs give the same bytes; it differs from the
+ * serial mode's in the last bits (another sum order).  The workspace ([16][heads][ceil(max_positions / split_keys)][head_dim + 2] floats) is allocated at the
+ * first call in this mode and freed with the model.
+ * stop_at_eos 1 (with a request whose eos_token_id >= 0): every 8 steps the host enqueues a 4-byte copy of the device's count of unfinished sequences behind the
+ * step, and before it enqueues a step it waits for the newest copy taken 16 or more steps back and stops once that count is 0.  tokens and counts equal those of
+ * the same call without the flag byte for byte (the tokens of steps never enqueued are set to eos on the host), logits up to and including the last step at which
+ * a sequence was still decoding (later rows are not written in either mode).  With t_stop the index, over all steps of the call (prefill steps included), of the
+ * step at which the last sequence emitted eos:   steps_enqueued <= t_stop + 1 + 16 + 8   (kLmStopLookahead, kLmStopStride).
+ * oar_lm_set_decode takes the model's mutex; OAR_INVALID_INPUT for a null model, another mode, a split_keys that is neither 0 nor a multiple of 64 in 64..4096,
+ * or a stop_at_eos outside {0, 1}.  oar_lm_cost then reports 6 layers + 2 kernels and counts the partials written and read.
+ * oar_lm_decode_stats: the steps the last oar_lm_generate call had scheduled and the steps it enqueued (equal unless it stopped at eos; 0 before any call). */
+typedef enum { OAR_LM_ATTN_SERIAL = 0, OAR_LM_ATTN_SPLIT = 1 } oar_lm_attention_mode;
+oar_status oar_lm_set_decode(oar_lm* lm, int32_t attention, int32_t split_keys, int32_t stop_at_eos);
+oar_status oar_lm_decode_stats(const oar_lm* lm, int64_t* steps_limit, int64_t* steps_enqueued);
+/* The attention of one step alone: kcache / vcache are [n_seq][kv_heads][max_positions][head_dim]; row i (of n_rows, 1 .. 16) is the query q[i] ([n_rows][heads
+ * head_dim]) of sequence row_seq[i] at position row_pos[i] and sees keys 0 .. row_pos[i] of that sequence, scale head_dim^-0.5.  split_keys 0 runs the serial
+ * kernel (lm_decode.hip), a multiple of 64 in 64..4096 the split pair (lm_decode_split.hip) over a workspace filled with 0xFF bytes.  The output is [n_rows][heads
+ * head_dim] from float o_off on; o_io / o_floats / o_off as for oar_k_lm_prefill_attention.  Nothing is launched unless every check passes: OAR_UNSUPPORTED_OP
+ * for a head_dim that is no multiple of 4 in 8..128; OAR_INVALID_INPUT for a null buffer, heads no multiple of kv_heads, n_seq < 1, n_rows outside 1..16, a row
+ * outside the sequences or the cache, another split_keys, o_off no multiple of 4 floats, or an output that does not fit o_floats. */
+oar_status oar_k_lm_decode_attention(const float* q, const float* kcache, const float* vcache, int32_t n_seq, int32_t max_positions, int32_t n_rows,
+                                     const int32_t* row_seq, const int32_t* row_pos, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t split_keys,
+                                     float* o_io, size_t o_floats, size_t o_off);
+
 /* ------------------------------------------------------------------------------------------------ VL: the vision stage
  * The vision encoder and projector of the oar-ocr-vl crate's PaddleOCR-VL (vision.rs, projector.rs): a SigLIP-style pre-LN ViT over the patches of an
  * image (patch Linear + bilinearly resampled position table; per layer LayerNorm, fused q / k / v Linear, attention with 2-D rotary embedding, out_proj +

@@ -155,6 +155,7 @@ EXPORTS = [
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
     "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm", "oar_k_vis_attention", "oar_k_vis_pos_embed",
     "oar_lm_create", "oar_lm_destroy", "oar_lm_generate", "oar_lm_cost", "oar_lm_set_prefill", "oar_lm_prefill_cost", "oar_k_lm_gemm", "oar_k_lm_prefill_attention",
+    "oar_lm_set_decode", "oar_lm_decode_stats", "oar_k_lm_decode_attention",
     "oar_vis_create", "oar_vis_destroy", "oar_vis_encode", "oar_vis_cost",
 ]
 
@@ -241,6 +242,7 @@ def lib():
     L.oar_k_vis_pos_embed.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_lm_gemm.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_lm_prefill_attention.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
+    L.oar_k_lm_decode_attention.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_add_layernorm.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t, C.c_size_t]
     L.oar_image_decode.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.oar_image_free.argtypes = [C.POINTER(C.c_uint8)]
@@ -1740,6 +1742,30 @@ def k_lm_prefill_attention(q, kcache, vcache, starts, lens, heads, o_io, o_off):
         raise ValueError(f"k_lm_prefill_attention: q has {q.size} floats, the sequences need {want}")
     out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
     _check(lib().oar_k_lm_prefill_attention(None if q is None else _p(q), _p(kc), _p(vc), n_seq, maxpos, _p(st), _p(ln), heads, kvh, dh, _p(out), out.size, o_off))
+    return out
+
+
+def k_lm_decode_attention(q, kcache, vcache, row_seq, row_pos, heads, o_io, o_off, split_keys=0):
+    """The attention of one step of the language-model chain alone: kcache / vcache [n_seq, kv_heads, max_positions, head_dim]; row i is the query q[i] of
+    sequence row_seq[i] at position row_pos[i] and sees keys 0 .. row_pos[i].  split_keys 0: the serial kernel of lm_decode.hip; a multiple of 64 in 64..4096:
+    lm_decode_split.hip.  o_io as in k_mha_attention, the output being [n_rows][heads head_dim] from o_off on.  The library cannot see the arrays' lengths, so
+    they are checked here (ValueError)."""
+    kc = np.ascontiguousarray(kcache, np.float32)
+    vc = np.ascontiguousarray(vcache, np.float32)
+    if kc.ndim != 4 or kc.shape != vc.shape:
+        raise ValueError(f"k_lm_decode_attention: kcache {kc.shape} and vcache {vc.shape} must be one [n_seq, kv_heads, max_positions, head_dim] shape")
+    n_seq, kvh, maxpos, dh = kc.shape
+    rs = np.ascontiguousarray(row_seq, np.int32).reshape(-1)
+    rp = np.ascontiguousarray(row_pos, np.int32).reshape(-1)
+    if rs.size != rp.size:
+        raise ValueError(f"k_lm_decode_attention: {rs.size} row_seq and {rp.size} row_pos")
+    q = None if q is None else np.ascontiguousarray(q, np.float32).reshape(-1)
+    want = rs.size * heads * dh
+    if q is not None and q.size != want:
+        raise ValueError(f"k_lm_decode_attention: q has {q.size} floats, the rows need {want}")
+    out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
+    _check(lib().oar_k_lm_decode_attention(None if q is None else _p(q), _p(kc), _p(vc), n_seq, maxpos, rs.size, _p(rs) if rs.size else None, _p(rp) if rp.size else None,
+                                           heads, kvh, dh, int(split_keys), _p(out), out.size, o_off))
     return out
 
 

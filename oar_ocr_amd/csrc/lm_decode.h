@@ -46,6 +46,41 @@ struct LmDecodeP {
     const int32_t* forced;       // [sequences][max_new] or null; < 0: not forced
     float* logits;               // [sequences][max_new][V] or null
     int max_new, eos;
+    float* split_ws;             // split-key attention: partials [16][H][ceil(maxpos / split_keys)][dh + 2], or null
+    int split_keys;              // keys of one span (a multiple of 64 in 64..4096); read in split mode only
+};
+
+// Split-key decode attention (lm_decode_split.hip): a row's keys are cut into spans of split_keys keys, one workgroup per (row, kv head, chunk of
+// query heads, span) writes one partial (maximum, sum, weighted value sum [dh]) per head, and a second launch merges a row's partials in span order.
+constexpr int kLmSplitThreads = 256;   // 4 waves: all stage a tile of keys and values, wave w scores and accumulates the heads w HPW .. of the chunk
+constexpr int kLmSplitWaves = kLmSplitThreads / 64;
+constexpr int kLmSplitTile = 64;       // keys staged in LDS at a time: lane j scores key j
+constexpr int kLmSplitMin = 64, kLmSplitMax = 4096;
+constexpr int kLmSplitDefault = 64;    // what split_keys 0 means (the measurement: DESIGN 4.43)
+constexpr int kLmMergeThreads = 128;   // one workgroup per (row, head), thread d
+enum : int { LM_ATTN_SERIAL = 0, LM_ATTN_SPLIT = 1 };
+// Stop at eos: every kLmStopStride steps the host copies state.alive (4 bytes) into a pinned ring behind the step and records an event; before it enqueues step i
+// it waits for the newest copy taken kLmStopLookahead or more steps back (long finished in the steady state: the device keeps a lookahead of queued steps) and
+// stops once that word is 0.  With t_stop the index, over all steps of the call, of the step whose lm_combine ended the last sequence:
+//     steps_enqueued <= t_stop + 1 + kLmStopLookahead + kLmStopStride.
+constexpr int kLmStopStride = 8, kLmStopLookahead = 16, kLmStopRing = 8;
+
+inline bool lm_split_keys_supported(int S) { return S >= kLmSplitMin && S <= kLmSplitMax && S % kLmSplitTile == 0; }
+inline int lm_split_spans(int n_keys, int S) { return (n_keys + S - 1) / S; }   // spans of a row that sees n_keys = p + 1 keys (of a cache: n_keys = maxpos)
+constexpr int lm_split_gt(int G) { return G >= 8 ? 8 : G > 2 ? 4 : G; }           // query heads per workgroup, as the serial kernel: 1, 2, 4 or 8
+constexpr int lm_split_ldk(int dh) { return 4 * ((dh / 4) | 1); }                 // floats of a staged key row: an odd number of float4s, so that 16 lanes reading 16 rows 16 bytes at a time cover all 64 banks
+inline size_t lm_split_lds_bytes(int dh, int gt) { return 4 * ((size_t)gt * dh + (size_t)kLmSplitTile * lm_split_ldk(dh) + (size_t)kLmSplitTile * dh + (size_t)gt * kLmSplitTile); }   // q | K tile | V tile | weights
+inline size_t lm_split_ws_floats(int H, int dh, int maxpos, int S) { return (size_t)kLmRows * H * lm_split_spans(maxpos, S) * (dh + 2); }
+inline int lm_launches_per_step_split(int L) { return 6 * L + 2; }
+
+struct LmAttnArgs {
+    const LmStep* st;
+    const float* q; int q_ld;
+    const float *kc, *vc;        // one layer's caches
+    int H, KVH, dh, maxpos;
+    float* o; int o_ld;
+    const int* alive;
+    float* ws; int split_keys;   // LM_ATTN_SPLIT only
 };
 
 inline int lm_pad4(int n) { return (n + 3) & ~3; }
@@ -65,7 +100,10 @@ constexpr int lm_attn_keys_per_wave(int dh) { return 64 / lm_attn_lanes_per_key(
 int lm_head_workgroups(int V);
 
 void lm_embed(ihipStream_t* s, const LmDecodeP& p, const int32_t* ids, const int32_t* xrows, int n);   // arena[xrows[i]] = E[ids[i]]
-void lm_step(ihipStream_t* s, const LmDecodeP& p, const LmStep* dev_step, int nrows, int nhead, int max_pos_in_step);
+void lm_step(ihipStream_t* s, const LmDecodeP& p, const LmStep* dev_step, int nrows, int nhead, int max_pos_in_step, int attention = LM_ATTN_SERIAL);
+// the attention block of a step: lm_attn_kernel (one launch), or lm_attn_split + lm_attn_merge (two); prefill chooses the profiler classes
+void lm_attention(ihipStream_t* s, const LmAttnArgs& a, int attention, int nrows, bool prefill, int max_pos_in_step);
+void lm_attention_split(ihipStream_t* s, const LmAttnArgs& a, int nrows, bool prefill, int max_pos_in_step);   // lm_decode_split.hip
 
 }  // namespace k
 }  // namespace oar

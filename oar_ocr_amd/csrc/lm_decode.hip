@@ -13,6 +13,7 @@
 //              5 lm_rows      Wdown + residual
 //   then       6 lm_head      final RMSNorm -> lm-head for the rows that need a token: logits (when asked for) and one (value, index) partial per workgroup and row
 //              7 lm_combine   lowest index among equal maxima -> the token; eos bookkeeping; the sequence's next input row = E[token] (or the forced token)
+// Opt-in (lm_step's `attention`): launch 2 as lm_attn_split + lm_attn_merge of lm_decode_split.hip, the keys of a row cut into spans: 6 L + 2 launches.
 // The rotary pair (d, d + dh / 2) of a head and the (gate, up) pair of an MLP column are ADJACENT rows of the stacked matrices (the host permutes them at upload),
 // so the wave that owns two rows holds both halves of a pair after its reduction.
 //
@@ -486,16 +487,33 @@ void lm_embed(hipStream_t s, const LmDecodeP& p, const int32_t* ids, const int32
     hipLaunchKernelGGL(lm_embed_kernel, dim3((unsigned)n), dim3(kLmThreads), 0, s, p.embed, p.bf16, p.V, p.D, lm_pad4(p.D), ids, xrows, p.arena);
 }
 
-void lm_step(hipStream_t s, const LmDecodeP& p, const LmStep* st, int nrows, int nhead, int max_pos_in_step) {
+void lm_attention(hipStream_t s, const LmAttnArgs& g, int attention, int nrows, bool prefill, int max_pos_in_step) {
+    if (attention == LM_ATTN_SPLIT) { lm_attention_split(s, g, nrows, prefill, max_pos_in_step); return; }
+    const int Hd = g.H * g.dh, Kd = g.KVH * g.dh, G = g.H / g.KVH;
+    const int gt = G >= 8 ? 8 : G > 2 ? 4 : G;   // 1, 2, 4 or 8 query heads per workgroup
+    const int gchunks = (G + gt - 1) / gt;
+    LmAttnP a{};
+    a.st = g.st; a.alive = g.alive; a.q = g.q; a.q_ld = g.q_ld; a.kc = g.kc; a.vc = g.vc; a.H = g.H; a.KVH = g.KVH; a.dh = g.dh; a.maxpos = g.maxpos;
+    a.scale = 1.0f / sqrtf((float)g.dh); a.o = g.o; a.o_ld = g.o_ld;
+    const double keys = (double)nrows * (max_pos_in_step + 1);
+    ProfScope ps(s, prefill ? "lm_prefill_attn" : "lm_attn", 4.0 * (2.0 * keys * Kd + 2.0 * nrows * Hd), 4.0 * keys * Hd);
+    const dim3 grid((unsigned)g.KVH, (unsigned)nrows, (unsigned)gchunks);
+    if (gt == 8) hipLaunchKernelGGL(lm_attn_kernel<8>, grid, dim3(kLmAttnThreads), 0, s, a);
+    else if (gt == 4) hipLaunchKernelGGL(lm_attn_kernel<4>, grid, dim3(kLmAttnThreads), 0, s, a);
+    else if (gt == 2) hipLaunchKernelGGL(lm_attn_kernel<2>, grid, dim3(kLmAttnThreads), 0, s, a);
+    else hipLaunchKernelGGL(lm_attn_kernel<1>, grid, dim3(kLmAttnThreads), 0, s, a);
+}
+
+void lm_step(hipStream_t s, const LmDecodeP& p, const LmStep* st, int nrows, int nhead, int max_pos_in_step, int attention) {
     OAR_CHECK(nrows >= 1 && nrows <= kLmRows && nhead >= 0 && nhead <= nrows && lm_head_dim_supported(p.dh) && p.KVH >= 1 && p.H % p.KVH == 0, OAR_INTERNAL,
               "lm_step: rows or head size outside the kernels' limits");
-    const int D = p.D, Hd = p.H * p.dh, Kd = p.KVH * p.dh, G = p.H / p.KVH;
+    OAR_CHECK(attention == LM_ATTN_SERIAL || (attention == LM_ATTN_SPLIT && p.split_ws && lm_split_keys_supported(p.split_keys)), OAR_INTERNAL,
+              "lm_step: split attention without its workspace or span");
+    const int D = p.D, Hd = p.H * p.dh, Kd = p.KVH * p.dh;
     // profiler classes: a step all of whose rows give a token (a decode step; a one-position prompt's prefill is one too) is lm_rows / lm_attn / lm_head / lm_combine,
     // a step with prompt positions that give none is lm_prefill_*: the two can be timed apart
     const bool prefill = nhead < nrows;
     const int* alive = &p.state->alive;
-    const int gt = G >= 8 ? 8 : G > 2 ? 4 : G;   // 1, 2, 4 or 8 query heads per workgroup
-    const int gchunks = (G + gt - 1) / gt;
     for (int l = 0; l < p.L; ++l) {
         const LmLayerW& Lw = p.layers[l];
         float* kc = p.kcache + (size_t)l * p.cache_layer;
@@ -504,18 +522,10 @@ void lm_step(hipStream_t s, const LmDecodeP& p, const LmStep* st, int nrows, int
         r.st = st; r.alive = alive; r.xin = p.arena; r.xin_ld = D; r.xin_arena = 1; r.K = D; r.N = Hd + 2 * Kd; r.W = Lw.w_qkv; r.bias = Lw.b_qkv; r.rms_g = Lw.ln1; r.eps = p.eps;
         r.q = p.q; r.q_ld = Hd; r.kc = kc; r.vc = vc; r.nq = Hd; r.nk = Kd; r.dh = p.dh; r.kvh = p.KVH; r.maxpos = p.maxpos; r.sec0 = p.sec0; r.sec1 = p.sec1; r.inv_freq = p.inv_freq;
         launch_rows<LM_QKV>(s, r, nrows, p.bf16, prefill);
-        LmAttnP a{};
-        a.st = st; a.alive = alive; a.q = p.q; a.q_ld = Hd; a.kc = kc; a.vc = vc; a.H = p.H; a.KVH = p.KVH; a.dh = p.dh; a.maxpos = p.maxpos;
-        a.scale = 1.0f / sqrtf((float)p.dh); a.o = p.o; a.o_ld = Hd;
-        {
-            const double keys = (double)nrows * (max_pos_in_step + 1);
-            ProfScope ps(s, prefill ? "lm_prefill_attn" : "lm_attn", 4.0 * (2.0 * keys * Kd + 2.0 * nrows * Hd), 4.0 * keys * Hd);
-            const dim3 grid((unsigned)p.KVH, (unsigned)nrows, (unsigned)gchunks);
-            if (gt == 8) hipLaunchKernelGGL(lm_attn_kernel<8>, grid, dim3(kLmAttnThreads), 0, s, a);
-            else if (gt == 4) hipLaunchKernelGGL(lm_attn_kernel<4>, grid, dim3(kLmAttnThreads), 0, s, a);
-            else if (gt == 2) hipLaunchKernelGGL(lm_attn_kernel<2>, grid, dim3(kLmAttnThreads), 0, s, a);
-            else hipLaunchKernelGGL(lm_attn_kernel<1>, grid, dim3(kLmAttnThreads), 0, s, a);
-        }
+        LmAttnArgs a{};
+        a.st = st; a.alive = alive; a.q = p.q; a.q_ld = Hd; a.kc = kc; a.vc = vc; a.H = p.H; a.KVH = p.KVH; a.dh = p.dh; a.maxpos = p.maxpos; a.o = p.o; a.o_ld = Hd;
+        a.ws = p.split_ws; a.split_keys = p.split_keys;
+        lm_attention(s, a, attention, nrows, prefill, max_pos_in_step);
         r = LmRowsP{};
         r.st = st; r.alive = alive; r.xin = p.o; r.xin_ld = Hd; r.K = Hd; r.N = D; r.W = Lw.w_o; r.y = p.arena; r.y_ld = D;
         launch_rows<LM_PLAIN>(s, r, nrows, p.bf16, prefill);

@@ -2,6 +2,8 @@
 // uploads them, and drives prefill and decode as one schedule of <= 16-row steps.  C ABI: oar_lm_create / oar_lm_generate / oar_lm_cost / oar_lm_destroy.
 // Opt-in (oar_lm_set_prefill): the prompt positions before each prompt's last run as token-major GEMMs and one causal flash-attention launch per layer
 // (lm_prefill_gemm.hip, lm_prefill_attn.hip) into the same cache, then the chain above takes over with the last positions.
+// Opt-in (oar_lm_set_decode): the steps' attention cut over the keys (lm_decode_split.hip), and a call that stops enqueuing steps once a copy of
+// the device's `alive` word, looked at a fixed number of steps behind the enqueue, says that every sequence has ended.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -109,7 +111,7 @@ struct oar_lm {
     int device = 0;
     int bf16 = 0;
     hipStream_t stream = nullptr;
-    std::mutex mu;
+    mutable std::mutex mu;
     std::vector<std::unique_ptr<DevMem>> mem;
     std::vector<k::LmLayerW> layers;
     k::LmDecodeP P{};
@@ -118,7 +120,18 @@ struct oar_lm {
     double weight_bytes = 0;
     int prefill_mode = OAR_LM_PREFILL_ROWS;
     int chunk_rows = k::kLmPrefillDefaultChunk;
+    int attention = OAR_LM_ATTN_SERIAL;
+    int split_keys = k::kLmSplitDefault;
+    int stop_at_eos = 0;
+    DevMem split_ws;   // the split mode's partials, allocated at its first use
+    size_t split_ws_cap = 0;
+    int32_t* stop_ring = nullptr;   // pinned [kLmStopRing]: copies of state.alive
+    hipEvent_t stop_ev[k::kLmStopRing] = {};
+    int64_t steps_limit = 0, steps_enqueued = 0;   // of the last call
     ~oar_lm() {
+        for (hipEvent_t e : stop_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stop_ring) (void)hipHostFree(stop_ring);
         if (stream) {
             Profiler::get().drop_events();
             (void)hipStreamDestroy(stream);
@@ -264,9 +277,14 @@ oar_status oar_lm_cost(const oar_lm* lm, int32_t n_rows, int32_t cache_len, doub
         const double D = c.hidden, Hd = (double)c.heads * c.head_dim, Kd = (double)c.kv_heads * c.head_dim, F = c.intermediate, V = c.vocab, L = c.layers, B = n_rows, n = cache_len;
         const double macs = L * (D * (Hd + 2 * Kd) + Hd * D + 3.0 * F * D + 2.0 * n * Hd) + V * D;
         const double acts = 4.0 * B * (L * (2 * D + 2 * (Hd + 2 * Kd) + 2 * Hd + 3 * D + 2 * F + 2 * D) + D + 2.0 * k::lm_head_workgroups(c.vocab) + D);
+        int attention, split_keys;
+        { std::lock_guard<std::mutex> lk(lm->mu); attention = lm->attention; split_keys = lm->split_keys; }
+        const bool split = attention == OAR_LM_ATTN_SPLIT;
+        // split mode: every span's partial (m, l, acc[dh]) per row and head is written by lm_attn_split and read by lm_attn_merge
+        const double parts = split ? 2.0 * 4.0 * B * L * c.heads * (double)std::max(1, k::lm_split_spans(cache_len, split_keys)) * (c.head_dim + 2) : 0.0;
         if (flops) *flops = 2.0 * macs * B;
-        if (bytes) *bytes = lm->weight_bytes + 4.0 * B * L * 2.0 * n * Kd + acts;
-        if (n_kernels) *n_kernels = k::lm_launches_per_step(c.layers);
+        if (bytes) *bytes = lm->weight_bytes + 4.0 * B * L * 2.0 * n * Kd + acts + parts;
+        if (n_kernels) *n_kernels = split ? k::lm_launches_per_step_split(c.layers) : k::lm_launches_per_step(c.layers);
     });
 }
 
@@ -293,6 +311,8 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
         OAR_CHECK(total < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: prompts too long");
         std::lock_guard<std::mutex> lk(lm->mu);
         const bool gemm = lm->prefill_mode == OAR_LM_PREFILL_GEMM;
+        const int attention = lm->attention;
+        const bool stop = lm->stop_at_eos && req->eos_token_id >= 0;
         // the schedule: prompt rows of all sequences in order, 16 to a step; then one step per generated token.  GEMM prefill: the prompt rows before each
         // prompt's last go to the GEMM phase's row table instead, and the first step holds the last rows alone.
         std::vector<k::LmStep> steps;
@@ -376,6 +396,20 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
         uint8_t* w = static_cast<uint8_t*>(lm->work.p);
         k::LmDecodeP P = lm->P;
         P.layers = lm->layers.data();
+        P.split_ws = nullptr; P.split_keys = lm->split_keys;
+        if (attention == OAR_LM_ATTN_SPLIT) {
+            const size_t ws_b = k::lm_split_ws_floats(c.heads, c.head_dim, c.max_positions, lm->split_keys) * 4;
+            if (ws_b > lm->split_ws_cap) {
+                if (lm->split_ws.p) { OAR_HIP(hipFree(lm->split_ws.p)); lm->split_ws.p = nullptr; lm->split_ws_cap = 0; }
+                lm->split_ws.alloc(ws_b);
+                lm->split_ws_cap = ws_b;
+            }
+            P.split_ws = static_cast<float*>(lm->split_ws.p);
+        }
+        if (stop && !lm->stop_ring) {
+            OAR_HIP(hipHostMalloc(reinterpret_cast<void**>(&lm->stop_ring), sizeof(int32_t) * k::kLmStopRing, hipHostMallocDefault));
+            for (hipEvent_t& e : lm->stop_ev) OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
         P.arena = reinterpret_cast<float*>(w); P.xdec0 = xdec0;
         P.tokens = reinterpret_cast<int32_t*>(w + arena_b);
         int32_t* d_forced = reinterpret_cast<int32_t*>(w + arena_b + tok_b);
@@ -460,12 +494,40 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                 row0 += (size_t)M;
             }
         }
-        for (size_t i = 0; i < steps.size(); ++i) k::lm_step(s, P, d_steps + i, steps[i].nrows, steps[i].nhead, step_maxpos[i]);
+        // stop at eos: copy c is taken behind step (c + 1) kLmStopStride - 1; before step i the host waits for the newest copy taken at a step
+        // <= i - kLmStopLookahead -- the device still holds the steps after it -- and enqueues nothing more once that copy of `alive` is 0
+        size_t enqueued = 0;
+        int64_t seen = -1;   // the newest copy the host has looked at
+        for (size_t i = 0; i < steps.size(); ++i) {
+            if (stop) {
+                const int64_t c = ((int64_t)i - k::kLmStopLookahead + 1) / k::kLmStopStride - 1;   // the newest copy whose step (c + 1) stride - 1 <= i - lookahead
+                if ((int64_t)i >= k::kLmStopLookahead && c >= 0 && c > seen) {
+                    OAR_HIP(hipEventSynchronize(lm->stop_ev[c % k::kLmStopRing]));
+                    seen = c;
+                }
+                if (seen >= 0 && *static_cast<volatile int32_t*>(lm->stop_ring + seen % k::kLmStopRing) == 0) break;
+            }
+            k::lm_step(s, P, d_steps + i, steps[i].nrows, steps[i].nhead, step_maxpos[i], attention);
+            enqueued = i + 1;
+            if (stop && (i + 1) % k::kLmStopStride == 0) {
+                const size_t slot = ((i + 1) / k::kLmStopStride - 1) % k::kLmStopRing;
+                OAR_HIP(hipMemcpyAsync(lm->stop_ring + slot, &P.state->alive, 4, hipMemcpyDeviceToHost, s));
+                OAR_HIP(hipEventRecord(lm->stop_ev[slot], s));
+            }
+        }
+        lm->steps_limit = (int64_t)steps.size();
+        lm->steps_enqueued = (int64_t)enqueued;
         OAR_HIP(hipGetLastError());
         OAR_HIP(hipMemcpyAsync(req->tokens, P.tokens, (size_t)S * MN * 4, hipMemcpyDeviceToHost, s));
         if (P.logits) OAR_HIP(hipMemcpyAsync(req->logits, P.logits, (size_t)S * MN * V * 4, hipMemcpyDeviceToHost, s));
         OAR_HIP(hipStreamSynchronize(s));
         if (Profiler::get().enabled) Profiler::get().flush();
+        if (enqueued < steps.size()) {   // the steps never enqueued would have written eos: every sequence had ended
+            const size_t first_decode = steps.size() - (size_t)(MN - 1);   // step first_decode + g - 1 gives token g >= 1
+            for (int g = 1; g < MN; ++g)
+                if (first_decode + (size_t)g - 1 >= enqueued)
+                    for (int q = 0; q < S; ++q) req->tokens[(size_t)q * MN + g] = req->eos_token_id;
+        }
         for (int q = 0; q < S; ++q) {
             int n = MN;
             if (req->eos_token_id >= 0)
@@ -484,6 +546,28 @@ oar_status oar_lm_set_prefill(oar_lm* lm, int32_t mode, int32_t chunk_rows) {
         std::lock_guard<std::mutex> lk(lm->mu);
         lm->prefill_mode = mode;
         lm->chunk_rows = chunk_rows == 0 ? k::kLmPrefillDefaultChunk : chunk_rows;
+    });
+}
+
+oar_status oar_lm_set_decode(oar_lm* lm, int32_t attention, int32_t split_keys, int32_t stop_at_eos) {
+    return guard([&] {
+        OAR_CHECK(lm, OAR_INVALID_INPUT, "oar_lm_set_decode: null model");
+        OAR_CHECK(attention == OAR_LM_ATTN_SERIAL || attention == OAR_LM_ATTN_SPLIT, OAR_INVALID_INPUT, "oar_lm_set_decode: attention is neither OAR_LM_ATTN_SERIAL nor OAR_LM_ATTN_SPLIT");
+        OAR_CHECK(split_keys == 0 || k::lm_split_keys_supported(split_keys), OAR_INVALID_INPUT, "oar_lm_set_decode: split_keys is neither 0 nor a multiple of 64 in 64..4096");
+        OAR_CHECK(stop_at_eos == 0 || stop_at_eos == 1, OAR_INVALID_INPUT, "oar_lm_set_decode: stop_at_eos outside {0, 1}");
+        std::lock_guard<std::mutex> lk(lm->mu);
+        lm->attention = attention;
+        lm->split_keys = split_keys == 0 ? k::kLmSplitDefault : split_keys;
+        lm->stop_at_eos = stop_at_eos;
+    });
+}
+
+oar_status oar_lm_decode_stats(const oar_lm* lm, int64_t* steps_limit, int64_t* steps_enqueued) {
+    return guard([&] {
+        OAR_CHECK(lm, OAR_INVALID_INPUT, "oar_lm_decode_stats: null model");
+        std::lock_guard<std::mutex> lk(lm->mu);
+        if (steps_limit) *steps_limit = lm->steps_limit;
+        if (steps_enqueued) *steps_enqueued = lm->steps_enqueued;
     });
 }
 
@@ -585,6 +669,55 @@ oar_status oar_k_lm_prefill_attention(const float* q, const float* kcache, const
         double bytes = 0.0, flops = 0.0;
         k::lm_pf_attn_cost(tiles.data(), (int64_t)tiles.size(), head_dim, &bytes, &flops);
         k::lm_prefill_attention(nullptr, p, bytes, flops);
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// The attention of a decode step alone: split_keys 0 runs lm_attn_kernel, else lm_attn_split + lm_attn_merge over a workspace filled with 0xFF bytes (a partial
+// read without having been written shows as NaN).
+oar_status oar_k_lm_decode_attention(const float* q, const float* kcache, const float* vcache, int32_t n_seq, int32_t max_positions, int32_t n_rows, const int32_t* row_seq,
+                                     const int32_t* row_pos, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t split_keys, float* o_io, size_t o_floats, size_t o_off) {
+    return guard([&] {
+        OAR_CHECK(q && kcache && vcache && row_seq && row_pos && o_io, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: null buffer");
+        OAR_CHECK(heads >= 1 && heads < (1 << 16) && kv_heads >= 1 && heads % kv_heads == 0, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: heads outside 1..65535 or no multiple of kv_heads");
+        OAR_CHECK(k::lm_head_dim_supported(head_dim), OAR_UNSUPPORTED_OP, "oar_k_lm_decode_attention: head_dim must be a multiple of 4 in 8..128");
+        OAR_CHECK(n_seq >= 1 && n_seq <= (1 << 16) && max_positions >= 1 && max_positions <= (1 << 20), OAR_INVALID_INPUT, "oar_k_lm_decode_attention: n_seq outside 1..65536 or max_positions outside 1..2^20");
+        OAR_CHECK(n_rows >= 1 && n_rows <= k::kLmRows, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: n_rows outside 1..16");
+        OAR_CHECK(split_keys == 0 || k::lm_split_keys_supported(split_keys), OAR_INVALID_INPUT, "oar_k_lm_decode_attention: split_keys is neither 0 nor a multiple of 64 in 64..4096");
+        k::LmStep st{};
+        int mp = 0;
+        for (int32_t i = 0; i < n_rows; ++i) {
+            OAR_CHECK(row_seq[i] >= 0 && row_seq[i] < n_seq && row_pos[i] >= 0 && row_pos[i] < max_positions, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: a row outside the sequences or the cache");
+            st.rows[i].seq = row_seq[i]; st.rows[i].pos = row_pos[i];
+            mp = std::max(mp, (int)row_pos[i]);
+        }
+        st.nrows = n_rows;
+        const int64_t Hd = (int64_t)heads * head_dim;
+        OAR_CHECK((o_off & 3) == 0, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: o_off is no multiple of 4 floats");
+        OAR_CHECK(o_off <= o_floats && (uint64_t)n_rows * (uint64_t)Hd <= o_floats - o_off, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: the output does not fit o_floats");
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        const size_t qb = (size_t)n_rows * Hd * 4, cb = (size_t)n_seq * kv_heads * max_positions * head_dim * 4;
+        const size_t wsb = split_keys ? k::lm_split_ws_floats(heads, head_dim, max_positions, split_keys) * 4 : 0;
+        DevBuf dq, dk, dv, dout, dst, dal, dws;
+        dq.reserve(qb); dk.reserve(cb); dv.reserve(cb); dout.reserve(o_floats * 4); dst.reserve(sizeof st); dal.reserve(4);
+        OAR_HIP(hipMemcpy(dq.p, q, qb, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dk.p, kcache, cb, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dv.p, vcache, cb, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dst.p, &st, sizeof st, hipMemcpyHostToDevice));
+        const int32_t one = 1;
+        OAR_HIP(hipMemcpy(dal.p, &one, 4, hipMemcpyHostToDevice));
+        if (wsb) {
+            dws.reserve(wsb);
+            OAR_HIP(hipMemset(dws.p, 0xFF, wsb));
+        }
+        OAR_HIP(hipDeviceSynchronize());
+        k::LmAttnArgs a{};
+        a.st = dst.as<k::LmStep>(); a.q = dq.as<float>(); a.q_ld = (int)Hd; a.kc = dk.as<float>(); a.vc = dv.as<float>(); a.H = heads; a.KVH = kv_heads; a.dh = head_dim;
+        a.maxpos = max_positions; a.o = dout.as<float>() + o_off; a.o_ld = (int)Hd; a.alive = dal.as<int>(); a.ws = dws.as<float>(); a.split_keys = split_keys;
+        k::lm_attention(nullptr, a, split_keys ? k::LM_ATTN_SPLIT : k::LM_ATTN_SERIAL, n_rows, false, mp);
         OAR_HIP(hipGetLastError());
         OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
     });

@@ -41,6 +41,7 @@ class LmRequest(C.Structure):
 
 _bound = False
 PREFILL_MODES = {"rows": 0, "gemm": 1}          # OAR_LM_PREFILL_ROWS / OAR_LM_PREFILL_GEMM
+ATTENTION_MODES = {"serial": 0, "split": 1}     # OAR_LM_ATTN_SERIAL / OAR_LM_ATTN_SPLIT
 
 
 def _lib():
@@ -59,8 +60,20 @@ def _lib():
         L.oar_lm_set_prefill.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.oar_lm_prefill_cost.restype = C.c_int
         L.oar_lm_prefill_cost.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.oar_lm_set_decode.restype = C.c_int
+        L.oar_lm_set_decode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.oar_lm_decode_stats.restype = C.c_int
+        L.oar_lm_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _bound = True
     return L
+
+
+def _check_mode_names(prefill, decode_attention):
+    """Unknown mode names are refused before anything else happens (no device needed)."""
+    if isinstance(prefill, str) and prefill not in PREFILL_MODES:
+        raise api.OCRError(api.OAR_INVALID_INPUT, f"prefill must be 'rows' or 'gemm', got {prefill!r}")
+    if isinstance(decode_attention, str) and decode_attention not in ATTENTION_MODES:
+        raise api.OCRError(api.OAR_INVALID_INPUT, f"decode_attention must be 'serial' or 'split', got {decode_attention!r}")
 
 
 @dataclass
@@ -250,6 +263,21 @@ class CausalLM:
             raise api.OCRError(api.OAR_INVALID_INPUT, f"prefill must be 'rows' or 'gemm', got {mode!r}")
         api._check(_lib().oar_lm_set_prefill(self._h, int(code), 0 if chunk_rows is None else int(chunk_rows)))
 
+    def set_decode(self, attention="serial", split_keys: Optional[int] = None, stop_at_eos: bool = False):
+        """How the following generate calls run their steps: attention "serial" (one launch, a workgroup walks a row's keys) or "split" (the keys cut
+        into spans of split_keys, None: the default, 64; a second launch merges them); stop_at_eos: stop enqueuing steps once every sequence has emitted the
+        call's eos_token_id.  Integers reach the library as they are (it refuses what it does not know)."""
+        code = ATTENTION_MODES.get(attention, attention) if isinstance(attention, str) else attention
+        if isinstance(code, str):
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"decode_attention must be 'serial' or 'split', got {attention!r}")
+        api._check(_lib().oar_lm_set_decode(self._h, int(code), 0 if split_keys is None else int(split_keys), int(stop_at_eos)))
+
+    def decode_stats(self):
+        """(steps_limit, steps_enqueued) of the last generate call: the steps it had scheduled and the steps it enqueued (fewer only when it stopped at eos)."""
+        a, b = C.c_int64(), C.c_int64()
+        api._check(_lib().oar_lm_decode_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def prefill_cost(self, lengths):
         """(flops, bytes, launches) of the GEMM phase of a call with these prompt lengths, at the chunk size set last."""
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
@@ -259,12 +287,15 @@ class CausalLM:
 
     def generate(self, input_ids=None, inputs_embeds=None, position_ids=None, max_new_tokens: int = 16, eos_token_id: Optional[int] = None,
                  return_logits: bool = False, forced_tokens=None, logits_out: Optional[np.ndarray] = None, prefill: str = "rows",
-                 prefill_chunk: Optional[int] = None) -> LMOutput:
+                 prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None, stop_at_eos: bool = False) -> LMOutput:
         """Greedy generation for one sequence or a list of sequences (more than 16 run in groups of 16).  input_ids: [T] ints, or inputs_embeds: [T, hidden]
         floats; position_ids: [3, T] (default 0 .. T - 1 on all axes); forced_tokens: [max_new_tokens] per sequence, entries >= 0 are fed instead of the
         argmax.  logits_out: a flat float32 buffer of at least n_seq x max_new_tokens x vocab that receives the logits in place of a fresh array.
-        prefill: "rows" or "gemm" with prefill_chunk packed rows a chunk (set_prefill); the model keeps the setting of its last call."""
+        prefill: "rows" or "gemm" with prefill_chunk packed rows a chunk (set_prefill); decode_attention: "serial" or "split" with split_keys keys a span, and
+        stop_at_eos (set_decode); the model keeps the settings of its last call."""
+        _check_mode_names(prefill, decode_attention)
         self.set_prefill(prefill, prefill_chunk)
+        self.set_decode(decode_attention, split_keys, stop_at_eos)
         if (input_ids is None) == (inputs_embeds is None):
             raise api.OCRError(api.OAR_INVALID_INPUT, "generate: give exactly one of input_ids and inputs_embeds")
         src = input_ids if input_ids is not None else inputs_embeds
@@ -283,7 +314,7 @@ class CausalLM:
                 kw = {"input_ids" if input_ids is not None else "inputs_embeds": seqs[sl]}
                 outs.append(self.generate(position_ids=None if pos is None else pos[sl], max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                           return_logits=return_logits, forced_tokens=None if forced is None else forced[sl], prefill=prefill,
-                                          prefill_chunk=prefill_chunk, **kw))
+                                          prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys, stop_at_eos=stop_at_eos, **kw))
             return LMOutput(np.concatenate([o.tokens for o in outs]), np.concatenate([o.counts for o in outs]),
                             np.concatenate([o.logits for o in outs]) if return_logits else None)
         V, D = self.cfg.vocab_size, self.cfg.hidden_size
@@ -685,9 +716,12 @@ class PaddleOCRVL:
         self.close()
 
     def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None,
-                        prefill: str = "rows", prefill_chunk: Optional[int] = None) -> LMOutput:
+                        prefill: str = "rows", prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None,
+                        stop_at_eos: bool = False) -> LMOutput:
         """One sequence per image: ids = prefix + [image_token_id] x (h w / merge^2) + suffix; its embeddings are the table rows with the image span replaced
-        by the projector's rows, its positions come from rope_index.  The images are encoded in calls of at most 16 (and at most max_tokens patches)."""
+        by the projector's rows, its positions come from rope_index.  The images are encoded in calls of at most 16 (and at most max_tokens patches).
+        prefill / prefill_chunk / decode_attention / split_keys / stop_at_eos: as CausalLM.generate."""
+        _check_mode_names(prefill, decode_attention)
         m = self.vision.cfg.spatial_merge_size
         px, grids = preprocess_images(images, self.preproc)
         kp = px.shape[1]
@@ -714,4 +748,5 @@ class PaddleOCRVL:
             seqs.append(x)
             pos.append(rope_index(ids, grids[n:n + 1], self.image_token_id, self.vision_start_token_id, m)[0])
         return self.lm.generate(inputs_embeds=seqs, position_ids=pos, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
-                                forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk)
+                                forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
+                                stop_at_eos=stop_at_eos)

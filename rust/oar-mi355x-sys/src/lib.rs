@@ -34,6 +34,10 @@ pub type oar_lm_prefill_mode = c_int;
 pub const OAR_LM_PREFILL_ROWS: oar_lm_prefill_mode = 0;
 pub const OAR_LM_PREFILL_GEMM: oar_lm_prefill_mode = 1;
 
+pub type oar_lm_attention_mode = c_int;
+pub const OAR_LM_ATTN_SERIAL: oar_lm_attention_mode = 0;
+pub const OAR_LM_ATTN_SPLIT: oar_lm_attention_mode = 1;
+
 pub type oar_vis_act = c_int;
 pub const OAR_VIS_GELU_TANH: oar_vis_act = 0;
 pub const OAR_VIS_GELU_ERF: oar_vis_act = 1;
@@ -531,6 +535,9 @@ unsafe extern "C" {
     pub fn oar_lm_prefill_cost(lm: *mut oar_lm, n_seq: i32, lengths: *const i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
     pub fn oar_k_lm_gemm(x: *const f32, m: i32, k: i32, w: *const c_void, w_dtype: i32, n: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_k_lm_prefill_attention(q: *const f32, kcache: *const f32, vcache: *const f32, n_seq: i32, max_positions: i32, starts: *const i32, lens: *const i32, heads: i32, kv_heads: i32, head_dim: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_lm_set_decode(lm: *mut oar_lm, attention: i32, split_keys: i32, stop_at_eos: i32) -> oar_status;
+    pub fn oar_lm_decode_stats(lm: *const oar_lm, steps_limit: *mut i64, steps_enqueued: *mut i64) -> oar_status;
+    pub fn oar_k_lm_decode_attention(q: *const f32, kcache: *const f32, vcache: *const f32, n_seq: i32, max_positions: i32, n_rows: i32, row_seq: *const i32, row_pos: *const i32, heads: i32, kv_heads: i32, head_dim: i32, split_keys: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_vis_create(cfg: *const oar_vis_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_vis) -> oar_status;
     pub fn oar_vis_destroy(vis: *mut oar_vis);
     pub fn oar_vis_encode(vis: *mut oar_vis, req: *const oar_vis_request) -> oar_status;

@@ -11,6 +11,12 @@ torch-ROCm eager, f32 and bf16, as the only outside yardstick.  `--processes 3` 
 length of `--prefill`.  A GEMM line sums the `lm_gemm_*` classes plus the handover step (the decode classes of a call with one new token), and carries the floor of
 oar_lm_prefill_cost: flops / 157.3 TFLOP/s (the exact-f32 matrix peak) or bytes / 6.29 TB/s, whichever is larger.  `--no-decode` leaves the decode lines out.
 
+`--attention serial|split|both` chooses the attention of the decode lines; `--split-keys N [N ...]` the spans of the split arm (0: the library's default).
+With `both` the arms alternate inside one process: for every (weights, cache, sequences) the serial line, then one split line per N, on the same model and prompt.
+A split line carries `attention: "split"` and `split_keys`, and its classes are lm_rows / lm_attn_split / lm_attn_merge / lm_head / lm_combine.  `--decode-prefill gemm`
+fills the cache of the decode lines through the GEMM prefill (much faster at long caches; its handover step is one more decode step of the same classes and is counted).
+`--stop-at-eos T` adds two lines: the wall clock of a call with max_new_tokens 4096 whose sequences all end at token T, with stop_at_eos off and on.
+
 Usage: python tools/lm_decode_bench.py [--processes 3] [--seqs 1 4 16] [--cache 256 2048] [--steps 8] [--prefill 64 256 1024 4096] [--prefill-mode both] [--no-decode] [--no-torch]"""
 import argparse
 import json
@@ -28,6 +34,7 @@ CFG = dict(hidden_size=1024, num_hidden_layers=18, num_attention_heads=16, num_k
            rms_norm_eps=1e-5, rope_theta=500000.0, mrope_section=[16, 24, 24], qkv_bias=False, tie_word_embeddings=False)
 COPY_RATE, BOUNDARY_US, F32_MATRIX_PEAK = 6.29e12, 1.2, 157.3e12
 CLASSES = ("lm_rows", "lm_attn", "lm_head", "lm_combine")
+SPLIT_CLASSES = ("lm_rows", "lm_attn_split", "lm_attn_merge", "lm_head", "lm_combine")
 PREFILL_CLASSES = ("lm_prefill_rows", "lm_prefill_attn", "lm_prefill_head", "lm_prefill_combine")   # steps with prompt positions that give no token
 GEMM_CLASSES = ("lm_gemm_linear", "lm_gemm_attn")                                                    # the GEMM phase; its handover step runs under CLASSES
 
@@ -49,21 +56,21 @@ def bf16_bits(a):
     return ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
 
 
-def profiled(lm, ids, max_new, classes, prefill="rows"):
+def profiled(lm, ids, max_new, classes, prefill="rows", **kw):
     api.prof_reset()
     api.prof_filter(",".join(classes))                # (only these are bracketed with events: a long prefill in front of the decode steps runs as it is)
     api.prof_enable(True)
     try:
-        lm.generate(input_ids=ids, max_new_tokens=max_new, prefill=prefill)
+        lm.generate(input_ids=ids, max_new_tokens=max_new, prefill=prefill, **kw)
         return {e["name"]: e["total_ms"] * 1e3 for e in api.prof_snapshot() if e["name"].startswith("lm_")}
     finally:
         api.prof_enable(False)
         api.prof_filter("")
 
 
-def wall(lm, ids, max_new, prefill="rows"):
+def wall(lm, ids, max_new, prefill="rows", **kw):
     t = time.perf_counter()
-    lm.generate(input_ids=ids, max_new_tokens=max_new, prefill=prefill)
+    lm.generate(input_ids=ids, max_new_tokens=max_new, prefill=prefill, **kw)
     return (time.perf_counter() - t) * 1e6
 
 
@@ -110,7 +117,8 @@ def torch_step_us(cfg, n, C, dtype, steps):
 
 
 def child(a):
-    cfg = vl.CausalLMConfig(max_positions=max(max(a.cache), max(a.prefill)) + a.steps + 2, max_sequences=max(a.seqs), **CFG)
+    cfg = vl.CausalLMConfig(max_positions=max(max(a.cache), max(a.prefill), 4096 if a.stop_at_eos else 0) + a.steps + 2, max_sequences=max(a.seqs), **CFG)
+    arms = ([("serial", None)] if a.attention in ("serial", "both") else []) + ([("split", sk) for sk in a.split_keys] if a.attention in ("split", "both") else [])
     rng = np.random.default_rng(0)
     w32 = weights(cfg, rng)
     for dtype in a.dtypes:
@@ -118,14 +126,35 @@ def child(a):
         with vl.CausalLM.from_state_dict(cfg, w) as lm:
             del w
             lm.generate(input_ids=[1, 2, 3], max_new_tokens=3)                      # warm-up: code objects, LDS opt-in
+            if a.attention != "serial":
+                lm.generate(input_ids=[1, 2, 3], max_new_tokens=3, decode_attention="split")
+            if a.decode_prefill == "gemm":
+                lm.generate(input_ids=list(range(70)), max_new_tokens=1, prefill="gemm")
+            measured = a.steps + (1 if a.decode_prefill == "gemm" else 0)               # (the GEMM prefill's handover step runs under the decode classes)
             for C in ([] if a.no_decode else a.cache):
                 for n in a.seqs:
                     ids = [rng.integers(0, cfg.vocab_size, C).astype(np.int32) for _ in range(n)]
-                    pk = profiled(lm, ids, 1 + a.steps, CLASSES)
-                    per = {c: pk.get(c, 0.0) / a.steps for c in CLASSES}
-                    flops, nbytes, launches = lm.cost(n, C + a.steps // 2)
-                    print(json.dumps({"kind": "decode", "weights": dtype, "seqs": n, "cache": C, "kernel_us": sum(per.values()), "by_class_us": per,
-                                      "floor_us": nbytes / COPY_RATE * 1e6 + launches * BOUNDARY_US, "cost_bytes": nbytes, "launches": launches}), flush=True)
+                    for arm, sk in arms:                                                # the arms alternate: the same model, the same prompt, one after the other
+                        classes = CLASSES if arm == "serial" else SPLIT_CLASSES
+                        pk = profiled(lm, ids, 1 + a.steps, classes, prefill=a.decode_prefill, decode_attention=arm, split_keys=sk or None)
+                        per = {c: pk.get(c, 0.0) / measured for c in classes}
+                        flops, nbytes, launches = lm.cost(n, C + a.steps // 2)
+                        line = {"kind": "decode", "weights": dtype, "seqs": n, "cache": C, "kernel_us": sum(per.values()), "by_class_us": per,
+                                "floor_us": nbytes / COPY_RATE * 1e6 + launches * BOUNDARY_US, "cost_bytes": nbytes, "launches": launches}
+                        if a.attention != "serial":
+                            line.update(attention=arm, split_keys=sk)
+                        print(json.dumps(line), flush=True)
+            if a.stop_at_eos:
+                # sequences that all end at token T: eos is whatever the model emits there (random weights: found by a first call), the prompts are short
+                T = a.stop_at_eos
+                ids = [rng.integers(0, cfg.vocab_size, 4).astype(np.int32)]
+                eos = int(lm.generate(input_ids=ids, max_new_tokens=T + 1).tokens[0][T])
+                for flag in (False, True):
+                    lm.generate(input_ids=ids, max_new_tokens=8, eos_token_id=eos, stop_at_eos=flag)
+                    us = wall(lm, ids, 4096, eos_token_id=eos, stop_at_eos=flag)
+                    limit, enq = lm.decode_stats()
+                    print(json.dumps({"kind": "stop_at_eos_" + ("on" if flag else "off"), "weights": dtype, "wall_us": us, "steps_limit": limit, "steps_enqueued": enq}), flush=True)
+            lm.set_decode()
             for T in a.prefill:
                 ids = rng.integers(0, cfg.vocab_size, T).astype(np.int32)
                 if a.prefill_mode in ("rows", "both"):
@@ -134,11 +163,17 @@ def child(a):
                                       "by_class_us": {c.replace("_prefill", ""): p.get(c, 0.0) for c in PREFILL_CLASSES}}), flush=True)
                 if a.prefill_mode in ("gemm", "both"):
                     lm.generate(input_ids=ids[:70], max_new_tokens=1, prefill="gemm")        # warm-up of this arm's code objects
-                    p = profiled(lm, ids, 1, GEMM_CLASSES + CLASSES, prefill="gemm")
-                    flops, nbytes, launches = lm.prefill_cost([T])
-                    print(json.dumps({"kind": "prefill_gemm", "weights": dtype, "positions": T, "kernel_us": sum(p.get(c, 0.0) for c in GEMM_CLASSES + CLASSES),
-                                      "wall_us": wall(lm, ids, 1, "gemm"), "by_class_us": {c: p.get(c, 0.0) for c in GEMM_CLASSES + CLASSES},
-                                      "floor_us": max(flops / F32_MATRIX_PEAK, nbytes / COPY_RATE) * 1e6, "cost_flops": flops, "cost_bytes": nbytes, "launches": launches}), flush=True)
+                    for arm, sk in arms:
+                        classes = GEMM_CLASSES + (CLASSES if arm == "serial" else SPLIT_CLASSES)
+                        kw = dict(decode_attention=arm, split_keys=sk or None)
+                        p = profiled(lm, ids, 1, classes, prefill="gemm", **kw)
+                        flops, nbytes, launches = lm.prefill_cost([T])
+                        line = {"kind": "prefill_gemm", "weights": dtype, "positions": T, "kernel_us": sum(p.get(c, 0.0) for c in classes),
+                                "wall_us": wall(lm, ids, 1, "gemm", **kw), "by_class_us": {c: p.get(c, 0.0) for c in classes},
+                                "floor_us": max(flops / F32_MATRIX_PEAK, nbytes / COPY_RATE) * 1e6, "cost_flops": flops, "cost_bytes": nbytes, "launches": launches}
+                        if a.attention != "serial":
+                            line.update(attention=arm, split_keys=sk)
+                        print(json.dumps(line), flush=True)
 
 
 def torch_child(a):
@@ -160,6 +195,10 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--prefill", type=int, nargs="+", default=[1024])
     ap.add_argument("--prefill-mode", choices=["rows", "gemm", "both"], default="rows")
+    ap.add_argument("--attention", choices=["serial", "split", "both"], default="serial")
+    ap.add_argument("--split-keys", type=int, nargs="+", default=[0])
+    ap.add_argument("--decode-prefill", choices=["rows", "gemm"], default="rows")
+    ap.add_argument("--stop-at-eos", type=int, default=0)
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--child", action="store_true")
@@ -183,13 +222,17 @@ def main():
             sys.stderr.flush()
             if line.startswith("{"):
                 d = json.loads(line)
-                key = (d["kind"], d["weights"], d.get("seqs"), d.get("cache", d.get("positions")))
+                key = (d["kind"], d["weights"], d.get("seqs"), d.get("cache", d.get("positions")), d.get("attention"), d.get("split_keys"))
                 rows.setdefault(key, []).append(d)
         if r.wait() != 0:
             sys.exit(r.returncode)
     stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1), "max": round(float(np.max(v)), 1)}   # noqa: E731
     for key, ds in rows.items():
         out = {"kind": key[0], "weights": key[1], "seqs": key[2], "cache_or_positions": key[3], "processes": len(ds)}
+        if key[4] is not None:
+            out.update(attention=key[4], split_keys=key[5])
+        if "steps_enqueued" in ds[0]:
+            out.update(steps_limit=ds[0]["steps_limit"], steps_enqueued=ds[0]["steps_enqueued"])
         for f in ("kernel_us", "wall_us", "step_us"):
             if f in ds[0]:
                 out[f] = stat([d[f] for d in ds])
