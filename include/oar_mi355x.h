@@ -718,6 +718,24 @@ oar_status oar_k_lm_decode_attention(const float* q, const float* kcache, const 
                                      const int32_t* row_seq, const int32_t* row_pos, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t split_keys,
                                      float* o_io, size_t o_floats, size_t o_off);
 
+/* ------------------------------------------------------------------------------------------------ VL: queued generation
+ * oar_lm_generate_queue takes oar_lm_generate's request with any n_seq in 1 .. 65535 and gives the same outputs, indexed by a sequence's place in the request:
+ * the sequences wait in request order for one of `slots` cache slots (1 .. cfg.max_sequences; 0: max_sequences), and a slot whose sequence has produced
+ * max_new_tokens, or whose eos the host has seen, is handed to the next waiting sequence.  The chain's steps are the same <= 16 rows of (slot, position) pairs, so
+ * every sequence's tokens, counts and logits are those of the same sequence run alone in the model's prefill mode, attention mode and split_keys, byte for byte.
+ * tokens are eos from a sequence's first eos on; logits rows behind a sequence's eos row are zero.  With OAR_LM_PREFILL_GEMM the sequences admitted at one
+ * scheduling point share one packed GEMM phase.  stop_at_eos has no meaning here (retirement is the stop).  The host looks at the device's `done` flags through a
+ * pinned copy taken behind every step and read 2 steps behind the enqueue, so a sequence gets at most 2 + 1 decode rows after the step that produced its eos; prompts
+ * and forced tokens are uploaded before the first step and the outputs downloaded once after the last.  The call takes the model's mutex.
+ * OAR_INVALID_INPUT: a null argument, n_seq outside 1 .. 65535, slots outside 0 .. max_sequences, and everything oar_lm_generate refuses in a request.
+ * oar_lm_queue_check: those checks against a configuration alone (no model, no device).
+ * oar_lm_queue_stats: the first n_stats (<= 8) figures of the model's last queued call: steps enqueued, rows enqueued, dead rows (decode rows given to sequences
+ * after their eos step), admissions, GEMM phases, the most dead rows of one sequence, the fewest sequences one slot held, the fewest
+ * turnovers of one slot (a slot that held one sequence was turned over twice: to it, and away from it). */
+oar_status oar_lm_generate_queue(oar_lm* lm, const oar_lm_request* req, int32_t slots);
+oar_status oar_lm_queue_check(const oar_lm_cfg* cfg, const oar_lm_request* req, int32_t slots);
+oar_status oar_lm_queue_stats(const oar_lm* lm, int64_t* stats, int32_t n_stats);
+
 /* ------------------------------------------------------------------------------------------------ VL: the vision stage
  * The vision encoder and projector of the oar-ocr-vl crate's PaddleOCR-VL (vision.rs, projector.rs): a SigLIP-style pre-LN ViT over the patches of an
  * image (patch Linear + bilinearly resampled position table; per layer LayerNorm, fused q / k / v Linear, attention with 2-D rotary embedding, out_proj +

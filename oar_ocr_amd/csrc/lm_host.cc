@@ -15,6 +15,7 @@
 #include "common.h"
 #include "lm_decode.h"
 #include "lm_prefill.h"
+#include "lm_queue.h"
 
 using namespace oar;
 
@@ -104,6 +105,28 @@ size_t rope_src(size_t n, int dh) {
     return head * dh + i + s * (dh / 2);
 }
 
+
+// What every generate entry asks of a request, the number of sequences aside (the caller has checked it): returns the prompt rows of the call.
+int64_t check_request(const oar_lm_cfg& c, const oar_lm_request& r, const std::string& fn) {
+    const int S = r.n_seq, MN = r.max_new_tokens, V = c.vocab;
+    OAR_CHECK(MN >= 1, OAR_INVALID_INPUT, fn + ": max_new_tokens must be positive");
+    OAR_CHECK(r.lengths && r.tokens && r.counts && (r.inputs_embeds || r.input_ids), OAR_INVALID_INPUT, fn + ": null lengths, outputs or inputs");
+    OAR_CHECK(r.eos_token_id >= -1 && r.eos_token_id < V, OAR_INVALID_INPUT, fn + ": eos_token_id outside the vocabulary");
+    int64_t total = 0;
+    for (int s = 0; s < S; ++s) {
+        const int T = r.lengths[s];
+        OAR_CHECK(T >= 1 && (int64_t)T + MN <= c.max_positions, OAR_INVALID_INPUT, fn + ": prompt length + max_new_tokens exceeds max_positions (sequence " + std::to_string(s) + ")");
+        if (r.inputs_embeds) OAR_CHECK(r.inputs_embeds[s] != nullptr, OAR_INVALID_INPUT, fn + ": null inputs_embeds entry");
+        else {
+            OAR_CHECK(r.input_ids[s] != nullptr, OAR_INVALID_INPUT, fn + ": null input_ids entry");
+            for (int t = 0; t < T; ++t) OAR_CHECK(r.input_ids[s][t] >= 0 && r.input_ids[s][t] < V, OAR_INVALID_INPUT, fn + ": token id outside the vocabulary");
+        }
+        total += T;
+    }
+    OAR_CHECK(total < (1 << 24), OAR_INVALID_INPUT, fn + ": prompts too long");
+    return total;
+}
+
 }  // namespace
 
 struct oar_lm {
@@ -128,7 +151,14 @@ struct oar_lm {
     int32_t* stop_ring = nullptr;   // pinned [kLmStopRing]: copies of state.alive
     hipEvent_t stop_ev[k::kLmStopRing] = {};
     int64_t steps_limit = 0, steps_enqueued = 0;   // of the last call
+    uint8_t* queue_pin = nullptr;   // pinned rings of queued generation: LmState copies | LmQueueStage tables | GEMM-phase tables
+    size_t queue_pin_cap = 0;
+    hipEvent_t queue_ev[k::kLmQueueRing] = {};
+    k::LmQueueStats queue_stats{};   // of the last queued call
     ~oar_lm() {
+        for (hipEvent_t e : queue_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (queue_pin) (void)hipHostFree(queue_pin);
         for (hipEvent_t e : stop_ev)
             if (e) (void)hipEventDestroy(e);
         if (stop_ring) (void)hipHostFree(stop_ring);
@@ -148,6 +178,119 @@ struct oar_lm {
         return mem.back()->p;
     }
 };
+
+namespace {
+
+// Carves the per-call device memory: take() gives the next 256-byte aligned offset.
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+};
+
+// The per-call device memory of a model, grown when a call needs more.
+uint8_t* work_bytes(oar_lm* lm, size_t need) {
+    if (need > lm->work_cap) {
+        if (lm->work.p) { OAR_HIP(hipFree(lm->work.p)); lm->work.p = nullptr; lm->work_cap = 0; }
+        lm->work.alloc(need);
+        lm->work_cap = need;
+    }
+    return static_cast<uint8_t*>(lm->work.p);
+}
+
+// The chain's parameters for one call: the model's, with the split mode's workspace (allocated at its first use) when the call's attention is split.
+k::LmDecodeP call_params(oar_lm* lm, int attention) {
+    const oar_lm_cfg& c = lm->cfg;
+    k::LmDecodeP P = lm->P;
+    P.layers = lm->layers.data();
+    P.split_ws = nullptr; P.split_keys = lm->split_keys;
+    if (attention == OAR_LM_ATTN_SPLIT) {
+        const size_t ws_b = k::lm_split_ws_floats(c.heads, c.head_dim, c.max_positions, lm->split_keys) * 4;
+        if (ws_b > lm->split_ws_cap) {
+            if (lm->split_ws.p) { OAR_HIP(hipFree(lm->split_ws.p)); lm->split_ws.p = nullptr; lm->split_ws_cap = 0; }
+            lm->split_ws.alloc(ws_b);
+            lm->split_ws_cap = ws_b;
+        }
+        P.split_ws = static_cast<float*>(lm->split_ws.p);
+    }
+    return P;
+}
+
+// The prompts of a request into the arena, sequence after sequence from row 0: the embeddings as they are, or the ids through lm_embed.
+void upload_prompts(const oar_lm_request& r, const k::LmDecodeP& P, int32_t* d_ids, int32_t* d_xrows, hipStream_t s) {
+    const int S = r.n_seq, D = P.D;
+    if (r.inputs_embeds) {
+        size_t row = 0;
+        for (int q = 0; q < S; ++q) {
+            OAR_HIP(hipMemcpyAsync(P.arena + row * D, r.inputs_embeds[q], (size_t)r.lengths[q] * D * 4, hipMemcpyHostToDevice, s));
+            row += (size_t)r.lengths[q];
+        }
+    } else {
+        std::vector<int32_t> ids, xr;
+        for (int q = 0; q < S; ++q)
+            for (int t = 0; t < r.lengths[q]; ++t) { xr.push_back((int32_t)ids.size()); ids.push_back(r.input_ids[q][t]); }
+        OAR_HIP(hipMemcpyAsync(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
+        OAR_HIP(hipMemcpyAsync(d_xrows, xr.data(), xr.size() * 4, hipMemcpyHostToDevice, s));
+        OAR_HIP(hipStreamSynchronize(s));   // (the two host vectors are pageable and end with this block)
+        k::lm_embed(s, P, d_ids, d_xrows, (int)ids.size());
+    }
+}
+
+// GEMM prefill of packed rows already on the device, chunk after chunk (chunk[ci] rows, tiles tile0[ci] .. tile0[ci + 1]; host_tiles: the same tiles,
+// for the cost): per chunk and layer q/k/v GEMM (RMSNorm in front, bias, M-RoPE, k / v into the cache), causal attention, o GEMM + residual, gate / up GEMM
+// (RMSNorm in front, silu(g) u), down GEMM + residual; the last layer stops after its q/k/v launch
+void gemm_phase(const oar_lm* lm, const k::LmDecodeP& P, hipStream_t s, const k::LmPfRow* d_pfrows, const k::LmPfTile* d_pftiles, const k::LmPfTile* host_tiles,
+                const std::vector<int>& pf_chunk, const std::vector<size_t>& pf_tile0, float* pf_q, float* pf_o, float* pf_h) {
+    const oar_lm_cfg& c = lm->cfg;
+    const int D = c.hidden, Hd = c.heads * c.head_dim, Kd = c.kv_heads * c.head_dim, F = c.intermediate;
+    size_t row0 = 0;
+    for (size_t ci = 0; ci < pf_chunk.size(); ++ci) {
+        const int M = pf_chunk[ci];
+        const k::LmPfRow* rows = d_pfrows + row0;
+        const k::LmPfTile* tiles = d_pftiles + pf_tile0[ci];
+        const int n_tiles = (int)(pf_tile0[ci + 1] - pf_tile0[ci]);
+        double abytes = 0.0, aflops = 0.0;
+        k::lm_pf_attn_cost(host_tiles + pf_tile0[ci], n_tiles, c.head_dim, &abytes, &aflops);
+        for (int l = 0; l < c.layers; ++l) {
+            const k::LmLayerW& Lw = lm->layers[(size_t)l];
+            float* kc = P.kcache + (size_t)l * P.cache_layer;
+            float* vc = P.vcache + (size_t)l * P.cache_layer;
+            k::LmGemmP g{};
+            g.mode = k::LM_GEMM_QKV; g.bf16 = P.bf16; g.M = M; g.N = Hd + 2 * Kd; g.K = D; g.Kp = k::lm_pad4(D); g.x = P.arena; g.x_ld = D; g.x_gather = 1; g.rows = rows;
+            g.w = Lw.w_qkv; g.bias = Lw.b_qkv; g.rms_g = Lw.ln1; g.eps = P.eps; g.q = pf_q; g.q_ld = Hd; g.kc = kc; g.vc = vc; g.nq = Hd; g.nk = Kd; g.dh = c.head_dim;
+            g.kvh = c.kv_heads; g.maxpos = P.maxpos; g.sec0 = P.sec0; g.sec1 = P.sec1; g.inv_freq = P.inv_freq;
+            k::lm_gemm(s, g);
+            if (l == c.layers - 1) break;   // nothing reads these rows' hidden state after the last layer's keys and values
+            k::LmPfAttnP a{};
+            a.q = pf_q; a.q_ld = Hd; a.kc = kc; a.vc = vc; a.H = c.heads; a.KVH = c.kv_heads; a.dh = c.head_dim; a.maxpos = P.maxpos;
+            a.scale = 1.0f / sqrtf((float)c.head_dim); a.o = pf_o; a.o_ld = Hd; a.tiles = tiles; a.n_tiles = n_tiles;
+            k::lm_prefill_attention(s, a, abytes, aflops);
+            g = k::LmGemmP{};
+            g.mode = k::LM_GEMM_RESID; g.bf16 = P.bf16; g.M = M; g.N = D; g.K = Hd; g.Kp = k::lm_pad4(Hd); g.x = pf_o; g.x_ld = Hd; g.rows = rows; g.w = Lw.w_o;
+            g.y = P.arena; g.y_ld = D; g.y_scatter = 1;
+            k::lm_gemm(s, g);
+            g = k::LmGemmP{};
+            g.mode = k::LM_GEMM_GATE; g.bf16 = P.bf16; g.M = M; g.N = 2 * F; g.K = D; g.Kp = k::lm_pad4(D); g.x = P.arena; g.x_ld = D; g.x_gather = 1; g.rows = rows;
+            g.w = Lw.w_gu; g.rms_g = Lw.ln2; g.eps = P.eps; g.y = pf_h; g.y_ld = F;
+            k::lm_gemm(s, g);
+            g = k::LmGemmP{};
+            g.mode = k::LM_GEMM_RESID; g.bf16 = P.bf16; g.M = M; g.N = D; g.K = F; g.Kp = k::lm_pad4(F); g.x = pf_h; g.x_ld = F; g.rows = rows; g.w = Lw.w_down;
+            g.y = P.arena; g.y_ld = D; g.y_scatter = 1;
+            k::lm_gemm(s, g);
+        }
+        row0 += (size_t)M;
+    }
+}
+
+// Rotary positions of prompt position t of a sequence of length T (pid: its [3][T] position ids, or null); mx gathers the largest.
+void prompt_positions(const int32_t* pid, int T, int t, int32_t rp[3], int64_t& mx, const std::string& fn) {
+    for (int a = 0; a < 3; ++a) {
+        rp[a] = pid ? pid[(size_t)a * T + t] : t;
+        OAR_CHECK(rp[a] >= 0 && rp[a] < (1 << 24), OAR_INVALID_INPUT, fn + ": position id outside 0..2^24");
+        if (pid) mx = std::max<int64_t>(mx, rp[a]);
+    }
+}
+
+}  // namespace
 
 oar_status oar_lm_create(const oar_lm_cfg* cfg, const oar_lm_tensor* tensors, int32_t n_tensors, int32_t device_id, oar_lm** out) {
     return guard([&] {
@@ -294,21 +437,7 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
         const oar_lm_cfg& c = lm->cfg;
         const int S = req->n_seq, MN = req->max_new_tokens, D = c.hidden, V = c.vocab;
         OAR_CHECK(S >= 1 && S <= c.max_sequences, OAR_INVALID_INPUT, "oar_lm_generate: n_seq outside 1..max_sequences");
-        OAR_CHECK(MN >= 1, OAR_INVALID_INPUT, "oar_lm_generate: max_new_tokens must be positive");
-        OAR_CHECK(req->lengths && req->tokens && req->counts && (req->inputs_embeds || req->input_ids), OAR_INVALID_INPUT, "oar_lm_generate: null lengths, outputs or inputs");
-        OAR_CHECK(req->eos_token_id >= -1 && req->eos_token_id < V, OAR_INVALID_INPUT, "oar_lm_generate: eos_token_id outside the vocabulary");
-        int64_t total = 0;
-        for (int s = 0; s < S; ++s) {
-            const int T = req->lengths[s];
-            OAR_CHECK(T >= 1 && (int64_t)T + MN <= c.max_positions, OAR_INVALID_INPUT, "oar_lm_generate: prompt length + max_new_tokens exceeds max_positions (sequence " + std::to_string(s) + ")");
-            if (req->inputs_embeds) OAR_CHECK(req->inputs_embeds[s] != nullptr, OAR_INVALID_INPUT, "oar_lm_generate: null inputs_embeds entry");
-            else {
-                OAR_CHECK(req->input_ids[s] != nullptr, OAR_INVALID_INPUT, "oar_lm_generate: null input_ids entry");
-                for (int t = 0; t < T; ++t) OAR_CHECK(req->input_ids[s][t] >= 0 && req->input_ids[s][t] < V, OAR_INVALID_INPUT, "oar_lm_generate: token id outside the vocabulary");
-            }
-            total += T;
-        }
-        OAR_CHECK(total < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: prompts too long");
+        const int64_t total = check_request(c, *req, "oar_lm_generate");
         std::lock_guard<std::mutex> lk(lm->mu);
         const bool gemm = lm->prefill_mode == OAR_LM_PREFILL_GEMM;
         const int attention = lm->attention;
@@ -329,11 +458,7 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                 for (int t = 0; t < T; ++t) {
                     k::LmRow& R = cur.rows[cur.nrows];
                     R.seq = s; R.pos = t; R.xrow = xrow++; R.gen = t == T - 1 ? 0 : -1; R.pad = 0;
-                    for (int a = 0; a < 3; ++a) {
-                        R.rp[a] = pid ? pid[(size_t)a * T + t] : t;
-                        OAR_CHECK(R.rp[a] >= 0 && R.rp[a] < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: position id outside 0..2^24");
-                        if (pid) mx = std::max<int64_t>(mx, R.rp[a]);
-                    }
+                    prompt_positions(pid, T, t, R.rp, mx, "oar_lm_generate");
                     if (gemm && R.gen < 0) {   // (the slot is filled again by the next row)
                         pf_rows.push_back(k::LmPfRow{R.seq, R.pos, {R.rp[0], R.rp[1], R.rp[2]}, R.xrow, {0, 0}});
                         continue;
@@ -382,41 +507,25 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
         OAR_HIP(hipSetDevice(lm->device));
         hipStream_t s = lm->stream;
         // per-call device memory: arena | tokens | forced | steps | ids + xrows | logits | GEMM prefill: rows | tiles | q | o | h
-        auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t arena_b = align(((size_t)total + S) * D * 4), tok_b = align((size_t)S * MN * 4), steps_b = align(steps.size() * sizeof(k::LmStep)), ids_b = align((size_t)total * 4);
-        const size_t logits_b = req->logits ? align((size_t)S * MN * V * 4) : 0;
-        const size_t pfr_b = align(pf_rows.size() * sizeof(k::LmPfRow)), pft_b = align(pf_tiles.size() * sizeof(k::LmPfTile));
-        const size_t pfq_b = align((size_t)pf_cap * Hd_ * 4), pfh_b = align((size_t)pf_cap * c.intermediate * 4);
-        const size_t need = arena_b + 2 * tok_b + steps_b + 2 * ids_b + logits_b + pfr_b + pft_b + 2 * pfq_b + pfh_b;
-        if (need > lm->work_cap) {
-            if (lm->work.p) { OAR_HIP(hipFree(lm->work.p)); lm->work.p = nullptr; lm->work_cap = 0; }
-            lm->work.alloc(need);
-            lm->work_cap = need;
-        }
-        uint8_t* w = static_cast<uint8_t*>(lm->work.p);
-        k::LmDecodeP P = lm->P;
-        P.layers = lm->layers.data();
-        P.split_ws = nullptr; P.split_keys = lm->split_keys;
-        if (attention == OAR_LM_ATTN_SPLIT) {
-            const size_t ws_b = k::lm_split_ws_floats(c.heads, c.head_dim, c.max_positions, lm->split_keys) * 4;
-            if (ws_b > lm->split_ws_cap) {
-                if (lm->split_ws.p) { OAR_HIP(hipFree(lm->split_ws.p)); lm->split_ws.p = nullptr; lm->split_ws_cap = 0; }
-                lm->split_ws.alloc(ws_b);
-                lm->split_ws_cap = ws_b;
-            }
-            P.split_ws = static_cast<float*>(lm->split_ws.p);
-        }
+        Carver cv;
+        const size_t arena_o = cv.take(((size_t)total + S) * D * 4), tok_o = cv.take((size_t)S * MN * 4), forced_o = cv.take((size_t)S * MN * 4);
+        const size_t steps_o = cv.take(steps.size() * sizeof(k::LmStep)), ids_o = cv.take((size_t)total * 4), xrows_o = cv.take((size_t)total * 4);
+        const size_t logits_o = cv.take(req->logits ? (size_t)S * MN * V * 4 : 0);
+        const size_t pfr_o = cv.take(pf_rows.size() * sizeof(k::LmPfRow)), pft_o = cv.take(pf_tiles.size() * sizeof(k::LmPfTile));
+        const size_t pfq_o = cv.take((size_t)pf_cap * Hd_ * 4), pfo_o = cv.take((size_t)pf_cap * Hd_ * 4), pfh_o = cv.take((size_t)pf_cap * c.intermediate * 4);
+        uint8_t* w = work_bytes(lm, cv.off);
+        k::LmDecodeP P = call_params(lm, attention);
         if (stop && !lm->stop_ring) {
             OAR_HIP(hipHostMalloc(reinterpret_cast<void**>(&lm->stop_ring), sizeof(int32_t) * k::kLmStopRing, hipHostMallocDefault));
             for (hipEvent_t& e : lm->stop_ev) OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        P.arena = reinterpret_cast<float*>(w); P.xdec0 = xdec0;
-        P.tokens = reinterpret_cast<int32_t*>(w + arena_b);
-        int32_t* d_forced = reinterpret_cast<int32_t*>(w + arena_b + tok_b);
-        k::LmStep* d_steps = reinterpret_cast<k::LmStep*>(w + arena_b + 2 * tok_b);
-        int32_t* d_ids = reinterpret_cast<int32_t*>(w + arena_b + 2 * tok_b + steps_b);
-        int32_t* d_xrows = reinterpret_cast<int32_t*>(w + arena_b + 2 * tok_b + steps_b + ids_b);
-        P.logits = req->logits ? reinterpret_cast<float*>(w + arena_b + 2 * tok_b + steps_b + 2 * ids_b) : nullptr;
+        P.arena = reinterpret_cast<float*>(w + arena_o); P.xdec0 = xdec0;
+        P.tokens = reinterpret_cast<int32_t*>(w + tok_o);
+        int32_t* d_forced = reinterpret_cast<int32_t*>(w + forced_o);
+        k::LmStep* d_steps = reinterpret_cast<k::LmStep*>(w + steps_o);
+        int32_t* d_ids = reinterpret_cast<int32_t*>(w + ids_o);
+        int32_t* d_xrows = reinterpret_cast<int32_t*>(w + xrows_o);
+        P.logits = req->logits ? reinterpret_cast<float*>(w + logits_o) : nullptr;
         P.forced = req->forced_tokens ? d_forced : nullptr;
         P.max_new = MN; P.eos = req->eos_token_id;
         OAR_HIP(hipMemsetAsync(P.tokens, 0, (size_t)S * MN * 4, s));
@@ -426,74 +535,18 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
         k::LmState st0{};
         st0.alive = S;
         OAR_HIP(hipMemcpyAsync(P.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
-        if (req->inputs_embeds) {
-            size_t row = 0;
-            for (int q = 0; q < S; ++q) {
-                OAR_HIP(hipMemcpyAsync(P.arena + row * D, req->inputs_embeds[q], (size_t)req->lengths[q] * D * 4, hipMemcpyHostToDevice, s));
-                row += (size_t)req->lengths[q];
-            }
-        } else {
-            std::vector<int32_t> ids, xr;
-            for (int q = 0; q < S; ++q)
-                for (int t = 0; t < req->lengths[q]; ++t) { xr.push_back((int32_t)ids.size()); ids.push_back(req->input_ids[q][t]); }
-            OAR_HIP(hipMemcpyAsync(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
-            OAR_HIP(hipMemcpyAsync(d_xrows, xr.data(), xr.size() * 4, hipMemcpyHostToDevice, s));
-            OAR_HIP(hipStreamSynchronize(s));   // (the two host vectors are pageable and end with this block)
-            k::lm_embed(s, P, d_ids, d_xrows, (int)ids.size());
-        }
-        uint8_t* wpf = w + arena_b + 2 * tok_b + steps_b + 2 * ids_b + logits_b;
-        k::LmPfRow* d_pfrows = reinterpret_cast<k::LmPfRow*>(wpf);
-        k::LmPfTile* d_pftiles = reinterpret_cast<k::LmPfTile*>(wpf + pfr_b);
-        float* pf_q = reinterpret_cast<float*>(wpf + pfr_b + pft_b);
-        float* pf_o = reinterpret_cast<float*>(wpf + pfr_b + pft_b + pfq_b);
-        float* pf_h = reinterpret_cast<float*>(wpf + pfr_b + pft_b + 2 * pfq_b);
+        upload_prompts(*req, P, d_ids, d_xrows, s);
+        k::LmPfRow* d_pfrows = reinterpret_cast<k::LmPfRow*>(w + pfr_o);
+        k::LmPfTile* d_pftiles = reinterpret_cast<k::LmPfTile*>(w + pft_o);
+        float* pf_q = reinterpret_cast<float*>(w + pfq_o);
+        float* pf_o = reinterpret_cast<float*>(w + pfo_o);
+        float* pf_h = reinterpret_cast<float*>(w + pfh_o);
         if (!pf_rows.empty()) {
             OAR_HIP(hipMemcpyAsync(d_pfrows, pf_rows.data(), pf_rows.size() * sizeof(k::LmPfRow), hipMemcpyHostToDevice, s));
             OAR_HIP(hipMemcpyAsync(d_pftiles, pf_tiles.data(), pf_tiles.size() * sizeof(k::LmPfTile), hipMemcpyHostToDevice, s));
         }
         OAR_HIP(hipStreamSynchronize(s));       // (pageable sources: steps, st0, the GEMM phase's tables)
-        {
-            // GEMM prefill: per chunk and layer q/k/v GEMM (RMSNorm in front, bias, M-RoPE, k / v into the cache), causal attention, o GEMM +
-            // residual, gate / up GEMM (RMSNorm in front, silu(g) u), down GEMM + residual; the last layer stops after its q/k/v launch
-            const int Hd = (int)Hd_, Kd = c.kv_heads * c.head_dim, F = c.intermediate;
-            size_t row0 = 0;
-            for (size_t ci = 0; ci < pf_chunk.size(); ++ci) {
-                const int M = pf_chunk[ci];
-                const k::LmPfRow* rows = d_pfrows + row0;
-                const k::LmPfTile* tiles = d_pftiles + pf_tile0[ci];
-                const int n_tiles = (int)(pf_tile0[ci + 1] - pf_tile0[ci]);
-                double abytes = 0.0, aflops = 0.0;
-                k::lm_pf_attn_cost(pf_tiles.data() + pf_tile0[ci], n_tiles, c.head_dim, &abytes, &aflops);
-                for (int l = 0; l < c.layers; ++l) {
-                    const k::LmLayerW& Lw = lm->layers[(size_t)l];
-                    float* kc = P.kcache + (size_t)l * P.cache_layer;
-                    float* vc = P.vcache + (size_t)l * P.cache_layer;
-                    k::LmGemmP g{};
-                    g.mode = k::LM_GEMM_QKV; g.bf16 = P.bf16; g.M = M; g.N = Hd + 2 * Kd; g.K = D; g.Kp = k::lm_pad4(D); g.x = P.arena; g.x_ld = D; g.x_gather = 1; g.rows = rows;
-                    g.w = Lw.w_qkv; g.bias = Lw.b_qkv; g.rms_g = Lw.ln1; g.eps = P.eps; g.q = pf_q; g.q_ld = Hd; g.kc = kc; g.vc = vc; g.nq = Hd; g.nk = Kd; g.dh = c.head_dim;
-                    g.kvh = c.kv_heads; g.maxpos = P.maxpos; g.sec0 = P.sec0; g.sec1 = P.sec1; g.inv_freq = P.inv_freq;
-                    k::lm_gemm(s, g);
-                    if (l == c.layers - 1) break;   // nothing reads these rows' hidden state after the last layer's keys and values
-                    k::LmPfAttnP a{};
-                    a.q = pf_q; a.q_ld = Hd; a.kc = kc; a.vc = vc; a.H = c.heads; a.KVH = c.kv_heads; a.dh = c.head_dim; a.maxpos = P.maxpos;
-                    a.scale = 1.0f / sqrtf((float)c.head_dim); a.o = pf_o; a.o_ld = Hd; a.tiles = tiles; a.n_tiles = n_tiles;
-                    k::lm_prefill_attention(s, a, abytes, aflops);
-                    g = k::LmGemmP{};
-                    g.mode = k::LM_GEMM_RESID; g.bf16 = P.bf16; g.M = M; g.N = D; g.K = Hd; g.Kp = k::lm_pad4(Hd); g.x = pf_o; g.x_ld = Hd; g.rows = rows; g.w = Lw.w_o;
-                    g.y = P.arena; g.y_ld = D; g.y_scatter = 1;
-                    k::lm_gemm(s, g);
-                    g = k::LmGemmP{};
-                    g.mode = k::LM_GEMM_GATE; g.bf16 = P.bf16; g.M = M; g.N = 2 * F; g.K = D; g.Kp = k::lm_pad4(D); g.x = P.arena; g.x_ld = D; g.x_gather = 1; g.rows = rows;
-                    g.w = Lw.w_gu; g.rms_g = Lw.ln2; g.eps = P.eps; g.y = pf_h; g.y_ld = F;
-                    k::lm_gemm(s, g);
-                    g = k::LmGemmP{};
-                    g.mode = k::LM_GEMM_RESID; g.bf16 = P.bf16; g.M = M; g.N = D; g.K = F; g.Kp = k::lm_pad4(F); g.x = pf_h; g.x_ld = F; g.rows = rows; g.w = Lw.w_down;
-                    g.y = P.arena; g.y_ld = D; g.y_scatter = 1;
-                    k::lm_gemm(s, g);
-                }
-                row0 += (size_t)M;
-            }
-        }
+        gemm_phase(lm, P, s, d_pfrows, d_pftiles, pf_tiles.data(), pf_chunk, pf_tile0, pf_q, pf_o, pf_h);
         // stop at eos: copy c is taken behind step (c + 1) kLmStopStride - 1; before step i the host waits for the newest copy taken at a step
         // <= i - kLmStopLookahead -- the device still holds the steps after it -- and enqueues nothing more once that copy of `alive` is 0
         size_t enqueued = 0;
@@ -535,6 +588,184 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                     if (req->tokens[(size_t)q * MN + g] == req->eos_token_id) { n = g + 1; break; }
             req->counts[q] = n;
         }
+    });
+}
+
+namespace {
+
+void queue_check(const oar_lm_cfg* cfg, const oar_lm_request* req, int32_t slots) {
+    OAR_CHECK(cfg && req, OAR_INVALID_INPUT, "oar_lm_generate_queue: null argument");
+    OAR_CHECK(cfg->max_sequences >= 1 && cfg->max_sequences <= k::kLmRows && cfg->vocab >= 2 && cfg->max_positions >= 2, OAR_INVALID_INPUT,
+              "oar_lm_generate_queue: max_sequences outside 1..16, vocab or max_positions below 2");
+    OAR_CHECK(req->n_seq >= 1 && req->n_seq <= k::kLmQueueMaxSeq, OAR_INVALID_INPUT, "oar_lm_generate_queue: n_seq outside 1..65535");
+    OAR_CHECK(slots >= 0 && slots <= cfg->max_sequences, OAR_INVALID_INPUT, "oar_lm_generate_queue: slots outside 0..max_sequences");
+    check_request(*cfg, *req, "oar_lm_generate_queue");
+}
+
+}  // namespace
+
+// What oar_lm_generate_queue asks of its arguments; needs no model and no device.
+oar_status oar_lm_queue_check(const oar_lm_cfg* cfg, const oar_lm_request* req, int32_t slots) {
+    return guard([&] { queue_check(cfg, req, slots); });
+}
+
+oar_status oar_lm_generate_queue(oar_lm* lm, const oar_lm_request* req, int32_t slots_arg) {
+    return guard([&] {
+        static const std::string fn = "oar_lm_generate_queue";
+        OAR_CHECK(lm && req, OAR_INVALID_INPUT, fn + ": null argument");
+        const oar_lm_cfg& c = lm->cfg;
+        queue_check(&c, req, slots_arg);
+        const int S = req->n_seq, MN = req->max_new_tokens, D = c.hidden, V = c.vocab, slots = slots_arg == 0 ? c.max_sequences : slots_arg;
+        // every sequence's arena rows and positions
+        std::vector<k::LmQueueSeq> seqs((size_t)S);
+        int64_t total = 0;
+        for (int q = 0; q < S; ++q) {
+            const int T = req->lengths[q];
+            const int32_t* pid = req->position_ids ? req->position_ids[q] : nullptr;
+            int64_t mx = pid ? INT64_MIN : T - 1;
+            int32_t rp[3];
+            for (int t = 0; t < T; ++t) prompt_positions(pid, T, t, rp, mx, fn);
+            OAR_CHECK(mx + MN < (1 << 24), OAR_INVALID_INPUT, fn + ": position id outside 0..2^24");
+            seqs[(size_t)q] = k::LmQueueSeq{T, (int32_t)total, (int32_t)(mx + 1), pid};
+            total += T;
+        }
+        std::lock_guard<std::mutex> lk(lm->mu);
+        const bool gemm = lm->prefill_mode == OAR_LM_PREFILL_GEMM;
+        const int attention = lm->attention;
+        const int xdec0 = (int)total;
+        size_t pf_rows_cap = 0, pf_tiles_cap = 0;
+        if (gemm) k::lm_queue_phase_caps(req->lengths, S, slots, lm->chunk_rows, c.heads, &pf_rows_cap, &pf_tiles_cap);
+        const size_t pf_cap = std::min<size_t>(pf_rows_cap, (size_t)lm->chunk_rows), Hd = (size_t)c.heads * c.head_dim;
+
+        OAR_HIP(hipSetDevice(lm->device));
+        hipStream_t s = lm->stream;
+        // per-call device memory: arena | the slots' tokens, forced tokens, logits | every sequence's tokens, forced tokens, logits | stage | ids + xrows |
+        // GEMM phase: rows | tiles | q | o | h
+        const bool forced = req->forced_tokens != nullptr, logits = req->logits != nullptr;
+        Carver cv;
+        const size_t arena_o = cv.take(((size_t)total + slots) * D * 4), stok_o = cv.take((size_t)slots * MN * 4), sforced_o = cv.take(forced ? (size_t)slots * MN * 4 : 0);
+        const size_t slogits_o = cv.take(logits ? (size_t)slots * MN * V * 4 : 0), otok_o = cv.take((size_t)S * MN * 4), oforced_o = cv.take(forced ? (size_t)S * MN * 4 : 0);
+        const size_t ologits_o = cv.take(logits ? (size_t)S * MN * V * 4 : 0), stage_o = cv.take(sizeof(k::LmQueueStage));
+        const size_t ids_o = cv.take((size_t)total * 4), xrows_o = cv.take((size_t)total * 4);
+        const size_t pfr_o = cv.take(pf_rows_cap * sizeof(k::LmPfRow)), pft_o = cv.take(pf_tiles_cap * sizeof(k::LmPfTile));
+        const size_t pfq_o = cv.take(pf_cap * Hd * 4), pfo_o = cv.take(pf_cap * Hd * 4), pfh_o = cv.take(pf_cap * c.intermediate * 4);
+        uint8_t* w = work_bytes(lm, cv.off);
+        k::LmDecodeP P = call_params(lm, attention);
+        // pinned rings, entry i mod kLmQueueRing for step i: LmState copies | stages | GEMM-phase rows | tiles
+        Carver pin;
+        const size_t pstate_o = pin.take(sizeof(k::LmState) * k::kLmQueueRing), pstage_o = pin.take(sizeof(k::LmQueueStage) * k::kLmQueueRing);
+        const size_t prow_b = (pf_rows_cap * sizeof(k::LmPfRow) + 255) & ~(size_t)255, ptile_b = (pf_tiles_cap * sizeof(k::LmPfTile) + 255) & ~(size_t)255;
+        const size_t prow_o = pin.take(prow_b * k::kLmQueueRing), ptile_o = pin.take(ptile_b * k::kLmQueueRing);
+        if (pin.off > lm->queue_pin_cap) {
+            if (lm->queue_pin) { OAR_HIP(hipHostFree(lm->queue_pin)); lm->queue_pin = nullptr; lm->queue_pin_cap = 0; }
+            OAR_HIP(hipHostMalloc(reinterpret_cast<void**>(&lm->queue_pin), pin.off, hipHostMallocDefault));
+            lm->queue_pin_cap = pin.off;
+        }
+        for (hipEvent_t& e : lm->queue_ev)
+            if (!e) OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        k::LmState* pin_state = reinterpret_cast<k::LmState*>(lm->queue_pin + pstate_o);
+        k::LmQueueStage* pin_stage = reinterpret_cast<k::LmQueueStage*>(lm->queue_pin + pstage_o);
+
+        P.arena = reinterpret_cast<float*>(w + arena_o); P.xdec0 = xdec0;
+        P.tokens = reinterpret_cast<int32_t*>(w + stok_o);
+        P.forced = forced ? reinterpret_cast<int32_t*>(w + sforced_o) : nullptr;
+        P.logits = logits ? reinterpret_cast<float*>(w + slogits_o) : nullptr;
+        P.max_new = MN; P.eos = req->eos_token_id;
+        k::LmQueueStage* d_stage = reinterpret_cast<k::LmQueueStage*>(w + stage_o);
+        k::LmPfRow* d_pfrows = reinterpret_cast<k::LmPfRow*>(w + pfr_o);
+        k::LmPfTile* d_pftiles = reinterpret_cast<k::LmPfTile*>(w + pft_o);
+        k::LmQueueTurnP tp{};
+        tp.turn = d_stage->turn; tp.slot_tokens = P.tokens; tp.out_tokens = reinterpret_cast<int32_t*>(w + otok_o);
+        tp.slot_forced = forced ? reinterpret_cast<int32_t*>(w + sforced_o) : nullptr; tp.all_forced = forced ? reinterpret_cast<const int32_t*>(w + oforced_o) : nullptr;
+        tp.slot_logits = P.logits; tp.out_logits = logits ? reinterpret_cast<float*>(w + ologits_o) : nullptr;
+        tp.state = P.state; tp.max_new = MN; tp.V = V; tp.eos = req->eos_token_id;
+        // everything the steps read is on the device before the first step: prompts, forced tokens, zeroed slot rows.  `alive` starts at n_seq: the chain's
+        // alive == 0 guard cannot fire while sequences wait
+        OAR_HIP(hipMemsetAsync(P.tokens, 0, (size_t)slots * MN * 4, s));
+        OAR_HIP(hipMemsetAsync(tp.out_tokens, 0, (size_t)S * MN * 4, s));
+        if (logits) OAR_HIP(hipMemsetAsync(P.logits, 0, (size_t)slots * MN * V * 4, s));
+        if (forced) {
+            OAR_HIP(hipMemsetAsync(tp.slot_forced, 0xFF, (size_t)slots * MN * 4, s));
+            OAR_HIP(hipMemcpyAsync(w + oforced_o, req->forced_tokens, (size_t)S * MN * 4, hipMemcpyHostToDevice, s));
+        }
+        k::LmState st0{};
+        st0.alive = S;
+        OAR_HIP(hipMemcpyAsync(P.state, &st0, sizeof st0, hipMemcpyHostToDevice, s));
+        upload_prompts(*req, P, reinterpret_cast<int32_t*>(w + ids_o), reinterpret_cast<int32_t*>(w + xrows_o), s);
+        OAR_HIP(hipStreamSynchronize(s));       // (pageable sources: forced tokens, st0, the prompts)
+
+        // the step loop: nothing blocks the host but the lagged event (lm_queue.h)
+        k::LmQueue Q(seqs.data(), S, slots, MN, gemm, xdec0);
+        std::vector<k::LmQueueAdmit> admits;
+        k::LmQueuePhase ph;
+        k::LmState seen_state{};
+        int64_t seen = -1, gemm_phases = 0;
+        for (;;) {
+            const int64_t i = Q.step();
+            const size_t e = (size_t)(i % k::kLmQueueRing);
+            const int64_t cpy = k::lm_queue_copy_for(i);
+            if (cpy > seen) {
+                OAR_HIP(hipEventSynchronize(lm->queue_ev[cpy % k::kLmQueueRing]));
+                seen_state = pin_state[cpy % k::kLmQueueRing];
+                seen = cpy;
+            }
+            k::LmQueueStage& st = pin_stage[e];
+            int n_turn = 0, max_pos = 0;
+            const bool more = Q.next(seen >= 0 ? seen_state.done : nullptr, seen >= 0 ? k::lm_queue_copy_step(seen) : -1, st, n_turn, max_pos, admits);
+            if (!more && n_turn == 0) break;
+            OAR_HIP(hipMemcpyAsync(d_stage, &st, sizeof st, hipMemcpyHostToDevice, s));
+            if (n_turn) { tp.n_turn = n_turn; k::lm_queue_turnover(s, tp); }
+            if (!more) break;
+            if (!admits.empty()) {   // one packed GEMM phase for everything admitted at this point
+                k::LmPfRow* prow = reinterpret_cast<k::LmPfRow*>(lm->queue_pin + prow_o + e * prow_b);
+                k::LmPfTile* ptile = reinterpret_cast<k::LmPfTile*>(lm->queue_pin + ptile_o + e * ptile_b);
+                OAR_CHECK(k::lm_queue_pack(seqs.data(), admits.data(), (int)admits.size(), lm->chunk_rows, c.heads, prow, pf_rows_cap, ptile, pf_tiles_cap, ph), OAR_INTERNAL,
+                          fn + ": a GEMM phase outgrew its tables");
+                OAR_HIP(hipMemcpyAsync(d_pfrows, prow, ph.n_rows * sizeof(k::LmPfRow), hipMemcpyHostToDevice, s));
+                OAR_HIP(hipMemcpyAsync(d_pftiles, ptile, ph.n_tiles * sizeof(k::LmPfTile), hipMemcpyHostToDevice, s));
+                gemm_phase(lm, P, s, d_pfrows, d_pftiles, ptile, ph.chunk, ph.tile0, reinterpret_cast<float*>(w + pfq_o), reinterpret_cast<float*>(w + pfo_o),
+                           reinterpret_cast<float*>(w + pfh_o));
+                ++gemm_phases;
+            }
+            k::lm_step(s, P, &d_stage->step, st.step.nrows, st.step.nhead, max_pos, attention);
+            if ((i + 1) % k::kLmQueueStride == 0) {
+                const size_t ce = (size_t)(((i + 1) / k::kLmQueueStride - 1) % k::kLmQueueRing);
+                OAR_HIP(hipMemcpyAsync(pin_state + ce, P.state, sizeof(k::LmState), hipMemcpyDeviceToHost, s));
+                OAR_HIP(hipEventRecord(lm->queue_ev[ce], s));
+            }
+        }
+        OAR_HIP(hipGetLastError());
+        OAR_HIP(hipMemcpyAsync(req->tokens, tp.out_tokens, (size_t)S * MN * 4, hipMemcpyDeviceToHost, s));
+        if (logits) OAR_HIP(hipMemcpyAsync(req->logits, tp.out_logits, (size_t)S * MN * V * 4, hipMemcpyDeviceToHost, s));
+        OAR_HIP(hipStreamSynchronize(s));
+        if (Profiler::get().enabled) Profiler::get().flush();
+        k::LmQueueStats qs{};
+        qs.steps = Q.step(); qs.rows = Q.rows(); qs.admissions = Q.admissions(); qs.gemm_phases = gemm_phases; qs.min_slot_admissions = Q.min_slot_admissions(); qs.min_slot_turnovers = Q.min_slot_turnovers();
+        for (int q = 0; q < S; ++q) {
+            int n = MN;
+            if (req->eos_token_id >= 0)
+                for (int g = 0; g < MN; ++g)
+                    if (req->tokens[(size_t)q * MN + g] == req->eos_token_id) { n = g + 1; break; }
+            req->counts[q] = n;
+            // rows the sequence got after its eos step: their logits were written by the chain and are zeroed here, as the rows behind them are
+            const int dead = Q.produced()[(size_t)q] - n;
+            if (dead > 0) {
+                qs.dead_rows += dead;
+                qs.max_dead_rows = std::max<int64_t>(qs.max_dead_rows, dead);
+                if (logits) std::memset(req->logits + ((size_t)q * MN + n) * V, 0, (size_t)dead * V * 4);
+            }
+        }
+        lm->queue_stats = qs;
+    });
+}
+
+oar_status oar_lm_queue_stats(const oar_lm* lm, int64_t* stats, int32_t n_stats) {
+    return guard([&] {
+        OAR_CHECK(lm && stats && n_stats >= 0, OAR_INVALID_INPUT, "oar_lm_queue_stats: null argument");
+        std::lock_guard<std::mutex> lk(lm->mu);
+        const k::LmQueueStats& q = lm->queue_stats;
+        const int64_t v[8] = {q.steps, q.rows, q.dead_rows, q.admissions, q.gemm_phases, q.max_dead_rows, q.min_slot_admissions, q.min_slot_turnovers};
+        for (int32_t i = 0; i < n_stats && i < 8; ++i) stats[i] = v[i];
     });
 }
 

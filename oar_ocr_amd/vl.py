@@ -42,6 +42,8 @@ class LmRequest(C.Structure):
 _bound = False
 PREFILL_MODES = {"rows": 0, "gemm": 1}          # OAR_LM_PREFILL_ROWS / OAR_LM_PREFILL_GEMM
 ATTENTION_MODES = {"serial": 0, "split": 1}     # OAR_LM_ATTN_SERIAL / OAR_LM_ATTN_SPLIT
+SCHEDULES = ("groups", "refill")                # oar_lm_generate in groups of 16 / oar_lm_generate_queue
+QUEUE_STATS = ("steps", "rows", "dead_rows", "admissions", "gemm_phases", "max_dead_rows", "min_slot_admissions", "min_slot_turnovers")   # oar_lm_queue_stats, in its order
 
 
 def _lib():
@@ -64,6 +66,12 @@ def _lib():
         L.oar_lm_set_decode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         L.oar_lm_decode_stats.restype = C.c_int
         L.oar_lm_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.oar_lm_generate_queue.restype = C.c_int
+        L.oar_lm_generate_queue.argtypes = [C.c_void_p, C.POINTER(LmRequest), C.c_int32]
+        L.oar_lm_queue_check.restype = C.c_int
+        L.oar_lm_queue_check.argtypes = [C.POINTER(LmCfg), C.POINTER(LmRequest), C.c_int32]
+        L.oar_lm_queue_stats.restype = C.c_int
+        L.oar_lm_queue_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
         _bound = True
     return L
 
@@ -278,6 +286,14 @@ class CausalLM:
         api._check(_lib().oar_lm_decode_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def queue_stats(self):
+        """Of the last generate call with schedule="refill" (DESIGN 4.44): steps and rows enqueued, dead rows (decode rows given to sequences after their eos
+        step), admissions, GEMM phases, the most dead rows of one sequence, the fewest sequences one slot held and the
+        fewest turnovers of one slot."""
+        v = (C.c_int64 * len(QUEUE_STATS))()
+        api._check(_lib().oar_lm_queue_stats(self._h, v, len(QUEUE_STATS)))
+        return dict(zip(QUEUE_STATS, (int(x) for x in v)))
+
     def prefill_cost(self, lengths):
         """(flops, bytes, launches) of the GEMM phase of a call with these prompt lengths, at the chunk size set last."""
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
@@ -287,13 +303,19 @@ class CausalLM:
 
     def generate(self, input_ids=None, inputs_embeds=None, position_ids=None, max_new_tokens: int = 16, eos_token_id: Optional[int] = None,
                  return_logits: bool = False, forced_tokens=None, logits_out: Optional[np.ndarray] = None, prefill: str = "rows",
-                 prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None, stop_at_eos: bool = False) -> LMOutput:
-        """Greedy generation for one sequence or a list of sequences (more than 16 run in groups of 16).  input_ids: [T] ints, or inputs_embeds: [T, hidden]
+                 prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None, stop_at_eos: bool = False,
+                 schedule: str = "groups", slots: Optional[int] = None) -> LMOutput:
+        """Greedy generation for one sequence or a list of sequences.  schedule "groups": more than 16 run in groups of 16, one after the other; "refill"
+        (DESIGN 4.44): any number share `slots` cache slots (None: the model's max_sequences) and a finished sequence's slot goes to the next waiting one, with
+        the same bytes per sequence, logits_out for any number of sequences, and stop_at_eos without meaning.  input_ids: [T] ints, or inputs_embeds: [T, hidden]
         floats; position_ids: [3, T] (default 0 .. T - 1 on all axes); forced_tokens: [max_new_tokens] per sequence, entries >= 0 are fed instead of the
         argmax.  logits_out: a flat float32 buffer of at least n_seq x max_new_tokens x vocab that receives the logits in place of a fresh array.
         prefill: "rows" or "gemm" with prefill_chunk packed rows a chunk (set_prefill); decode_attention: "serial" or "split" with split_keys keys a span, and
         stop_at_eos (set_decode); the model keeps the settings of its last call."""
         _check_mode_names(prefill, decode_attention)
+        if schedule not in SCHEDULES:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"schedule must be 'groups' or 'refill', got {schedule!r}")
+        refill = schedule == "refill"
         self.set_prefill(prefill, prefill_chunk)
         self.set_decode(decode_attention, split_keys, stop_at_eos)
         if (input_ids is None) == (inputs_embeds is None):
@@ -305,7 +327,7 @@ class CausalLM:
         n = len(seqs)
         if n == 0:
             raise api.OCRError(api.OAR_INVALID_INPUT, "generate: no sequence")
-        if n > MAX_SEQUENCES:
+        if n > MAX_SEQUENCES and not refill:
             if logits_out is not None:
                 raise api.OCRError(api.OAR_INVALID_INPUT, "generate: logits_out serves at most 16 sequences")
             outs = []
@@ -370,7 +392,10 @@ class CausalLM:
                 logits = np.empty(need, np.float32)
             req.logits = logits.ctypes.data
         req.tokens, req.counts = tokens.ctypes.data, counts.ctypes.data
-        api._check(_lib().oar_lm_generate(self._h, C.byref(req)))
+        if refill:
+            api._check(_lib().oar_lm_generate_queue(self._h, C.byref(req), 0 if slots is None else int(slots)))
+        else:
+            api._check(_lib().oar_lm_generate(self._h, C.byref(req)))
         if logits is not None:
             logits = logits[:n * tokens.shape[1] * V].reshape(n, tokens.shape[1], V)
         if single:
@@ -717,10 +742,10 @@ class PaddleOCRVL:
 
     def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None,
                         prefill: str = "rows", prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None,
-                        stop_at_eos: bool = False) -> LMOutput:
+                        stop_at_eos: bool = False, schedule: str = "groups", slots: Optional[int] = None) -> LMOutput:
         """One sequence per image: ids = prefix + [image_token_id] x (h w / merge^2) + suffix; its embeddings are the table rows with the image span replaced
         by the projector's rows, its positions come from rope_index.  The images are encoded in calls of at most 16 (and at most max_tokens patches).
-        prefill / prefill_chunk / decode_attention / split_keys / stop_at_eos: as CausalLM.generate."""
+        prefill / prefill_chunk / decode_attention / split_keys / stop_at_eos / schedule / slots: as CausalLM.generate."""
         _check_mode_names(prefill, decode_attention)
         m = self.vision.cfg.spatial_merge_size
         px, grids = preprocess_images(images, self.preproc)
@@ -749,4 +774,4 @@ class PaddleOCRVL:
             pos.append(rope_index(ids, grids[n:n + 1], self.image_token_id, self.vision_start_token_id, m)[0])
         return self.lm.generate(inputs_embeds=seqs, position_ids=pos, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
                                 forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
-                                stop_at_eos=stop_at_eos)
+                                stop_at_eos=stop_at_eos, schedule=schedule, slots=slots)

@@ -538,6 +538,9 @@ unsafe extern "C" {
     pub fn oar_lm_set_decode(lm: *mut oar_lm, attention: i32, split_keys: i32, stop_at_eos: i32) -> oar_status;
     pub fn oar_lm_decode_stats(lm: *const oar_lm, steps_limit: *mut i64, steps_enqueued: *mut i64) -> oar_status;
     pub fn oar_k_lm_decode_attention(q: *const f32, kcache: *const f32, vcache: *const f32, n_seq: i32, max_positions: i32, n_rows: i32, row_seq: *const i32, row_pos: *const i32, heads: i32, kv_heads: i32, head_dim: i32, split_keys: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_lm_generate_queue(lm: *mut oar_lm, req: *const oar_lm_request, slots: i32) -> oar_status;
+    pub fn oar_lm_queue_check(cfg: *const oar_lm_cfg, req: *const oar_lm_request, slots: i32) -> oar_status;
+    pub fn oar_lm_queue_stats(lm: *const oar_lm, stats: *mut i64, n_stats: i32) -> oar_status;
     pub fn oar_vis_create(cfg: *const oar_vis_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_vis) -> oar_status;
     pub fn oar_vis_destroy(vis: *mut oar_vis);
     pub fn oar_vis_encode(vis: *mut oar_vis, req: *const oar_vis_request) -> oar_status;

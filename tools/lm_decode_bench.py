@@ -16,6 +16,13 @@ With `both` the arms alternate inside one process: for every (weights, cache, se
 A split line carries `attention: "split"` and `split_keys`, and its classes are lm_rows / lm_attn_split / lm_attn_merge / lm_head / lm_combine.  `--decode-prefill gemm`
 fills the cache of the decode lines through the GEMM prefill (much faster at long caches; its handover step is one more decode step of the same classes and is counted).
 `--stop-at-eos T` adds two lines: the wall clock of a call with max_new_tokens 4096 whose sequences all end at token T, with stop_at_eos off and on.
+`--queue N` measures queued generation instead of the lines above: N prompts of mixed lengths (16 .. 512), bf16 weights, prefill "gemm", split attention,
+`--queue-new` tokens asked for.  Random weights would never emit one token in two sequences, so the lengths are made to spread: the lm-head row of the eos token is
+scaled by `--queue-eos-gain`, and every step is fed a random forced token instead of its argmax (both arms alike), so that eos wins at about two percent of the steps,
+independently from step to step; a first call prints the histogram of the lengths.  Two arms alternate in the process: "groups"
+(generate in groups of 16 with stop_at_eos, summed over the groups) and "refill" (schedule="refill", slots 16); each prints wall clock, steps, rows, dead rows and
+tokens per second; then the same pair without eos (even lengths: refill should tie), and the kernel time of the refill arm's GEMM phases, during which the decoding
+slots wait.  `--lib PATH` loads another build of the library (build.py's OAR_LM_QUEUE_LAG), `--lag S/L` labels its lines.
 
 Usage: python tools/lm_decode_bench.py [--processes 3] [--seqs 1 4 16] [--cache 256 2048] [--steps 8] [--prefill 64 256 1024 4096] [--prefill-mode both] [--no-decode] [--no-torch]"""
 import argparse
@@ -176,6 +183,65 @@ def child(a):
                         print(json.dumps(line), flush=True)
 
 
+def queue_child(a):
+    """--queue: the groups schedule against the refill schedule on one list of prompts."""
+    if a.lib:
+        api.LIB_PATH = Path(a.lib).resolve()
+    N, MN, eos = a.queue, a.queue_new, 7
+    cfg = vl.CausalLMConfig(max_positions=512 + MN + 2, max_sequences=16, **CFG)
+    rng = np.random.default_rng(0)
+    w = weights(cfg, rng)
+    w["lm_head.weight"][eos] *= np.float32(a.queue_eos_gain)
+    w = {k: (bf16_bits(v) if v.ndim == 2 else v) for k, v in w.items()}
+    ids = [rng.integers(0, cfg.vocab_size, int(T)).astype(np.int32) for T in rng.integers(16, 513, N)]
+    forced = [row for row in rng.integers(0, cfg.vocab_size, (N, MN)).astype(np.int32)]
+    mode = dict(prefill="gemm", decode_attention="split")
+
+    def groups(lm, eos_id):
+        t = time.perf_counter()
+        steps = rows = live = 0
+        for i in range(0, N, 16):
+            out = lm.generate(input_ids=ids[i:i + 16], max_new_tokens=MN, eos_token_id=eos_id, stop_at_eos=True, forced_tokens=forced[i:i + 16], **mode)
+            enq = lm.decode_stats()[1]
+            steps, rows, live = steps + enq, rows + enq * len(out.counts), live + int(out.counts.sum())
+        return dict(wall_us=(time.perf_counter() - t) * 1e6, steps=steps, rows=rows, dead_rows=rows - live, tokens=live)
+
+    def refill(lm, eos_id):
+        t = time.perf_counter()
+        out = lm.generate(input_ids=ids, max_new_tokens=MN, eos_token_id=eos_id, schedule="refill", forced_tokens=forced, **mode)
+        us = (time.perf_counter() - t) * 1e6
+        q = lm.queue_stats()
+        return dict(wall_us=us, steps=q["steps"], rows=q["rows"], dead_rows=q["dead_rows"], tokens=int(out.counts.sum()), gemm_phases=q["gemm_phases"],
+                    max_dead_rows=q["max_dead_rows"])
+
+    with vl.CausalLM.from_state_dict(cfg, w) as lm:
+        del w
+        free = lm.generate(input_ids=ids, max_new_tokens=MN, eos_token_id=eos, schedule="refill", forced_tokens=forced, **mode)   # warm-up of the code objects, and the lengths
+        hist = np.bincount(np.minimum(free.counts - 1, MN - 1) * 8 // MN, minlength=8).tolist()
+        print(json.dumps({"kind": "queue_lengths", "weights": "bf16", "n": N, "max_new": MN, "eighths_of_max_new": hist, "at_limit": int((free.counts == MN).sum()),
+                          "mean": float(free.counts.mean())}), flush=True)
+        groups(lm, eos)
+        for workload, eos_id in (("uneven", eos), ("even", None)):
+            for rep in range(a.queue_reps if eos_id is not None else 1):                                             # the arms alternate
+                for arm, fn in (("groups", groups), ("refill", refill)):
+                    r = fn(lm, eos_id)
+                    r.update(kind="queue", weights="bf16", arm=arm, workload=workload, lag=a.lag, rep=rep, tokens_per_s=r["tokens"] / r["wall_us"] * 1e6)
+                    print(json.dumps(r), flush=True)
+        api.prof_reset()
+        api.prof_filter(",".join(GEMM_CLASSES))
+        api.prof_enable(True)
+        try:
+            lm.generate(input_ids=ids, max_new_tokens=MN, eos_token_id=eos, schedule="refill", forced_tokens=forced, **mode)
+            p = {e["name"]: (e["total_ms"] * 1e3, e["launches"]) for e in api.prof_snapshot() if e["name"] in GEMM_CLASSES}
+        finally:
+            api.prof_enable(False)
+            api.prof_filter("")
+        q = lm.queue_stats()
+        print(json.dumps({"kind": "queue_gemm_phases", "weights": "bf16", "lag": a.lag, "phases": q["gemm_phases"], "admissions": q["admissions"],
+                          "kernel_us": sum(v[0] for v in p.values()), "launches": sum(v[1] for v in p.values()),
+                          "kernel_us_per_phase": sum(v[0] for v in p.values()) / max(q["gemm_phases"], 1)}), flush=True)
+
+
 def torch_child(a):
     """In a process of its own: torch brings its own HIP runtime."""
     import torch
@@ -184,6 +250,30 @@ def torch_child(a):
         for C in a.cache:
             for n in a.seqs:
                 print(json.dumps({"kind": "torch_eager", "weights": name, "seqs": n, "cache": C, "step_us": torch_step_us(cfg, n, C, dt, a.steps)}), flush=True)
+
+
+def queue_main(a):
+    if a.child or a.processes <= 1:
+        queue_child(a)
+        return
+    rows = {}
+    for _ in range(a.processes):                                                     # fresh processes, one after the other
+        r = subprocess.Popen([sys.executable, __file__, "--child"] + sys.argv[1:], stdout=subprocess.PIPE, text=True)
+        for line in r.stdout:
+            sys.stderr.write(line)
+            sys.stderr.flush()
+            if line.startswith("{"):
+                d = json.loads(line)
+                rows.setdefault((d["kind"], d.get("arm"), d.get("workload"), d.get("lag")), []).append(d)
+        if r.wait() != 0:
+            sys.exit(r.returncode)
+    stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1), "max": round(float(np.max(v)), 1)}   # noqa: E731
+    for (kind, arm, workload, lag), ds in rows.items():
+        out = {"kind": kind, "arm": arm, "workload": workload, "lag": lag, "samples": len(ds)}
+        out.update({f: stat([d[f] for d in ds]) for f in ("wall_us", "tokens_per_s", "kernel_us", "kernel_us_per_phase") if f in ds[0]})
+        out.update({f: ds[0][f] for f in ("steps", "rows", "dead_rows", "tokens", "gemm_phases", "max_dead_rows", "phases", "launches", "eighths_of_max_new", "at_limit", "mean")
+                    if f in ds[0]})
+        print(json.dumps(out), flush=True)
 
 
 def main():
@@ -199,6 +289,12 @@ def main():
     ap.add_argument("--split-keys", type=int, nargs="+", default=[0])
     ap.add_argument("--decode-prefill", choices=["rows", "gemm"], default="rows")
     ap.add_argument("--stop-at-eos", type=int, default=0)
+    ap.add_argument("--queue", type=int, default=0)
+    ap.add_argument("--queue-new", type=int, default=128)
+    ap.add_argument("--queue-eos-gain", type=float, default=3.3)
+    ap.add_argument("--queue-reps", type=int, default=2)
+    ap.add_argument("--lib", default="")
+    ap.add_argument("--lag", default="")
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--child", action="store_true")
@@ -206,6 +302,9 @@ def main():
     a = ap.parse_args()
     if a.torch_child:
         torch_child(a)
+        return
+    if a.queue:
+        queue_main(a)
         return
     if a.child or a.processes <= 1:
         child(a)
