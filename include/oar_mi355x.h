@@ -851,9 +851,11 @@ oar_status oar_debug_inject_failure(const char* site, int32_t count);
 /* ------------------------------------------------------------------------------------------------ profiling
  * Per-kernel-class accumulators filled from hipEvents recorded on the engine's own stream while cfg.profile
  * is set.  class_name e.g. "conv_igemm", "dwconv", "softmax".  alg_bytes / alg_flops are the algorithmic
- * totals of the timed launches. */
+ * totals of the timed launches.
+ * ABI: `name` grew from 48 to 96 characters (sizeof(oar_prof_entry) 80 -> 128).  A caller of oar_prof_snapshot compiled against the older
+ * header passes an array of smaller elements and must be rebuilt against this one. */
 typedef struct {
-    char name[48];
+    char name[96];   /* as long as the launch sites' own buffers: an OAR_PROF_DETAIL=1 name carries the layer's shape and the kernel variant */
     uint64_t launches;
     double total_ms;
     double alg_bytes;

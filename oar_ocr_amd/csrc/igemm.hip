@@ -397,7 +397,16 @@ void conv_igemm(hipStream_t s, const ConvP& c, const char* prof_class) {
     const char* cls = lk ? "conv_lk_x6" : rs3_cls ? "conv_rs3_x6" : x6_os ? "conv_igemm_os_x6" : x6 ? "conv_igemm_ws_x6" : ws ? "conv_igemm_ws" : "conv_igemm";   // one profiler class per kernel
     if (prof_class) cls = prof_class;
     if (Profiler::get().detail) {
-        snprintf(pname, sizeof pname, "conv_igemm%s M=%ld K=%d N=%d k%dx%d s%d%s", lk ? "_lk_x6" : rs3_cls ? "_rs3_x6" : x6_os ? "_os_x6" : x6 ? "_x6" : ws ? "_ws" : "", p.M, p.K, p.gemm_cout, c.kh, c.kw, c.sh, c.convt2x2 ? " convT" : "");
+        // the f32 paths name the instantiation that runs as well (synth/f32_cases.py restates this choice, tests/test_gpu_f32_conv_kernels.py compares the two)
+        char var[32] = "";
+        if (!x6) {
+            if (ws3) snprintf(var, sizeof var, " ws3 NT=%d", nfrag);
+            else if (ws_nt > 0) snprintf(var, sizeof var, " ws NT=%d PF=%d", ws_nt, igemm_ws_pf(ws_nt));
+            else if (small) snprintf(var, sizeof var, " small%s NT=%d", is1x1 && p.se ? " SE" : "", NT);
+            else snprintf(var, sizeof var, " tile NT=%d PF=%d", NT, PF);
+        }
+        const int len = snprintf(pname, sizeof pname, "conv_igemm%s M=%ld K=%d N=%d k%dx%d s%d%s%s", lk ? "_lk_x6" : rs3_cls ? "_rs3_x6" : x6_os ? "_os_x6" : x6 ? "_x6" : ws ? "_ws" : "", p.M, p.K, p.gemm_cout, c.kh, c.kw, c.sh, c.convt2x2 ? " convT" : "", var);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "conv_igemm: the detail name does not fit its buffer");
         cls = pname;
     }
     ProfScope ps(s, cls, bytes, flops);

@@ -251,6 +251,8 @@ __device__ __forceinline__ bool igemm_init_acc(const IgemmP& p, f32x4 (&acc)[NT]
 }
 
 // weight-stationary variant (igemm_ws.inc, instantiated in igemm_ws_1x1.hip / igemm_ws_gen.hip)
+// pixel fragments per wave tile of the instantiation with `nt` cout fragments: the launch switch and the profiler's detail name both take it from here
+constexpr int igemm_ws_pf(int nt) { return nt >= 6 ? 1 : 2; }
 void conv_igemm_ws_1x1(hipStream_t s, const IgemmP& p, int ws_nt, int ny, size_t lds);
 void conv_igemm_ws_gen(hipStream_t s, const IgemmP& p, int ws_nt, int ny, size_t lds);
 // weight-stationary bf16x6 variant for 1x1 / Linear layers (igemm_ws_x6.hip); p.KC = ceil(K/32), p.w in x6 fragment order

@@ -273,12 +273,12 @@ static void launch_igemm_ws(hipStream_t s, const IgemmP& p, int ny, size_t lds) 
 
 void IGEMM_WS_ENTRY(hipStream_t s, const IgemmP& p, int ws_nt, int ny, size_t lds) {
     switch (ws_nt) {
-        case 8: launch_igemm_ws<8, 1, IGEMM_WS_IS1X1>(s, p, ny, lds); break;
-        case 6: launch_igemm_ws<6, 1, IGEMM_WS_IS1X1>(s, p, ny, lds); break;
-        case 4: launch_igemm_ws<4, 2, IGEMM_WS_IS1X1>(s, p, ny, lds); break;
-        case 3: launch_igemm_ws<3, 2, IGEMM_WS_IS1X1>(s, p, ny, lds); break;
-        case 2: launch_igemm_ws<2, 2, IGEMM_WS_IS1X1>(s, p, ny, lds); break;
-        default: launch_igemm_ws<1, 2, IGEMM_WS_IS1X1>(s, p, ny, lds); break;
+        case 8: launch_igemm_ws<8, igemm_ws_pf(8), IGEMM_WS_IS1X1>(s, p, ny, lds); break;
+        case 6: launch_igemm_ws<6, igemm_ws_pf(6), IGEMM_WS_IS1X1>(s, p, ny, lds); break;
+        case 4: launch_igemm_ws<4, igemm_ws_pf(4), IGEMM_WS_IS1X1>(s, p, ny, lds); break;
+        case 3: launch_igemm_ws<3, igemm_ws_pf(3), IGEMM_WS_IS1X1>(s, p, ny, lds); break;
+        case 2: launch_igemm_ws<2, igemm_ws_pf(2), IGEMM_WS_IS1X1>(s, p, ny, lds); break;
+        default: launch_igemm_ws<1, igemm_ws_pf(1), IGEMM_WS_IS1X1>(s, p, ny, lds); break;
     }
 }
 

@@ -173,18 +173,25 @@ void conv_dw(hipStream_t s, const ConvP& p) {
     double flops = 2.0 * (double)p.N * p.Ho * p.Wo * p.Cout * p.kh * p.kw;
     char pname[96];
     const char* cls = "conv_dw";
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "conv_dw px=%ld C=%d k%d s%d", (long)p.N * p.Ho * p.Wo, p.Cout, p.kh, p.sh); cls = pname; }
-    ProfScope ps(s, cls, bytes, flops, /*single_launch=*/true);
     const bool sq = p.kh == p.kw && p.dh == 1 && p.dw == 1;
     constexpr int TW = kDwTW;
     auto threads_for = [&](int th) { return (long)p.N * ((p.Ho + th - 1) / th) * ((p.Wo + TW - 1) / TW) * (p.Cout / 4); };
     const int TH = dw_tile_rows(p);
-    long tiled = threads_for(TH);
-    dim3 g((grid_for(tiled) + 7) / 8 * 8), b(256);
     const size_t lds = (size_t)p.kh * p.kw * p.Cout * sizeof(float);
     // weights of all channels in LDS: up to 96 KB (C = 768 at 5 x 5 needs 77 KB -- beyond the default 64 KB limit the kernel is
     // opted in per instantiation; two workgroups per CU still beat the generic kernel's 1 TB/s by 3x)
     const bool fits = lds <= 96 * 1024;
+    if (Profiler::get().detail) {   // with the instantiation that runs (restated in synth/f32_cases.py)
+        char var[48];
+        if (p.gap_part || dw_tiled_shape(p)) snprintf(var, sizeof var, "tiled k=%d s=%dx%d TH=%d%s%s", p.kh, p.sh, p.sw, TH, p.gap_part ? " gap" : "", lds > 64 * 1024 ? " lds96" : "");
+        else snprintf(var, sizeof var, "generic");
+        const int len = snprintf(pname, sizeof pname, "conv_dw px=%ld C=%d k%d s%d %s", (long)p.N * p.Ho * p.Wo, p.Cout, p.kh, p.sh, var);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "conv_dw: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, bytes, flops, /*single_launch=*/true);
+    long tiled = threads_for(TH);
+    dim3 g((grid_for(tiled) + 7) / 8 * 8), b(256);
 #define DW2(KV, SHV, SWV, THV)                                                                                                                              \
     do {                                                                                                                                                    \
         if (lds > 64 * 1024) {                                                                                                                              \
@@ -445,13 +452,21 @@ void conv_direct(hipStream_t s, const ConvP& p) {
     if (total == 0) return;
     double bytes = 4.0 * ((double)p.N * p.H * p.W * p.Cin + (double)total + (double)p.kh * p.kw * (p.Cin / p.groups) * p.Cout);
     double flops = 2.0 * (double)total * p.kh * p.kw * (p.Cin / p.groups);
-    if (p.groups == 1 && p.Cin <= 4 && p.kh * p.kw * p.Cin <= 128) {
-        ProfScope ps(s, "conv_smallcin", bytes, flops);
+    char pname[96];
+    const bool smallcin = p.groups == 1 && p.Cin <= 4 && p.kh * p.kw * p.Cin <= 128;
+    const char* cls = smallcin ? "conv_smallcin" : "conv_direct";
+    if (Profiler::get().detail) {
+        const int len = snprintf(pname, sizeof pname, "%s px=%ld Cin=%d Cout=%d g%d k%dx%d s%dx%d", cls, (long)p.N * p.Ho * p.Wo, p.Cin, p.Cout, p.groups, p.kh, p.kw, p.sh, p.sw);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "conv_direct: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    if (smallcin) {
+        ProfScope ps(s, cls, bytes, flops);
         long pixels = (long)p.N * p.Ho * p.Wo;
         hipLaunchKernelGGL(conv_smallcin_kernel, dim3(grid_for(pixels, 256, 256L * 16), (p.Cout + 15) / 16), dim3(256), 0, s, p);
         return;
     }
-    ProfScope ps(s, "conv_direct", bytes, flops);
+    ProfScope ps(s, cls, bytes, flops);
     hipLaunchKernelGGL(conv_direct_kernel, dim3(grid_for(total)), dim3(256), 0, s, p);
 }
 
@@ -560,7 +575,14 @@ __global__ __launch_bounds__(256) void convt_direct_kernel(ConvP p) {
 void convt_direct(hipStream_t s, const ConvP& p) {
     long total = (long)p.N * p.Ho * p.Wo * p.Cout;
     if (total == 0) return;
-    ProfScope ps(s, "convt_direct", 4.0 * ((double)p.N * p.H * p.W * p.Cin + (double)total), 2.0 * (double)p.N * p.H * p.W * p.Cin * p.Cout * p.kh * p.kw);
+    char pname[96];
+    const char* cls = "convt_direct";
+    if (Profiler::get().detail) {
+        const int len = snprintf(pname, sizeof pname, "convt_direct px=%ld Cin=%d Cout=%d k%dx%d s%dx%d", (long)p.N * p.Ho * p.Wo, p.Cin, p.Cout, p.kh, p.kw, p.sh, p.sw);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "convt_direct: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 4.0 * ((double)p.N * p.H * p.W * p.Cin + (double)total), 2.0 * (double)p.N * p.H * p.W * p.Cin * p.Cout * p.kh * p.kw);
     hipLaunchKernelGGL(convt_direct_kernel, dim3(grid_for(total)), dim3(256), 0, s, p);
 }
 

@@ -29,6 +29,71 @@ np.savez(d + "/out.npz", y=y, names=np.array(names))
 """
 
 
+_CHILD_MANY = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from oar_ocr_amd import api
+d, count = sys.argv[2], int(sys.argv[3])
+api.prof_enable(True)
+for i in range(count):
+    eng = api.OrtInfer(open(f"{d}/job{i}.onnx", "rb").read(), profile=True)
+    with np.load(f"{d}/job{i}.in.npz") as z:
+        feed = [(k, z[k]) for k in z.files]
+    api.prof_reset()
+    first = eng.infer(feed)
+    again = eng.infer(feed)
+    names = sorted({e["name"] for e in api.prof_snapshot() if e["launches"]})
+    eng.close()
+    same = len(first) == len(again) and all(a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes() for (_, a), (_, b) in zip(first, again))
+    np.savez(f"{d}/job{i}.out.npz", names=np.array(names), same=np.array(same), **{f"y{j}": a for j, (_, a) in enumerate(first)})
+    print("job", i, "done", flush=True)
+api.prof_enable(False)
+"""
+
+
+def infer_many_in_child(jobs, env: dict, workdir, timeout: float = 300.0):
+    """jobs: [(model bytes, {input name: array})] -> one ChildResult per job: outputs() (the first run's arrays, in graph order), names (the profiler
+    classes that ran during the job) and same (the job ran twice in the child: were the two runs' outputs byte-identical?).  All jobs run in ONE fresh
+    child started with `env` on top of this process's environment -- one child at a time, its own time limit, never retried."""
+    d = Path(workdir)
+    d.mkdir(parents=True, exist_ok=True)
+    count = 0
+    for model, feed in jobs:     # (any iterable: a generator keeps one job's inputs in memory at a time)
+        (d / f"job{count}.onnx").write_bytes(model)
+        np.savez(d / f"job{count}.in.npz", **{k: np.ascontiguousarray(v, np.float32) for k, v in feed.items()})
+        out = d / f"job{count}.out.npz"
+        if out.exists():
+            out.unlink()
+        count += 1
+    r = subprocess.run([sys.executable, "-c", _CHILD_MANY, str(ROOT), str(d), str(count)], env={**os.environ, **{k: str(v) for k, v in env.items()}},
+                       timeout=timeout, capture_output=True, text=True)
+    for i in range(count):
+        (d / f"job{i}.in.npz").unlink()
+    assert r.returncode == 0 and all((d / f"job{i}.out.npz").exists() for i in range(count)), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    res = []
+    for i in range(count):
+        with np.load(d / f"job{i}.out.npz") as z:
+            res.append(ChildResult(d / f"job{i}.out.npz", {str(n) for n in z["names"]}, bool(z["same"])))
+    return res
+
+
+class ChildResult:
+    """one job of infer_many_in_child: names, same, and outputs() -- read from the child's file when asked for, so that a long list of large results
+    does not sit in memory at once"""
+
+    def __init__(self, path, names, same):
+        self.path, self.names, self.same = path, names, same
+
+    def discard(self):
+        """delete the child's file (the caller is done with this job)"""
+        Path(self.path).unlink(missing_ok=True)
+
+    def outputs(self):
+        with np.load(self.path) as z:
+            return [z[f"y{j}"] for j in range(sum(1 for k in z.files if k.startswith("y")))]
+
+
 def infer_in_child(model: bytes, x, env: dict, workdir, timeout: float = 120.0):
     """-> (first output, set of profiler classes that ran) of OrtInfer(model).infer(x) in a child process started with `env` on top of this one's"""
     d = Path(workdir)

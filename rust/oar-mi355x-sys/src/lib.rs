@@ -424,7 +424,7 @@ pub struct oar_vis_request {
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
 pub struct oar_prof_entry {
-    pub name: [c_char; 48],
+    pub name: [c_char; 96],
     pub launches: u64,
     pub total_ms: f64,
     pub alg_bytes: f64,

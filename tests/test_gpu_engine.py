@@ -337,19 +337,35 @@ def _conv_graph(cin, cout, k, seed, relu=True, group=1, strides=(1, 1)):
     return g.model()
 
 
+def _check_ran(model, x, cls):
+    """_check, and the profiler class `cls` ran (the name every case id promises)"""
+    _check(model, x)
+    eng = api.OrtInfer(model, profile=True)
+    try:
+        api.prof_enable(True); api.prof_reset()
+        eng.infer(x)
+        names = {e["name"] for e in api.prof_snapshot() if e["launches"]}
+    finally:
+        api.prof_enable(False)
+        eng.close()
+    assert cls in names, (cls, sorted(names))
+
+
 @pytest.mark.parametrize("case", [
-    ("ws_x6 1x1 192->192", 37, 192, 192, 12, 80, 1),       # bf16x6 weight-stationary kernel (K, N >= 96, many pixels)
-    ("ws_x6 1x1 104->96 K tail", 80, 104, 96, 12, 80, 1),   # K = 104: zero-padded tail of the last 32-deep chunk
-    ("ws f32 1x1 48->96", 128, 48, 96, 12, 80, 1),         # f32 weight-stationary kernel (N >= 96, K < 96)
-    ("ws3 3x3 64->16", 2, 64, 16, 240, 240, 3),            # 3x3 same conv with DPP tap reuse (M >= 100000)
-    ("ws3 3x3 32->32 ragged", 3, 32, 32, 150, 231, 3),     # two cout fragments, row length not a multiple of the tile
-    ("per-tile 1x1 24->32", 2, 24, 32, 240, 240, 1),       # per-wave-tile kernel, K not a multiple of 16
+    ("ws_x6 1x1 192->192", 37, 192, 192, 12, 80, 1, "conv_igemm_ws_x6"),       # bf16x6 weight-stationary kernel (K, N >= 96, many pixels)
+    ("ws_x6 1x1 104->96 K tail", 80, 104, 96, 12, 80, 1, "conv_igemm_ws_x6"),   # K = 104: zero-padded tail of the last 32-deep chunk
+    ("ws f32 1x1 48->96", 128, 48, 96, 12, 80, 1, "conv_igemm_ws"),            # f32 weight-stationary kernel (N >= 96, K < 96)
+    ("rs3_x6 3x3 64->16 (ws3 before the row-streaming kernel)", 2, 64, 16, 240, 240, 3, "conv_rs3_x6"),   # Cin 64, Cout <= 16, M >= 100000: a bf16x6 layer since igemm_rs3_x6.hip; ws3 at this shape: tests/test_gpu_f32_conv_kernels.py "ws3 NT1 64->8 (rs3 off) relu"
+    ("ws3 3x3 32->32 ragged", 3, 32, 32, 150, 231, 3, "conv_igemm_ws"),        # 3x3 same conv with DPP tap reuse (M >= 100000): two cout fragments, row length not a multiple of the tile
+    ("per-tile 1x1 24->32", 2, 24, 32, 240, 240, 1, "conv_igemm"),             # per-wave-tile kernel, K not a multiple of 16
 ])
 def test_igemm_kernels_at_bench_shapes(case):
-    """Each implicit-GEMM kernel at a shape large enough to select it (see conv_igemm's rules), against torch-CPU conv2d."""
-    name, n, cin, cout, h, w, k = case
+    """Each implicit-GEMM kernel at a shape large enough to select it (see conv_igemm's rules), against torch-CPU conv2d; the profiler class the id names
+    ran.  (Which variant inside a class -- ws / ws3, tile / small, NT, PF -- is asserted in tests/test_gpu_f32_conv_kernels.py, where a child process
+    runs with per-variant profiler names.)"""
+    name, n, cin, cout, h, w, k, cls = case
     x = np.random.default_rng(len(name)).standard_normal((n, cin, h, w)).astype(np.float32)
-    _check(_conv_graph(cin, cout, k, seed=n + cin), x)
+    _check_ran(_conv_graph(cin, cout, k, seed=n + cin), x, cls)
 
 
 @pytest.mark.parametrize("case", [
@@ -449,13 +465,14 @@ def test_output_stationary_x6_kernel(case):
     ("5x5 s1 ragged", 3, 128, 61, 75, 5, (1, 1)),          # partial tiles in both directions
     ("5x5 s2", 2, 64, 90, 90, 5, (2, 2)),
     ("3x3 s1 C=48", 2, 48, 120, 120, 3, (1, 1)),
-    ("5x5 one row per thread", 1, 128, 20, 20, 5, (1, 1)), # too few threads for 2-row tiles
+    ("5x5 one row per thread", 1, 128, 20, 20, 5, (1, 1)), # too few threads for 2-row tiles (rows per thread are visible in the per-variant names only: asserted in tests/test_gpu_f32_conv_kernels.py, "dw ... TH1" / "TH2")
 ])
 def test_depthwise_kernels_at_bench_shapes(case):
-    """The register-tiled depthwise kernel (kernels.hip) at the bench's layer shapes, against torch-CPU conv2d."""
+    """The register-tiled depthwise kernel (kernels.hip) at the bench's layer shapes, against torch-CPU conv2d; the conv_dw class ran (tiled or generic,
+    one or two rows per thread: tests/test_gpu_f32_conv_kernels.py)."""
     name, n, c, h, w, k, strides = case
     x = np.random.default_rng(len(name)).standard_normal((n, c, h, w)).astype(np.float32)
-    _check(_conv_graph(c, c, k, seed=n + c, group=c, strides=strides), x)
+    _check_ran(_conv_graph(c, c, k, seed=n + c, group=c, strides=strides), x, "conv_dw")
 
 
 def _attention_graph(dim, heads, seed, scaled=True):
