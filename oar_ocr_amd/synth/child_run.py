@@ -1,6 +1,6 @@
 """One inference in a fresh Python process: for switches the native library reads once per process (OAR_IGEMM_X6, OAR_IGEMM_RS3, ...), which a test
 cannot flip inside its own.  The model, the input and the result travel through files of a directory the caller owns; one child at a time, its own
-time limit, never retried."""
+time limit, never retried.  infer_* run api.OrtInfer, recognize_many_in_child runs api.TextRecognitionPredictor (the recognizer seam: its fused CTC tail)."""
 from __future__ import annotations
 
 import os
@@ -50,6 +50,63 @@ for i in range(count):
     print("job", i, "done", flush=True)
 api.prof_enable(False)
 """
+
+
+_CHILD_REC = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from oar_ocr_amd import api
+from oar_ocr_amd.synth import models
+d, count = sys.argv[2], int(sys.argv[3])
+api.prof_enable(True)
+for i in range(count):
+    with np.load(f"{d}/job{i}.in.npz") as z:
+        crops, classes = list(z["crops"]), int(z["classes"])
+    pred = api.TextRecognitionPredictor(open(f"{d}/job{i}.onnx", "rb").read(), api.read_dict(models.synth_dict(classes - 2)))
+    api.prof_reset()
+    first = pred.predict(crops)
+    again = pred.predict(crops)
+    names = sorted({e["name"] for e in api.prof_snapshot() if e["launches"]})
+    pred.close()
+    same = first.indices.tobytes() == again.indices.tobytes() and first.probs.tobytes() == again.probs.tobytes()
+    np.savez(f"{d}/job{i}.out.npz", names=np.array(names), same=np.array(same), indices=first.indices, probs=first.probs)
+    print("job", i, "done", flush=True)
+api.prof_enable(False)
+"""
+
+
+class RecResult:
+    """one job of recognize_many_in_child"""
+
+    def __init__(self, indices, probs, names, same):
+        self.indices, self.probs, self.names, self.same = indices, probs, names, same
+
+
+def recognize_many_in_child(jobs, env: dict, workdir, timeout: float = 300.0):
+    """jobs: [(model bytes, classes, crops)] with crops a list of equally sized u8 [h, w, 3] images and `classes` the model's vocabulary size (blank and
+    space included: the dictionary is models.synth_dict(classes - 2)).  Every job is one TextRecognitionPredictor and two predict() calls in ONE fresh
+    child started with `env` on top of this process's environment -> one RecResult per job: indices and probs [n, T] of the first call, names (the
+    profiler classes that ran during the job) and same (were the two calls' results byte-identical?).  One child at a time, its own time limit, never
+    retried."""
+    d = Path(workdir)
+    d.mkdir(parents=True, exist_ok=True)
+    count = 0
+    for model, classes, crops in jobs:
+        (d / f"job{count}.onnx").write_bytes(model)
+        np.savez(d / f"job{count}.in.npz", crops=np.stack([np.ascontiguousarray(c, np.uint8) for c in crops]), classes=np.array(classes))
+        (d / f"job{count}.out.npz").unlink(missing_ok=True)
+        count += 1
+    r = subprocess.run([sys.executable, "-c", _CHILD_REC, str(ROOT), str(d), str(count)], env={**os.environ, **{k: str(v) for k, v in env.items()}},
+                       timeout=timeout, capture_output=True, text=True)
+    for i in range(count):
+        (d / f"job{i}.in.npz").unlink()
+    assert r.returncode == 0 and all((d / f"job{i}.out.npz").exists() for i in range(count)), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    res = []
+    for i in range(count):
+        with np.load(d / f"job{i}.out.npz") as z:
+            res.append(RecResult(z["indices"], z["probs"], {str(n) for n in z["names"]}, bool(z["same"])))
+    return res
 
 
 def infer_many_in_child(jobs, env: dict, workdir, timeout: float = 300.0):

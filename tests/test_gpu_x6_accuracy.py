@@ -13,6 +13,7 @@ import pytest
 from oar_ocr_amd import api
 from oar_ocr_amd.synth import x6_cases as C
 from oar_ocr_amd.synth.child_run import infer_in_child
+from oar_ocr_amd.synth.ctc_tail_cases import ctc_model as _ctc_model
 from oar_ocr_amd.synth.onnx_writer import GraphBuilder
 
 pytestmark = pytest.mark.gpu
@@ -228,20 +229,6 @@ def test_attention_x6_kernel(case, family):
     err = float(np.abs(got.astype(np.float64) - b["f64"]).max())
     _fused_report(name, "attention_x6", family, b, err)
     assert err <= b["tol"], (name, family, err, b["tol"])
-
-
-def _ctc_model(K, V, sel, fb, w, b, head=True):
-    """[n, 3, 48, W] -> Conv 48 x 8 / stride 48 x 8 (one selected pixel per feature) -> [n, T, K] (head=False: the output) -> Linear K -> V -> Softmax"""
-    g = GraphBuilder("ctc")
-    g.add_input("x", ["N", 3, 48, "W"])
-    f = g.op("Conv", ["x", g.init(sel), g.init(fb)], kernel_shape=[48, 8], strides=[48, 8], pads=[0, 0, 0, 0], group=1, dilations=[1, 1])
-    f = g.op("Transpose", [g.op("Squeeze", [f, g.init(np.array([2], np.int64), "axes")])], perm=[0, 2, 1])
-    if not head:
-        g.add_output(f, ["N", "T", K])
-        return g.model()
-    z = g.op("Add", [g.op("MatMul", [f, g.init(w)]), g.init(b)])
-    g.add_output(g.op("Softmax", [z], axis=2), ["N", "T", V])
-    return g.model()
 
 
 @pytest.mark.parametrize("family", ["normal", "positive"])
