@@ -613,7 +613,8 @@ oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_
  * The decoder-only language model of the oar-ocr-vl crate (PaddleOCR-VL's ERNIE-4.5 text decoder, oar-ocr-vl/src/models/paddleocr_vl/ernie.rs; the
  * Qwen2-VL family differs in configuration only): RMSNorm, M-RoPE (runtime/attention.rs select_rope_sections), grouped-query attention over a
  * key / value cache, SwiGLU MLP, greedy argmax (lowest index among equal maxima).  Prefill and decode run the same chain of 5 layers + 2 HIP launches
- * per step of <= 16 rows (lm_decode.hip).  Not built: the tokenizer, sampling (the vision stage: below).                                    */
+ * per step of <= 16 rows (lm_decode.hip).  Not built: the tokenizer, sampling with a random generator (repetition penalty and no-repeat-ngram:
+ * oar_lm_generate_ex below; the vision stage: below).                                                                                                     */
 typedef struct oar_lm oar_lm;
 typedef enum { OAR_LM_F32 = 1, OAR_LM_BF16 = 16 } oar_lm_dtype;
 typedef struct {
@@ -735,6 +736,39 @@ oar_status oar_k_lm_decode_attention(const float* q, const float* kcache, const 
 oar_status oar_lm_generate_queue(oar_lm* lm, const oar_lm_request* req, int32_t slots);
 oar_status oar_lm_queue_check(const oar_lm_cfg* cfg, const oar_lm_request* req, int32_t slots);
 oar_status oar_lm_queue_stats(const oar_lm* lm, int64_t* stats, int32_t n_stats);
+
+/* ------------------------------------------------------------------------------------------------ VL: logits processors in greedy decode
+ * oar_lm_generate_ex is oar_lm_generate with two processors in front of the arg-max, as HuggingFace's RepetitionPenaltyLogitsProcessor and
+ * NoRepeatNGramLogitsProcessor define them (the reference's MinerU2.5 bans repeated n-grams under top_k = 1, its HunyuanOCR applies repetition_penalty under
+ * do_sample = False): the penalty first, then the ban, then the arg-max.  Both run on the device (lm_logits.hip), between the lm-head and lm_combine; the host
+ * uploads the prompt part of the history with the call's other tables and adds nothing between steps.
+ * The history of a sequence is the ids the caller gives for its prompt (history_ids[i][0 .. history_lengths[i]), each length 0 .. 65536 and not tied to the prompt
+ * length; both NULL: the request's input_ids), then every token fed back so far: the forced token where forced_tokens gives one, else the chosen token.
+ * repetition_penalty r (finite, >= 1; 1: off): for every distinct id t of the history with 0 <= t < vocab, x = logits[t] becomes x < 0 ? x * r : x / r in f32
+ * with the correctly rounded division; presence counts, not occurrences.
+ * no_repeat_ngram_size n (>= 0; <= 1: off): with H = the history's length >= n, token history[i + n - 1] is banned for every i in 0 .. H - n with
+ * history[i .. i + n - 2] == history[H - n + 1 .. H - 1]; a banned token's value is -inf.  Ids >= vocab take part in the comparison and are ignored as bans.
+ * The choice is the lowest index among equal maxima (a NaN never wins; no candidate: token 0).  The eos, done and alive rules, what tokens holds after a
+ * sequence's eos and the row fed back are oar_lm_generate's, and the returned logits are the raw logits: the bytes a call without processors gives for the same
+ * fed tokens.  A step then has 5 layers + 3 launches (6 layers + 3 with OAR_LM_ATTN_SPLIT).  lp NULL, or both processors off, IS oar_lm_generate: the same
+ * bytes and launches.  The workspace (step logits [16][vocab], histories, presence bitmaps) is allocated at the first call with a processor on and freed with
+ * the model.  Everything is checked before the device is touched.  OAR_INVALID_INPUT: what oar_lm_generate refuses, r < 1 or not finite, n < 0, and with a
+ * processor on: a negative history id, a history length outside 0 .. 65536, inputs_embeds without history_ids, history_ids without history_lengths or with a
+ * null entry of non-zero length; OAR_UNSUPPORTED_OP: n > 1 with a vocabulary above 2^19 (the bans of a row are a bitmap in LDS).
+ * oar_lm_logits_check: those checks against a configuration alone (no model, no device).
+ * oar_k_lm_select: the select kernel alone on caller-chosen rows: logits [n_rows][vocab] (n_rows 1 .. 16), row i with the history hist_ids[i][0 .. hist_lengths[i])
+ * (its last id reaches the kernel as the token fed back by the step before); token i is written to tokens_io[off + i], the rest of tokens_io stays untouched.
+ * OAR_INVALID_INPUT: a null buffer, n_rows outside 1..16, vocab outside 2 .. 2^24 - 1, a bad history, r or n as above, or tokens that do not fit n_tokens. */
+typedef struct {
+    float repetition_penalty;                /* >= 1, finite; 1: off                                                              */
+    int32_t no_repeat_ngram_size;            /* >= 0; 0 and 1: off                                                                */
+    const int32_t* history_lengths;          /* NULL: the request's input_ids are the history                                    */
+    const int32_t* const* history_ids;       /* [n_seq] -> [history_lengths[i]]                                                   */
+} oar_lm_logits_cfg;
+oar_status oar_lm_generate_ex(oar_lm* lm, const oar_lm_request* req, const oar_lm_logits_cfg* lp);
+oar_status oar_lm_logits_check(const oar_lm_cfg* cfg, const oar_lm_request* req, const oar_lm_logits_cfg* lp);
+oar_status oar_k_lm_select(const float* logits, int32_t n_rows, int32_t vocab, const int32_t* hist_lengths, const int32_t* const* hist_ids,
+                           float repetition_penalty, int32_t no_repeat_ngram_size, int32_t* tokens_io, size_t n_tokens, size_t off);
 
 /* ------------------------------------------------------------------------------------------------ VL: the vision stage
  * The vision encoder and projector of the oar-ocr-vl crate's PaddleOCR-VL (vision.rs, projector.rs): a SigLIP-style pre-LN ViT over the patches of an

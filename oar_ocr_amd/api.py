@@ -156,6 +156,7 @@ EXPORTS = [
     "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm", "oar_k_vis_attention", "oar_k_vis_pos_embed",
     "oar_lm_create", "oar_lm_destroy", "oar_lm_generate", "oar_lm_cost", "oar_lm_set_prefill", "oar_lm_prefill_cost", "oar_k_lm_gemm", "oar_k_lm_prefill_attention",
     "oar_lm_set_decode", "oar_lm_decode_stats", "oar_k_lm_decode_attention",
+    "oar_lm_generate_ex", "oar_lm_logits_check", "oar_k_lm_select",
     "oar_vis_create", "oar_vis_destroy", "oar_vis_encode", "oar_vis_cost",
 ]
 
@@ -243,6 +244,8 @@ def lib():
     L.oar_k_lm_gemm.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_lm_prefill_attention.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_lm_decode_attention.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
+    if hasattr(L, "oar_k_lm_select"):   # (absent from a build of an earlier commit loaded through LIB_PATH: tools/lm_decode_bench.py --parent-lib)
+        L.oar_k_lm_select.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t]
     L.oar_k_add_layernorm.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.c_size_t, C.c_size_t]
     L.oar_image_decode.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.oar_image_free.argtypes = [C.POINTER(C.c_uint8)]
@@ -1766,6 +1769,20 @@ def k_lm_decode_attention(q, kcache, vcache, row_seq, row_pos, heads, o_io, o_of
     out = np.array(o_io, np.float32, copy=True, order="C").reshape(-1)
     _check(lib().oar_k_lm_decode_attention(None if q is None else _p(q), _p(kc), _p(vc), n_seq, maxpos, rs.size, _p(rs) if rs.size else None, _p(rp) if rp.size else None,
                                            heads, kvh, dh, int(split_keys), _p(out), out.size, o_off))
+    return out
+
+
+def k_lm_select(logits, histories, repetition_penalty, no_repeat_ngram_size, tokens_io, off=0):
+    """lm_select_kernel alone (lm_logits.hip): logits [n_rows, vocab], histories: one sequence of ids per row.  Returns a copy of tokens_io (int32)
+    with row i's token -- repetition penalty, then the n-gram ban, then the lowest index among equal maxima -- at off + i and everything else untouched."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    if lg.ndim != 2 or len(histories) != lg.shape[0]:
+        raise ValueError(f"k_lm_select: logits {lg.shape} must be [n_rows, vocab] with one history per row, got {len(histories)}")
+    hs = [np.ascontiguousarray(h, np.int32).reshape(-1) for h in histories]
+    lens = np.asarray([h.size for h in hs], np.int32)
+    ptrs = (C.c_void_p * max(len(hs), 1))(*[h.ctypes.data if h.size else None for h in hs])
+    out = np.array(tokens_io, np.int32, copy=True, order="C").reshape(-1)
+    _check(lib().oar_k_lm_select(_p(lg), lg.shape[0], lg.shape[1], _p(lens), ptrs, float(repetition_penalty), int(no_repeat_ngram_size), _p(out), out.size, int(off)))
     return out
 
 

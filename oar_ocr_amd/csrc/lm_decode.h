@@ -48,6 +48,14 @@ struct LmDecodeP {
     int max_new, eos;
     float* split_ws;             // split-key attention: partials [16][H][ceil(maxpos / split_keys)][dh + 2], or null
     int split_keys;              // keys of one span (a multiple of 64 in 64..4096); read in split mode only
+    // logits processors (lm_logits.hip): select != 0 runs the lm-head that also fills step_logits, then lm_select, and lm_combine on its one candidate
+    int select;
+    float* step_logits;          // [16][pad4(V)], row = the head row's slot in the step
+    void* part1;                 // float2 [16]
+    int32_t* hist; int hist_cap; // [16][hist_cap]: the prompt ids, then every token fed back
+    const int32_t* hlen;         // [16]: ids of the prompt part
+    uint32_t* seen;              // [16][ceil(V / 32)]: bit t = id t is in the history
+    float penalty; int ngram;
 };
 
 // Split-key decode attention (lm_decode_split.hip): a row's keys are cut into spans of split_keys keys, one workgroup per (row, kv head, chunk of

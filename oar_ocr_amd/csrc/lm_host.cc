@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "lm_decode.h"
+#include "lm_logits.h"
 #include "lm_prefill.h"
 #include "lm_queue.h"
 
@@ -148,6 +149,8 @@ struct oar_lm {
     int stop_at_eos = 0;
     DevMem split_ws;   // the split mode's partials, allocated at its first use
     size_t split_ws_cap = 0;
+    DevMem logits_ws;   // the logits processors' step buffer, candidates, histories and presence bitmaps, allocated at their first use
+    size_t logits_ws_cap = 0;
     int32_t* stop_ring = nullptr;   // pinned [kLmStopRing]: copies of state.alive
     hipEvent_t stop_ev[k::kLmStopRing] = {};
     int64_t steps_limit = 0, steps_enqueued = 0;   // of the last call
@@ -431,13 +434,91 @@ oar_status oar_lm_cost(const oar_lm* lm, int32_t n_rows, int32_t cache_len, doub
     });
 }
 
-oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
-    return guard([&] {
-        OAR_CHECK(lm && req, OAR_INVALID_INPUT, "oar_lm_generate: null argument");
+namespace {
+
+// The logits processors of a call: what oar_lm_logits_cfg asks for, checked; hist[i] / hlen[i] the prompt part of sequence i's history.
+struct LogitsPlan {
+    bool on = false;
+    float r = 1.0f;
+    int n = 0;
+    std::vector<const int32_t*> hist;
+    std::vector<int32_t> hlen;
+};
+
+void check_processors(float r, int n, int V, const std::string& fn) {
+    OAR_CHECK(std::isfinite(r) && r >= 1.0f, OAR_INVALID_INPUT, fn + ": repetition_penalty must be finite and >= 1");
+    OAR_CHECK(n >= 0, OAR_INVALID_INPUT, fn + ": no_repeat_ngram_size must be >= 0");
+    OAR_CHECK(n <= 1 || V <= k::kLmSelectMaxVocab, OAR_UNSUPPORTED_OP, fn + ": no_repeat_ngram_size with a vocabulary above 2^19");
+}
+
+void check_history(const int32_t* ids, int64_t len, const std::string& fn) {
+    OAR_CHECK(len >= 0 && len <= k::kLmHistoryMax, OAR_INVALID_INPUT, fn + ": history length outside 0..65536");
+    OAR_CHECK(ids != nullptr || len == 0, OAR_INVALID_INPUT, fn + ": null history_ids entry");
+    for (int64_t t = 0; t < len; ++t) OAR_CHECK(ids[t] >= 0, OAR_INVALID_INPUT, fn + ": negative history id");
+}
+
+LogitsPlan logits_plan(const oar_lm_cfg& c, const oar_lm_request& r, const oar_lm_logits_cfg* lp, const std::string& fn) {
+    LogitsPlan g;
+    if (!lp) return g;
+    check_processors(lp->repetition_penalty, lp->no_repeat_ngram_size, c.vocab, fn);
+    g.r = lp->repetition_penalty; g.n = lp->no_repeat_ngram_size;
+    g.on = g.r != 1.0f || g.n > 1;
+    if (!g.on) return g;
+    OAR_CHECK((lp->history_ids == nullptr) == (lp->history_lengths == nullptr), OAR_INVALID_INPUT, fn + ": history_ids and history_lengths go together");
+    OAR_CHECK(lp->history_ids || !r.inputs_embeds, OAR_INVALID_INPUT, fn + ": inputs_embeds with a logits processor need history_ids");
+    for (int s = 0; s < r.n_seq; ++s) {
+        const int32_t* ids = lp->history_ids ? lp->history_ids[s] : r.input_ids[s];
+        const int64_t len = lp->history_ids ? lp->history_lengths[s] : r.lengths[s];
+        check_history(ids, len, fn);
+        g.hist.push_back(ids); g.hlen.push_back((int32_t)len);
+    }
+    return g;
+}
+
+// Host tables of histories: hist [rows][cap] and seen [rows][words] from the first hlen[i] ids of ids[i].
+void history_tables(const std::vector<const int32_t*>& ids, const std::vector<int32_t>& hlen, int V, int cap, std::vector<int32_t>& hist, std::vector<uint32_t>& seen) {
+    const size_t rows = ids.size(), words = (size_t)k::lm_select_words(V);
+    hist.assign(rows * (size_t)cap, 0);
+    seen.assign(rows * words, 0u);
+    for (size_t q = 0; q < rows; ++q)
+        for (int32_t t = 0; t < hlen[q]; ++t) {
+            const int32_t id = ids[q][t];
+            hist[q * (size_t)cap + (size_t)t] = id;
+            if (id < V) seen[q * words + (size_t)(id >> 5)] |= 1u << (id & 31);
+        }
+}
+
+// The processors' workspace (grown when a call needs more) and the call's prompt histories into it, enqueued on s from the two host vectors (the caller
+// synchronises before they go): P gets the select branch's pointers.
+void logits_tables(oar_lm* lm, const LogitsPlan& g, int S, int MN, k::LmDecodeP& P, std::vector<int32_t>& hist, std::vector<uint32_t>& seen, hipStream_t s) {
+    const int V = lm->cfg.vocab, words = k::lm_select_words(V);
+    const int cap = *std::max_element(g.hlen.begin(), g.hlen.end()) + MN;
+    Carver cv;
+    const size_t step_o = cv.take((size_t)k::kLmRows * k::lm_select_ld(V) * 4), part_o = cv.take((size_t)k::kLmRows * 8), hlen_o = cv.take((size_t)k::kLmRows * 4);
+    const size_t seen_o = cv.take((size_t)k::kLmRows * words * 4), hist_o = cv.take((size_t)k::kLmRows * cap * 4);
+    if (cv.off > lm->logits_ws_cap) {
+        if (lm->logits_ws.p) { OAR_HIP(hipFree(lm->logits_ws.p)); lm->logits_ws.p = nullptr; lm->logits_ws_cap = 0; }
+        lm->logits_ws.alloc(cv.off);
+        lm->logits_ws_cap = cv.off;
+    }
+    uint8_t* w = static_cast<uint8_t*>(lm->logits_ws.p);
+    history_tables(g.hist, g.hlen, V, cap, hist, seen);
+    OAR_HIP(hipMemcpyAsync(w + hlen_o, g.hlen.data(), (size_t)S * 4, hipMemcpyHostToDevice, s));
+    OAR_HIP(hipMemcpyAsync(w + seen_o, seen.data(), seen.size() * 4, hipMemcpyHostToDevice, s));
+    OAR_HIP(hipMemcpyAsync(w + hist_o, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, s));
+    P.select = 1; P.step_logits = reinterpret_cast<float*>(w + step_o); P.part1 = w + part_o; P.hlen = reinterpret_cast<const int32_t*>(w + hlen_o);
+    P.seen = reinterpret_cast<uint32_t*>(w + seen_o); P.hist = reinterpret_cast<int32_t*>(w + hist_o); P.hist_cap = cap; P.penalty = g.r; P.ngram = g.n;
+}
+
+// oar_lm_generate (lp null) and oar_lm_generate_ex: one schedule; a processor that is on adds its tables and lm_step's select branch, nothing else
+void generate_impl(oar_lm* lm, const oar_lm_request* req, const oar_lm_logits_cfg* lp, const std::string& fn) {
+    {
+        OAR_CHECK(lm && req, OAR_INVALID_INPUT, fn + ": null argument");
         const oar_lm_cfg& c = lm->cfg;
         const int S = req->n_seq, MN = req->max_new_tokens, D = c.hidden, V = c.vocab;
-        OAR_CHECK(S >= 1 && S <= c.max_sequences, OAR_INVALID_INPUT, "oar_lm_generate: n_seq outside 1..max_sequences");
-        const int64_t total = check_request(c, *req, "oar_lm_generate");
+        OAR_CHECK(S >= 1 && S <= c.max_sequences, OAR_INVALID_INPUT, fn + ": n_seq outside 1..max_sequences");
+        const int64_t total = check_request(c, *req, fn);
+        const LogitsPlan lg = logits_plan(c, *req, lp, fn);
         std::lock_guard<std::mutex> lk(lm->mu);
         const bool gemm = lm->prefill_mode == OAR_LM_PREFILL_GEMM;
         const int attention = lm->attention;
@@ -458,7 +539,7 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                 for (int t = 0; t < T; ++t) {
                     k::LmRow& R = cur.rows[cur.nrows];
                     R.seq = s; R.pos = t; R.xrow = xrow++; R.gen = t == T - 1 ? 0 : -1; R.pad = 0;
-                    prompt_positions(pid, T, t, R.rp, mx, "oar_lm_generate");
+                    prompt_positions(pid, T, t, R.rp, mx, fn);
                     if (gemm && R.gen < 0) {   // (the slot is filled again by the next row)
                         pf_rows.push_back(k::LmPfRow{R.seq, R.pos, {R.rp[0], R.rp[1], R.rp[2]}, R.xrow, {0, 0}});
                         continue;
@@ -467,7 +548,7 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                     mp = std::max(mp, t);
                     if (++cur.nrows == k::kLmRows) { steps.push_back(cur); step_maxpos.push_back(mp); cur = k::LmStep{}; mp = 0; }
                 }
-                OAR_CHECK(mx + MN < (1 << 24), OAR_INVALID_INPUT, "oar_lm_generate: position id outside 0..2^24");
+                OAR_CHECK(mx + MN < (1 << 24), OAR_INVALID_INPUT, fn + ": position id outside 0..2^24");
                 next_pos[(size_t)s] = (int32_t)(mx + 1);
             }
             if (cur.nrows) { steps.push_back(cur); step_maxpos.push_back(mp); }
@@ -500,7 +581,7 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                 pf_cap = std::max(pf_cap, pf_chunk[ci]);
             }
             pf_tile0.push_back(pf_tiles.size());
-            OAR_CHECK(pf_tiles.size() < ((size_t)1 << 31), OAR_INVALID_INPUT, "oar_lm_generate: prompts too long");
+            OAR_CHECK(pf_tiles.size() < ((size_t)1 << 31), OAR_INVALID_INPUT, fn + ": prompts too long");
         }
         const size_t Hd_ = (size_t)c.heads * c.head_dim;
 
@@ -515,6 +596,9 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
         const size_t pfq_o = cv.take((size_t)pf_cap * Hd_ * 4), pfo_o = cv.take((size_t)pf_cap * Hd_ * 4), pfh_o = cv.take((size_t)pf_cap * c.intermediate * 4);
         uint8_t* w = work_bytes(lm, cv.off);
         k::LmDecodeP P = call_params(lm, attention);
+        std::vector<int32_t> lg_hist;
+        std::vector<uint32_t> lg_seen;
+        if (lg.on) logits_tables(lm, lg, S, MN, P, lg_hist, lg_seen, s);
         if (stop && !lm->stop_ring) {
             OAR_HIP(hipHostMalloc(reinterpret_cast<void**>(&lm->stop_ring), sizeof(int32_t) * k::kLmStopRing, hipHostMallocDefault));
             for (hipEvent_t& e : lm->stop_ev) OAR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -588,7 +672,17 @@ oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
                     if (req->tokens[(size_t)q * MN + g] == req->eos_token_id) { n = g + 1; break; }
             req->counts[q] = n;
         }
-    });
+    }
+}
+
+}  // namespace
+
+oar_status oar_lm_generate(oar_lm* lm, const oar_lm_request* req) {
+    return guard([&] { generate_impl(lm, req, nullptr, "oar_lm_generate"); });
+}
+
+oar_status oar_lm_generate_ex(oar_lm* lm, const oar_lm_request* req, const oar_lm_logits_cfg* lp) {
+    return guard([&] { generate_impl(lm, req, lp, "oar_lm_generate_ex"); });
 }
 
 namespace {
@@ -951,5 +1045,73 @@ oar_status oar_k_lm_decode_attention(const float* q, const float* kcache, const 
         k::lm_attention(nullptr, a, split_keys ? k::LM_ATTN_SPLIT : k::LM_ATTN_SERIAL, n_rows, false, mp);
         OAR_HIP(hipGetLastError());
         OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// What oar_lm_generate_ex asks of its arguments; needs no model and no device.
+oar_status oar_lm_logits_check(const oar_lm_cfg* cfg, const oar_lm_request* req, const oar_lm_logits_cfg* lp) {
+    return guard([&] {
+        static const std::string fn = "oar_lm_generate_ex";
+        OAR_CHECK(cfg && req, OAR_INVALID_INPUT, fn + ": null argument");
+        OAR_CHECK(cfg->max_sequences >= 1 && cfg->max_sequences <= k::kLmRows && cfg->vocab >= 2 && cfg->max_positions >= 2, OAR_INVALID_INPUT,
+                  fn + ": max_sequences outside 1..16, vocab or max_positions below 2");
+        OAR_CHECK(req->n_seq >= 1 && req->n_seq <= cfg->max_sequences, OAR_INVALID_INPUT, fn + ": n_seq outside 1..max_sequences");
+        check_request(*cfg, *req, fn);
+        (void)logits_plan(*cfg, *req, lp, fn);
+    });
+}
+
+// lm_select_kernel alone.  Row i is sequence i of a one-step call: with a history of H >= 1 ids the row is generated token 1 of a sequence whose prompt part is the
+// first H - 1 ids and whose token 0 -- the token "fed back by the step before" -- is the last id, so the kernel's append runs too; H = 0 is token 0 of an empty prompt.
+oar_status oar_k_lm_select(const float* logits, int32_t n_rows, int32_t vocab, const int32_t* hist_lengths, const int32_t* const* hist_ids, float repetition_penalty,
+                           int32_t no_repeat_ngram_size, int32_t* tokens_io, size_t n_tokens, size_t off) {
+    return guard([&] {
+        static const std::string fn = "oar_k_lm_select";
+        OAR_CHECK(logits && hist_lengths && hist_ids && tokens_io, OAR_INVALID_INPUT, fn + ": null buffer");
+        OAR_CHECK(n_rows >= 1 && n_rows <= k::kLmRows, OAR_INVALID_INPUT, fn + ": n_rows outside 1..16");
+        OAR_CHECK(vocab >= 2 && vocab < (1 << 24), OAR_INVALID_INPUT, fn + ": vocab outside 2..2^24 - 1");
+        check_processors(repetition_penalty, no_repeat_ngram_size, vocab, fn);
+        OAR_CHECK(off <= n_tokens && (size_t)n_rows <= n_tokens - off, OAR_INVALID_INPUT, fn + ": the tokens do not fit n_tokens");
+        std::vector<const int32_t*> ids;
+        std::vector<int32_t> hlen;
+        k::LmStep st{};
+        std::vector<int32_t> toks((size_t)k::kLmRows * 2, 0);
+        int cap = 1;
+        for (int32_t i = 0; i < n_rows; ++i) {
+            const int64_t H = hist_lengths[i];
+            check_history(hist_ids[i], H, fn);
+            ids.push_back(hist_ids[i]); hlen.push_back(H > 0 ? (int32_t)H - 1 : 0);
+            st.rows[i].seq = i; st.rows[i].gen = H > 0 ? 1 : 0;
+            if (H > 0) toks[(size_t)i * 2] = hist_ids[i][H - 1];
+            st.head[i] = i;
+            cap = std::max(cap, (int)H);
+        }
+        st.nrows = st.nhead = n_rows;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        const int ld = k::lm_select_ld(vocab), words = k::lm_select_words(vocab);
+        std::vector<int32_t> hist;
+        std::vector<uint32_t> seen;
+        history_tables(ids, hlen, vocab, cap, hist, seen);
+        DevBuf dl, dst, dh, dn, dsn, dt, dp, dout;
+        dl.reserve((size_t)n_rows * ld * 4); dst.reserve(sizeof st); dh.reserve(hist.size() * 4); dn.reserve((size_t)k::kLmRows * 4); dsn.reserve(seen.size() * 4);
+        dt.reserve(toks.size() * 4); dp.reserve((size_t)k::kLmRows * 8); dout.reserve((size_t)k::kLmRows * 4);
+        OAR_HIP(hipMemcpy2D(dl.p, (size_t)ld * 4, logits, (size_t)vocab * 4, (size_t)vocab * 4, (size_t)n_rows, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dst.p, &st, sizeof st, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dh.p, hist.data(), hist.size() * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dn.p, hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dsn.p, seen.data(), seen.size() * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemcpy(dt.p, toks.data(), toks.size() * 4, hipMemcpyHostToDevice));
+        OAR_HIP(hipMemset(dout.p, 0xFF, (size_t)k::kLmRows * 4));
+        OAR_HIP(hipDeviceSynchronize());
+        k::LmSelectP p{};
+        p.st = dst.as<k::LmStep>(); p.logits = dl.as<float>(); p.ld = ld; p.V = vocab; p.words = words; p.hist = dh.as<int32_t>(); p.cap = cap; p.hlen = dn.as<int32_t>();
+        p.seen = dsn.as<uint32_t>(); p.tokens = dt.as<int32_t>(); p.max_new = 2; p.penalty = repetition_penalty; p.ngram = no_repeat_ngram_size; p.part = dp.p;
+        p.tok_out = dout.as<int32_t>();
+        k::lm_select(nullptr, p, n_rows, false);
+        OAR_HIP(hipGetLastError());
+        std::vector<int32_t> out((size_t)k::kLmRows);
+        OAR_HIP(hipMemcpy(out.data(), dout.p, out.size() * 4, hipMemcpyDeviceToHost));
+        for (int32_t i = 0; i < n_rows; ++i) tokens_io[off + (size_t)i] = out[(size_t)i];
     });
 }

@@ -39,6 +39,10 @@ class LmRequest(C.Structure):
                 ("logits", C.c_void_p), ("tokens", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class LmLogitsCfg(C.Structure):
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("history_lengths", C.c_void_p), ("history_ids", C.POINTER(C.c_void_p))]
+
+
 _bound = False
 PREFILL_MODES = {"rows": 0, "gemm": 1}          # OAR_LM_PREFILL_ROWS / OAR_LM_PREFILL_GEMM
 ATTENTION_MODES = {"serial": 0, "split": 1}     # OAR_LM_ATTN_SERIAL / OAR_LM_ATTN_SPLIT
@@ -70,10 +74,43 @@ def _lib():
         L.oar_lm_generate_queue.argtypes = [C.c_void_p, C.POINTER(LmRequest), C.c_int32]
         L.oar_lm_queue_check.restype = C.c_int
         L.oar_lm_queue_check.argtypes = [C.POINTER(LmCfg), C.POINTER(LmRequest), C.c_int32]
+        if hasattr(L, "oar_lm_generate_ex"):   # (absent from a build of an earlier commit loaded through api.LIB_PATH)
+            L.oar_lm_generate_ex.restype = C.c_int
+            L.oar_lm_generate_ex.argtypes = [C.c_void_p, C.POINTER(LmRequest), C.POINTER(LmLogitsCfg)]
+            L.oar_lm_logits_check.restype = C.c_int
+            L.oar_lm_logits_check.argtypes = [C.POINTER(LmCfg), C.POINTER(LmRequest), C.POINTER(LmLogitsCfg)]
         L.oar_lm_queue_stats.restype = C.c_int
         L.oar_lm_queue_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
         _bound = True
     return L
+
+
+GENERATION_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "eos_token_id")
+
+
+def read_generation_defaults(path) -> dict:
+    """What a `generation_config.json` in a checkpoint directory says about repetition_penalty, no_repeat_ngram_size and eos_token_id ({} without the file).
+    Nothing applies these by itself: pass them to generate."""
+    f = Path(path) / "generation_config.json"
+    if not f.exists():
+        return {}
+    d = json.loads(f.read_text())
+    return {k: d[k] for k in GENERATION_KEYS if d.get(k) is not None}
+
+
+def _logits_cfg(n: int, repetition_penalty, no_repeat_ngram_size, history, keep) -> LmLogitsCfg:
+    """The processors of a call over n sequences; history: None (the input ids), or one id sequence per sequence.  Arrays the struct points to go to `keep`."""
+    lp = LmLogitsCfg()
+    lp.repetition_penalty, lp.no_repeat_ngram_size = float(repetition_penalty), int(no_repeat_ngram_size)
+    if history is not None:
+        if len(history) != n:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"generate: {len(history)} histories for {n} sequences")
+        hs = [np.ascontiguousarray(h, np.int32).reshape(-1) for h in history]
+        lens = np.asarray([h.size for h in hs], np.int32)
+        ptrs = (C.c_void_p * n)(*[h.ctypes.data if h.size else None for h in hs])
+        keep += hs + [lens, ptrs]
+        lp.history_lengths, lp.history_ids = lens.ctypes.data, C.cast(ptrs, C.POINTER(C.c_void_p))
+    return lp
 
 
 def _check_mode_names(prefill, decode_attention):
@@ -199,6 +236,7 @@ class LMOutput:
 class CausalLM:
     def __init__(self, cfg: CausalLMConfig, handle):
         self.cfg, self._h = cfg, handle
+        self.generation_defaults: dict = {}   # from_dir: what the checkpoint's generation_config.json says (not applied by itself)
 
     @classmethod
     def from_state_dict(cls, cfg: CausalLMConfig, tensors: dict, prefix: str = "", device_id: int = 0) -> "CausalLM":
@@ -238,7 +276,9 @@ class CausalLM:
         tensors = {}
         for f in files:
             tensors.update(read_safetensors(f, names=want))
-        return cls.from_state_dict(cfg, tensors, prefix=prefix, device_id=device_id)
+        lm = cls.from_state_dict(cfg, tensors, prefix=prefix, device_id=device_id)
+        lm.generation_defaults = read_generation_defaults(path)
+        return lm
 
     def close(self):
         if self._h:
@@ -304,18 +344,24 @@ class CausalLM:
     def generate(self, input_ids=None, inputs_embeds=None, position_ids=None, max_new_tokens: int = 16, eos_token_id: Optional[int] = None,
                  return_logits: bool = False, forced_tokens=None, logits_out: Optional[np.ndarray] = None, prefill: str = "rows",
                  prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None, stop_at_eos: bool = False,
-                 schedule: str = "groups", slots: Optional[int] = None) -> LMOutput:
+                 schedule: str = "groups", slots: Optional[int] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, history_ids=None) -> LMOutput:
         """Greedy generation for one sequence or a list of sequences.  schedule "groups": more than 16 run in groups of 16, one after the other; "refill"
         (DESIGN 4.44): any number share `slots` cache slots (None: the model's max_sequences) and a finished sequence's slot goes to the next waiting one, with
         the same bytes per sequence, logits_out for any number of sequences, and stop_at_eos without meaning.  input_ids: [T] ints, or inputs_embeds: [T, hidden]
         floats; position_ids: [3, T] (default 0 .. T - 1 on all axes); forced_tokens: [max_new_tokens] per sequence, entries >= 0 are fed instead of the
         argmax.  logits_out: a flat float32 buffer of at least n_seq x max_new_tokens x vocab that receives the logits in place of a fresh array.
         prefill: "rows" or "gemm" with prefill_chunk packed rows a chunk (set_prefill); decode_attention: "serial" or "split" with split_keys keys a span, and
-        stop_at_eos (set_decode); the model keeps the settings of its last call."""
+        stop_at_eos (set_decode); the model keeps the settings of its last call.
+        repetition_penalty r >= 1 and no_repeat_ngram_size n (schedule "groups" only): before the arg-max every id of the sequence's history --
+        history_ids (one id sequence per sequence; default: input_ids), then every token fed back -- has its logit x replaced by x < 0 ? x r : x / r, then the
+        continuation of every earlier occurrence of the last n - 1 ids is banned.  Returned logits stay the raw logits.  The defaults are today's path."""
         _check_mode_names(prefill, decode_attention)
         if schedule not in SCHEDULES:
             raise api.OCRError(api.OAR_INVALID_INPUT, f"schedule must be 'groups' or 'refill', got {schedule!r}")
         refill = schedule == "refill"
+        processors = not (repetition_penalty == 1.0 and no_repeat_ngram_size == 0 and history_ids is None)
+        if refill and (repetition_penalty != 1.0 or no_repeat_ngram_size > 1):
+            raise api.OCRError(api.OAR_UNSUPPORTED_OP, "generate: schedule 'refill' does not run the logits processors (a refilled slot's history is not re-seeded)")
         self.set_prefill(prefill, prefill_chunk)
         self.set_decode(decode_attention, split_keys, stop_at_eos)
         if (input_ids is None) == (inputs_embeds is None):
@@ -324,6 +370,7 @@ class CausalLM:
         single = not isinstance(src, (list, tuple)) or (input_ids is not None and len(src) > 0 and np.isscalar(src[0]))
         wrap = (lambda v: None if v is None else [v]) if single else (lambda v: v)
         seqs, pos, forced = wrap(src), wrap(position_ids), wrap(forced_tokens)
+        hist = wrap(history_ids) if single and history_ids is not None and (len(history_ids) == 0 or np.isscalar(history_ids[0])) else history_ids
         n = len(seqs)
         if n == 0:
             raise api.OCRError(api.OAR_INVALID_INPUT, "generate: no sequence")
@@ -336,7 +383,9 @@ class CausalLM:
                 kw = {"input_ids" if input_ids is not None else "inputs_embeds": seqs[sl]}
                 outs.append(self.generate(position_ids=None if pos is None else pos[sl], max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                           return_logits=return_logits, forced_tokens=None if forced is None else forced[sl], prefill=prefill,
-                                          prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys, stop_at_eos=stop_at_eos, **kw))
+                                          prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys, stop_at_eos=stop_at_eos,
+                                          repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                          history_ids=None if hist is None else list(hist[sl]), **kw))
             return LMOutput(np.concatenate([o.tokens for o in outs]), np.concatenate([o.counts for o in outs]),
                             np.concatenate([o.logits for o in outs]) if return_logits else None)
         V, D = self.cfg.vocab_size, self.cfg.hidden_size
@@ -394,6 +443,8 @@ class CausalLM:
         req.tokens, req.counts = tokens.ctypes.data, counts.ctypes.data
         if refill:
             api._check(_lib().oar_lm_generate_queue(self._h, C.byref(req), 0 if slots is None else int(slots)))
+        elif processors:
+            api._check(_lib().oar_lm_generate_ex(self._h, C.byref(req), C.byref(_logits_cfg(n, repetition_penalty, no_repeat_ngram_size, hist, keep))))
         else:
             api._check(_lib().oar_lm_generate(self._h, C.byref(req)))
         if logits is not None:
@@ -704,6 +755,7 @@ class PaddleOCRVL:
     def __init__(self, vision: VisionEncoder, lm: CausalLM, embed_table: np.ndarray, preproc: ImageProcessorConfig, image_token_id: int, vision_start_token_id: int):
         self.vision, self.lm, self.embed_table, self.preproc = vision, lm, embed_table, preproc
         self.image_token_id, self.vision_start_token_id = int(image_token_id), int(vision_start_token_id)
+        self.generation_defaults: dict = {}   # from_dir: the checkpoint's generation_config.json (not applied by itself)
 
     @classmethod
     def from_state_dict(cls, cfg_json: dict, preproc_json: dict, tensors: dict, device_id: int = 0, lm_overrides: Optional[dict] = None,
@@ -728,7 +780,10 @@ class PaddleOCRVL:
         tensors = {}
         for f in files:
             tensors.update(read_safetensors(f))
-        return cls.from_state_dict(json.loads((path / "config.json").read_text()), json.loads((path / "preprocessor_config.json").read_text()), tensors, device_id=device_id, **kw)
+        m = cls.from_state_dict(json.loads((path / "config.json").read_text()), json.loads((path / "preprocessor_config.json").read_text()), tensors, device_id=device_id, **kw)
+        m.generation_defaults = read_generation_defaults(path)
+        m.lm.generation_defaults = dict(m.generation_defaults)
+        return m
 
     def close(self):
         self.vision.close()
@@ -742,11 +797,16 @@ class PaddleOCRVL:
 
     def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None,
                         prefill: str = "rows", prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None,
-                        stop_at_eos: bool = False, schedule: str = "groups", slots: Optional[int] = None) -> LMOutput:
+                        stop_at_eos: bool = False, schedule: str = "groups", slots: Optional[int] = None, repetition_penalty: float = 1.0,
+                        no_repeat_ngram_size: int = 0) -> LMOutput:
         """One sequence per image: ids = prefix + [image_token_id] x (h w / merge^2) + suffix; its embeddings are the table rows with the image span replaced
         by the projector's rows, its positions come from rope_index.  The images are encoded in calls of at most 16 (and at most max_tokens patches).
-        prefill / prefill_chunk / decode_attention / split_keys / stop_at_eos / schedule / slots: as CausalLM.generate."""
+        prefill / prefill_chunk / decode_attention / split_keys / stop_at_eos / schedule / slots: as CausalLM.generate; so are repetition_penalty and
+        no_repeat_ngram_size, whose history is the expanded ids (prefix, one image id per image token, suffix)."""
         _check_mode_names(prefill, decode_attention)
+        processors = repetition_penalty != 1.0 or no_repeat_ngram_size != 0
+        if schedule == "refill" and (repetition_penalty != 1.0 or no_repeat_ngram_size > 1):
+            raise api.OCRError(api.OAR_UNSUPPORTED_OP, "generate_tokens: schedule 'refill' does not run the logits processors")
         m = self.vision.cfg.spatial_merge_size
         px, grids = preprocess_images(images, self.preproc)
         kp = px.shape[1]
@@ -764,14 +824,16 @@ class PaddleOCRVL:
                 embeds[n] = e[off:off + counts[n] // (m * m)]
                 off += counts[n] // (m * m)
             i = j
-        seqs, pos = [], []
+        seqs, pos, hist = [], [], []
         for n in range(len(images)):
             n_img = int(counts[n]) // (m * m)
             ids = list(prefix_ids) + [self.image_token_id] * n_img + list(suffix_ids)
             x = _widen_rows(self.embed_table, ids)
             x[len(prefix_ids):len(prefix_ids) + n_img] = embeds[n]
             seqs.append(x)
+            hist.append(np.asarray(ids, np.int32))
             pos.append(rope_index(ids, grids[n:n + 1], self.image_token_id, self.vision_start_token_id, m)[0])
         return self.lm.generate(inputs_embeds=seqs, position_ids=pos, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
                                 forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
-                                stop_at_eos=stop_at_eos, schedule=schedule, slots=slots)
+                                stop_at_eos=stop_at_eos, schedule=schedule, slots=slots, repetition_penalty=repetition_penalty,
+                                no_repeat_ngram_size=no_repeat_ngram_size, history_ids=hist if processors else None)

@@ -394,6 +394,15 @@ pub struct oar_lm_request {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
+pub struct oar_lm_logits_cfg {
+    pub repetition_penalty: f32,
+    pub no_repeat_ngram_size: i32,
+    pub history_lengths: *const i32,
+    pub history_ids: *const *const i32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
 pub struct oar_vis_cfg {
     pub hidden: i32,
     pub layers: i32,
@@ -541,6 +550,9 @@ unsafe extern "C" {
     pub fn oar_lm_generate_queue(lm: *mut oar_lm, req: *const oar_lm_request, slots: i32) -> oar_status;
     pub fn oar_lm_queue_check(cfg: *const oar_lm_cfg, req: *const oar_lm_request, slots: i32) -> oar_status;
     pub fn oar_lm_queue_stats(lm: *const oar_lm, stats: *mut i64, n_stats: i32) -> oar_status;
+    pub fn oar_lm_generate_ex(lm: *mut oar_lm, req: *const oar_lm_request, lp: *const oar_lm_logits_cfg) -> oar_status;
+    pub fn oar_lm_logits_check(cfg: *const oar_lm_cfg, req: *const oar_lm_request, lp: *const oar_lm_logits_cfg) -> oar_status;
+    pub fn oar_k_lm_select(logits: *const f32, n_rows: i32, vocab: i32, hist_lengths: *const i32, hist_ids: *const *const i32, repetition_penalty: f32, no_repeat_ngram_size: i32, tokens_io: *mut i32, n_tokens: usize, off: usize) -> oar_status;
     pub fn oar_vis_create(cfg: *const oar_vis_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_vis) -> oar_status;
     pub fn oar_vis_destroy(vis: *mut oar_vis);
     pub fn oar_vis_encode(vis: *mut oar_vis, req: *const oar_vis_request) -> oar_status;

@@ -23,6 +23,10 @@ independently from step to step; a first call prints the histogram of the length
 (generate in groups of 16 with stop_at_eos, summed over the groups) and "refill" (schedule="refill", slots 16); each prints wall clock, steps, rows, dead rows and
 tokens per second; then the same pair without eos (even lengths: refill should tie), and the kernel time of the refill arm's GEMM phases, during which the decoding
 slots wait.  `--lib PATH` loads another build of the library (build.py's OAR_LM_QUEUE_LAG), `--lag S/L` labels its lines.
+`--logits-processors R N` measures the decode step with repetition_penalty R and no_repeat_ngram_size N instead of the lines above: for every
+(weights, cache, sequences) the plain arm and the processors arm alternate on one model and prompt (the prompt's ids are the history); a line carries the step's
+kernel time, its classes and, for the processors arm, the `lm_select` class alone.  `--parent-lib PATH` adds, after every process, a fresh process that loads the
+library built from the parent commit and measures the plain arm with it (arm "parent").  Defaults of this mode: --seqs 1 16 --cache 256.
 
 Usage: python tools/lm_decode_bench.py [--processes 3] [--seqs 1 4 16] [--cache 256 2048] [--steps 8] [--prefill 64 256 1024 4096] [--prefill-mode both] [--no-decode] [--no-torch]"""
 import argparse
@@ -242,6 +246,60 @@ def queue_child(a):
                           "kernel_us_per_phase": sum(v[0] for v in p.values()) / max(q["gemm_phases"], 1)}), flush=True)
 
 
+def logits_child(a):
+    """--logits-processors: the plain step and the step with processors, alternating; with --lib (another build, which may lack the entry): the plain arm alone."""
+    if a.lib:
+        api.LIB_PATH = Path(a.lib).resolve()
+    r, n = float(a.logits_processors[0]), int(a.logits_processors[1])
+    cfg = vl.CausalLMConfig(max_positions=max(a.cache) + a.steps + 2, max_sequences=max(a.seqs), **CFG)
+    rng = np.random.default_rng(0)
+    w32 = weights(cfg, rng)
+    arms = [("parent", {})] if a.lib else [("plain", {}), ("processors", dict(repetition_penalty=r, no_repeat_ngram_size=n))]
+    for dtype in a.dtypes:
+        w = w32 if dtype == "f32" else {k: (bf16_bits(v) if v.ndim == 2 else v) for k, v in w32.items()}
+        with vl.CausalLM.from_state_dict(cfg, w) as lm:
+            del w
+            for _, kw in arms:
+                lm.generate(input_ids=[1, 2, 3], max_new_tokens=3, **kw)                # warm-up: code objects, LDS opt-in, the processors' workspace
+            for C in a.cache:
+                for ns in a.seqs:
+                    ids = [rng.integers(0, cfg.vocab_size, C).astype(np.int32) for _ in range(ns)]
+                    for rep_ in range(2):                                                 # the arms alternate, twice; the second round is reported
+                        for arm, kw in arms:
+                            classes = CLASSES + (("lm_select",) if kw else ())
+                            pk = profiled(lm, ids, 1 + a.steps, classes, **kw)
+                            per = {c: pk.get(c, 0.0) / a.steps for c in classes}
+                            if rep_:
+                                print(json.dumps({"kind": "decode_logits", "arm": arm, "weights": dtype, "seqs": ns, "cache": C, "kernel_us": sum(per.values()), "by_class_us": per,
+                                                  "select_us": per.get("lm_select"), "repetition_penalty": r, "no_repeat_ngram_size": n}), flush=True)
+
+
+def logits_main(a):
+    if a.child or a.processes <= 1 and not a.parent_lib:
+        logits_child(a)
+        return
+    rows = {}
+    argv = [x for x in sys.argv[1:]]
+    for _ in range(max(a.processes, 1)):                                             # fresh processes, one after the other; the parent's build right behind this one
+        for extra in [[]] + ([["--lib", a.parent_lib]] if a.parent_lib else []):
+            p = subprocess.Popen([sys.executable, __file__, "--child"] + argv + extra, stdout=subprocess.PIPE, text=True)
+            for line in p.stdout:
+                sys.stderr.write(line)
+                sys.stderr.flush()
+                if line.startswith("{"):
+                    d = json.loads(line)
+                    rows.setdefault((d["arm"], d["weights"], d["seqs"], d["cache"]), []).append(d)
+            if p.wait() != 0:
+                sys.exit(p.returncode)
+    stat = lambda v: {"median": round(float(np.median(v)), 1), "min": round(float(np.min(v)), 1), "max": round(float(np.max(v)), 1)}   # noqa: E731
+    for (arm, wt, ns, C), ds in rows.items():
+        out = {"kind": "decode_logits", "arm": arm, "weights": wt, "seqs": ns, "cache": C, "processes": len(ds), "kernel_us": stat([d["kernel_us"] for d in ds]),
+               "by_class_us": {c: round(float(np.median([d["by_class_us"][c] for d in ds])), 1) for c in ds[0]["by_class_us"]}}
+        if ds[0]["select_us"] is not None:
+            out["select_us"] = stat([d["select_us"] for d in ds])
+        print(json.dumps(out), flush=True)
+
+
 def torch_child(a):
     """In a process of its own: torch brings its own HIP runtime."""
     import torch
@@ -294,6 +352,8 @@ def main():
     ap.add_argument("--queue-eos-gain", type=float, default=3.3)
     ap.add_argument("--queue-reps", type=int, default=2)
     ap.add_argument("--lib", default="")
+    ap.add_argument("--logits-processors", nargs=2, metavar=("R", "N"), default=None)
+    ap.add_argument("--parent-lib", default="")
     ap.add_argument("--lag", default="")
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-torch", action="store_true")
@@ -305,6 +365,13 @@ def main():
         return
     if a.queue:
         queue_main(a)
+        return
+    if a.logits_processors:
+        if "--seqs" not in sys.argv:
+            a.seqs = [1, 16]
+        if "--cache" not in sys.argv:
+            a.cache = [256]
+        logits_main(a)
         return
     if a.child or a.processes <= 1:
         child(a)
