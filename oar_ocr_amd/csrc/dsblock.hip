@@ -92,7 +92,7 @@ void dsblock_wa(hipStream_t s, const DsBlockP& b, const WaShape& sh) {
     const double flops = 2.0 * px_out * b.C * (b.ks * b.ks + (double)b.Cout);
     char pname[96];
     const char* cls = "dsblock_wa";   // one profiler class per kernel FAMILY (row-streaming: HBM-bound; chunk-streamed: instruction-bound; bench.py roofline.by_family)
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k3 s1x1 wa%d", (long)px_out, b.C, b.Cout, sh.P); cls = pname; }
+    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k3 s1x1 wa%d nf%d", (long)px_out, b.C, b.Cout, sh.P, sh.nf); cls = pname; }   // detail names carry the instantiation: here the fragment count
     ProfScope ps(s, cls, bytes, flops, true);
     if (sh.nf <= 4) dsblock_wa_launch_a(s, p, sh.nf, (int)grid, sh.lds, ps.start(), ps.stop());
     else dsblock_wa_launch_b(s, p, sh.nf, (int)grid, sh.lds, ps.start(), ps.stop());
@@ -158,7 +158,7 @@ void dsblock_rs(hipStream_t s, const DsBlockP& b, const RsShape& sh) {
     const double flops = 2.0 * px_out * b.C * (b.ks * b.ks + (double)b.Cout);
     char pname[96];
     const char* cls = "dsblock_rs";   // one profiler class per kernel FAMILY (row-streaming: HBM-bound; chunk-streamed: instruction-bound; bench.py roofline.by_family)
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k3 s%dx%d rs R%d", (long)px_out, b.C, b.Cout, b.sh, b.sw, sh.R); cls = pname; }
+    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k3 s%dx%d rs R%d %d-%d %s acts%d w%d", (long)px_out, b.C, b.Cout, b.sh, b.sw, sh.R, sh.nch, sh.nf, sh.x6 ? "x6" : "f32", sh.acts, sh.wpw); cls = pname; }
     ProfScope ps(s, cls, bytes, flops, true);
     const char* de = getenv("OAR_DSB_DBG");
     if (de && atoi(de) > 0 && b.sh == 1 && b.sw == 1 && sh.nch == 3 && sh.nf == 3 && sh.acts == 1 && !sh.x6) dsblock_rs_launch_dbg(s, p, atoi(de), grid, sh.lds, ps.start(), ps.stop());
@@ -208,7 +208,7 @@ void dsblock_cs(hipStream_t s, const DsBlockP& b, const CsShape& sh) {
     const double flops = 2.0 * px_out * b.C * (b.ks * b.ks + (double)b.Cout);
     char pname[96];
     const char* cls = "dsblock_cs";   // one profiler class per kernel FAMILY (row-streaming: HBM-bound; chunk-streamed: instruction-bound; bench.py roofline.by_family)
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k%d s%dx%d cs", (long)px_out, b.C, b.Cout, b.ks, b.sh, b.sw); cls = pname; }
+    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k%d s%dx%d %s", (long)px_out, b.C, b.Cout, b.ks, b.sh, b.sw, dsblock_cs_uses_pc(b.ks, b.sh, b.sw, sh.nch, sh.nf) ? "pc" : "cs"); cls = pname; }
     ProfScope ps(s, cls, bytes, flops, true);
     dsblock_cs_launch(s, p, b.ks, b.sh, b.sw, sh.nch, sh.nf, sh.acts, sh.grid, sh.lds, ps.start(), ps.stop());
 }
@@ -281,7 +281,7 @@ void dsblock2(hipStream_t s, const DsBlockP& a, const DsBlockP& b) {
     const double flops = 2.0 * px * (a.C * (9.0 + a.Cout) + b.C * (9.0 + b.Cout));
     char pname[96];
     const char* cls = "dsblock_rs";   // the row-streaming family (one launch, two blocks: its algorithmic bytes are the first block's input + the second's output)
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock2 px=%ld C=%d-%d-%d rs2 R%d", (long)px, a.C, a.Cout, b.Cout, sh.R); cls = pname; }
+    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock2 px=%ld C=%d-%d-%d rs2 R%d %d-%d-%d w%d %s lag%d acts%d", (long)px, a.C, a.Cout, b.Cout, sh.R, sh.nch1, sh.nf1, sh.nf2, sh.wpw, dsblock_rs2_regw(sh.nch1, sh.nf1, sh.nf2) ? "regw" : "ldsw", dsblock_rs2_lag(sh.nch1, sh.nf1, sh.nf2), sh.acts); cls = pname; }
     ProfScope ps(s, cls, bytes, flops, true);
     dsblock_rs2_launch(s, p, sh.nch1, sh.nf1, sh.nf2, sh.acts, 256, sh.lds, ps.start(), ps.stop());
 }
@@ -340,7 +340,7 @@ void dsblock(hipStream_t s, const DsBlockP& b) {
     const double flops = 2.0 * px_out * b.C * (b.ks * b.ks + (double)b.Cout);
     char pname[96];
     const char* cls = "dsblock";   // one profiler class per kernel FAMILY (row-streaming: HBM-bound; chunk-streamed: instruction-bound; bench.py roofline.by_family)
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k%d s%dx%d t%dx%d", (long)px_out, b.C, b.Cout, b.ks, b.sh, b.sw, sh.TR, sh.TC); cls = pname; }
+    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "dsblock px=%ld C=%d N=%d k%d s%dx%d t%dx%d l%dx%d", (long)px_out, b.C, b.Cout, b.ks, b.sh, b.sw, sh.TR, sh.TC, sh.nfw, sh.pfw); cls = pname; }
     ProfScope ps(s, cls, bytes, flops, true);
     if (b.ks == 3 && b.sw == 1) dsblock_launch_k3s1(s, p, sh.nfw, sh.pfw, (int)grid, sh.lds, ps.start(), ps.stop());
     else if (b.ks == 3) dsblock_launch_k3s2(s, p, sh.nfw, sh.pfw, (int)grid, sh.lds, ps.start(), ps.stop());

@@ -20,6 +20,8 @@ void dsblock_cs_launch(hipStream_t s, const DsCsP& p, int ks, int sh, int sw, in
 
 // dsblock_pc.hip: the producer / consumer kernel for the same work items and weight blocks; false = no instantiation for the shape
 bool dsblock_pc_launch(hipStream_t s, const DsCsP& p, int ks, int sh, int sw, int nch, int nft, int acts, int grid, hipEvent_t e0, hipEvent_t e1);
+bool dsblock_pc_has(int ks, int sh, int sw, int nch, int nft);        // is there a producer / consumer instantiation for the shape
+bool dsblock_cs_uses_pc(int ks, int sh, int sw, int nch, int nft);    // will dsblock_cs_launch hand the shape to it (OAR_DSB_PC on and instantiated): the profiler's detail name
 
 }  // namespace k
 }  // namespace oar

@@ -17,6 +17,7 @@ void launch_pc(K kernel, hipStream_t s, const DsCsP& p, int grid, size_t lds, hi
 }
 }  // namespace
 
+#define OAR_PC_INSTANCES(X) X(5, 1, 1, 12, 12, 4)   // every instantiation, one X(ks, sh, sw, nch, nft, rows) each: the launch and dsblock_pc_has read the same list
 #define OAR_PC_CASE(KS, SH, SW, NCH, NFT, ROWS) \
     if (ks == KS && sh == SH && sw == SW && nch == NCH && nft == NFT) { \
         constexpr size_t lds = pc_lds_bytes(KS, SH, SW, NFT, ROWS); \
@@ -37,7 +38,12 @@ bool dsblock_pc_launch(hipStream_t s, const DsCsP& p, int ks, int sh, int sw, in
         }
     }
 #endif
-    OAR_PC_CASE(5, 1, 1, 12, 12, 4)
+    OAR_PC_INSTANCES(OAR_PC_CASE)
+    return false;
+}
+#define OAR_PC_HAS(KS, SH, SW, NCH, NFT, ROWS) if (ks == KS && sh == SH && sw == SW && nch == NCH && nft == NFT) return true;
+bool dsblock_pc_has(int ks, int sh, int sw, int nch, int nft) {
+    OAR_PC_INSTANCES(OAR_PC_HAS)
     return false;
 }
 }  // namespace k
