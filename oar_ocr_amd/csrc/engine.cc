@@ -81,16 +81,25 @@ const float* Engine::upload_const(const std::string& key, const std::vector<floa
     return (const float*)p;
 }
 
-// activations that may be folded into a conv / linear / add epilogue (apply_act).  The rest of is_unary_act only ever runs
-// as a stand-alone element-wise kernel (apply_unary): every extra case in apply_act costs registers in each conv epilogue --
+// The operator table (behind the planner, where the columns are explained): ONE row per operator name the engine knows.  Engine::supported_ops(), what
+// Planner::dispatch does with a plan-time input (device_data_inputs / reads_host_values) and which handler it calls are all read from it.
+struct Planner;
+enum class HostInputs { NONE, DATA0, DATA01, READS_HOST };
+struct OpRow {
+    const char* name;
+    bool pub;
+    HostInputs host_inputs;
+    void (Planner::*plan)(const GNode&);
+    int code;
+};
+static const OpRow* op_table(size_t& count);            // the rows, sorted by name
+static const OpRow* find_op(const std::string& name);   // null: no such row
+
+// activations that may be folded into a conv / linear / add epilogue (apply_act).  The other unary activations (the rows of the operator table that
+// op_unary_act plans) only ever run as a stand-alone element-wise kernel (apply_unary): every extra case in apply_act costs registers in each conv epilogue --
 // with all of them in, the depthwise kernel lost a wave per SIMD and a quarter of its bandwidth.
 static bool is_fusable_act(const std::string& op) {
     return op == "Relu" || op == "HardSwish" || op == "HardSigmoid" || op == "Sigmoid" || op == "LeakyRelu" || op == "Tanh" || op == "Gelu";
-}
-static bool is_unary_act(const std::string& op) {
-    return op == "Relu" || op == "HardSwish" || op == "HardSigmoid" || op == "Sigmoid" || op == "LeakyRelu" || op == "Tanh" || op == "Erf" ||
-           op == "Sqrt" || op == "Exp" || op == "Abs" || op == "Neg" || op == "Reciprocal" || op == "Log" || op == "Gelu" || op == "Softplus" ||
-           op == "Floor" || op == "Ceil" || op == "Round" || op == "Not";
 }
 static Act act_of(const GNode& n) {
     Act a;
@@ -3054,7 +3063,6 @@ struct Planner {
                 const bool still_ok = wi != E.inits_.end() && wi->second.dims.size() == 4 && wi->second.dims[2] == 1 && wi->second.dims[3] == 1 && n.residual.empty() &&
                                       !(n.in.size() > 3 && !n.in[3].empty()) && n.out.size() == 1 &&
                                       k::conv_msrc_ok((long)(pd[0] * pd[2] * pd[3]), (int)pd[1], (int)wi->second.dims[0]);
-                if (getenv("OAR_DEBUG_CONCAT")) fprintf(stderr, "  conv %s reads pending concat: still_ok=%d (w4=%d res=%d gate=%d nout=%zu)\n", n.out[0].c_str(), (int)still_ok, (int)(wi != E.inits_.end() && wi->second.dims.size() == 4), (int)!n.residual.empty(), (int)(n.in.size() > 3 && !n.in[3].empty()), n.out.size());
                 if (still_ok) { msrc = pit->second; TInfo keep = vals[n.in[0]]; pending_concat.erase(pit); vals[n.in[0]] = keep; }
             }
         }
@@ -4330,7 +4338,6 @@ struct Planner {
             for (auto& t : xs) plain = plain && t.dims.size() == 4 && (t.dims[1] & 3) == 0;
             // (round 6, later) ... or no launch at all when the only reader is a 1x1 convolution that can read the sources itself (pending_concat above)
             static const bool defer_on = [] { const char* e = getenv("OAR_CONCAT_DEFER"); return !(e && e[0] == '0'); }();
-            if (getenv("OAR_DEBUG_CONCAT")) fprintf(stderr, "concat %s: plain=%d absorb=%d r=%d inner=%ld n=%zu consumer=%d\n", n.out[0].c_str(), (int)plain, (int)absorb, r, (long)inner, xs.size(), concat_consumer.count(n.out[0]) ? concat_consumer[n.out[0]] : -1);
             if (plain && defer_on && xs.size() <= 8 && concat_consumer.count(n.out[0])) {
                 const GNode& cn = E.nodes_[concat_consumer[n.out[0]]];
                 auto wi = E.inits_.find(cn.in.size() > 1 ? cn.in[1] : std::string());
@@ -4339,10 +4346,6 @@ struct Planner {
                           attr_ok("strides", 1) && attr_ok("pads", 0) && attr_ok("dilations", 1) && cn.residual.empty() && !(cn.in.size() > 3 && !cn.in[3].empty()) &&
                           cn.as("auto_pad", "NOTSET") == "NOTSET";
                 for (auto& t : xs) ok = ok && t.layout == Layout::CLAST && (t.dims[1] & 7) == 0 && t.dims[0] == od[0] && t.dims[2] == od[2] && t.dims[3] == od[3] && !t.host_int;   // (channels-last already: a converted copy would be a temporary of THIS node)
-                if (getenv("OAR_DEBUG_CONCAT")) {
-                    fprintf(stderr, "  ok before msrc check = %d (K=%ld N=%ld) res=%d gate=%d autopad=%s\n", (int)ok, (long)od[1], wi != E.inits_.end() ? (long)wi->second.dims[0] : -1L, (int)!cn.residual.empty(), (int)(cn.in.size() > 3 && !cn.in[3].empty()), cn.as("auto_pad", "NOTSET").c_str());
-                    for (auto& t : xs) fprintf(stderr, "    src layout=%d C=%ld host=%d\n", (int)(t.layout == Layout::CLAST), (long)t.dims[1], (int)t.host_int);
-                }
                 ok = ok && k::conv_msrc_ok((long)(od[0] * od[2] * od[3]), (int)od[1], (int)wi->second.dims[0]) && (wi->second.dims[0] & 3) == 0;
                 if (ok) {
                     PendingConcat pc;
@@ -5444,15 +5447,12 @@ struct Planner {
     // data inputs of the operators that only exist on the device (their other inputs are plan-time parameters: shapes, axes, pads, K)
     static const std::vector<int>* device_data_inputs(const std::string& op) {
         static const std::vector<int> first{0}, both{0, 1};
-        static const std::set<std::string> one = {"Clip", "ReduceMean", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "ArgMax", "ArgMin", "Softmax", "Expand", "Tile", "Transpose",
-                                                  "Pad", "Resize", "GlobalAveragePool", "AveragePool", "MaxPool", "LayerNormalization", "Linear", "Gemm", "TopK", "Flatten", "Split"};
-        if (op == "MatMul" || op == "GridSample") return &both;
-        return one.count(op) || is_unary_act(op) ? &first : nullptr;
+        const OpRow* r = find_op(op);
+        return !r ? nullptr : r->host_inputs == HostInputs::DATA0 ? &first : r->host_inputs == HostInputs::DATA01 ? &both : nullptr;
     }
     static bool reads_host_values(const std::string& op) {
-        static const std::set<std::string> s = {"Add", "Sub", "Mul", "Div", "Pow", "PRelu", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Where", "Reshape", "Squeeze", "Unsqueeze",
-                                                "Slice", "Gather", "GatherND", "GatherElements", "Concat", "Identity", "Cast", "ConstantOfShape", "Shape", "Range", "SLADecode", "FormulaDecode"};
-        return s.count(op) != 0;
+        const OpRow* r = find_op(op);
+        return r && r->host_inputs == HostInputs::READS_HOST;
     }
     std::string device_shadow(const std::string& name) {
         const std::string sn = name + "::dev";
@@ -5499,100 +5499,174 @@ struct Planner {
             const TInfo& t = info(s);
             OAR_CHECK(t.host_int || t.loc.kind != Loc::NONE, OAR_INTERNAL, "planner: input '" + s + "' of " + node_label() + " has no storage");
         }
-        if (op == "ConstantOfShape") return op_constant_of_shape(n);
-        if (op == "Conv") return op_conv(n);
-        if (op == "ConvTranspose") return op_convt(n);
-        if (op == "BatchNormalization") return op_bn(n);
-        if (is_unary_act(op)) return op_unary(n, act_of(n));
-        if (op == "Clip") {
-            // an absent bound is no bound: from opset 11 on (bounds as inputs) +-inf pass through; the attribute form (opset 6) defaults to +-FLT_MAX by its own text
-            const float none = (opset >= 11 || opset == 0) ? INFINITY : 3.402823466e38f;
-            Act a; a.kind = k::ACT_CLIP; a.alpha = n.af("min", -none); a.beta = n.af("max", none);
-            if (has_input(n, 1)) { const TInfo& t = get(n.in[1]); OAR_CHECK(t.ht, OAR_UNSUPPORTED_OP, "Clip: dynamic min"); a.alpha = t.ht->f[0]; }
-            if (has_input(n, 2)) { const TInfo& t = get(n.in[2]); OAR_CHECK(t.ht, OAR_UNSUPPORTED_OP, "Clip: dynamic max"); a.beta = t.ht->f[0]; }
-            return op_unary(n, a);
-        }
-        if (op == "Add") return op_binary(n, 0);
-        if (op == "Sub") return op_binary(n, 1);
-        if (op == "Mul") return op_binary(n, 2);
-        if (op == "Div") return op_binary(n, 3);
-        if (op == "Pow") return op_binary(n, 4);
-        if (op == "PRelu") return op_binary(n, 5);
-        if (op == "Max") return op_binary(n, 6);
-        if (op == "Min") return op_binary(n, 7);
-        if (op == "Equal") return op_binary(n, 8);
-        if (op == "Less") return op_binary(n, 9);
-        if (op == "Greater") return op_binary(n, 10);
-        if (op == "And") return op_binary(n, 11);
-        if (op == "Or") return op_binary(n, 12);
-        if (op == "ReduceMean") return op_reduce(n, 0);
-        if (op == "ReduceSum") return op_reduce(n, 1);
-        if (op == "ReduceMax") return op_reduce(n, 2);
-        if (op == "ArgMax") return op_argreduce(n, false);
-        if (op == "ArgMin") return op_argreduce(n, true);
-        if (op == "ReduceMin") return op_reduce(n, 3);
-        if (op == "ReduceProd") return op_reduce(n, 4);
-        if (op == "Expand") return op_expand(n);
-        if (op == "Tile") return op_tile(n);
-        if (op == "Where") return op_where(n);
-        if (op == "GridSample") return op_grid_sample(n);
-        if (op == "Pad") return op_pad(n);
-        if (op == "GlobalAveragePool") return op_gap(n);
-        if (op == "AveragePool") return op_pool(n, false);
-        if (op == "MaxPool") return op_pool(n, true);
-        if (op == "Resize") return op_resize(n);
-        if (op == "Concat") return op_concat(n);
-        if (op == "Reshape") return op_reshape(n);
-        if (op == "Flatten") return op_flatten(n);
-        if (op == "Squeeze") return op_squeeze(n);
-        if (op == "Unsqueeze") return op_unsqueeze(n);
-        if (op == "Transpose") return op_transpose(n);
-        if (op == "Split") return op_split(n);
-        if (op == "Slice") return op_slice(n);
-        if (op == "Gather") return op_gather(n);
-        if (op == "GatherND") return op_gather_nd(n);
-        if (op == "GatherElements") return op_gather_elements(n);
-        if (op == "TopK") return op_topk(n);
-        if (op == "Linear") return op_linear(n, false);
-        if (op == "Gemm") return op_linear(n, true);
-        if (op == "MatMul") return op_matmul(n);
-        if (op == "Softmax") return op_softmax(n);
-        if (op == "Attention") return op_attention(n);
-        if (op == "WindowAttention") return op_window_attention(n);
-        if (op == "DeformableAttention") return op_deformable_attention(n);
-        if (op == "RelPosAttention") return op_relpos_attention(n);
-        if (op == "MultiHeadAttention") return op_mha_attention(n);
-        if (op == "SLADecode") return op_sla_decode(n);
-        if (op == "FormulaDecode") return op_formula_decode(n);
-        if (op == "SEGate") return op_se_gate(n);
-        if (op == "DSBlock") return op_dsblock(n);
-        if (op == "LayerNormalization") return op_layernorm(n);
-        if (op == "Identity") { const TInfo& x = get(n.in[0]); if (x.host_int) { vals[n.out[0]] = x; } else { TInfo xx = x; alias_out(n.out[0], xx, xx.dims, xx.layout); } return; }
-        if (op == "Cast") {   // device tensors are f32 whatever they are called: float <-> bool casts of 0/1 masks are aliases
-            const TInfo& x = get(n.in[0]);
-            const int64_t to = n.ai("to", 1);
-            OAR_CHECK(to == 1 || to == 9 || to == 10 || to == 11 || x.is_int, OAR_UNSUPPORTED_OP, "Cast of a device tensor to an integer type");
-            bool mask = x.is01;
-            if (to == 9 && !mask && x.ht) { mask = true; for (float v : x.ht->f) mask = mask && (v == 1.0f || (v == 0.0f && !std::signbit(v))); }   // (-0.0 would come back as -0.0)
-            if (to == 9 && !mask) {   // any other float: bool(x) is x != 0, one launch of the flat binary kernel as Or(x, x)
-                const TInfo xx = x;
-                TInfo& y = new_out(n.out[0], xx.dims, xx.layout);
-                y.is01 = true;
-                const Loc xl = xx.loc, yl = y.loc;
-                const int64_t cnt = numel(xx.dims);
-                const std::vector<int64_t> d{cnt}, st{1};
-                step([=](const RunCtx& c) { k::binary(c.s, c.at(xl), c.at(xl), c.mut(yl), 12, 1, d.data(), st.data(), st.data(), Act()); }, (double)cnt, 8.0 * cnt);
-                return;
-            }
-            TInfo xx = x;
-            TInfo& y = alias_out(n.out[0], xx, xx.dims, xx.layout);
-            y.is_int = x.is_int && !(to == 1 || to == 10 || to == 11);   // (a float Cast of an index tensor is a float tensor: views keep the mark now)
-            y.is01 = mask;
-            return;
-        }
+        const OpRow* row = find_op(op);
+        if (row && row->plan) { row_code = row->code; return (this->*row->plan)(n); }
         fail(OAR_UNSUPPORTED_OP, "operator '" + op + "' is not implemented (node output " + (n.out.empty() ? "?" : n.out[0]) + ")");
     }
+
+    // ------------------------------------------------------------------ handlers of the operator table that have no op_* of their own above
+    void op_unary_act(const GNode& n) { op_unary(n, act_of(n)); }
+    int row_code = 0;   // the `code` of the row dispatch() is calling through
+    void op_binary_code(const GNode& n) { op_binary(n, row_code); }
+    void op_reduce_code(const GNode& n) { op_reduce(n, row_code); }
+    void op_argmax(const GNode& n) { op_argreduce(n, false); }
+    void op_argmin(const GNode& n) { op_argreduce(n, true); }
+    void op_average_pool(const GNode& n) { op_pool(n, false); }
+    void op_max_pool(const GNode& n) { op_pool(n, true); }
+    void op_conv_transpose(const GNode& n) { op_convt(n); }
+    void op_linear_node(const GNode& n) { op_linear(n, false); }
+    void op_gemm(const GNode& n) { op_linear(n, true); }
+    void op_clip(const GNode& n) {
+        // an absent bound is no bound: from opset 11 on (bounds as inputs) +-inf pass through; the attribute form (opset 6) defaults to +-FLT_MAX by its own text
+        const float none = (opset >= 11 || opset == 0) ? INFINITY : 3.402823466e38f;
+        Act a; a.kind = k::ACT_CLIP; a.alpha = n.af("min", -none); a.beta = n.af("max", none);
+        if (has_input(n, 1)) { const TInfo& t = get(n.in[1]); OAR_CHECK(t.ht, OAR_UNSUPPORTED_OP, "Clip: dynamic min"); a.alpha = t.ht->f[0]; }
+        if (has_input(n, 2)) { const TInfo& t = get(n.in[2]); OAR_CHECK(t.ht, OAR_UNSUPPORTED_OP, "Clip: dynamic max"); a.beta = t.ht->f[0]; }
+        return op_unary(n, a);
+    }
+    void op_identity(const GNode& n) { const TInfo& x = get(n.in[0]); if (x.host_int) { vals[n.out[0]] = x; } else { TInfo xx = x; alias_out(n.out[0], xx, xx.dims, xx.layout); } return; }
+    void op_cast(const GNode& n) {   // device tensors are f32 whatever they are called: float <-> bool casts of 0/1 masks are aliases
+        const TInfo& x = get(n.in[0]);
+        const int64_t to = n.ai("to", 1);
+        OAR_CHECK(to == 1 || to == 9 || to == 10 || to == 11 || x.is_int, OAR_UNSUPPORTED_OP, "Cast of a device tensor to an integer type");
+        bool mask = x.is01;
+        if (to == 9 && !mask && x.ht) { mask = true; for (float v : x.ht->f) mask = mask && (v == 1.0f || (v == 0.0f && !std::signbit(v))); }   // (-0.0 would come back as -0.0)
+        if (to == 9 && !mask) {   // any other float: bool(x) is x != 0, one launch of the flat binary kernel as Or(x, x)
+            const TInfo xx = x;
+            TInfo& y = new_out(n.out[0], xx.dims, xx.layout);
+            y.is01 = true;
+            const Loc xl = xx.loc, yl = y.loc;
+            const int64_t cnt = numel(xx.dims);
+            const std::vector<int64_t> d{cnt}, st{1};
+            step([=](const RunCtx& c) { k::binary(c.s, c.at(xl), c.at(xl), c.mut(yl), 12, 1, d.data(), st.data(), st.data(), Act()); }, (double)cnt, 8.0 * cnt);
+            return;
+        }
+        TInfo xx = x;
+        TInfo& y = alias_out(n.out[0], xx, xx.dims, xx.layout);
+        y.is_int = x.is_int && !(to == 1 || to == 10 || to == 11);   // (a float Cast of an index tensor is a float tensor: views keep the mark now)
+        y.is01 = mask;
+        return;
+    }
 };
+
+// ---- the operator table: one row per operator name the engine knows, sorted by name (find_op searches it).
+//   pub          the name may stand in a model file: Engine::supported_ops() is the rows that have it.  The other names are made by the load-time rewrites only.
+//   host_inputs  what dispatch() does where an input's value is known at plan time (TInfo::host_int) and so has no device bytes:
+//                  DATA0, DATA01  the operator exists only as a kernel: data input 0 / inputs 0 and 1 are uploaded once (device_shadow); its other inputs are
+//                                 plan-time parameters (shapes, axes, pads, K)
+//                  READS_HOST     the operator reads host values itself (the binary family, Where, the views, Gather, Concat, ...)
+//                  NONE           neither: a plan-time value in input 0 is refused
+//   plan         the planner's handler.  Null: the name never reaches a handler -- Constant, Dropout and Loop leave the graph at load time, Shape is dispatch()'s
+//                first case and Range exists only as a plan-time evaluation (op_host)
+//   code         what op_binary_code / op_reduce_code hand on: k::binary's operator, k::reduce_lastdim's mode
+// A new operator is one row here (and, for a unary activation, its case in act_of).  The rows live inside a host function: a table at namespace scope would be
+// emitted for the device too, where the handlers do not exist.
+static const OpRow* op_table(size_t& count) {
+    constexpr HostInputs NONE = HostInputs::NONE, DATA0 = HostInputs::DATA0, DATA01 = HostInputs::DATA01, READS_HOST = HostInputs::READS_HOST;
+    static const OpRow rows[] = {
+        {"Abs",                 true,  DATA0,      &Planner::op_unary_act},
+        {"Add",                 true,  READS_HOST, &Planner::op_binary_code, 0},
+        {"And",                 true,  READS_HOST, &Planner::op_binary_code, 11},
+        {"ArgMax",              true,  DATA0,      &Planner::op_argmax},
+        {"ArgMin",              true,  DATA0,      &Planner::op_argmin},
+        {"Attention",           false, NONE,       &Planner::op_attention},
+        {"AveragePool",         true,  DATA0,      &Planner::op_average_pool},
+        {"BatchNormalization",  true,  NONE,       &Planner::op_bn},
+        {"Cast",                true,  READS_HOST, &Planner::op_cast},
+        {"Ceil",                true,  DATA0,      &Planner::op_unary_act},
+        {"Clip",                true,  DATA0,      &Planner::op_clip},
+        {"Concat",              true,  READS_HOST, &Planner::op_concat},
+        {"Constant",            true,  NONE,       nullptr},
+        {"ConstantOfShape",     true,  READS_HOST, &Planner::op_constant_of_shape},
+        {"Conv",                true,  NONE,       &Planner::op_conv},
+        {"ConvTranspose",       true,  NONE,       &Planner::op_conv_transpose},
+        {"DSBlock",             false, NONE,       &Planner::op_dsblock},
+        {"DeformableAttention", false, NONE,       &Planner::op_deformable_attention},
+        {"Div",                 true,  READS_HOST, &Planner::op_binary_code, 3},
+        {"Dropout",             true,  NONE,       nullptr},
+        {"Equal",               true,  READS_HOST, &Planner::op_binary_code, 8},
+        {"Erf",                 true,  DATA0,      &Planner::op_unary_act},
+        {"Exp",                 true,  DATA0,      &Planner::op_unary_act},
+        {"Expand",              true,  DATA0,      &Planner::op_expand},
+        {"Flatten",             true,  DATA0,      &Planner::op_flatten},
+        {"Floor",               true,  DATA0,      &Planner::op_unary_act},
+        {"FormulaDecode",       false, READS_HOST, &Planner::op_formula_decode},
+        {"Gather",              true,  READS_HOST, &Planner::op_gather},
+        {"GatherElements",      true,  READS_HOST, &Planner::op_gather_elements},
+        {"GatherND",            true,  READS_HOST, &Planner::op_gather_nd},
+        {"Gelu",                true,  DATA0,      &Planner::op_unary_act},
+        {"Gemm",                true,  DATA0,      &Planner::op_gemm},
+        {"GlobalAveragePool",   true,  DATA0,      &Planner::op_gap},
+        {"Greater",             true,  READS_HOST, &Planner::op_binary_code, 10},
+        {"GridSample",          true,  DATA01,     &Planner::op_grid_sample},
+        {"HardSigmoid",         true,  DATA0,      &Planner::op_unary_act},
+        {"HardSwish",           true,  DATA0,      &Planner::op_unary_act},
+        {"Identity",            true,  READS_HOST, &Planner::op_identity},
+        {"LayerNormalization",  true,  DATA0,      &Planner::op_layernorm},
+        {"LeakyRelu",           true,  DATA0,      &Planner::op_unary_act},
+        {"Less",                true,  READS_HOST, &Planner::op_binary_code, 9},
+        {"Linear",              false, DATA0,      &Planner::op_linear_node},
+        {"Log",                 true,  DATA0,      &Planner::op_unary_act},
+        {"Loop",                true,  NONE,       nullptr},
+        {"MatMul",              true,  DATA01,     &Planner::op_matmul},
+        {"Max",                 true,  READS_HOST, &Planner::op_binary_code, 6},
+        {"MaxPool",             true,  DATA0,      &Planner::op_max_pool},
+        {"Min",                 true,  READS_HOST, &Planner::op_binary_code, 7},
+        {"Mul",                 true,  READS_HOST, &Planner::op_binary_code, 2},
+        {"MultiHeadAttention",  false, NONE,       &Planner::op_mha_attention},
+        {"Neg",                 true,  DATA0,      &Planner::op_unary_act},
+        {"Not",                 true,  DATA0,      &Planner::op_unary_act},
+        {"Or",                  true,  READS_HOST, &Planner::op_binary_code, 12},
+        {"PRelu",               true,  READS_HOST, &Planner::op_binary_code, 5},
+        {"Pad",                 true,  DATA0,      &Planner::op_pad},
+        {"Pow",                 true,  READS_HOST, &Planner::op_binary_code, 4},
+        {"Range",               true,  READS_HOST, nullptr},
+        {"Reciprocal",          true,  DATA0,      &Planner::op_unary_act},
+        {"ReduceMax",           true,  DATA0,      &Planner::op_reduce_code, 2},
+        {"ReduceMean",          true,  DATA0,      &Planner::op_reduce_code, 0},
+        {"ReduceMin",           true,  DATA0,      &Planner::op_reduce_code, 3},
+        {"ReduceProd",          true,  DATA0,      &Planner::op_reduce_code, 4},
+        {"ReduceSum",           true,  DATA0,      &Planner::op_reduce_code, 1},
+        {"RelPosAttention",     false, NONE,       &Planner::op_relpos_attention},
+        {"Relu",                true,  DATA0,      &Planner::op_unary_act},
+        {"Reshape",             true,  READS_HOST, &Planner::op_reshape},
+        {"Resize",              true,  DATA0,      &Planner::op_resize},
+        {"Round",               true,  DATA0,      &Planner::op_unary_act},
+        {"SEGate",              false, NONE,       &Planner::op_se_gate},
+        {"SLADecode",           false, READS_HOST, &Planner::op_sla_decode},
+        {"Shape",               true,  READS_HOST, nullptr},
+        {"Sigmoid",             true,  DATA0,      &Planner::op_unary_act},
+        {"Slice",               true,  READS_HOST, &Planner::op_slice},
+        {"Softmax",             true,  DATA0,      &Planner::op_softmax},
+        {"Softplus",            true,  DATA0,      &Planner::op_unary_act},
+        {"Split",               true,  DATA0,      &Planner::op_split},
+        {"Sqrt",                true,  DATA0,      &Planner::op_unary_act},
+        {"Squeeze",             true,  READS_HOST, &Planner::op_squeeze},
+        {"Sub",                 true,  READS_HOST, &Planner::op_binary_code, 1},
+        {"Tanh",                true,  DATA0,      &Planner::op_unary_act},
+        {"Tile",                true,  DATA0,      &Planner::op_tile},
+        {"TopK",                true,  DATA0,      &Planner::op_topk},
+        {"Transpose",           true,  DATA0,      &Planner::op_transpose},
+        {"Unsqueeze",           true,  READS_HOST, &Planner::op_unsqueeze},
+        {"Where",               true,  READS_HOST, &Planner::op_where},
+        {"WindowAttention",     false, NONE,       &Planner::op_window_attention},
+    };
+    count = sizeof(rows) / sizeof(rows[0]);
+    static const bool sorted = [&] {   // checked once, at the first look-up: find_op searches by name
+        OAR_CHECK(std::is_sorted(rows, rows + count, [](const OpRow& a, const OpRow& b) { return std::strcmp(a.name, b.name) < 0; }), OAR_INTERNAL,
+                  "the operator table is not sorted by name");
+        return true;
+    }();
+    (void)sorted;
+    return rows;
+}
+
+static const OpRow* find_op(const std::string& name) {
+    size_t count = 0;
+    const OpRow* rows = op_table(count);
+    const OpRow* r = std::lower_bound(rows, rows + count, name, [](const OpRow& a, const std::string& b) { return b.compare(a.name) > 0; });
+    return r != rows + count && name == r->name ? r : nullptr;
+}
 
 std::vector<float> igemm_to_fragments(int fmt, const std::vector<float>& w, int64_t rows, int64_t K) { return Planner::to_fragments(fmt, w, rows, K); }
 
@@ -5638,15 +5712,16 @@ void Engine::validate_model(const OnnxModel& m) {
     }
 }
 
-// every operator name dispatch() (or a load-time rewrite) accepts -- oar_onnx_inspect reports the rest
+// every operator name a model file may hold: the public rows of the operator table -- oar_onnx_inspect reports the rest
+// (Loop: the SLA decode step and the formula decode step only, see match_sla_loop / match_formula_loop)
 const std::set<std::string>& Engine::supported_ops() {
-    static const std::set<std::string> ops = {
-        "Constant", "Dropout", "Identity", "Cast", "Shape", "Conv", "ConvTranspose", "BatchNormalization", "Relu", "HardSwish", "HardSigmoid", "Sigmoid",
-        "LeakyRelu", "Tanh", "Erf", "Sqrt", "Exp", "Abs", "Neg", "Reciprocal", "Log", "Gelu", "Softplus", "Clip", "Add", "Sub", "Mul", "Div", "Pow", "PRelu",
-        "ReduceMean", "GridSample", "Pad", "GlobalAveragePool", "AveragePool", "MaxPool", "Resize", "Concat", "Reshape", "Flatten", "Squeeze", "Unsqueeze",
-        "Transpose", "Split", "Slice", "Gather", "Gemm", "MatMul", "Softmax", "LayerNormalization", "Max", "Min", "Equal", "Less", "Greater", "And", "Or", "Not",
-        "Floor", "Ceil", "Round", "ReduceSum", "ReduceMax", "ReduceMin", "ReduceProd", "Expand", "Tile", "Where", "ConstantOfShape", "Range", "ArgMax", "ArgMin",
-        "TopK", "GatherND", "GatherElements", "Loop"};   // (Loop: the SLA decode step and the formula decode step only, see match_sla_loop / match_formula_loop)
+    static const std::set<std::string> ops = [] {
+        std::set<std::string> s;
+        size_t count = 0;
+        const OpRow* rows = op_table(count);
+        for (size_t i = 0; i < count; ++i) if (rows[i].pub) s.insert(rows[i].name);
+        return s;
+    }();
     return ops;
 }
 
