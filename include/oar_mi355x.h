@@ -155,6 +155,13 @@ oar_status oar_engine_decode_stats(oar_engine* e, oar_decode_stats* out);
  * indexed), OAR_UNSUPPORTED_OP when an operator is missing.  Stands where `Session::builder().commit_from_file`
  * fails in the reference (core/inference/session.rs:30-44). */
 oar_status oar_onnx_inspect(const uint8_t* onnx, size_t onnx_len, char* summary, size_t cap);
+/* Host-only view of what loading makes of a model (no GPU needed): parses, validates and rewrites the graph exactly as
+ * oar_engine_create does and writes a listing: one line per node after the rewrite passes, in order (op, outputs,
+ * inputs, fused activation, bias, residual, attributes), one per initializer (name, dtype, dims, payload hash), the
+ * nodes each rewritten LayerNormalization replaced and the add + LayerNorm switch.  *needed (may be null) receives the
+ * listing's length without the terminating 0; a listing longer than cap - 1 is cut.  An inspection aid: the format
+ * may change between versions.  Errors as oar_engine_create's for the model file (never OAR_DEVICE). */
+oar_status oar_onnx_rewrite(const uint8_t* onnx, size_t onnx_len, char* text, size_t cap, size_t* needed);
 
 /* ------------------------------------------------------------------------------------------------ Seam B: detection
  * TextDetectionAdapter::execute (domain/adapters/text_detection_adapter.rs:36-79) -> DBModel::forward

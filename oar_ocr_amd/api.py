@@ -150,7 +150,7 @@ EXPORTS = [
     "oar_host_candidates", "oar_host_unclip", "oar_host_mini_box", "oar_host_convex_hull", "oar_host_sort_quad_boxes", "oar_host_pool_selftest", "oar_host_plan_crop",
     "oar_cls_create", "oar_cls_destroy", "oar_cls_run", "oar_cls_result_free", "oar_cls_preprocess", "oar_rect_create", "oar_rect_destroy",
     "oar_rect_run", "oar_ocr_attach", "oar_k_rotate_rgb", "oar_k_bgr_planes_to_rgb", "oar_host_rotate_back_points",
-    "oar_engine_cache_stats", "oar_onnx_inspect", "oar_host_contours", "oar_ctc_dict_create", "oar_ctc_dict_destroy", "oar_ctc_dict_classes",
+    "oar_engine_cache_stats", "oar_onnx_inspect", "oar_onnx_rewrite", "oar_host_contours", "oar_ctc_dict_create", "oar_ctc_dict_destroy", "oar_ctc_dict_classes",
     "oar_ctc_decode", "oar_ocr_decode", "oar_text_result_free", "oar_db_postprocess_ex", "oar_k_dilate", "oar_k_poly_scores", "oar_debug_inject_failure", "oar_k_contours", "oar_host_contours_bits",
     "oar_k_unclip", "oar_k_rec_preprocess_flip", "oar_layout_create", "oar_layout_destroy", "oar_layout_run", "oar_layout_result_free", "oar_layout_preprocess", "oar_k_resize_filter", "oar_k_layout_postprocess", "oar_layout_run_ppdoc", "oar_k_ppdoc_postprocess", "oar_host_nms_with_merge", "oar_image_decode_device", "oar_ocr_predict_async", "oar_ocr_wait", "oar_ctc_word_boxes", "oar_char_positions_to_word_boxes", "oar_ocr_word_boxes", "oar_word_boxes_free", "oar_image_decode", "oar_image_free", "oar_host_approx_poly_dp", "oar_host_perimeter", "oar_host_unclip_poly", "oar_host_offset_ring", "oar_host_ring_outline", "oar_host_sort_poly_boxes",
     "oar_engine_set_decode_stop", "oar_engine_decode_stats", "oar_k_mha_attention", "oar_k_relpos_attention", "oar_k_add_layernorm", "oar_k_vis_attention", "oar_k_vis_pos_embed",
@@ -191,6 +191,7 @@ def lib():
     L.oar_engine_set_decode_stop.argtypes = [vp, C.c_int64]
     L.oar_engine_decode_stats.argtypes = [vp, C.POINTER(DecodeStats)]
     L.oar_onnx_inspect.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_size_t]
+    L.oar_onnx_rewrite.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.oar_det_create.argtypes = [vp, C.c_size_t, C.POINTER(DetCfg), C.POINTER(vp)]
     L.oar_det_destroy.argtypes = [vp]
     L.oar_det_destroy.restype = None
@@ -394,6 +395,16 @@ def onnx_inspect(model: bytes) -> str:
     b = (C.c_char * max(len(model), 1)).from_buffer_copy(model or b"\0")
     st = lib().oar_onnx_inspect(C.cast(b, C.c_void_p), len(model), buf, 8192)
     _check(st)
+    return buf.value.decode()
+
+
+def onnx_rewrite(model: bytes) -> str:
+    """Host-only: what loading makes of a model (parse, validate, the rewrite passes) as a listing, one line per node / initializer.  An inspection aid."""
+    b = (C.c_char * max(len(model), 1)).from_buffer_copy(model or b"\0")
+    need = C.c_size_t(0)
+    _check(lib().oar_onnx_rewrite(C.cast(b, C.c_void_p), len(model), None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value + 1)
+    _check(lib().oar_onnx_rewrite(C.cast(b, C.c_void_p), len(model), buf, need.value + 1, None))
     return buf.value.decode()
 
 

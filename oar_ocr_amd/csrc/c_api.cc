@@ -392,6 +392,18 @@ oar_status oar_engine_decode_stats(oar_engine* e, oar_decode_stats* out) {
     });
 }
 
+oar_status oar_onnx_rewrite(const uint8_t* onnx, size_t onnx_len, char* text, size_t cap, size_t* needed) {
+    if (text && cap) text[0] = 0;
+    if (needed) *needed = 0;
+    return guard([&] {
+        OnnxModel m = parse_onnx(onnx, onnx_len);
+        Engine::validate_model(m);
+        const std::string s = graph_listing(rewrite_graph(m));
+        if (needed) *needed = s.size();
+        if (text && cap) snprintf(text, cap, "%s", s.c_str());
+    });
+}
+
 oar_status oar_onnx_inspect(const uint8_t* onnx, size_t onnx_len, char* summary, size_t cap) {
     if (summary && cap) summary[0] = 0;
     return guard([&] {

@@ -1,5 +1,5 @@
 // deformable_attention.hip -- multi-scale deformable attention (the cross-attention of an RT-DETR decoder layer) as ONE launch.  The engine's rewrite pass 3c
-// (engine.cc) emits it for the exported spelling  Split the value per level -> Transpose + Reshape to [N nh, c, h, w] -> GridSample with the grid 2 loc - 1 ->
+// (engine_rewrite.cc) emits it for the exported spelling  Split the value per level -> Transpose + Reshape to [N nh, c, h, w] -> GridSample with the grid 2 loc - 1 ->
 // Concat -> Mul by the softmax weights -> ReduceSum  (DESIGN 4.34).  The value projection already writes [N, Lv, nh, c] with the c channels of a (location,
 // head) contiguous, so a tap is read straight from there: neither the per-level copies, nor the channels-last conversions, nor the [N nh, c, Q, L P] sample
 // tensor exist.

@@ -14,27 +14,13 @@
 #include <vector>
 
 #include "common.h"
+#include "graph_rewrite.h"   // GNode, rewrite_graph: the host-only half of loading
 #include "kernels.h"
 #include "onnx_parse.h"
 
 namespace oar {
 
 enum class Layout : int { NATIVE = 0, CLAST = 1 };  // CLAST: logical [n, C, s...] stored as [n, s..., C]
-
-struct GNode {  // graph node after load-time rewrites
-    std::string op;
-    std::vector<std::string> in, out;
-    std::map<std::string, Attr> attrs;
-    k::Act act;                 // fused activation
-    std::string bias;           // fused bias initializer (Linear)
-    std::string residual;       // fused residual input
-    int id = 0;
-    int64_t ai(const char* k, int64_t d) const { auto it = attrs.find(k); return it == attrs.end() ? d : it->second.i; }
-    float af(const char* k, float d) const { auto it = attrs.find(k); return it == attrs.end() ? d : it->second.f; }
-    std::string as(const char* k, const std::string& d) const { auto it = attrs.find(k); return it == attrs.end() ? d : it->second.s; }
-    std::vector<int64_t> ais(const char* k) const { auto it = attrs.find(k); return it == attrs.end() ? std::vector<int64_t>{} : it->second.is; }
-    bool has(const char* k) const { return attrs.count(k) != 0; }
-};
 
 struct Loc {  // where a value lives at run time
     enum Kind { NONE, INPUT, ARENA, CONST, EXTRA } kind = NONE;
@@ -136,11 +122,6 @@ class Engine {
 
    private:
     friend struct Planner;
-    void rewrite_graph(OnnxModel& m);
-    void match_sla_loop(const GNode& loop, GNode& linear, GNode& decode);   // a Loop whose body is the SLA decode step -> Linear + SLADecode; throws OAR_UNSUPPORTED_OP otherwise
-    // a Loop whose body is the greedy step of a transformer decoder with a key / value cache -> FormulaDecode; `dropped_inputs` receives the (empty) initial caches,
-    // which leave the graph; throws OAR_UNSUPPORTED_OP otherwise
-    void match_formula_loop(const GNode& loop, const std::vector<GNode>& outer_nodes, GNode& decode, std::vector<std::string>& dropped_inputs);
     const float* upload_const(const std::string& key, const std::vector<float>& v);
 
     int device_ = 0;

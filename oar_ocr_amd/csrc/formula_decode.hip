@@ -1,5 +1,5 @@
 // formula_decode.hip -- the greedy autoregressive decode of a PP-FormulaNet-style head (an MBart-order, pre-norm transformer decoder with a
-// key / value cache) as a fixed chain of short launches per step.  The engine's Loop rewrite (engine.cc, match_formula_loop) emits it.
+// key / value cache) as a fixed chain of short launches per step.  The engine's Loop rewrite (engine_loops.cc, match_formula_loop) emits it.
 //
 // A decode step at batch <= 16 is weight streaming: every matrix is read once per step for the whole batch, across all CUs, and a kernel
 // boundary is the all-to-all seam each LayerNorm / GEMV pair needs.  There is no grid-wide barrier and no flag in global memory: nothing here

@@ -1,5 +1,5 @@
 // mha_attention.hip -- ordinary multi-head attention with separate q / k / v sources as ONE launch: the self-attention of an RT-DETR decoder
-// layer and the AIFI layer of its hybrid encoder, where q and k are projections of x + pos and v of x.  The engine's rewrite pass 3e (engine.cc) emits it for
+// layer and the AIFI layer of its hybrid encoder, where q and k are projections of x + pos and v of x.  The engine's rewrite pass 3e (engine_rewrite.cc) emits it for
 // the spelling  heads(q) heads(k)^T, scaled on either side -> Softmax -> heads(v) -> merge:  q, k, v are three pointers, each viewed as [N][T][nh][dh] with a
 // row stride of its own, so the head split and merge are address arithmetic and o [N][Tq][nh dh] is written in token order.
 //

@@ -1,5 +1,5 @@
 // relpos_attention.hip -- the attention of one SAM / Vary ViT block (the encoder of the larger PP-FormulaNet files) as ONE launch, windowed or
-// global, with the decomposed relative-position bias  q . Rh[qy, ky] + q . Rw[qx, kx]  that depends on the query.  The engine's rewrite pass 3d (engine.cc)
+// global, with the decomposed relative-position bias  q . Rh[qy, ky] + q . Rw[qx, kx]  that depends on the query.  The engine's rewrite pass 3d (engine_rewrite.cc)
 // emits it for the spelling  [pad -> window partition ->] fused qkv Linear -> heads -> scores + rel terms -> Softmax -> values -> projection [-> window reverse
 // -> crop]:  a Linear is per token, so the fused projection reads the unpadded tokens in image order and this kernel gathers a key set's rows by address
 // (a window, or the whole grid); a padding token is a key carrying bqkv's k / v rows and is skipped as a query.

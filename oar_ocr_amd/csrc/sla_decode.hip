@@ -1,5 +1,5 @@
 // sla_decode.hip -- the SLANet structure head (PaddleOCR SLAHead._decode: AttentionGRUCell + GRUCell + the two output
-// heads) as ONE launch: every step of the greedy recurrence, all images.  The engine's Loop rewrite (engine.cc) emits it.
+// heads) as ONE launch: every step of the greedy recurrence, all images.  The engine's Loop rewrite (engine_loops.cc, match_sla_loop) emits it.
 //
 // One workgroup of 1024 threads (16 waves, one CU) per image; images are independent, so there is no communication
 // between workgroups and nothing ever waits on global memory.  The workgroup walks all M steps; the phases of a step are

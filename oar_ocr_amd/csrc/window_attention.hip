@@ -1,5 +1,5 @@
 // window_attention.hip -- the attention of one Swin block (UniMERNet's encoder; plain, padded, shifted and masked windows) as ONE launch.  The engine's rewrite pass 3b
-// (engine.cc) emits it for the spelling  window partition -> q / k / v Linear -> per-window multi-head attention with an additive relative-position bias ->
+// (engine_rewrite.cc) emits it for the spelling  window partition -> q / k / v Linear -> per-window multi-head attention with an additive relative-position bias ->
 // projection -> window reverse:  a Linear is per token, so the three projections read the tokens in image order and this kernel gathers a window's rows by
 // address -- neither partition copy, nor the reverse copy, nor any permuted copy of q, k, v or the output exists.
 //

@@ -458,6 +458,7 @@ unsafe extern "C" {
     pub fn oar_engine_set_decode_stop(e: *mut oar_engine, token: i64) -> oar_status;
     pub fn oar_engine_decode_stats(e: *mut oar_engine, out: *mut oar_decode_stats) -> oar_status;
     pub fn oar_onnx_inspect(onnx: *const u8, onnx_len: usize, summary: *mut c_char, cap: usize) -> oar_status;
+    pub fn oar_onnx_rewrite(onnx: *const u8, onnx_len: usize, text: *mut c_char, cap: usize, needed: *mut usize) -> oar_status;
     pub fn oar_det_create(onnx: *const u8, onnx_len: usize, cfg: *const oar_det_cfg, out: *mut *mut oar_det) -> oar_status;
     pub fn oar_det_destroy(d: *mut oar_det);
     pub fn oar_det_run(d: *mut oar_det, rgb: *const *const u8, widths: *const u32, heights: *const u32, n_images: u32, thresh: f32, box_thresh: f32, unclip_ratio: f32, out: *mut oar_det_result) -> oar_status;

@@ -1,7 +1,7 @@
 """BASELINE C3 on graphs of the size and kind it names: the PP-HGNetV2 / LK-PAN detector (21.7 M parameters, dense 3x3 and
 9x9 convolutions) and the SVTRv2 recognizer (20.5 M parameters, grouped 5x5 mixing + global attention over 480 ... 2400 tokens) of
 oar_ocr_amd/synth/models.py, against the torch-CPU oracle; plus the two pieces the engine grew for them: the streaming bf16x6 attention kernel
-(csrc/attention_x6.hip) and the decomposed-GELU rewrite (engine.cc pass 2b).  Tolerance as in test_gpu_engine.py: 2e-4 (north_star allows 1e-3)."""
+(csrc/attention_x6.hip) and the decomposed-GELU rewrite (engine_rewrite.cc pass 2b).  Tolerance as in test_gpu_engine.py: 2e-4 (north_star allows 1e-3)."""
 import numpy as np
 import pytest
 

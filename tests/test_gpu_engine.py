@@ -863,7 +863,7 @@ def test_non_f32_declared_inputs_and_oversized_integer_outputs_are_errors():
 
 def test_squeeze_excite_scale_rides_on_the_pointwise_conv(monkeypatch):
     """Mul(x, SEGate) -> Conv 1x1 (the tail of a PP-LCNet squeeze-excite block): on layers the bf16x6 weight-stationary kernel takes,
-    the gate is multiplied into the pixels as they are loaded (engine.cc pass 8, igemm_ws_x6.hip SE variant) -- no `binary` launch, the
+    the gate is multiplied into the pixels as they are loaded (engine_rewrite.cc pass 8, igemm_ws_x6.hip SE variant) -- no `binary` launch, the
     scaled map never reaches HBM -- and the result is BIT-identical to running the Mul (same v_mul_f32, then the same split); layers
     the kernel does not take (the detector's 30 x 30 maps) run the Mul after all.  Both against the torch oracle."""
     rec, _ = models.build_rec("tiny", vocab=6906, seed=1)
@@ -906,7 +906,7 @@ def test_squeeze_excite_scale_rides_on_the_pointwise_conv(monkeypatch):
 def test_squeeze_excite_pool_comes_from_the_depthwise_epilogue(monkeypatch):
     """GlobalAveragePool(depthwise conv) (the squeeze of an SE block): the 5 x 5 depthwise kernel writes per-tile sums of its activated
     output and `global_avgpool_finish` -- since round 5 the squeeze-excite gate kernel itself, when the pooled vector feeds nothing else --
-    reduces them (engine.cc pass 9): the feature map is not read a second time.  Same numbers as the
+    reduces them (engine_rewrite.cc pass 9): the feature map is not read a second time.  Same numbers as the
     oracle, equal to the separate pool to f32 rounding (another summation order: tile sums first), argmax unchanged; 3 x 3 depthwise
     convs (no pooled variant) pool separately."""
     rec, _ = models.build_rec("tiny", vocab=6906, seed=1)

@@ -1,4 +1,4 @@
-"""Decomposed LayerNorm as one launch and residual add + LayerNorm fused, through the engine (rewrite passes 2c and 10 of engine.cc,
+"""Decomposed LayerNorm as one launch and residual add + LayerNorm fused, through the engine (rewrite passes 2c and 10 of engine_rewrite.cc,
 Planner::fuse_chains).  Launch classes come from api.prof_snapshot(); every knob is read when the model is loaded, so each test sets it in front of
 OrtInfer.  Tolerance, as elsewhere: noise = max |f32 - f64| of the same graph through the oracles, tol = max(16 noise, 2^-19).
 
