@@ -205,10 +205,12 @@ __device__ __forceinline__ void ch_gemm_lds(const ChainOpD& op, const ChView& in
             for (int u = 0; u < 4; ++u) {
                 f32x4 b[MB];
                 const int dt = tap - op.pad;
+                const bool live = g + u < kb1;   // a step past the slice: its weights are zero, and so must its tokens be -- they belong to channels, or to the NEXT tap's row, that
+                                                 // this slice does not cover, and 0 x a non-finite value there would put a NaN into an output whose own window is finite
 #pragma unroll
                 for (int m = 0; m < MB; ++m) {
                     const int row = trow[m] + dt;
-                    const bool ok = (unsigned)row < (unsigned)T;   // outside the sample: the convolution's zero padding / a tile row past T (computed, never stored)
+                    const bool ok = live && (unsigned)row < (unsigned)T;   // outside the sample: the convolution's zero padding / a tile row past T (computed, never stored)
                     const f32x4 v = CH_LDS(ch_lf4, inb + 4u * (unsigned)((ok ? row : 0) * in.ld + c0));
 #pragma unroll
                     for (int e = 0; e < 4; ++e) b[m][e] = ok ? v[e] : 0.f;
@@ -336,7 +338,7 @@ __device__ __forceinline__ void ch_layernorm(const ChainOpD& op, const ChView& x
     for (int row = wave * 4 + (lane >> 4); row < T + 3; row += kWaves * 4) {   // (+3: the lanes of a wave stay together for the DPP steps)
         const bool live = row < T;
         const int xr = (live ? row : T - 1) * x.ld;
-        if (C <= 256 && (C & 3) == 0) {
+        if (C <= 256 && (C & 3) == 0) {   // (= chain_ln_float4, kernels.h)
             float4 xv[4];
             float s = 0.f;
 #pragma unroll
@@ -562,6 +564,8 @@ __global__ __launch_bounds__(kChainThreads) void chain_kernel(const ChainOpD* __
             case CH_GEMM: {
                 const bool has_res = op.res.kind >= 0;
                 const ChView res = ch_view(op.res, op.res_ld, row0, arena, input, lbase);
+                // (kernels.h restates these conditions as chain_gemm_path, chain_ln_float4 and chain_attn_tiles for the name of what ran; routed through them the kernel
+                // compiles to other code -- one register fewer, 1.3 KB more -- so the conditions stay spelled out here and tests/test_chain_cases_cpu.py holds the two to each other)
                 if (in.lds && op.mb == 1 && ((op.K >> 4) + op.ksplit - 1) / op.ksplit < 4) ch_gemm_lds_short(op, in, out, res, has_res, T, lbase, wave, lane);
                 else if (in.lds && op.mb == 1) ch_gemm_lds<1>(op, in, out, res, has_res, T, lbase, wave, lane);
                 else if (in.lds && op.mb == 2) ch_gemm_lds<2>(op, in, out, res, has_res, T, lbase, wave, lane);
@@ -598,11 +602,68 @@ size_t chain_lds_bytes(const ChainOpD& op, int T) {   // scratch at the bottom o
     return 0;
 }
 
+std::string chain_op_token(const ChainOpD& op, int T) {
+    switch (op.type) {
+        case CH_GEMM: {
+            static const char* const kPath[] = {"gs", "g1", "g2", "g3", "gh"};
+            std::string t = kPath[chain_gemm_path(op.in.kind == 3, op.mb, op.K, op.ksplit)];
+            if (op.ksplit > 1) t += "k" + std::to_string(op.ksplit);
+            if (op.res.kind >= 0) t += "r";
+            switch (op.act) {
+                case ACT_NONE: break;
+                case ACT_RELU: t += "R"; break;
+                case ACT_HSWISH: t += "H"; break;
+                case ACT_HSIGMOID: t += "G"; break;
+                case ACT_SIGMOID: t += "S"; break;
+                case ACT_SWISH: t += "W"; break;
+                default: t += "?"; break;
+            }
+            return t;
+        }
+        case CH_LN: return chain_ln_float4(op.N) ? "n4" : "n1";
+        case CH_ATTN: { const int tiles = chain_attn_tiles(T, op.hd); return (tiles ? "a" + std::to_string(tiles) : std::string("aa")) + "d" + std::to_string(op.hd); }
+        case CH_POOL: return "p";
+        default: return "c";
+    }
+}
+
+std::string chain_detail_name(int n_samples, int T, const std::string& sig) {
+    constexpr size_t kFit = 95;   // oar_prof_entry::name holds 96 bytes
+    const std::string head = "chain n=" + std::to_string(n_samples) + " T=" + std::to_string(T);
+    if (head.size() + 1 + sig.size() <= kFit) return head + " " + sig;
+    std::vector<std::pair<std::string, int>> seen;   // distinct tokens in the order of their first appearance
+    for (size_t a = 0; a < sig.size();) {
+        size_t b = sig.find(' ', a);
+        if (b == std::string::npos) b = sig.size();
+        const std::string tok = sig.substr(a, b - a);
+        auto it = std::find_if(seen.begin(), seen.end(), [&](const std::pair<std::string, int>& e) { return e.first == tok; });
+        if (it == seen.end()) seen.push_back({tok, 1}); else ++it->second;
+        a = b + 1;
+    }
+    std::string counted = head;
+    for (const auto& e : seen) counted += " " + e.first + (e.second > 1 ? "x" + std::to_string(e.second) : std::string());
+    if (counted.size() <= kFit) return counted;
+    // the families: the first two letters of a token (a product's path, n4 / n1, a<tiles>), or its one letter
+    std::vector<std::pair<std::string, int>> fam;
+    for (const auto& e : seen) {
+        const std::string f = e.first.substr(0, std::min<size_t>(2, e.first.size()));
+        auto it = std::find_if(fam.begin(), fam.end(), [&](const std::pair<std::string, int>& x) { return x.first == f; });
+        if (it == fam.end()) fam.push_back({f, e.second}); else it->second += e.second;
+    }
+    std::string fams = head + " ~";
+    for (const auto& e : fam) fams += " " + e.first + "x" + std::to_string(e.second);
+    OAR_CHECK(fams.size() <= kFit, OAR_INTERNAL, "chain: the detail name does not fit its buffer");   // (one launch has one T, so at most ten families -- five product paths, n4, n1, one attention form, p, c -- of at most 7 bytes each behind a head of 21)
+    return fams;
+}
+
 void chain_run(hipStream_t s, const ChainLaunch& L, char* arena, const char* input) {
     if (L.n_samples <= 0 || L.T <= 0 || L.n_ops <= 0) return;
     OAR_CHECK(L.lds + 640 <= 160 * 1024 && L.max_hd <= kChainMaxHd, OAR_INTERNAL, "chain: LDS / head size beyond what the planner may fuse");
     OAR_MAX_LDS_ONCE(chain_kernel<kChainMaxHd>, 160 * 1024);
-    ProfScope ps(s, "chain", L.bytes, L.flops, true);
+    const char* cls = "chain";
+    std::string pname;
+    if (Profiler::get().detail) { pname = chain_detail_name(L.n_samples, L.T, L.sig); cls = pname.c_str(); }   // detail names carry the path of every operator
+    ProfScope ps(s, cls, L.bytes, L.flops, true);
     // OAR_CHAIN_DBG=1: per-operator wall-clock stamps of workgroup 0 (100 MHz constant clock), printed after a synchronising read-back
     static const bool dbg_on = [] { const char* e = getenv("OAR_CHAIN_DBG"); return e && atoi(e) != 0; }();
     unsigned long long* dbg = nullptr;

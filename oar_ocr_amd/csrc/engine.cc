@@ -659,6 +659,7 @@ struct Planner {
                 L.tab_l = small_l + (int)((((size_t)small * 4 + 255) & ~(size_t)255) / 4);
                 L.consts = consts->as<float>(); L.small = small; L.total_consts = (int)blob.size(); L.small_l = small_l;
                 L.bytes = bytes; L.flops = flops;
+                for (const auto& d : ops) L.sig += (L.sig.empty() ? "" : " ") + k::chain_op_token(d, (int)T);   // every operator's final in.kind, mb and ksplit are known here
                 const int n_ops = hi - lo;
                 out.push_back([L, table, consts](const RunCtx& c) { k::chain_run(c.s, L, c.arena, reinterpret_cast<const char*>(c.input)); });
                 if (names) out_ops.push_back("chain of " + std::to_string(hi - lo) + " steps from " + P.step_ops[(size_t)lo]);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace oar {
@@ -439,13 +440,39 @@ struct ChainOpD {
     int w_l = -1;                // LN gamma: float offset in LDS, -1 = none
 };
 static_assert(sizeof(ChainOpD) % 4 == 0, "ChainOpD is copied to LDS word by word");
+// The kernel's three device-side choices, restated for the name of what ran: Planner::fuse_chains builds the launch's path signature from them.  The `switch`
+// at the bottom of chain_kernel keeps its own spelling of the same conditions (calling these there changes its generated code), and
+// tests/test_chain_cases_cpu.py reads both sources and holds them, and oar_ocr_amd/synth/chain_cases.py's Python restatement, to each other.
+enum ChainGemmPath : int { CH_G_SHORT = 0, CH_G_LDS1 = 1, CH_G_LDS2 = 2, CH_G_LDS3 = 3, CH_G_HBM = 4 };
+// product: tokens in HBM -> the general path; one token tile per item and a K slice of fewer than four 16-wide steps -> the guarded short loop; else mb tiles per item
+__host__ __device__ inline int chain_gemm_path(bool in_lds, int mb, int K, int ksplit) {
+    if (in_lds && mb == 1 && ((K >> 4) + ksplit - 1) / ksplit < 4) return CH_G_SHORT;
+    if (in_lds && mb == 1) return CH_G_LDS1;
+    if (in_lds && mb == 2) return CH_G_LDS2;
+    if (in_lds) return CH_G_LDS3;
+    return CH_G_HBM;
+}
+// LayerNorm: the row as float4s in registers, or float by float
+__host__ __device__ inline bool chain_ln_float4(int C) { return C <= 256 && (C & 3) == 0; }
+// attention: 1..4 = ch_attention_mfma<token tiles>, 0 = ch_attention_any
+__host__ __device__ inline int chain_attn_tiles(int T, int hd) {
+    if (T <= 64 && (hd & 3) == 0) return T <= 16 ? 1 : T <= 32 ? 2 : T <= 48 ? 3 : 4;
+    return 0;
+}
 struct ChainLaunch {
     const ChainOpD* ops = nullptr; int n_ops = 0, n_samples = 0, T = 0, max_hd = 0;
     size_t lds = 0;              // dynamic LDS: split-K scratch | resident tensors | small constants | operator table
     const float* consts = nullptr; int small = 0, total_consts = 0, small_l = 0;   // constant blob (floats): [0, small) -> LDS at float offset small_l
     int tab_l = 0;               // float offset in LDS of the operator table copy
     double bytes = 0, flops = 0;
+    std::string sig;             // the path of every operator, one token each in table order (chain_op_token), space-separated: the OAR_PROF_DETAIL name
 };
+// One operator's token: products gs / g1 / g2 / g3 / gh (chain_gemm_path) + k<ksplit> when split + r with a residual + the activation's letter
+// (R relu, H hard-swish, G hard-sigmoid, S sigmoid, W swish); LayerNorm n4 / n1; attention a1..a4 / aa + d<head size>; p pool; c copy.
+std::string chain_op_token(const ChainOpD& op, int T);
+// "chain n=.. T=.. <tokens>" for the profiler's 96-byte names: the tokens as a list; where that does not fit, each distinct token once, in the order of its first
+// appearance, with x<count>; where that does not fit either, the count of every token family.  Never truncated.
+std::string chain_detail_name(int n_samples, int T, const std::string& sig);
 constexpr size_t kChainLdsBudget = 159 * 1024;   // LDS a chain may plan with (the launch adds 640 bytes of debug stamps)
 constexpr int kChainMaxHd = 16;   // attention head size the chain kernel is instantiated for (a 32-wide variant spills: wider heads stay unfused)
 inline bool chain_act_ok(int kind) { return kind == ACT_NONE || kind == ACT_RELU || kind == ACT_HSWISH || kind == ACT_HSIGMOID || kind == ACT_SIGMOID || kind == ACT_SWISH; }
