@@ -593,7 +593,7 @@ __global__ __launch_bounds__(256) void pool2d_kernel(PoolP p) {
         int c = (int)(i % p.C); long pix = i / p.C;
         int ow = (int)(pix % p.Wo); long t = pix / p.Wo;
         int oh = (int)(t % p.Ho); long n = t / p.Ho;
-        float acc = p.is_max ? -3.402823466e38f : 0.f;
+        float acc = p.is_max ? -INFINITY : 0.f;   // (a window of -inf only is -inf: ONNX MaxPool, torch max_pool2d)
         int cnt = 0;
         for (int a = 0; a < p.kh; ++a) {
             int ih = oh * p.sh - p.pt + a;
@@ -670,14 +670,20 @@ int global_avgpool_splits(int N, int HW, int C) {
 }
 void global_avgpool(hipStream_t s, const float* x, float* y, int N, int HW, int C, float* partial) {
     if (N == 0 || C == 0) return;
-    char pname[64];
+    const bool vec = (C & 3) == 0 && C / 4 <= 256;
+    const int splits = vec && partial ? global_avgpool_splits(N, HW, C) : 1;
+    char pname[96];
     const char* cls = "global_avgpool";
-    if (Profiler::get().detail) { snprintf(pname, sizeof pname, "global_avgpool N=%d HW=%d C=%d", N, HW, C); cls = pname; }
+    if (Profiler::get().detail) {
+        const int len = vec ? snprintf(pname, sizeof pname, "global_avgpool N=%d HW=%d C=%d splits=%d", N, HW, C, splits)
+                            : snprintf(pname, sizeof pname, "global_avgpool N=%d HW=%d C=%d scalar", N, HW, C);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "global_avgpool: the detail name does not fit its buffer");
+        cls = pname;
+    }
     ProfScope ps(s, cls, 4.0 * (double)N * HW * C, 0.0);
-    if ((C & 3) == 0 && C / 4 <= 256) {
+    if (vec) {
         const int C4 = C / 4, parts = 256 / C4;
         const size_t lds = (size_t)parts * C4 * sizeof(float4);
-        const int splits = partial ? global_avgpool_splits(N, HW, C) : 1;
         if (splits == 1) {
             hipLaunchKernelGGL(global_avgpool_kernel, dim3(N), dim3(256), lds, s, x, y, HW, C, 1, (float)HW);
         } else {
@@ -1086,7 +1092,14 @@ __global__ __launch_bounds__(256) void gemm_batched_kernel(GemmP p) {
 }
 void gemm_batched(hipStream_t s, const GemmP& p) {
     if (p.batch == 0 || p.M == 0 || p.N == 0) return;
-    ProfScope ps(s, "gemm_batched", 4.0 * (double)p.batch * ((double)p.M * p.K + (double)p.K * p.N + (double)p.M * p.N), 2.0 * (double)p.batch * p.M * p.N * p.K);
+    char pname[96];
+    const char* cls = "gemm_batched";
+    if (Profiler::get().detail) {
+        const int len = snprintf(pname, sizeof pname, "gemm_batched b=%d M=%d N=%d K=%d tB=%d", (int)p.batch, (int)p.M, (int)p.N, (int)p.K, p.transB ? 1 : 0);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "gemm_batched: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 4.0 * (double)p.batch * ((double)p.M * p.K + (double)p.K * p.N + (double)p.M * p.N), 2.0 * (double)p.batch * p.M * p.N * p.K);
     dim3 grid((p.N + 63) / 64, (p.M + 63) / 64, p.batch);
     hipLaunchKernelGGL(gemm_batched_kernel, grid, dim3(256), 0, s, p);
 }
@@ -1167,11 +1180,20 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float4* __restr
 }
 void layernorm(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps, const char* prof_class) {
     if (rows == 0) return;
-    ProfScope ps(s, prof_class ? prof_class : "layernorm", 8.0 * (double)rows * C, 8.0 * (double)rows * C);
     static const bool v4 = [] { const char* e = getenv("OAR_LN_V4"); return !e || atoi(e) != 0; }();
     const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0;
-    if (v4 && (C & 3) == 0 && C <= 1024 && aligned) {
-        const int C4 = C / 4, nv = (C4 + 31) / 32;
+    const bool half_wave = v4 && (C & 3) == 0 && C <= 1024 && aligned;
+    const int nv = half_wave ? (C / 4 + 31) / 32 : 0;
+    char pname[96];
+    const char* cls = prof_class ? prof_class : "layernorm";
+    if (Profiler::get().detail) {
+        const int len = half_wave ? snprintf(pname, sizeof pname, "%s v4x%d C=%d", cls, nv <= 4 ? nv : 8, C) : snprintf(pname, sizeof pname, "%s wave C=%d", cls, C);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "layernorm: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 8.0 * (double)rows * C, 8.0 * (double)rows * C);
+    if (half_wave) {
+        const int C4 = C / 4;
         const dim3 grid((unsigned)((rows + 7) / 8));
         const float invC = 1.0f / (float)C;
         auto X = reinterpret_cast<const float4*>(x); auto G = reinterpret_cast<const float4*>(gamma); auto B = reinterpret_cast<const float4*>(beta); auto Y = reinterpret_cast<float4*>(y);
@@ -1266,7 +1288,9 @@ void softmax_argmax(hipStream_t s, const float* logits, int64_t rows, int C, int
     if (rows == 0 || C == 0) return;
     OAR_CHECK((size_t)C * 4 <= 150 * 1024, OAR_UNSUPPORTED_OP, "softmax_argmax: row longer than the LDS staging buffer");
     ProfScope ps(s, "softmax_argmax", 4.0 * (double)rows * C, 4.0 * (double)rows * C);
-    hipLaunchKernelGGL(softmax_argmax_kernel, dim3((unsigned)rows), dim3(256), (size_t)C * sizeof(float), s, logits, C, ld, idx, prob);
+    const size_t lds = (size_t)C * sizeof(float);
+    if (lds > 64 * 1024) OAR_MAX_LDS_ONCE(softmax_argmax_kernel, 150 * 1024);
+    hipLaunchKernelGGL(softmax_argmax_kernel, dim3((unsigned)rows), dim3(256), lds, s, logits, C, ld, idx, prob);
 }
 
 // merges the per-tile softmax partials of the CTC heads' epilogues: 16 lanes per row (round 5: one thread per row left 40 workgroups walking 54 tiles
@@ -1300,11 +1324,20 @@ void ctc_combine(hipStream_t s, const float* part, int64_t rows, int tiles, int6
 
 void softmax_lastdim(hipStream_t s, const float* x, float* y, int64_t rows, int C) {
     if (rows == 0 || C == 0) return;
-    ProfScope ps(s, "softmax", 8.0 * (double)rows * C, 4.0 * (double)rows * C);
+    char pname[96];
+    const char* cls = "softmax";
+    if (Profiler::get().detail) {
+        const int len = snprintf(pname, sizeof pname, C <= 1024 ? "softmax wave C=%d" : "softmax block C=%d", C);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "softmax: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 8.0 * (double)rows * C, 4.0 * (double)rows * C);
     if (C <= 1024) hipLaunchKernelGGL(softmax_wave_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, y, (long)rows, C);
     else {
         OAR_CHECK((size_t)C * 4 <= 150 * 1024, OAR_UNSUPPORTED_OP, "softmax: row longer than the LDS staging buffer");
-        hipLaunchKernelGGL(softmax_block_kernel, dim3((unsigned)rows), dim3(256), (size_t)C * sizeof(float), s, x, y, C);
+        const size_t lds = (size_t)C * sizeof(float);
+        if (lds > 64 * 1024) OAR_MAX_LDS_ONCE(softmax_block_kernel, 150 * 1024);
+        hipLaunchKernelGGL(softmax_block_kernel, dim3((unsigned)rows), dim3(256), lds, s, x, y, C);
     }
 }
 
@@ -1419,7 +1452,14 @@ void se_fc(hipStream_t s, const float* x, const float* w1, const float* b1, Act 
     const int gparts = tiles > 0 ? std::max(1, 256 / (C >> 2)) : 0;
     const size_t lds = (size_t)(C + Cmid + std::max(parts * slice, gparts * C)) * sizeof(float);
     OAR_CHECK(lds <= 64 * 1024, OAR_UNSUPPORTED_OP, "se_fc: vectors exceed LDS");
-    ProfScope ps(s, "se_fc", 4.0 * ((double)N * ((double)C * std::max(tiles, 1) + Cout) + (double)Cmid * (C + Cout)), 2.0 * N * (double)Cmid * (C + Cout));
+    char pname[96];
+    const char* cls = "se_fc";
+    if (Profiler::get().detail) {
+        const int len = snprintf(pname, sizeof pname, "se_fc G=%d slice=%d parts=%d tiles=%d", G, slice, parts, tiles);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "se_fc: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 4.0 * ((double)N * ((double)C * std::max(tiles, 1) + Cout) + (double)Cmid * (C + Cout)), 2.0 * N * (double)Cmid * (C + Cout));
     hipLaunchKernelGGL(se_fc_kernel, dim3((unsigned)N, (unsigned)G), dim3(1024), lds, s, x, w1, b1, act1, w2, b2, act2, y, C, Cmid, Cout, slice, parts, tiles, (float)hw);
 }
 
@@ -1720,8 +1760,16 @@ void attention(hipStream_t s, const float* qkv, float* out, int n, int T, int he
     OAR_CHECK(hd >= 1 && hd <= 64, OAR_UNSUPPORTED_OP, "attention: head_dim must be in 1..=64");
     if (attention_x6_on() && attention_x6_supported(T, heads, hd) && T > 32) return attention_x6(s, qkv, out, n, T, heads, hd, scale);
     const double nh = (double)n * heads;
-    ProfScope ps(s, "attention", 4.0 * nh * T * 4.0 * hd, 4.0 * nh * T * T * hd);
-    if (!attention_whole_head_fits(T, hd)) {
+    const bool whole = attention_whole_head_fits(T, hd);
+    char pname[96];
+    const char* cls = "attention";
+    if (Profiler::get().detail) {
+        const int len = snprintf(pname, sizeof pname, whole ? "attention whole HD=%d T=%d" : "attention stream HD=%d T=%d", hd <= 16 ? 16 : hd <= 32 ? 32 : 64, T);
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "attention: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 4.0 * nh * T * 4.0 * hd, 4.0 * nh * T * T * hd);
+    if (!whole) {
         if (hd <= 16) launch_attention_stream<16>(s, qkv, out, n, T, heads, hd, scale);
         else if (hd <= 32) launch_attention_stream<32>(s, qkv, out, n, T, heads, hd, scale);
         else launch_attention_stream<64>(s, qkv, out, n, T, heads, hd, scale);

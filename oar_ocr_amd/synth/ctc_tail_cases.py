@@ -245,16 +245,20 @@ CASES = (
     Case("r4 K120 V1100 no partials", "R4", 120, 1100, env=_P0),
     Case("r4 K120 V2065 no partials negative", "R4", 120, 2065, family="negative", env=_P0),
     Case("r4 K64 V4113 no partials designed", "R4", 64, 4113, family="designed", env=_P0, **_ONE),
+    Case("r4 K16 V18385", "R4", 16, 18385, family="positive", **_ONE),                      # the PP-OCRv5 mobile vocabulary: 73.5 KB of LDS per row, over 64 KB.  (positive: every
+                                                                                            # column carries 1 / V of the sum; an in-order f32 sum of 18385 `normal` terms is noisier than 2^-16)
     # R5: V % 16 == 0 -> unpadded logits, softmax_argmax(C = ld = V)
     Case("r5 K64 V1104 normal", "R5", 64, 1104),
     Case("r5 K120 V2080 negative", "R5", 120, 2080, family="negative"),
     Case("r5 K48 V2080 designed", "R5", 48, 2080, family="designed", **_ONE),
+    Case("r5 K64 V18400", "R5", 64, 18400, family="positive", **_ONE),
     # R6: K % 4 != 0 -> gemm_batched, softmax_argmax
     Case("r6 K30 V1100 normal", "R6", 30, 1100),
     Case("r6 K67 V2065 negative", "R6", 67, 2065, family="negative"),
     Case("r6 K67 V1104 positive", "R6", 67, 1104, family="positive"),
     Case("r6 K30 V1100 gemm one crop", "R6", 30, 1100, spelling="gemm", **_ONE),
     Case("r6 K67 V4113 designed", "R6", 67, 4113, family="designed"),
+    Case("r6 K30 V18385", "R6", 30, 18385, family="positive", **_ONE),
     # R7: V <= 1024 -> the graph's Softmax, then pp::ctc_argmax
     Case("r7 K64 V97 normal", "R7", 64, 97, seam=True),
     Case("r7 K30 V97 negative", "R7", 30, 97, family="negative", seam=True),
