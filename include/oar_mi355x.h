@@ -816,6 +816,69 @@ oar_status oar_vis_encode(oar_vis* vis, const oar_vis_request* req);
  * launch reads and writes, n_kernels = 7 per layer (8 with the tanh GELU, which is a launch of its own) + 2 (embedding) + 1 (post_layernorm) + 4 (projector). */
 oar_status oar_vis_cost(const oar_vis* vis, int32_t n_images, const int32_t* grids_hw, double* flops, double* bytes, int32_t* n_kernels);
 
+/* ------------------------------------------------------------------------------------------------ VL: the Qwen2-VL and Qwen2.5-VL vision towers
+ * The two vision towers of the oar-ocr-vl crate's backbones (qwen2_vl.rs: MinerU2.5; qwen25_vl.rs: NaviDC-OCR's windowed tower).  Patches come
+ * in MERGE-GROUPED order (hb, wb, mi, mj), a patch's values in (c, tp, dy, dx) order.  Patch Linear without bias and without a position table; 2-D rotary
+ * tables from the patches' own (row, column), head part [row | column]; per block: norm, fused attn.qkv [T][3][heads][dh], attention over segments (the
+ * PaddleOCR-VL tower's kernel, a window being a segment), attn.proj + residual, norm, MLP + residual.
+ *   OAR_QVIS_QWEN2:   LayerNorm (eps 1e-6), fc1 + act + fc2; every block attends over one segment per image.
+ *   OAR_QVIS_QWEN2_5: RMSNorm (eps 1e-6), down(act(gate(x)) up(x)) with biases; the merge units are permuted into window order in front of the blocks, the
+ *                     blocks in fullatt_block_indexes attend over one segment per image and all others over the windows; the merged rows are put back in
+ *                     raster order behind the merger.
+ * Merger: ln_q (LayerNorm / RMSNorm), merge^2 consecutive rows as one, mlp.0 + erf GELU, mlp.2.  Images of one call do not see each other.
+ * Not built: the tokenizer, the chat template, video (t > 1), MinerU's two-step page pipeline, MinerU-Diffusion's decoder and abstractor.              */
+typedef struct oar_qvis oar_qvis;
+typedef enum { OAR_QVIS_QWEN2 = 0, OAR_QVIS_QWEN2_5 = 1 } oar_qvis_kind;
+typedef enum { OAR_QVIS_QUICK_GELU = 0, OAR_QVIS_SILU = 1, OAR_QVIS_GELU_ERF = 2 } oar_qvis_act;
+typedef struct {
+    int32_t kind;                /* oar_qvis_kind                                                                                     */
+    int32_t embed, layers, heads, intermediate, patch, temporal_patch, channels, merge;
+    int32_t out_hidden;          /* the merger's output width (the text model's hidden size)                                          */
+    int32_t act;                 /* oar_qvis_act: the MLP's activation (the merger's is always the erf GELU)                          */
+    int32_t window_size;         /* QWEN2_5: pixels, a positive multiple of merge patch; QWEN2: not read                              */
+    int32_t n_fullatt;           /* QWEN2_5: the number of entries of fullatt_block_indexes                                           */
+    const int32_t* fullatt_block_indexes;   /* each below layers                                                                       */
+    float rope_theta;            /* 10000                                                                                             */
+    int32_t max_tokens;          /* patches per call: the device buffers are allocated once, at create                                */
+    int32_t max_images;          /* 1 .. 16                                                                                           */
+} oar_qvis_cfg;
+/* tensors: the checkpoint's names with the tower's prefix ("visual.") cut off: "patch_embed.proj.weight" [embed, channels temporal_patch patch^2] (a 5-D
+ * weight reshaped), "blocks.{i}.norm{1,2}.weight" (QWEN2: and ".bias"), "blocks.{i}.attn.{qkv,proj}.{weight,bias}" (q / k / v arrive fused, [3 embed, embed]),
+ * QWEN2: "blocks.{i}.mlp.fc{1,2}.{weight,bias}", QWEN2_5: "blocks.{i}.mlp.{gate,up,down}_proj.{weight,bias}" (gate and up are stacked at upload into one
+ * [2 intermediate, embed] Linear), "merger.ln_q.weight" (QWEN2: and ".bias"), "merger.mlp.{0,2}.{weight,bias}".  f32 or bf16; bf16 is widened at upload, so a
+ * bf16 checkpoint computes exactly what its widened values compute.  OAR_INVALID_INPUT: sizes <= 0, embed % heads, a row width that is no multiple of 4,
+ * window_size no positive multiple of merge patch, a full-attention index >= layers, max_images outside 1..16, a missing tensor or one with the wrong shape or
+ * dtype; OAR_UNSUPPORTED_OP: a head size that is no multiple of 8 in 8..80, an unknown act.  All of that is reported before the device is touched. */
+oar_status oar_qvis_create(const oar_qvis_cfg* cfg, const oar_lm_tensor* tensors, int32_t n_tensors, int32_t device_id, oar_qvis** out);
+void oar_qvis_destroy(oar_qvis* vis);
+typedef struct {
+    int32_t n_images;            /* 1 .. cfg.max_images                                                                               */
+    const int32_t* grids;        /* [n_images][2] = (h, w) in patches, each a multiple of cfg.merge; sum h w <= cfg.max_tokens         */
+    const float* pixel_values;   /* [sum h w][channels temporal_patch patch patch], patches in merge-grouped order                    */
+    float* embeds;               /* out [sum h w / merge^2][out_hidden], in raster order of the merged grid                           */
+    float* features;             /* NULL, or out [sum h w][embed]: the last block's output, in the caller's (merge-grouped) order     */
+} oar_qvis_request;
+/* Every argument is checked before anything is launched (OAR_INVALID_INPUT). */
+oar_status oar_qvis_encode(oar_qvis* vis, const oar_qvis_request* req);
+/* Analytic cost of one call: flops = 2 x MACs of the Linears and the attention, bytes = every weight once + the activations each launch reads and writes,
+ * n_kernels = 1 (patch Linear) + layers x per_block + 3 (merger: norm, mlp.0 with the GELU in its epilogue, mlp.2) + (QWEN2_5: 2, the gathers into window
+ * order and back), with per_block = 8 for QWEN2_5 (norm, qkv, attention, proj, norm, stacked gate / up, act(gate) up, down) and for QWEN2 with quick_gelu
+ * (norm, qkv, attention, proj, norm, fc1, act, fc2), 7 for QWEN2 with silu or the erf GELU, which the Linear's epilogue has.                         */
+oar_status oar_qvis_cost(const oar_qvis* vis, int32_t n_images, const int32_t* grids_hw, double* flops, double* bytes, int32_t* n_kernels);
+/* Every argument check of create (without the tensors) and, with n_images > 0, of a request's grids; no device is touched. */
+oar_status oar_qvis_check(const oar_qvis_cfg* cfg, int32_t n_images, const int32_t* grids_hw);
+/* The window plan the QWEN2_5 chain uses (host code): window_index [units] (slot -> source merge unit), reverse_index [units] (its inverse), and the window
+ * segments (seg_start, seg_len in patches; at most `units` of them, units = sum h w / merge^2 being the room each array must have); *n_seg their number.
+ * window_side = window_size / (merge patch) units; partial windows at the right and lower edge; windows without a unit give no segment. */
+oar_status oar_qvis_window_plan(int32_t merge, int32_t patch, int32_t window_size, int32_t n_images, const int32_t* grids_hw, int32_t* window_index,
+                                int32_t* reverse_index, int32_t* seg_start, int32_t* seg_len, int32_t* n_seg);
+/* qvis_misc.hip on host arrays (o_io: in and out, only [o_off, o_off + rows x width) is written; offsets multiples of 4 floats).
+ * rmsnorm: x [rows][d], g [d] -> x / sqrt(mean(x^2) + eps) g.  act: in [rows][f] (gated == 0, run in place on a copy) or [rows][2 f] (gated: act(in[:, :f])
+ * in[:, f:]); in_floats: what `in` holds, at least rows x f x (1 + gated).  row_gather: out[r] = in[idx[r]], rows of row_floats, every idx in [0, n_in_rows). */
+oar_status oar_k_qvis_rmsnorm(const float* x, const float* g, int64_t rows, int32_t d, float eps, float* o_io, size_t o_floats, size_t o_off);
+oar_status oar_k_qvis_act(const float* in, size_t in_floats, int64_t rows, int32_t f, int32_t act, int32_t gated, float* o_io, size_t o_floats, size_t o_off);
+oar_status oar_k_qvis_row_gather(const float* in, int64_t n_in_rows, int32_t row_floats, const int32_t* idx, int64_t n_rows, float* o_io, size_t o_floats, size_t o_off);
+
 /* ------------------------------------------------------------------------------------------------ image decode
  * load_image_from_memory (oar-ocr-core/src/utils/image.rs:65-68: image::load_from_memory + DynamicImage::to_rgb8) for the
  * formats this library decodes itself.  PNG: every colour type / bit depth / interlace mode, to the bytes the image crate

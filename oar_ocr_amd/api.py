@@ -158,6 +158,7 @@ EXPORTS = [
     "oar_lm_set_decode", "oar_lm_decode_stats", "oar_k_lm_decode_attention",
     "oar_lm_generate_ex", "oar_lm_logits_check", "oar_k_lm_select",
     "oar_vis_create", "oar_vis_destroy", "oar_vis_encode", "oar_vis_cost",
+    "oar_qvis_create", "oar_qvis_destroy", "oar_qvis_encode", "oar_qvis_cost", "oar_qvis_check", "oar_qvis_window_plan", "oar_k_qvis_rmsnorm", "oar_k_qvis_act", "oar_k_qvis_row_gather",
 ]
 
 

@@ -10,40 +10,12 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
-#include "engine.h"
-#include "kernels.h"
+#include "vis_common.h"
 
 using namespace oar;
+using namespace oar::vishost;
 
 namespace {
-
-template <typename F>
-oar_status guard(F&& f) {
-    try {
-        f();
-        return OAR_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        set_last_error("host allocation failed");
-        return OAR_OOM;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OAR_INTERNAL;
-    } catch (...) {
-        set_last_error("unknown error");
-        return OAR_INTERNAL;
-    }
-}
-
-struct DevMem {   // one allocation, freed with the model
-    void* p = nullptr;
-    ~DevMem() { if (p) { (void)hipFree(p); (void)hipGetLastError(); } }
-    void alloc(size_t bytes) { OAR_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
-    void upload(const void* src, size_t bytes) { alloc(bytes); OAR_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)); }
-};
 
 void check_cfg(const oar_vis_cfg& c) {
     OAR_CHECK(c.hidden > 0 && c.layers > 0 && c.heads > 0 && c.intermediate > 0 && c.patch > 0 && c.channels > 0 && c.pos_grid > 0 && c.merge > 0 && c.text_hidden > 0,
@@ -60,47 +32,8 @@ void check_cfg(const oar_vis_cfg& c) {
     OAR_CHECK(k::vis_attention_supported(c.heads, c.hidden / c.heads), OAR_UNSUPPORTED_OP, "oar_vis_create: the head size must be a multiple of 8 in 8..80");
 }
 
-struct Table {
-    std::map<std::string, const oar_lm_tensor*> by_name;
-    const oar_lm_tensor& need(const std::string& name, int64_t d0, int64_t d1) const {   // [d0] (d1 < 0) or [d0, d1]
-        auto it = by_name.find(name);
-        OAR_CHECK(it != by_name.end(), OAR_INVALID_INPUT, "oar_vis_create: tensor '" + name + "' is missing");
-        const oar_lm_tensor& t = *it->second;
-        OAR_CHECK(t.data != nullptr, OAR_INVALID_INPUT, "oar_vis_create: tensor '" + name + "' has no data");
-        OAR_CHECK(t.dtype == OAR_LM_F32 || t.dtype == OAR_LM_BF16, OAR_INVALID_INPUT, "oar_vis_create: tensor '" + name + "' is neither f32 nor bf16");
-        const bool ok = d1 < 0 ? (t.rank == 1 && t.dims[0] == d0) : (t.rank == 2 && t.dims[0] == d0 && t.dims[1] == d1);
-        OAR_CHECK(ok, OAR_INVALID_INPUT, "oar_vis_create: tensor '" + name + "' has the wrong shape");
-        return t;
-    }
-};
-
-std::vector<float> widen(const oar_lm_tensor& t, size_t n) {
-    std::vector<float> v(n);
-    if (t.dtype == OAR_LM_F32) std::memcpy(v.data(), t.data, n * 4);
-    else
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t u = (uint32_t) static_cast<const uint16_t*>(t.data)[i] << 16;
-            std::memcpy(&v[i], &u, 4);
-        }
-    return v;
-}
-
-struct Lin {   // y [M][N] = act(x [M][K] W^T + b) (+ residual)
-    const float *w = nullptr, *b = nullptr;
-    int K = 0, N = 0, fmt = 0;
-};
 struct LayerW { const float *ln1g, *ln1b, *ln2g, *ln2b; Lin qkv, out, fc1, fc2; };
 struct LayerT { const oar_lm_tensor *ln1g, *ln1b, *ln2g, *ln2b, *qw, *qb, *kw, *kb, *vw, *vb, *ow, *ob, *f1w, *f1b, *f2w, *f2b; };
-
-void run_linear(hipStream_t s, const Lin& l, const float* x, float* y, int M, int act, const float* residual) {
-    k::ConvP p{};
-    p.w_fmt = l.fmt;
-    p.N = 1; p.H = 1; p.W = M; p.Cin = l.K; p.Ho = 1; p.Wo = M; p.Cout = l.N;
-    p.kh = p.kw = p.sh = p.sw = p.dh = p.dw = 1; p.groups = 1;
-    p.act.kind = act;
-    p.x = x; p.w = l.w; p.bias = l.b; p.residual = residual; p.y = y; p.y_ld = l.N;
-    k::conv_igemm(s, p, "vis_linear");
-}
 
 // grids [n][2] -> the image table; every check of a request's composition
 k::VisGrids check_grids(const oar_vis_cfg& c, int32_t n, const int32_t* grids, const char* who) {
@@ -123,12 +56,11 @@ k::VisGrids check_grids(const oar_vis_cfg& c, int32_t n, const int32_t* grids, c
 
 }  // namespace
 
-struct oar_vis {
+struct oar_vis : VisDevice {
     oar_vis_cfg cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
-    std::vector<std::unique_ptr<DevMem>> mem;
     std::vector<LayerW> layers;
     Lin patch, p1, p2;
     const float *pos_table = nullptr, *postg = nullptr, *postb = nullptr, *preg = nullptr, *preb = nullptr;
@@ -139,35 +71,11 @@ struct oar_vis {
     k::VisTile* tiles = nullptr;
     int max_tiles = 0;
     std::vector<float> inv_freq;   // [dh / 4], f32
-    double weight_bytes = 0;
     ~oar_vis() {
         if (stream) {
             Profiler::get().drop_events();
             (void)hipStreamDestroy(stream);
         }
-    }
-    const float* up(const std::vector<float>& v) {
-        mem.emplace_back(new DevMem());
-        mem.back()->upload(v.data(), v.size() * 4);
-        weight_bytes += 4.0 * v.size();
-        return static_cast<const float*>(mem.back()->p);
-    }
-    template <class T>
-    T* raw(size_t count) {
-        mem.emplace_back(new DevMem());
-        mem.back()->alloc(count * sizeof(T));
-        return static_cast<T*>(mem.back()->p);
-    }
-    // The format is chosen once, from the largest row count the Linear can see, and must then serve EVERY smaller call: bf16x6 weights stay only where
-    // k::igemm_x6_serves_any_rows says so (igemm_weight_format also answers bf16x6 for the output-stationary kernel, which refuses small row counts).
-    Lin linear(const std::vector<float>& w, const std::vector<float>& b, int N, int K, long rows) {
-        Lin l;
-        l.K = K; l.N = N;
-        l.fmt = k::igemm_weight_format(rows, K, N, true);
-        if (l.fmt != k::IGEMM_W_K16 && !(l.fmt == k::IGEMM_W_X6 && k::igemm_x6_serves_any_rows(K, N))) l.fmt = k::IGEMM_W_K16;
-        l.w = up(igemm_to_fragments(l.fmt, w, N, K));
-        l.b = up(b);
-        return l;
     }
 };
 
@@ -177,7 +85,7 @@ oar_status oar_vis_create(const oar_vis_cfg* cfg, const oar_lm_tensor* tensors, 
         *out = nullptr;
         const oar_vis_cfg c = *cfg;
         check_cfg(c);
-        Table T;
+        Table T{"oar_vis_create"};
         for (int32_t i = 0; i < n_tensors; ++i)
             if (tensors[i].name) T.by_name[tensors[i].name] = &tensors[i];
         const int D = c.hidden, L = c.layers, F = c.intermediate, Kp = c.channels * c.patch * c.patch, G = c.pos_grid, m2 = c.merge * c.merge, TH = c.text_hidden, dh = D / c.heads;

@@ -4,7 +4,8 @@ encoder and projector in front of it (vis_attention.hip, vis_host.cc; DESIGN 4.4
 `CausalLM` is PaddleOCR-VL's ERNIE-4.5 text decoder (oar-ocr-vl/src/models/paddleocr_vl/ernie.rs) and, by configuration, the Qwen2-VL
 family's: RMSNorm, M-RoPE, grouped-query attention over a key / value cache, SwiGLU, greedy decoding.  `VisionEncoder` turns patches into
 the decoder's input rows, `preprocess_images` RGB images into patches, `PaddleOCRVL.generate_tokens` images into generated token ids.
-The tokenizer and the chat template are not built: prompts are token ids."""
+`QwenVisionEncoder`, `preprocess_images_qwen` and `QwenVL` are the same for the Qwen2-VL tower (MinerU2.5) and the windowed Qwen2.5-VL tower (NaviDC-OCR)
+of oar-ocr-vl/src/backbones (qvis_misc.hip, qvis_host.cc).  The tokenizer and the chat template are not built: prompts are token ids."""
 from __future__ import annotations
 
 import ctypes as C
@@ -749,6 +750,41 @@ def _widen_rows(table: np.ndarray, ids) -> np.ndarray:
     return np.ascontiguousarray(rows, np.float32)
 
 
+def _generate_from_patches(model, px, grids, prefix_ids, suffix_ids, processors: bool, **gen) -> LMOutput:
+    """What the composite models share behind their preprocessing (model: .vision with cfg.spatial_merge_size / max_images / max_tokens and encode, .lm,
+    .embed_table, .image_token_id, .vision_start_token_id): the images are encoded in calls of at most max_images images and max_tokens patches; one sequence
+    per image, ids = prefix + [image_token_id] x (h w / merge^2) + suffix, its embeddings the table rows with the image span replaced by the encoder's rows,
+    its positions from rope_index; the expanded ids are the processors' history."""
+    vis = model.vision
+    m = vis.cfg.spatial_merge_size
+    n_images = grids.shape[0]
+    kp = px.shape[1]
+    counts = grids[:, 0].astype(np.int64) * grids[:, 1]
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    embeds = [None] * n_images
+    i = 0
+    while i < n_images:                                      # greedy groups: <= 16 images and <= max_tokens patches (a single larger image is refused by the library)
+        j = i + 1
+        while j < n_images and j - i < vis.cfg.max_images and starts[j + 1] - starts[i] <= vis.cfg.max_tokens:
+            j += 1
+        e = vis.encode(px[starts[i]:starts[j]].reshape(-1, kp), grids[i:j])
+        off = 0
+        for n in range(i, j):
+            embeds[n] = e[off:off + counts[n] // (m * m)]
+            off += counts[n] // (m * m)
+        i = j
+    seqs, pos, hist = [], [], []
+    for n in range(n_images):
+        n_img = int(counts[n]) // (m * m)
+        ids = list(prefix_ids) + [model.image_token_id] * n_img + list(suffix_ids)
+        x = _widen_rows(model.embed_table, ids)
+        x[len(prefix_ids):len(prefix_ids) + n_img] = embeds[n]
+        seqs.append(x)
+        hist.append(np.asarray(ids, np.int32))
+        pos.append(rope_index(ids, grids[n:n + 1], model.image_token_id, model.vision_start_token_id, m)[0])
+    return model.lm.generate(inputs_embeds=seqs, position_ids=pos, history_ids=hist if processors else None, **gen)
+
+
 class PaddleOCRVL:
     """Vision encoder + projector + text decoder: images and token-id prompts in, generated token ids out."""
 
@@ -807,33 +843,369 @@ class PaddleOCRVL:
         processors = repetition_penalty != 1.0 or no_repeat_ngram_size != 0
         if schedule == "refill" and (repetition_penalty != 1.0 or no_repeat_ngram_size > 1):
             raise api.OCRError(api.OAR_UNSUPPORTED_OP, "generate_tokens: schedule 'refill' does not run the logits processors")
-        m = self.vision.cfg.spatial_merge_size
         px, grids = preprocess_images(images, self.preproc)
-        kp = px.shape[1]
-        counts = grids[:, 0].astype(np.int64) * grids[:, 1]
-        starts = np.concatenate([[0], np.cumsum(counts)])
-        embeds = [None] * len(images)
-        i = 0
-        while i < len(images):                                   # greedy groups: <= 16 images and <= max_tokens patches (a single larger image is refused by the library)
-            j = i + 1
-            while j < len(images) and j - i < self.vision.cfg.max_images and starts[j + 1] - starts[i] <= self.vision.cfg.max_tokens:
-                j += 1
-            e = self.vision.encode(px[starts[i]:starts[j]].reshape(-1, kp), grids[i:j])
-            off = 0
-            for n in range(i, j):
-                embeds[n] = e[off:off + counts[n] // (m * m)]
-                off += counts[n] // (m * m)
-            i = j
-        seqs, pos, hist = [], [], []
-        for n in range(len(images)):
-            n_img = int(counts[n]) // (m * m)
-            ids = list(prefix_ids) + [self.image_token_id] * n_img + list(suffix_ids)
-            x = _widen_rows(self.embed_table, ids)
-            x[len(prefix_ids):len(prefix_ids) + n_img] = embeds[n]
-            seqs.append(x)
-            hist.append(np.asarray(ids, np.int32))
-            pos.append(rope_index(ids, grids[n:n + 1], self.image_token_id, self.vision_start_token_id, m)[0])
-        return self.lm.generate(inputs_embeds=seqs, position_ids=pos, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
-                                forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
-                                stop_at_eos=stop_at_eos, schedule=schedule, slots=slots, repetition_penalty=repetition_penalty,
-                                no_repeat_ngram_size=no_repeat_ngram_size, history_ids=hist if processors else None)
+        return _generate_from_patches(self, px, grids, prefix_ids, suffix_ids, processors, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
+                                      forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
+                                      stop_at_eos=stop_at_eos, schedule=schedule, slots=slots, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+
+
+# ================================================================================== the Qwen2-VL and Qwen2.5-VL vision towers
+OAR_QVIS_QWEN2, OAR_QVIS_QWEN2_5 = 0, 1
+QVIS_ACTS = {"quick_gelu": 0, "silu": 1, "gelu": 2, "gelu_new": 2, "gelu_pytorch_tanh": 2}   # (the reference implementation maps all three GELU names to the erf form)
+
+
+class QvisCfg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("embed", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("intermediate", C.c_int32), ("patch", C.c_int32),
+                ("temporal_patch", C.c_int32), ("channels", C.c_int32), ("merge", C.c_int32), ("out_hidden", C.c_int32), ("act", C.c_int32), ("window_size", C.c_int32),
+                ("n_fullatt", C.c_int32), ("fullatt_block_indexes", C.POINTER(C.c_int32)), ("rope_theta", C.c_float), ("max_tokens", C.c_int32), ("max_images", C.c_int32)]
+
+
+class QvisRequest(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("grids", C.c_void_p), ("pixel_values", C.c_void_p), ("embeds", C.c_void_p), ("features", C.c_void_p)]
+
+
+_qvis_bound = False
+
+
+def _qvis_lib():
+    global _qvis_bound
+    L = api.lib()
+    if not _qvis_bound:
+        vp = C.c_void_p
+        L.oar_qvis_create.restype = C.c_int
+        L.oar_qvis_create.argtypes = [C.POINTER(QvisCfg), C.POINTER(LmTensor), C.c_int32, C.c_int32, C.POINTER(vp)]
+        L.oar_qvis_destroy.restype = None
+        L.oar_qvis_destroy.argtypes = [vp]
+        L.oar_qvis_encode.restype = C.c_int
+        L.oar_qvis_encode.argtypes = [vp, C.POINTER(QvisRequest)]
+        L.oar_qvis_cost.restype = C.c_int
+        L.oar_qvis_cost.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.oar_qvis_check.restype = C.c_int
+        L.oar_qvis_check.argtypes = [C.POINTER(QvisCfg), C.c_int32, vp]
+        L.oar_qvis_window_plan.restype = C.c_int
+        L.oar_qvis_window_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+        L.oar_k_qvis_rmsnorm.restype = C.c_int
+        L.oar_k_qvis_rmsnorm.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_float, vp, C.c_size_t, C.c_size_t]
+        L.oar_k_qvis_act.restype = C.c_int
+        L.oar_k_qvis_act.argtypes = [vp, C.c_size_t, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_size_t]
+        L.oar_k_qvis_row_gather.restype = C.c_int
+        L.oar_k_qvis_row_gather.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int64, vp, C.c_size_t, C.c_size_t]
+        _qvis_bound = True
+    return L
+
+
+@dataclass
+class QwenVisionConfig:
+    kind: str                          # "qwen2" (MinerU2.5) | "qwen2_5" (the windowed tower of NaviDC-OCR)
+    embed_dim: int
+    depth: int
+    num_heads: int
+    intermediate_size: int
+    patch_size: int
+    out_hidden_size: int               # the text model's hidden size
+    temporal_patch_size: int = 2
+    in_channels: int = 3
+    spatial_merge_size: int = 2
+    hidden_act: str = "quick_gelu"
+    window_size: int = 0               # qwen2_5: pixels
+    fullatt_block_indexes: Sequence[int] = field(default_factory=list)
+    rope_theta: float = 10000.0
+    max_tokens: int = 5120             # patches per call
+    max_images: int = MAX_IMAGES
+
+    @classmethod
+    def from_hf_json(cls, d: dict, text_hidden: int, **overrides) -> "QwenVisionConfig":
+        """`config["vision_config"]`.  The kind follows from the keys: window_size / out_hidden_size / intermediate_size mean qwen2_5 (hidden_size is then the
+        tower's width, hidden_act defaults to silu); embed_dim / mlp_ratio mean qwen2 (intermediate = round(embed_dim mlp_ratio), hidden_size is the TEXT model's
+        width, hidden_act defaults to quick_gelu).  in_chans or in_channels: the channel count."""
+        chans = d.get("in_chans", d.get("in_channels", 3))
+        common = dict(depth=int(d["depth"]), num_heads=int(d["num_heads"]), patch_size=int(d["patch_size"]), temporal_patch_size=int(d.get("temporal_patch_size", 2)),
+                      in_channels=int(3 if chans is None else chans), spatial_merge_size=int(d.get("spatial_merge_size", 2)))
+        if "window_size" in d or "out_hidden_size" in d or "intermediate_size" in d:
+            kw = dict(kind="qwen2_5", embed_dim=int(d["hidden_size"]), intermediate_size=int(d["intermediate_size"]), out_hidden_size=int(d.get("out_hidden_size", text_hidden)),
+                      hidden_act=str(d.get("hidden_act", "silu")), window_size=int(d["window_size"]), fullatt_block_indexes=[int(v) for v in d.get("fullatt_block_indexes", [])])
+        elif "embed_dim" in d and "mlp_ratio" in d:
+            kw = dict(kind="qwen2", embed_dim=int(d["embed_dim"]), intermediate_size=int(round(float(d["embed_dim"]) * float(d["mlp_ratio"]))),
+                      out_hidden_size=int(d.get("hidden_size", text_hidden)), hidden_act=str(d.get("hidden_act", "quick_gelu")))
+        else:
+            raise api.OCRError(api.OAR_INVALID_INPUT, "vision_config has neither the Qwen2.5-VL keys (window_size, out_hidden_size, intermediate_size) nor the Qwen2-VL keys (embed_dim, mlp_ratio)")
+        kw.update(common)
+        kw.update(overrides)
+        return cls(**kw)
+
+    def act_code(self) -> int:
+        code = QVIS_ACTS.get(self.hidden_act)
+        if code is None:
+            raise api.OCRError(api.OAR_UNSUPPORTED_OP, f"unsupported vision hidden_act {self.hidden_act!r}")
+        return code
+
+    def to_c(self, keep: list, act: Optional[int] = None) -> QvisCfg:
+        """keep: receives the array the struct points to"""
+        if self.kind not in ("qwen2", "qwen2_5"):
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"vision kind must be 'qwen2' or 'qwen2_5', got {self.kind!r}")
+        c = QvisCfg()
+        c.kind = OAR_QVIS_QWEN2_5 if self.kind == "qwen2_5" else OAR_QVIS_QWEN2
+        c.embed, c.layers, c.heads, c.intermediate, c.patch, c.temporal_patch = self.embed_dim, self.depth, self.num_heads, self.intermediate_size, self.patch_size, self.temporal_patch_size
+        c.channels, c.merge, c.out_hidden, c.act, c.window_size = self.in_channels, self.spatial_merge_size, self.out_hidden_size, self.act_code() if act is None else act, self.window_size
+        full = np.ascontiguousarray(list(self.fullatt_block_indexes), np.int32)
+        keep.append(full)
+        c.n_fullatt = full.size
+        c.fullatt_block_indexes = full.ctypes.data_as(C.POINTER(C.c_int32)) if full.size else None
+        c.rope_theta, c.max_tokens, c.max_images = self.rope_theta, self.max_tokens, self.max_images
+        return c
+
+    @property
+    def patch_dim(self) -> int:
+        return self.in_channels * self.temporal_patch_size * self.patch_size ** 2
+
+
+def qvis_check(cfg: QwenVisionConfig, grids=None, act: Optional[int] = None):
+    """Every argument check of the library for this configuration (and these grids), without a device; raises OCRError.  act: a raw activation code."""
+    keep = []
+    g = None if grids is None else np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+    ptr = None if g is None else (g if g.size else np.zeros(2, np.int32)).ctypes.data   # (grids given but empty: a request without images, which is refused)
+    api._check(_qvis_lib().oar_qvis_check(C.byref(cfg.to_c(keep, act)), 0 if g is None else g.shape[0], ptr))
+
+
+def qvis_window_plan(grids, merge: int, patch: int, window_size: int):
+    """The library's window plan (host code, no device) -> (window_index, reverse_index, segments [(start, len)] in patches)."""
+    g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+    units = max(int((g[:, 0].astype(np.int64) // max(merge, 1) * (g[:, 1] // max(merge, 1))).sum()), 1) if g.size else 1
+    wi, ri, ss, sl = (np.zeros(units, np.int32) for _ in range(4))
+    n = C.c_int32()
+    api._check(_qvis_lib().oar_qvis_window_plan(merge, patch, window_size, g.shape[0], g.ctypes.data if g.size else None, wi.ctypes.data, ri.ctypes.data, ss.ctypes.data, sl.ctypes.data, C.byref(n)))
+    return wi, ri, [(int(a), int(b)) for a, b in zip(ss[:n.value], sl[:n.value])]
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def k_qvis_rmsnorm(x, g, eps, o_io, o_off):
+    """qvis_misc.hip: x [rows, d], g [d] -> o_io (a flat float32 array, written from o_off on); returns o_io"""
+    x, g = _f32(x), _f32(g)
+    api._check(_qvis_lib().oar_k_qvis_rmsnorm(x.ctypes.data, g.ctypes.data, x.shape[0], x.shape[1], eps, o_io.ctypes.data, o_io.size, o_off))
+    return o_io
+
+
+def k_qvis_act(buf, rows, f, act: str, gated: bool, o_io, o_off):
+    """qvis_misc.hip: buf a flat float32 array that starts with [rows, f] (plain) or [rows, 2 f] (gated) -> o_io from o_off on; returns o_io"""
+    buf = _f32(buf).reshape(-1)
+    api._check(_qvis_lib().oar_k_qvis_act(buf.ctypes.data, buf.size, rows, f, QVIS_ACTS[act], int(gated), o_io.ctypes.data, o_io.size, o_off))
+    return o_io
+
+
+def k_qvis_row_gather(x, idx, o_io, o_off):
+    """qvis_misc.hip: x [n_in, row_floats], idx [n] -> rows x[idx] in o_io from o_off on; returns o_io"""
+    x, idx = _f32(x), np.ascontiguousarray(idx, np.int32).reshape(-1)
+    api._check(_qvis_lib().oar_k_qvis_row_gather(x.ctypes.data, x.shape[0], x.shape[1], idx.ctypes.data, idx.size, o_io.ctypes.data, o_io.size, o_off))
+    return o_io
+
+
+class QwenVisionEncoder:
+    def __init__(self, cfg: QwenVisionConfig, handle):
+        self.cfg, self._h = cfg, handle
+
+    @classmethod
+    def from_state_dict(cls, cfg: QwenVisionConfig, tensors: dict, prefix: str = "visual.", device_id: int = 0) -> "QwenVisionEncoder":
+        """tensors: checkpoint name -> float array, uint16 array (bf16 bits) or torch tensor; the names under `prefix` are taken.  A 5-D patch weight
+        [embed, channels, temporal, patch, patch] is taken as the [embed, channels temporal patch^2] matrix it is."""
+        keep, table = [], []
+        for name, t in tensors.items():
+            if not name.startswith(prefix):
+                continue
+            a, code = _as_table_entry(name, t)
+            name = name[len(prefix):]
+            if name == "patch_embed.proj.weight" and a.ndim > 2:
+                a = a.reshape(a.shape[0], -1)
+            if a.ndim > 4:
+                raise api.OCRError(api.OAR_INVALID_INPUT, f"tensor {prefix}{name} has rank {a.ndim}: the tower has no tensor of a rank above 2 but the patch weight")
+            e = LmTensor()
+            e.name, e.dtype, e.rank, e.data = name.encode(), code, a.ndim, a.ctypes.data
+            for i, v in enumerate(a.shape):
+                e.dims[i] = v
+            keep.append(a)
+            table.append(e)
+        arr = (LmTensor * max(len(table), 1))(*table)
+        h = C.c_void_p()
+        api._check(_qvis_lib().oar_qvis_create(C.byref(cfg.to_c(keep)), arr, len(table), device_id, C.byref(h)))
+        return cls(cfg, h)
+
+    @classmethod
+    def from_dir(cls, path, prefix: str = "visual.", device_id: int = 0, **cfg_overrides) -> "QwenVisionEncoder":
+        path = Path(path)
+        d = json.loads((path / "config.json").read_text())
+        text_hidden = int((d.get("text_config") or {}).get("hidden_size", d.get("hidden_size")))
+        cfg = QwenVisionConfig.from_hf_json(d["vision_config"], text_hidden=text_hidden, **cfg_overrides)
+        files = sorted(path.glob("*.safetensors"))
+        if not files:
+            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
+        tensors = {}
+        for f in files:
+            tensors.update(read_safetensors(f, names=lambda n: n.startswith(prefix)))
+        return cls.from_state_dict(cfg, tensors, prefix=prefix, device_id=device_id)
+
+    def close(self):
+        if self._h:
+            _qvis_lib().oar_qvis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def cost(self, grids):
+        """(flops, bytes, launches) of one call over these grids."""
+        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+        f, b, n = C.c_double(), C.c_double(), C.c_int32()
+        api._check(_qvis_lib().oar_qvis_cost(self._h, g.shape[0], g.ctypes.data if g.size else None, C.byref(f), C.byref(b), C.byref(n)))
+        return f.value, b.value, n.value
+
+    def encode(self, pixel_values, grids, return_features: bool = False):
+        """pixel_values [sum h w, channels temporal p p] in merge-grouped order (preprocess_images_qwen), grids [n, 2] -> embeds [sum h w / merge^2, out_hidden]
+        in raster order of the merged grids (and features [sum h w, embed], the last block's output in the caller's order, when asked for); all images run
+        in ONE call, packed back to back, and do not see each other."""
+        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+        px = np.ascontiguousarray(pixel_values, np.float32)
+        T = int((g[:, 0].astype(np.int64) * g[:, 1]).sum()) if g.size else 0
+        if px.size != T * self.cfg.patch_dim:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"encode: pixel_values hold {px.size} floats, the grids need {T} x {self.cfg.patch_dim}")
+        m2 = self.cfg.spatial_merge_size ** 2
+        emb = np.empty((max(T // m2, 0), self.cfg.out_hidden_size), np.float32)
+        feat = np.empty((T, self.cfg.embed_dim), np.float32) if return_features else None
+        req = QvisRequest()
+        req.n_images, req.grids, req.pixel_values, req.embeds = g.shape[0], g.ctypes.data if g.size else None, px.ctypes.data, emb.ctypes.data
+        req.features = feat.ctypes.data if return_features else None
+        api._check(_qvis_lib().oar_qvis_encode(self._h, C.byref(req)))
+        return (emb, feat) if return_features else emb
+
+
+def patchify_merge_grouped(img_f32: np.ndarray, patch: int, merge: int, temporal: int) -> np.ndarray:
+    """[H, W, C] -> [H/p W/p, C temporal p p]: patches in (hb, wb, mi, mj) order, a patch's values in (c, tp, dy, dx) order with the one frame repeated"""
+    H, W, Cn = img_f32.shape
+    gh, gw = H // patch, W // patch
+    v = img_f32.reshape(gh // merge, merge, patch, gw // merge, merge, patch, Cn).transpose(0, 3, 1, 4, 6, 2, 5)     # hb, wb, mi, mj, c, dy, dx
+    v = np.repeat(v[:, :, :, :, :, None], temporal, 5)                                                               # ..., c, tp, dy, dx
+    return np.ascontiguousarray(v).reshape(gh * gw, Cn * temporal * patch * patch)
+
+
+def preprocess_images_qwen(images, cfg: ImageProcessorConfig, temporal_patch_size: int = 2, max_pixels: Optional[int] = None):
+    """images: [H, W, 3] uint8 RGB arrays -> (pixel_values [sum h w, 3 temporal p p] float32 in merge-grouped order, grids [n, 2] int32 = (h, w) in patches): the
+    resize path of preprocess_images (smart_resize with factor patch merge, the library's exact resize kernel), v * rescale_factor, (v - mean) / std, the frame
+    repeated temporal_patch_size times.  With do_resize an image smaller than one factor is refused, as the reference implementation does."""
+    if len(images) == 0:
+        raise api.OCRError(api.OAR_INVALID_INPUT, "preprocess_images_qwen: no images")
+    p, mg = int(cfg.patch_size), int(cfg.merge_size)
+    factor = p * mg
+    if temporal_patch_size < 1:
+        raise api.OCRError(api.OAR_INVALID_INPUT, "preprocess_images_qwen: temporal_patch_size must be positive")
+    if cfg.resample is None:
+        filt = "catmullrom"
+    else:
+        filt = _PIL_RESAMPLE.get(int(cfg.resample))
+        if filt is None:
+            raise api.OCRError(api.OAR_UNSUPPORTED_OP, f"preprocess_images_qwen: resample code {cfg.resample} has no resize filter here")
+    mean, std = np.asarray(cfg.image_mean, np.float32), np.asarray(cfg.image_std, np.float32)
+    rows, grids = [], []
+    for im in images:
+        im = np.ascontiguousarray(im, np.uint8)
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"preprocess_images_qwen: an image has shape {im.shape}, expected [H, W, 3]")
+        h, w = im.shape[:2]
+        if cfg.do_resize and (h < factor or w < factor):
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"preprocess_images_qwen: height/width must be >= factor {factor}, got {h}x{w}")
+        rh, rw = smart_resize(h, w, factor, cfg.min_pixels, cfg.max_pixels if max_pixels is None else max_pixels) if cfg.do_resize else (h, w)
+        if (rh, rw) != (h, w):
+            im = api.k_resize_filter(im, rw, rh, filt)
+        if rh % p or rw % p:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"preprocess_images_qwen: {rh}x{rw} is not divisible by patch_size={p}")
+        if (rh // p) % mg or (rw // p) % mg:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"preprocess_images_qwen: the grid {rh // p}x{rw // p} is not divisible by merge_size={mg}")
+        v = im.astype(np.float32)
+        if cfg.do_rescale:
+            v = v * np.float32(cfg.rescale_factor)
+        if cfg.do_normalize:
+            v = (v - mean) / std
+        rows.append(patchify_merge_grouped(v, p, mg, int(temporal_patch_size)))
+        grids.append((rh // p, rw // p))
+    return np.concatenate(rows), np.asarray(grids, np.int32).reshape(-1, 2)
+
+
+class QwenVL:
+    """A Qwen2-VL (MinerU2.5) or Qwen2.5-VL (NaviDC-OCR) vision tower + the Qwen2 text decoder: images and token-id prompts in, generated token ids out.
+    generation_defaults: what the checkpoint's generation_config.json says; nothing applies it.  (The reference implementation drives MinerU2.5 with
+    no_repeat_ngram_size = 100 when generation_config.json is silent about it: pass it to generate_tokens to decode as it does.)"""
+
+    def __init__(self, vision: QwenVisionEncoder, lm: CausalLM, embed_table: np.ndarray, preproc: ImageProcessorConfig, image_token_id: int, vision_start_token_id: int):
+        self.vision, self.lm, self.embed_table, self.preproc = vision, lm, embed_table, preproc
+        self.image_token_id, self.vision_start_token_id = int(image_token_id), int(vision_start_token_id)
+        self.generation_defaults: dict = {}
+
+    @classmethod
+    def from_state_dict(cls, cfg_json: dict, preproc_json: dict, tensors: dict, device_id: int = 0, lm_overrides: Optional[dict] = None,
+                        vision_overrides: Optional[dict] = None, vision_prefix: str = "visual.") -> "QwenVL":
+        """Qwen2 attention always has q / k / v biases and config.json does not say so (the reference implementation loads them unconditionally): qkv_bias is
+        set here unless lm_overrides says otherwise."""
+        lm_cfg = CausalLMConfig.from_hf_json(cfg_json, **{"qkv_bias": True, **(lm_overrides or {})})
+        vis_cfg = QwenVisionConfig.from_hf_json(cfg_json["vision_config"], text_hidden=lm_cfg.hidden_size, **(vision_overrides or {}))
+        table, _ = _as_table_entry("model.embed_tokens.weight", tensors["model.embed_tokens.weight"])
+        pj = dict(preproc_json)
+        size = pj.get("size") or {}
+        if "shortest_edge" in size and "longest_edge" in size:   # (the newer spelling of min_pixels / max_pixels, which the reference implementation reads first)
+            pj["min_pixels"], pj["max_pixels"] = int(size["shortest_edge"]), int(size["longest_edge"])
+        preproc = ImageProcessorConfig.from_json(pj)
+        if int(pj.get("temporal_patch_size", vis_cfg.temporal_patch_size)) != vis_cfg.temporal_patch_size:
+            raise api.OCRError(api.OAR_INVALID_INPUT, "the preprocessor's temporal_patch_size differs from the vision tower's")
+        vision = QwenVisionEncoder.from_state_dict(vis_cfg, tensors, prefix=vision_prefix, device_id=device_id)
+        try:
+            lm = CausalLM.from_state_dict(lm_cfg, tensors, device_id=device_id)
+        except Exception:
+            vision.close()
+            raise
+        return cls(vision, lm, table, preproc, cfg_json["image_token_id"], cfg_json["vision_start_token_id"])
+
+    @classmethod
+    def from_dir(cls, path, device_id: int = 0, **kw) -> "QwenVL":
+        path = Path(path)
+        files = sorted(path.glob("*.safetensors"))
+        if not files:
+            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
+        tensors = {}
+        for f in files:
+            tensors.update(read_safetensors(f))
+        m = cls.from_state_dict(json.loads((path / "config.json").read_text()), json.loads((path / "preprocessor_config.json").read_text()), tensors, device_id=device_id, **kw)
+        m.generation_defaults = read_generation_defaults(path)
+        m.lm.generation_defaults = dict(m.generation_defaults)
+        return m
+
+    def close(self):
+        self.vision.close()
+        self.lm.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None,
+                        prefill: str = "rows", prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None,
+                        stop_at_eos: bool = False, schedule: str = "groups", slots: Optional[int] = None, repetition_penalty: float = 1.0,
+                        no_repeat_ngram_size: int = 0) -> LMOutput:
+        """PaddleOCRVL.generate_tokens' arguments and meaning, with this model's preprocessing (preprocess_images_qwen) and tower."""
+        _check_mode_names(prefill, decode_attention)
+        processors = repetition_penalty != 1.0 or no_repeat_ngram_size != 0
+        if schedule == "refill" and (repetition_penalty != 1.0 or no_repeat_ngram_size > 1):
+            raise api.OCRError(api.OAR_UNSUPPORTED_OP, "generate_tokens: schedule 'refill' does not run the logits processors")
+        px, grids = preprocess_images_qwen(images, self.preproc, self.vision.cfg.temporal_patch_size)
+        return _generate_from_patches(self, px, grids, prefix_ids, suffix_ids, processors, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
+                                      forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
+                                      stop_at_eos=stop_at_eos, schedule=schedule, slots=slots, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)

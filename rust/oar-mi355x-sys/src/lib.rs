@@ -42,6 +42,15 @@ pub type oar_vis_act = c_int;
 pub const OAR_VIS_GELU_TANH: oar_vis_act = 0;
 pub const OAR_VIS_GELU_ERF: oar_vis_act = 1;
 
+pub type oar_qvis_kind = c_int;
+pub const OAR_QVIS_QWEN2: oar_qvis_kind = 0;
+pub const OAR_QVIS_QWEN2_5: oar_qvis_kind = 1;
+
+pub type oar_qvis_act = c_int;
+pub const OAR_QVIS_QUICK_GELU: oar_qvis_act = 0;
+pub const OAR_QVIS_SILU: oar_qvis_act = 1;
+pub const OAR_QVIS_GELU_ERF: oar_qvis_act = 2;
+
 pub const OAR_RECT_NATIVE_SIZE: u32 = 0xFFFFFFFF;
 
 #[repr(C)]
@@ -100,6 +109,12 @@ pub struct oar_lm {
 
 #[repr(C)]
 pub struct oar_vis {
+    _private: [u8; 0],
+    _marker: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)>,
+}
+
+#[repr(C)]
+pub struct oar_qvis {
     _private: [u8; 0],
     _marker: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)>,
 }
@@ -432,6 +447,38 @@ pub struct oar_vis_request {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
+pub struct oar_qvis_cfg {
+    pub kind: i32,
+    pub embed: i32,
+    pub layers: i32,
+    pub heads: i32,
+    pub intermediate: i32,
+    pub patch: i32,
+    pub temporal_patch: i32,
+    pub channels: i32,
+    pub merge: i32,
+    pub out_hidden: i32,
+    pub act: i32,
+    pub window_size: i32,
+    pub n_fullatt: i32,
+    pub fullatt_block_indexes: *const i32,
+    pub rope_theta: f32,
+    pub max_tokens: i32,
+    pub max_images: i32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct oar_qvis_request {
+    pub n_images: i32,
+    pub grids: *const i32,
+    pub pixel_values: *const f32,
+    pub embeds: *mut f32,
+    pub features: *mut f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
 pub struct oar_prof_entry {
     pub name: [c_char; 96],
     pub launches: u64,
@@ -558,6 +605,15 @@ unsafe extern "C" {
     pub fn oar_vis_destroy(vis: *mut oar_vis);
     pub fn oar_vis_encode(vis: *mut oar_vis, req: *const oar_vis_request) -> oar_status;
     pub fn oar_vis_cost(vis: *const oar_vis, n_images: i32, grids_hw: *const i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
+    pub fn oar_qvis_create(cfg: *const oar_qvis_cfg, tensors: *const oar_lm_tensor, n_tensors: i32, device_id: i32, out: *mut *mut oar_qvis) -> oar_status;
+    pub fn oar_qvis_destroy(vis: *mut oar_qvis);
+    pub fn oar_qvis_encode(vis: *mut oar_qvis, req: *const oar_qvis_request) -> oar_status;
+    pub fn oar_qvis_cost(vis: *const oar_qvis, n_images: i32, grids_hw: *const i32, flops: *mut f64, bytes: *mut f64, n_kernels: *mut i32) -> oar_status;
+    pub fn oar_qvis_check(cfg: *const oar_qvis_cfg, n_images: i32, grids_hw: *const i32) -> oar_status;
+    pub fn oar_qvis_window_plan(merge: i32, patch: i32, window_size: i32, n_images: i32, grids_hw: *const i32, window_index: *mut i32, reverse_index: *mut i32, seg_start: *mut i32, seg_len: *mut i32, n_seg: *mut i32) -> oar_status;
+    pub fn oar_k_qvis_rmsnorm(x: *const f32, g: *const f32, rows: i64, d: i32, eps: f32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_k_qvis_act(in_: *const f32, in_floats: usize, rows: i64, f: i32, act: i32, gated: i32, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
+    pub fn oar_k_qvis_row_gather(in_: *const f32, n_in_rows: i64, row_floats: i32, idx: *const i32, n_rows: i64, o_io: *mut f32, o_floats: usize, o_off: usize) -> oar_status;
     pub fn oar_image_decode(bytes: *const u8, len: usize, rgb: *mut *mut u8, width: *mut u32, height: *mut u32) -> oar_status;
     pub fn oar_image_free(rgb: *mut u8);
     pub fn oar_image_decode_device(bytes: *const u8, len: usize, device_id: i32, dev_rgb: *mut *mut c_void, width: *mut u32, height: *mut u32) -> oar_status;
