@@ -11,6 +11,7 @@
 #include "engine.h"
 #include "layout.h"
 #include "pipeline.h"
+#include "vis_common.h"
 
 namespace oar {
 const std::string& last_error();
@@ -73,34 +74,11 @@ bool decode_misc(const uint8_t* b, size_t n, std::vector<uint8_t>& rgb, uint32_t
 } }
 
 namespace {
-template <typename F>
-oar_status guard(F&& f) {
-    try {
-        f();
-        return OAR_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        set_last_error("host allocation failed");
-        return OAR_OOM;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OAR_INTERNAL;
-    } catch (...) {
-        set_last_error("unknown error");
-        return OAR_INTERNAL;
-    }
-}
 template <typename T>
 T* cmalloc(size_t n) {
     T* p = (T*)std::malloc(std::max<size_t>(n, 1) * sizeof(T));
     if (!p) throw std::bad_alloc();
     return p;
-}
-void require_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
 }
 void fill_det_result(const std::vector<DetBoxes>& boxes, oar_det_result* out) {
     std::memset(out, 0, sizeof *out);
@@ -870,18 +848,15 @@ oar_status oar_k_resize_filter(const uint8_t* rgb, uint32_t w, uint32_t h, uint3
         std::vector<pp::FilterTaps> tv, th;
         std::vector<float> wv, wh;
         const int mv = host::filter_taps(filter, (int)h, (int)nh, tv, wv), mh = host::filter_taps(filter, (int)w, (int)nw, th, wh);
-        DevBuf din, dout, dtmp, dtv, dwv, dth, dwh;
-        din.reserve((size_t)w * h * 3); dout.reserve((size_t)nw * nh * 3); dtmp.reserve((size_t)nh * w * 12);
-        dtv.reserve(tv.size() * sizeof(pp::FilterTaps)); dwv.reserve(wv.size() * 4); dth.reserve(th.size() * sizeof(pp::FilterTaps)); dwh.reserve(wh.size() * 4);
-        OAR_HIP(hipMemcpy(din.p, rgb, (size_t)w * h * 3, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dtv.p, tv.data(), tv.size() * sizeof(pp::FilterTaps), hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dwv.p, wv.data(), wv.size() * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dth.p, th.data(), th.size() * sizeof(pp::FilterTaps), hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dwh.p, wh.data(), wh.size() * 4, hipMemcpyHostToDevice));
-        pp::resize_filter(nullptr, din.as<uint8_t>(), (int)w, (int)h, dout.as<uint8_t>(), (int)nw, (int)nh, dtv.as<pp::FilterTaps>(), dwv.as<float>(), mv, dth.as<pp::FilterTaps>(),
-                          dwh.as<float>(), mh, dtmp.as<float>());
+        DirectCall dc;
+        const uint8_t* din = dc.in(rgb, (size_t)w * h * 3);
+        const pp::FilterTaps* dtv = dc.in(tv.data(), tv.size() * sizeof(pp::FilterTaps));
+        const float* dwv = dc.in(wv.data(), wv.size() * 4);
+        const pp::FilterTaps* dth = dc.in(th.data(), th.size() * sizeof(pp::FilterTaps));
+        const float* dwh = dc.in(wh.data(), wh.size() * 4);
+        pp::resize_filter(nullptr, din, (int)w, (int)h, dc.out(out, (size_t)nw * nh * 3), (int)nw, (int)nh, dtv, dwv, mv, dth, dwh, mh, dc.scratch<float>((size_t)nh * w * 12));
         OAR_HIP(hipDeviceSynchronize());
-        OAR_HIP(hipMemcpy(out, dout.p, (size_t)nw * nh * 3, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 oar_status oar_k_layout_postprocess(const float* pred, uint32_t n_images, uint32_t rows, uint32_t feat, const float* src_wh, uint32_t num_classes, int32_t model_type,
@@ -974,12 +949,11 @@ oar_status oar_k_rotate_rgb(const uint8_t* rgb, uint32_t w, uint32_t h, int32_t 
         require_device();
         const size_t bytes = (size_t)w * h * 3;
         if (bytes == 0) return;
-        DevBuf a, b;
-        a.reserve(bytes); b.reserve(bytes);
-        OAR_HIP(hipMemcpy(a.p, rgb, bytes, hipMemcpyHostToDevice));
-        pp::rotate_rgb(nullptr, a.as<uint8_t>(), (int)w, (int)h, quarter, b.as<uint8_t>());
+        DirectCall dc;
+        const uint8_t* a = dc.in(rgb, bytes);
+        pp::rotate_rgb(nullptr, a, (int)w, (int)h, quarter, dc.out(out, bytes));
         OAR_HIP(hipDeviceSynchronize());
-        OAR_HIP(hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 oar_status oar_k_bgr_planes_to_rgb(const float* planes, uint64_t plane, float scale, uint8_t* out) {
@@ -987,12 +961,11 @@ oar_status oar_k_bgr_planes_to_rgb(const float* planes, uint64_t plane, float sc
         OAR_CHECK(planes && out, OAR_INVALID_INPUT, "oar_k_bgr_planes_to_rgb: bad arguments");
         require_device();
         if (plane == 0) return;
-        DevBuf a, b;
-        a.reserve(plane * 12); b.reserve(plane * 3);
-        OAR_HIP(hipMemcpy(a.p, planes, plane * 12, hipMemcpyHostToDevice));
-        pp::bgr_planes_to_rgb(nullptr, a.as<float>(), (int64_t)plane, scale, b.as<uint8_t>());
+        DirectCall dc;
+        const float* a = dc.in(planes, plane * 12);
+        pp::bgr_planes_to_rgb(nullptr, a, (int64_t)plane, scale, dc.out(out, plane * 3));
         OAR_HIP(hipDeviceSynchronize());
-        OAR_HIP(hipMemcpy(out, b.p, plane * 3, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 oar_status oar_host_rotate_back_points(float* pts, uint32_t n_points, float angle, uint32_t rotated_w, uint32_t rotated_h) {
@@ -1041,12 +1014,11 @@ oar_status oar_k_normalize(const uint8_t* rgb, uint32_t w, uint32_t h, const int
         OAR_CHECK(rgb && out && src_channels && alpha && beta, OAR_INVALID_INPUT, "oar_k_normalize: bad arguments");
         require_device();
         size_t plane = (size_t)w * h;
-        DevBuf din, dout;
-        din.reserve(plane * 3); dout.reserve(plane * 12);
-        OAR_HIP(hipMemcpy(din.p, rgb, plane * 3, hipMemcpyHostToDevice));
+        DirectCall dc;
+        const uint8_t* din = dc.in(rgb, plane * 3);
         int src[3] = {src_channels[0], src_channels[1], src_channels[2]};
-        pp::normalize(nullptr, din.as<uint8_t>(), dout.as<float>(), 1, (int64_t)plane, src, alpha, beta, hwc_layout ? 1 : 0);
-        OAR_HIP(hipMemcpy(out, dout.p, plane * 12, hipMemcpyDeviceToHost));
+        pp::normalize(nullptr, din, dc.out(out, plane * 12), 1, (int64_t)plane, src, alpha, beta, hwc_layout ? 1 : 0);
+        dc.finish();
     });
 }
 
@@ -1088,11 +1060,10 @@ oar_status oar_k_resize_triangle(const uint8_t* rgb, uint32_t w, uint32_t h, uin
     return guard([&] {
         OAR_CHECK(rgb && out && w && h && nw && nh, OAR_INVALID_INPUT, "oar_k_resize_triangle: bad arguments");
         require_device();
-        DevBuf din, dout;
-        din.reserve((size_t)w * h * 3); dout.reserve((size_t)nw * nh * 3);
-        OAR_HIP(hipMemcpy(din.p, rgb, (size_t)w * h * 3, hipMemcpyHostToDevice));
-        pp::resize_triangle(nullptr, din.as<uint8_t>(), (int)w, (int)h, dout.as<uint8_t>(), (int)nw, (int)nh);
-        OAR_HIP(hipMemcpy(out, dout.p, (size_t)nw * nh * 3, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const uint8_t* din = dc.in(rgb, (size_t)w * h * 3);
+        pp::resize_triangle(nullptr, din, (int)w, (int)h, dc.out(out, (size_t)nw * nh * 3), (int)nw, (int)nh);
+        dc.finish();
     });
 }
 
@@ -1101,11 +1072,10 @@ oar_status oar_k_threshold(const float* pred, size_t n, float thresh, uint8_t* m
         OAR_CHECK((pred && mask) || n == 0, OAR_INVALID_INPUT, "oar_k_threshold: bad arguments");
         require_device();
         if (n == 0) return;
-        DevBuf din, dout;
-        din.reserve(n * 4); dout.reserve(n + 4);
-        OAR_HIP(hipMemcpy(din.p, pred, n * 4, hipMemcpyHostToDevice));
-        pp::threshold(nullptr, din.as<float>(), dout.as<uint8_t>(), (int64_t)n, thresh);
-        OAR_HIP(hipMemcpy(mask, dout.p, n, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const float* din = dc.in(pred, n * 4);
+        pp::threshold(nullptr, din, dc.out(mask, n, n + 4), (int64_t)n, thresh);
+        dc.finish();
     });
 }
 
@@ -1114,11 +1084,10 @@ oar_status oar_k_dilate(const uint8_t* mask, uint32_t height, uint32_t width, ui
         OAR_CHECK(mask && out && height && width, OAR_INVALID_INPUT, "oar_k_dilate: bad arguments");
         require_device();
         const size_t n = (size_t)height * width;
-        DevBuf din, dout;
-        din.reserve(n); dout.reserve(n);
-        OAR_HIP(hipMemcpy(din.p, mask, n, hipMemcpyHostToDevice));
-        pp::dilate3x3(nullptr, din.as<uint8_t>(), dout.as<uint8_t>(), 1, (int)height, (int)width);
-        OAR_HIP(hipMemcpy(out, dout.p, n, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const uint8_t* din = dc.in(mask, n);
+        pp::dilate3x3(nullptr, din, dc.out(out, n), 1, (int)height, (int)width);
+        dc.finish();
     });
 }
 
@@ -1147,12 +1116,11 @@ oar_status oar_k_ctc_argmax(const float* probs, size_t rows, size_t vocab, int64
         require_device();
         if (rows == 0 || vocab == 0) return;  // empty tensor => no entries (decode.rs:465-472)
         OAR_CHECK(probs && idx && prob, OAR_INVALID_INPUT, "oar_k_ctc_argmax: bad arguments");
-        DevBuf din, di, dp;
-        din.reserve(rows * vocab * 4); di.reserve(rows * 8); dp.reserve(rows * 4);
-        OAR_HIP(hipMemcpy(din.p, probs, rows * vocab * 4, hipMemcpyHostToDevice));
-        pp::ctc_argmax(nullptr, din.as<float>(), (int64_t)rows, (int)vocab, di.as<int64_t>(), dp.as<float>());
-        OAR_HIP(hipMemcpy(idx, di.p, rows * 8, hipMemcpyDeviceToHost));
-        OAR_HIP(hipMemcpy(prob, dp.p, rows * 4, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const float* din = dc.in(probs, rows * vocab * 4);
+        int64_t* di = dc.out(idx, rows * 8);
+        pp::ctc_argmax(nullptr, din, (int64_t)rows, (int)vocab, di, dc.out(prob, rows * 4));
+        dc.finish();
     });
 }
 
@@ -1163,12 +1131,11 @@ oar_status oar_k_unclip(const float* boxes, uint32_t n_boxes, float ratio, int32
         if (n_boxes == 0) return;
         std::vector<pp::ScoreBox> sb(n_boxes);
         for (uint32_t i = 0; i < n_boxes; ++i) { std::memcpy(sb[i].pts, boxes + (size_t)i * 8, 32); sb[i].image = 0; sb[i].pad = 0; }
-        DevBuf db, dout;
-        db.reserve(n_boxes * sizeof(pp::ScoreBox)); dout.reserve(n_boxes * sizeof(pp::UnclipOut));
-        OAR_HIP(hipMemcpy(db.p, sb.data(), n_boxes * sizeof(pp::ScoreBox), hipMemcpyHostToDevice));
-        pp::unclip_quads(nullptr, db.as<pp::ScoreBox>(), (int)n_boxes, ratio, dout.as<pp::UnclipOut>());
         std::vector<pp::UnclipOut> ho(n_boxes);
-        OAR_HIP(hipMemcpy(ho.data(), dout.p, n_boxes * sizeof(pp::UnclipOut), hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const pp::ScoreBox* db = dc.in(sb.data(), n_boxes * sizeof(pp::ScoreBox));
+        pp::unclip_quads(nullptr, db, (int)n_boxes, ratio, dc.out(ho.data(), n_boxes * sizeof(pp::UnclipOut)));
+        dc.finish();
         for (uint32_t i = 0; i < n_boxes; ++i) {
             counts[i] = ho[i].n_pts;
             const int m = std::min<int>(std::max(ho[i].n_pts, 0), (int)cap_points);
@@ -1182,14 +1149,13 @@ oar_status oar_k_box_scores(const float* pred, uint32_t height, uint32_t width, 
         if (n_boxes == 0) return;
         OAR_CHECK(pred && boxes && scores && height && width, OAR_INVALID_INPUT, "oar_k_box_scores: bad arguments");
         size_t hw = (size_t)height * width;
-        DevBuf dpred, db, ds;
-        dpred.reserve(hw * 4); db.reserve(n_boxes * sizeof(pp::ScoreBox)); ds.reserve(n_boxes * 4);
         std::vector<pp::ScoreBox> sb(n_boxes);
         for (uint32_t i = 0; i < n_boxes; ++i) { std::memcpy(sb[i].pts, boxes + (size_t)i * 8, 32); sb[i].image = 0; sb[i].pad = 0; }
-        OAR_HIP(hipMemcpy(dpred.p, pred, hw * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(db.p, sb.data(), n_boxes * sizeof(pp::ScoreBox), hipMemcpyHostToDevice));
-        pp::box_scores(nullptr, dpred.as<float>(), (int)height, (int)width, db.as<pp::ScoreBox>(), (int)n_boxes, ds.as<float>());
-        OAR_HIP(hipMemcpy(scores, ds.p, n_boxes * 4, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const float* dpred = dc.in(pred, hw * 4);
+        const pp::ScoreBox* db = dc.in(sb.data(), n_boxes * sizeof(pp::ScoreBox));
+        pp::box_scores(nullptr, dpred, (int)height, (int)width, db, (int)n_boxes, dc.out(scores, (size_t)n_boxes * 4));
+        dc.finish();
     });
 }
 
@@ -1221,11 +1187,7 @@ oar_status oar_k_rotate_crop(const uint8_t* rgb, uint32_t w, uint32_t h, const f
 
 // The two flash-attention kernels on caller-chosen layouts.  Every argument is checked before the device is asked for, so a bad call launches nothing (and
 // answers the same with or without a GPU): null pointers, then the kernel's own shape limits, then alignment and that each view lies inside its buffer.
-// off + (rows - 1) ld + width <= total, with rows, ld, width below 2^31 (the *_supported limits): no product or sum can wrap
-static bool view_fits(size_t off, int64_t rows, int64_t ld, int64_t width, size_t total) {
-    const uint64_t need = (uint64_t)(rows - 1) * (uint64_t)ld + (uint64_t)width;
-    return off <= total && need <= total - off;
-}
+// (view_fits, host_entry.h: off + (rows - 1) ld + width <= total)
 
 oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off, size_t k_off, size_t v_off, int32_t ldq, int32_t ldk, int32_t ldv, int32_t n,
                                int32_t tq, int32_t tk, int32_t heads, int32_t head_dim, float scale, int32_t scale_pre, float* o_io, size_t o_floats, size_t o_off) {
@@ -1240,19 +1202,16 @@ oar_status oar_k_mha_attention(const float* buf, size_t buf_floats, size_t q_off
                   OAR_INVALID_INPUT, "oar_k_mha_attention: a q / k / v view does not fit buf_floats");
         OAR_CHECK(view_fits(o_off, (int64_t)n * tq, D, D, o_floats), OAR_INVALID_INPUT, "oar_k_mha_attention: the output does not fit o_floats");
         require_device();
-        DevBuf din, dout;
-        din.reserve(buf_floats * 4); dout.reserve(o_floats * 4);
-        OAR_HIP(hipMemcpy(din.p, buf, buf_floats * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        DirectCall dc;
+        const float* din = dc.in(buf, buf_floats * 4);
         k::MhaAttnP p{};
-        p.q = din.as<float>() + q_off; p.k = din.as<float>() + k_off; p.v = din.as<float>() + v_off;
-        p.o = dout.as<float>() + o_off;
+        p.q = din + q_off; p.k = din + k_off; p.v = din + v_off;
+        p.o = dc.io(o_io, o_floats) + o_off;
         p.N = n; p.Tq = tq; p.Tk = tk; p.nh = heads; p.dh = head_dim;
         p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
         p.scale = scale; p.scale_pre = scale_pre ? 1 : 0;
         k::mha_attention(nullptr, p);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 
@@ -1275,32 +1234,20 @@ oar_status oar_k_vis_attention(const float* buf, size_t buf_floats, size_t qkv_o
         OAR_CHECK(((qkv_off | o_off) & 3) == 0, OAR_INVALID_INPUT, "oar_k_vis_attention: an offset is no multiple of 4 floats");
         OAR_CHECK(view_fits(qkv_off, T, ld, 3 * D, buf_floats), OAR_INVALID_INPUT, "oar_k_vis_attention: the qkv view does not fit buf_floats");
         OAR_CHECK(view_fits(o_off, T, D, D, o_floats), OAR_INVALID_INPUT, "oar_k_vis_attention: the output does not fit o_floats");
-        const int n_tiles = (int)k::vis_attention_tile_count(seg_lens, n_segs, heads);
-        std::vector<k::VisSeg> segs((size_t)n_segs);
-        std::vector<k::VisTile> tiles((size_t)n_tiles);
-        k::vis_attention_tables(seg_lens, n_segs, heads, segs.data(), tiles.data());
+        vishost::HostTables ht;
+        ht.build(seg_lens, n_segs, heads, head_dim);
         const size_t tab = (size_t)T * (head_dim / 2) * 4;
         require_device();
-        DevBuf din, dout, dcos, dsin, dsegs, dtiles;
-        din.reserve(buf_floats * 4); dout.reserve(o_floats * 4); dcos.reserve(tab); dsin.reserve(tab);
-        dsegs.reserve(segs.size() * sizeof(k::VisSeg)); dtiles.reserve(tiles.size() * sizeof(k::VisTile));
-        OAR_HIP(hipMemcpy(din.p, buf, buf_floats * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dcos.p, cos_tab, tab, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dsin.p, sin_tab, tab, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dsegs.p, segs.data(), segs.size() * sizeof(k::VisSeg), hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dtiles.p, tiles.data(), tiles.size() * sizeof(k::VisTile), hipMemcpyHostToDevice));
+        DirectCall dc;
         k::VisAttnP p{};
-        p.qkv = din.as<float>() + qkv_off; p.cos = dcos.as<float>(); p.sin = dsin.as<float>();
-        p.o = dout.as<float>() + o_off;
-        p.segs = dsegs.as<k::VisSeg>(); p.tiles = dtiles.as<k::VisTile>();
-        p.n_tiles = n_tiles; p.nh = heads; p.dh = head_dim; p.ld = ld;
+        p.qkv = dc.in(buf, buf_floats * 4) + qkv_off;
+        p.o = dc.io(o_io, o_floats) + o_off;
+        p.cos = dc.in(cos_tab, tab); p.sin = dc.in(sin_tab, tab);
+        p.segs = dc.in(ht.segs.data(), ht.segs.size() * sizeof(k::VisSeg)); p.tiles = dc.in(ht.tiles.data(), ht.tiles.size() * sizeof(k::VisTile));
+        p.n_tiles = (int)ht.tiles.size(); p.nh = heads; p.dh = head_dim; p.ld = ld;
         p.scale = (float)std::pow((double)head_dim, -0.5);
-        double bytes = 0.0, flops = 0.0;
-        k::vis_attention_cost(seg_lens, n_segs, heads, head_dim, &bytes, &flops);
-        k::vis_attention(nullptr, p, bytes, flops);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        k::vis_attention(nullptr, p, ht.bytes, ht.flops);
+        dc.finish();
     });
 }
 
@@ -1325,13 +1272,10 @@ oar_status oar_k_vis_pos_embed(const float* table, int32_t pos_grid, int32_t hid
         OAR_CHECK(view_fits(o_off, total, hidden, hidden, o_floats), OAR_INVALID_INPUT, "oar_k_vis_pos_embed: the output does not fit o_floats");
         const size_t tab = (size_t)pos_grid * pos_grid * hidden * 4;
         require_device();
-        DevBuf dt, dout;
-        dt.reserve(tab); dout.reserve(o_floats * 4);
-        OAR_HIP(hipMemcpy(dt.p, table, tab, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
-        k::vis_pos_embed(nullptr, dt.as<float>(), dout.as<float>() + o_off, g, pos_grid, hidden);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const float* dt = dc.in(table, tab);
+        k::vis_pos_embed(nullptr, dt, dc.io(o_io, o_floats) + o_off, g, pos_grid, hidden);
+        dc.finish();
     });
 }
 
@@ -1351,17 +1295,11 @@ oar_status oar_k_add_layernorm(const float* a, const float* b, int64_t b_rows, c
             OAR_CHECK(y_off + cnt <= s_off || s_off + cnt <= y_off, OAR_INVALID_INPUT, "oar_k_add_layernorm: y and the sum overlap");
         }
         require_device();
-        DevBuf da, db, dg, dbe, dout;
-        da.reserve(cnt * 4); db.reserve((size_t)b_rows * C * 4); dout.reserve(o_floats * 4);
-        OAR_HIP(hipMemcpy(da.p, a, cnt * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(db.p, b, (size_t)b_rows * C * 4, hipMemcpyHostToDevice));
-        if (gamma) { dg.reserve((size_t)C * 4); OAR_HIP(hipMemcpy(dg.p, gamma, (size_t)C * 4, hipMemcpyHostToDevice)); }
-        if (beta) { dbe.reserve((size_t)C * 4); OAR_HIP(hipMemcpy(dbe.p, beta, (size_t)C * 4, hipMemcpyHostToDevice)); }
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
-        k::add_layernorm(nullptr, da.as<float>(), db.as<float>(), b_rows, gamma ? dg.as<float>() : nullptr, beta ? dbe.as<float>() : nullptr,
-                         write_sum ? dout.as<float>() + s_off : nullptr, dout.as<float>() + y_off, rows, C, eps);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        DirectCall dc;
+        const float *da = dc.in(a, cnt * 4), *db = dc.in(b, (size_t)b_rows * C * 4), *dg = dc.in(gamma, (size_t)C * 4), *dbe = dc.in(beta, (size_t)C * 4);
+        float* dout = dc.io(o_io, o_floats);
+        k::add_layernorm(nullptr, da, db, b_rows, dg, dbe, write_sum ? dout + s_off : nullptr, dout + y_off, rows, C, eps);
+        dc.finish();
     });
 }
 
@@ -1376,24 +1314,14 @@ oar_status oar_k_relpos_attention(const float* qkv, int32_t b, int32_t h, int32_
         require_device();
         const size_t gh = ws ? ws : h, gw = ws ? ws : w;
         const size_t n_qkv = (size_t)tokens * 3 * (size_t)C, n_rh = gh * head_dim * gh, n_rw = gw * head_dim * gw;
-        DevBuf dqkv, drh, drw, db, dout;
-        dqkv.reserve(n_qkv * 4); drh.reserve(n_rh * 4); drw.reserve(n_rw * 4); dout.reserve(o_floats * 4);
-        OAR_HIP(hipMemcpy(dqkv.p, qkv, n_qkv * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(drh.p, rh, n_rh * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(drw.p, rw, n_rw * 4, hipMemcpyHostToDevice));
-        if (bqkv) {
-            db.reserve((size_t)3 * C * 4);
-            OAR_HIP(hipMemcpy(db.p, bqkv, (size_t)3 * C * 4, hipMemcpyHostToDevice));
-        }
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        DirectCall dc;
         k::RelPosAttnP p{};
-        p.qkv = dqkv.as<float>(); p.rh = drh.as<float>(); p.rw = drw.as<float>(); p.bqkv = bqkv ? db.as<float>() : nullptr;
-        p.o = dout.as<float>() + o_off;
+        p.qkv = dc.in(qkv, n_qkv * 4); p.rh = dc.in(rh, n_rh * 4); p.rw = dc.in(rw, n_rw * 4); p.bqkv = dc.in(bqkv, (size_t)3 * C * 4);
+        p.o = dc.io(o_io, o_floats) + o_off;
         p.B = b; p.H = h; p.W = w; p.ws = ws; p.nh = heads; p.dh = head_dim;
         p.scale = scale; p.scale_pre = scale_pre ? 1 : 0;
         k::relpos_attention(nullptr, p);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 
@@ -1482,8 +1410,7 @@ oar_status oar_k_contours(const uint8_t* mask, uint32_t width, uint32_t height, 
                           int32_t* pts_xy, int32_t* types, int64_t cap_points) {
     return guard([&] {
         OAR_CHECK(mask && width > 0 && height > 0 && n_contours, OAR_INVALID_INPUT, "oar_k_contours: bad arguments");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        require_device();
         DevBuf dm;
         const size_t hw = (size_t)width * height;
         dm.reserve(hw);

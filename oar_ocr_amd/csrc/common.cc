@@ -9,6 +9,18 @@ static thread_local std::string g_last_error;
 void set_last_error(const std::string& m) { g_last_error = m; }
 const std::string& last_error() { return g_last_error; }
 
+int require_device() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+    return n;
+}
+
+void open_device(int device_id, const std::string& range_msg) {
+    const int n = require_device();
+    OAR_CHECK(device_id >= 0 && device_id < n, OAR_DEVICE, range_msg);
+    OAR_HIP(hipSetDevice(device_id));
+}
+
 Profiler& Profiler::get() {
     static Profiler p;
     static bool init = [] { const char* e = getenv("OAR_PROF_DETAIL"); p.detail = e && e[0] == '1'; return true; }();

@@ -56,6 +56,11 @@ struct Error : std::runtime_error {
 
 void set_last_error(const std::string& m);
 
+// The device check of every entry that needs a GPU: OAR_DEVICE where none is visible (the library has no CPU fallback); returns the device count.
+int require_device();
+// require_device, then device_id against the count (OAR_DEVICE with the caller's own message), then hipSetDevice.
+void open_device(int device_id, const std::string& range_msg);
+
 // Growable device buffer (never shrinks).
 struct DevBuf {
     void* p = nullptr;

@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "host_entry.h"
 
 struct oar_ctc_dict {
     std::vector<std::string> chars;   // class i -> UTF-8 bytes of its character; [0] = blank ('\0')
@@ -159,20 +159,12 @@ void positions_word_boxes(const float* pts_xy, uint32_t n_points, const float* p
     }
 }
 
-template <typename F>
-oar_status guarded(F&& f) {
-    try { f(); return OAR_OK; }
-    catch (const oar::Error& e) { oar::set_last_error(e.what()); return e.code; }
-    catch (const std::bad_alloc&) { oar::set_last_error("host allocation failed"); return OAR_OOM; }
-    catch (const std::exception& e) { oar::set_last_error(e.what()); return OAR_INTERNAL; }
-    catch (...) { oar::set_last_error("unknown error"); return OAR_INTERNAL; }
-}
 }  // namespace
 
 extern "C" {
 
 oar_status oar_ctc_dict_create(const char* dict_utf8, size_t len, int32_t use_space_char, oar_ctc_dict** out) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(out && (dict_utf8 || len == 0), OAR_INVALID_INPUT, "oar_ctc_dict_create: bad arguments");
         *out = nullptr;
         std::unique_ptr<oar_ctc_dict> d(new oar_ctc_dict());
@@ -199,7 +191,7 @@ uint32_t oar_ctc_dict_classes(const oar_ctc_dict* d) { return d ? (uint32_t)d->c
 
 oar_status oar_ctc_decode(const oar_ctc_dict* dict, const int64_t* indices, const float* probs, uint32_t batch, uint32_t seq_len,
                           float score_threshold, oar_text_result* out) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(dict && out && (batch == 0 || seq_len == 0 || (indices && probs)), OAR_INVALID_INPUT, "oar_ctc_decode: bad arguments");
         if (seq_len == 0) batch = 0;   // an empty time axis collapses the batch (decode.rs:465-472, test :747-757)
         std::vector<Decoded> seqs(batch);
@@ -210,7 +202,7 @@ oar_status oar_ctc_decode(const oar_ctc_dict* dict, const int64_t* indices, cons
 }
 
 oar_status oar_ocr_decode(const oar_ctc_dict* dict, const oar_ocr_result* res, float score_threshold, oar_text_result* out) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(dict && res && out, OAR_INVALID_INPUT, "oar_ocr_decode: bad arguments");
         // A call's thousand text lines decoded into flat buffers sized from the totals (decode_one + pack gave every line a string and a
         // vector of its own: ~2 200 allocations per call, a third of the 0.3 ms this took); same statements per time step, same outputs.
@@ -270,7 +262,7 @@ oar_status oar_ocr_decode(const oar_ctc_dict* dict, const oar_ocr_result* res, f
 
 oar_status oar_ctc_word_boxes(const float* line_pts_xy, uint32_t n_points, const char* text_utf8, size_t text_len, const uint32_t* col_indices,
                               uint32_t n_cols, uint32_t seq_len, float wh_ratio, float max_wh_ratio, float* boxes, uint32_t cap_boxes, uint32_t* n_boxes) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(n_boxes && (n_points == 0 || line_pts_xy) && (text_len == 0 || text_utf8) && (n_cols == 0 || col_indices), OAR_INVALID_INPUT,
                   "oar_ctc_word_boxes: bad arguments");
         std::vector<float> out;
@@ -284,7 +276,7 @@ oar_status oar_ctc_word_boxes(const float* line_pts_xy, uint32_t n_points, const
 }
 
 oar_status oar_ocr_word_boxes(const oar_ocr_result* res, const oar_text_result* txt, oar_word_boxes* out) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(res && txt && out && res->n_regions == txt->n, OAR_INVALID_INPUT, "oar_ocr_word_boxes: result / text mismatch");
         std::memset(out, 0, sizeof *out);
         const uint32_t n = res->n_regions;
@@ -312,7 +304,7 @@ oar_status oar_ocr_word_boxes(const oar_ocr_result* res, const oar_text_result* 
 
 oar_status oar_char_positions_to_word_boxes(const float* line_pts_xy, uint32_t n_points, const float* char_positions, uint32_t n_positions,
                                             uint32_t char_count, float* boxes, uint32_t cap_boxes, uint32_t* n_boxes) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(n_boxes && (n_points == 0 || line_pts_xy) && (n_positions == 0 || char_positions), OAR_INVALID_INPUT, "oar_char_positions_to_word_boxes: bad arguments");
         std::vector<float> out;
         positions_word_boxes(line_pts_xy, n_points, char_positions, n_positions, char_count, out);
@@ -326,7 +318,7 @@ oar_status oar_char_positions_to_word_boxes(const float* line_pts_xy, uint32_t n
 
 // ---- multi-process hosts (header: "multi-process hosts"): block partition + the wire format of a rank's final results
 oar_status oar_shard_range(uint64_t n_items, uint32_t world_size, uint32_t rank, uint64_t* begin, uint64_t* end) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(begin && end && world_size > 0 && rank < world_size, OAR_INVALID_INPUT, "oar_shard_range: bad world_size / rank");
         const uint64_t base = n_items / world_size, rem = n_items % world_size;
         *begin = (uint64_t)rank * base + std::min<uint64_t>(rank, rem);
@@ -335,7 +327,7 @@ oar_status oar_shard_range(uint64_t n_items, uint32_t world_size, uint32_t rank,
 }
 
 oar_status oar_ocr_pack(const oar_ocr_result* res, const oar_text_result* txt, uint8_t** blob, size_t* len) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(res && txt && blob && len, OAR_INVALID_INPUT, "oar_ocr_pack: bad arguments");
         OAR_CHECK(txt->n == res->n_regions, OAR_SHAPE_MISMATCH, "oar_ocr_pack: the texts do not belong to this result");
         OAR_CHECK(!res->point_offsets, OAR_INVALID_INPUT, "oar_ocr_pack carries quad boxes only");
@@ -361,7 +353,7 @@ oar_status oar_ocr_pack(const oar_ocr_result* res, const oar_text_result* txt, u
 void oar_blob_free(uint8_t* blob) { std::free(blob); }
 
 oar_status oar_packed_merge(const uint8_t* const* blobs, const size_t* lens, uint32_t n_blobs, oar_packed_pages* out) {
-    return guarded([&] {
+    return oar::guard([&] {
         OAR_CHECK(out && (n_blobs == 0 || (blobs && lens)), OAR_INVALID_INPUT, "oar_packed_merge: bad arguments");
         std::memset(out, 0, sizeof *out);
         uint64_t n = 0, nr = 0, nb = 0;

@@ -16,11 +16,7 @@ using k::Act;
 // construction (the load-time graph rewrites it calls: engine_rewrite.cc, engine_loops.cc)
 // =================================================================================================
 Engine::Engine(const uint8_t* onnx, size_t len, int device_id, hipStream_t caller_stream) : device_(device_id) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
-    OAR_CHECK(device_id >= 0 && device_id < ndev, OAR_DEVICE, "device_id out of range");
-    OAR_HIP(hipSetDevice(device_));
+    open_device(device_id, "device_id out of range");
     if (caller_stream) { stream_ = caller_stream; owns_stream_ = false; }   // oar_engine_cfg.stream: the caller's stream, never destroyed here
     else OAR_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     OnnxModel m = parse_onnx(onnx, len);

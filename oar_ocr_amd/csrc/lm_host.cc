@@ -4,15 +4,15 @@
 // (lm_prefill_gemm.hip, lm_prefill_attn.hip) into the same cache, then the chain above takes over with the last positions.
 // Opt-in (oar_lm_set_decode): the steps' attention cut over the keys (lm_decode_split.hip), and a call that stops enqueuing steps once a copy of
 // the device's `alive` word, looked at a fixed number of steps behind the enqueue, says that every sequence has ended.
+// The entry guard, the device check, the tensor table, the allocations and the direct entries' device copies come from host_entry.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "host_entry.h"
 #include "lm_decode.h"
 #include "lm_logits.h"
 #include "lm_prefill.h"
@@ -21,40 +21,6 @@
 using namespace oar;
 
 namespace {
-
-template <typename F>
-oar_status guard(F&& f) {
-    try {
-        f();
-        return OAR_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        set_last_error("host allocation failed");
-        return OAR_OOM;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OAR_INTERNAL;
-    } catch (...) {
-        set_last_error("unknown error");
-        return OAR_INTERNAL;
-    }
-}
-
-float bf16_to_f32(uint16_t v) {
-    const uint32_t u = (uint32_t)v << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-
-struct DevMem {   // one allocation, freed with the model
-    void* p = nullptr;
-    ~DevMem() { if (p) { (void)hipFree(p); (void)hipGetLastError(); } }
-    void alloc(size_t bytes) { OAR_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
-    void upload(const void* src, size_t bytes) { alloc(bytes); OAR_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)); }
-};
 
 void check_cfg(const oar_lm_cfg& c) {
     OAR_CHECK(c.hidden > 0 && c.layers > 0 && c.heads > 0 && c.kv_heads > 0 && c.head_dim > 0 && c.intermediate > 0 && c.vocab >= 2, OAR_INVALID_INPUT,
@@ -70,28 +36,6 @@ void check_cfg(const oar_lm_cfg& c) {
     OAR_CHECK(c.max_positions >= 2 && c.max_positions <= (1 << 20), OAR_INVALID_INPUT, "oar_lm_create: max_positions must be in 2..2^20");
     OAR_CHECK((int64_t)c.heads * c.head_dim < (1 << 24) && c.hidden < (1 << 24) && c.intermediate < (1 << 24) && c.vocab < (1 << 24), OAR_INVALID_INPUT,
               "oar_lm_create: a dimension of 2^24 or more");
-}
-
-struct Table {
-    std::map<std::string, const oar_lm_tensor*> by_name;
-    const oar_lm_tensor& need(const std::string& name, int64_t d0, int64_t d1) const {
-        auto it = by_name.find(name);
-        OAR_CHECK(it != by_name.end(), OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' is missing");
-        const oar_lm_tensor& t = *it->second;
-        OAR_CHECK(t.data != nullptr, OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' has no data");
-        OAR_CHECK(t.dtype == OAR_LM_F32 || t.dtype == OAR_LM_BF16, OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' is neither f32 nor bf16");
-        const bool ok = d1 < 0 ? (t.rank == 1 && t.dims[0] == d0) : (t.rank == 2 && t.dims[0] == d0 && t.dims[1] == d1);
-        OAR_CHECK(ok, OAR_INVALID_INPUT, "oar_lm_create: tensor '" + name + "' has the wrong shape");
-        return t;
-    }
-};
-
-std::vector<float> widen(const oar_lm_tensor& t, size_t n) {
-    std::vector<float> v(n);
-    if (t.dtype == OAR_LM_F32) std::memcpy(v.data(), t.data, n * 4);
-    else
-        for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(static_cast<const uint16_t*>(t.data)[i]);
-    return v;
 }
 
 // Copies row `src_row` of t ([rows][K]) to row `dst_row` of a [.][Kp] matrix of t's own element size (the padding stays zero).
@@ -301,9 +245,7 @@ oar_status oar_lm_create(const oar_lm_cfg* cfg, const oar_lm_tensor* tensors, in
         *out = nullptr;
         const oar_lm_cfg c = *cfg;
         check_cfg(c);
-        Table T;
-        for (int32_t i = 0; i < n_tensors; ++i)
-            if (tensors[i].name) T.by_name[tensors[i].name] = &tensors[i];
+        const Table T("oar_lm_create", tensors, n_tensors);
         const int D = c.hidden, L = c.layers, H = c.heads, KVH = c.kv_heads, dh = c.head_dim, F = c.intermediate, V = c.vocab;
         const int Hd = H * dh, Kd = KVH * dh, Dp = k::lm_pad4(D), Hdp = k::lm_pad4(Hd), Fp = k::lm_pad4(F);
         // every tensor is looked up and checked before the device is touched
@@ -336,10 +278,7 @@ oar_status oar_lm_create(const oar_lm_cfg* cfg, const oar_lm_tensor* tensors, in
         }
         OAR_CHECK(lmw.dtype == wdt, OAR_INVALID_INPUT, "oar_lm_create: lm_head.weight and embed_tokens do not share one dtype");
 
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
-        OAR_CHECK(device_id >= 0 && device_id < ndev, OAR_DEVICE, "oar_lm_create: no such device");
-        OAR_HIP(hipSetDevice(device_id));
+        open_device(device_id, "oar_lm_create: no such device");
         std::unique_ptr<oar_lm> M(new oar_lm());
         M->cfg = c; M->device = device_id; M->bf16 = wdt == OAR_LM_BF16;
         OAR_HIP(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
@@ -939,21 +878,16 @@ oar_status oar_k_lm_gemm(const float* x, int32_t m, int32_t k_, const void* w, i
         OAR_CHECK(m >= 1 && m <= (1 << 21) && n >= 1 && n < (1 << 24) && k_ >= 4 && k_ < (1 << 24), OAR_INVALID_INPUT, "oar_k_lm_gemm: m outside 1..2^21, or n or k outside the limits");
         OAR_CHECK(k_ % 4 == 0, OAR_UNSUPPORTED_OP, "oar_k_lm_gemm: k must be a multiple of 4 (rows are read 16 bytes at a time)");
         const uint64_t out = (uint64_t)m * (uint64_t)n;
-        OAR_CHECK(o_off <= o_floats && out <= o_floats - o_off, OAR_INVALID_INPUT, "oar_k_lm_gemm: the output does not fit o_floats");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        OAR_CHECK(view_fits(o_off, out, o_floats), OAR_INVALID_INPUT, "oar_k_lm_gemm: the output does not fit o_floats");
+        require_device();
         const size_t es = w_dtype == OAR_LM_BF16 ? 2 : 4;
-        DevBuf dx, dw, dout;
-        dx.reserve((size_t)m * k_ * 4); dw.reserve((size_t)n * k_ * es); dout.reserve(o_floats * 4);
-        OAR_HIP(hipMemcpy(dx.p, x, (size_t)m * k_ * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dw.p, w, (size_t)n * k_ * es, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
+        DirectCall dc;
         k::LmGemmP p{};
-        p.mode = k::LM_GEMM_PLAIN; p.bf16 = w_dtype == OAR_LM_BF16; p.M = m; p.N = n; p.K = k_; p.Kp = k_; p.x = dx.as<float>(); p.x_ld = k_; p.w = dw.p;
-        p.y = dout.as<float>() + o_off; p.y_ld = n;
+        p.mode = k::LM_GEMM_PLAIN; p.bf16 = w_dtype == OAR_LM_BF16; p.M = m; p.N = n; p.K = k_; p.Kp = k_; p.x = dc.in(x, (size_t)m * k_ * 4); p.x_ld = k_;
+        p.w = dc.in(w, (size_t)n * k_ * es);
+        p.y = dc.io(o_io, o_floats) + o_off; p.y_ld = n;
         k::lm_gemm(nullptr, p);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 
@@ -975,27 +909,20 @@ oar_status oar_k_lm_prefill_attention(const float* q, const float* kcache, const
         const int64_t Hd = (int64_t)heads * head_dim, n_tiles = k::lm_pf_tile_count(spans.data(), n_seq, heads);
         OAR_CHECK(n_tiles < ((int64_t)1 << 31), OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: workgroup count above 2^31");
         OAR_CHECK((o_off & 3) == 0, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: o_off is no multiple of 4 floats");
-        OAR_CHECK(o_off <= o_floats && (uint64_t)rows * (uint64_t)Hd <= o_floats - o_off, OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: the output does not fit o_floats");
+        OAR_CHECK(view_fits(o_off, (uint64_t)rows * (uint64_t)Hd, o_floats), OAR_INVALID_INPUT, "oar_k_lm_prefill_attention: the output does not fit o_floats");
         std::vector<k::LmPfTile> tiles;
         k::lm_pf_tiles(spans.data(), n_seq, heads, tiles);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        require_device();
         const size_t qb = (size_t)rows * Hd * 4, cb = (size_t)n_seq * kv_heads * max_positions * head_dim * 4;
-        DevBuf dq, dk, dv, dout, dt;
-        dq.reserve(qb); dk.reserve(cb); dv.reserve(cb); dout.reserve(o_floats * 4); dt.reserve(tiles.size() * sizeof(k::LmPfTile));
-        OAR_HIP(hipMemcpy(dq.p, q, qb, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dk.p, kcache, cb, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dv.p, vcache, cb, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dt.p, tiles.data(), tiles.size() * sizeof(k::LmPfTile), hipMemcpyHostToDevice));
+        DirectCall dc;
         k::LmPfAttnP p{};
-        p.q = dq.as<float>(); p.q_ld = (int)Hd; p.kc = dk.as<float>(); p.vc = dv.as<float>(); p.H = heads; p.KVH = kv_heads; p.dh = head_dim; p.maxpos = max_positions;
-        p.scale = 1.0f / sqrtf((float)head_dim); p.o = dout.as<float>() + o_off; p.o_ld = (int)Hd; p.tiles = dt.as<k::LmPfTile>(); p.n_tiles = (int)tiles.size();
+        p.q = dc.in(q, qb); p.q_ld = (int)Hd; p.kc = dc.in(kcache, cb); p.vc = dc.in(vcache, cb); p.H = heads; p.KVH = kv_heads; p.dh = head_dim; p.maxpos = max_positions;
+        p.scale = 1.0f / sqrtf((float)head_dim); p.o = dc.io(o_io, o_floats) + o_off; p.o_ld = (int)Hd;
+        p.tiles = dc.in(tiles.data(), tiles.size() * sizeof(k::LmPfTile)); p.n_tiles = (int)tiles.size();
         double bytes = 0.0, flops = 0.0;
         k::lm_pf_attn_cost(tiles.data(), (int64_t)tiles.size(), head_dim, &bytes, &flops);
         k::lm_prefill_attention(nullptr, p, bytes, flops);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 
@@ -1020,31 +947,19 @@ oar_status oar_k_lm_decode_attention(const float* q, const float* kcache, const 
         st.nrows = n_rows;
         const int64_t Hd = (int64_t)heads * head_dim;
         OAR_CHECK((o_off & 3) == 0, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: o_off is no multiple of 4 floats");
-        OAR_CHECK(o_off <= o_floats && (uint64_t)n_rows * (uint64_t)Hd <= o_floats - o_off, OAR_INVALID_INPUT, "oar_k_lm_decode_attention: the output does not fit o_floats");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        OAR_CHECK(view_fits(o_off, (uint64_t)n_rows * (uint64_t)Hd, o_floats), OAR_INVALID_INPUT, "oar_k_lm_decode_attention: the output does not fit o_floats");
+        require_device();
         const size_t qb = (size_t)n_rows * Hd * 4, cb = (size_t)n_seq * kv_heads * max_positions * head_dim * 4;
         const size_t wsb = split_keys ? k::lm_split_ws_floats(heads, head_dim, max_positions, split_keys) * 4 : 0;
-        DevBuf dq, dk, dv, dout, dst, dal, dws;
-        dq.reserve(qb); dk.reserve(cb); dv.reserve(cb); dout.reserve(o_floats * 4); dst.reserve(sizeof st); dal.reserve(4);
-        OAR_HIP(hipMemcpy(dq.p, q, qb, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dk.p, kcache, cb, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dv.p, vcache, cb, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dout.p, o_io, o_floats * 4, hipMemcpyHostToDevice));
-        OAR_HIP(hipMemcpy(dst.p, &st, sizeof st, hipMemcpyHostToDevice));
-        const int32_t one = 1;
-        OAR_HIP(hipMemcpy(dal.p, &one, 4, hipMemcpyHostToDevice));
-        if (wsb) {
-            dws.reserve(wsb);
-            OAR_HIP(hipMemset(dws.p, 0xFF, wsb));
-        }
-        OAR_HIP(hipDeviceSynchronize());
+        DirectCall dc;
+        const int one = 1;
         k::LmAttnArgs a{};
-        a.st = dst.as<k::LmStep>(); a.q = dq.as<float>(); a.q_ld = (int)Hd; a.kc = dk.as<float>(); a.vc = dv.as<float>(); a.H = heads; a.KVH = kv_heads; a.dh = head_dim;
-        a.maxpos = max_positions; a.o = dout.as<float>() + o_off; a.o_ld = (int)Hd; a.alive = dal.as<int>(); a.ws = dws.as<float>(); a.split_keys = split_keys;
+        a.q = dc.in(q, qb); a.q_ld = (int)Hd; a.kc = dc.in(kcache, cb); a.vc = dc.in(vcache, cb); a.H = heads; a.KVH = kv_heads; a.dh = head_dim;
+        a.maxpos = max_positions; a.o = dc.io(o_io, o_floats) + o_off; a.o_ld = (int)Hd; a.st = dc.in(&st, sizeof st); a.alive = dc.in(&one, 4);
+        a.ws = dc.scratch<float>(wsb, 0xFF); a.split_keys = split_keys;
+        OAR_HIP(hipDeviceSynchronize());
         k::lm_attention(nullptr, a, split_keys ? k::LM_ATTN_SPLIT : k::LM_ATTN_SERIAL, n_rows, false, mp);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        dc.finish();
     });
 }
 
@@ -1071,7 +986,7 @@ oar_status oar_k_lm_select(const float* logits, int32_t n_rows, int32_t vocab, c
         OAR_CHECK(n_rows >= 1 && n_rows <= k::kLmRows, OAR_INVALID_INPUT, fn + ": n_rows outside 1..16");
         OAR_CHECK(vocab >= 2 && vocab < (1 << 24), OAR_INVALID_INPUT, fn + ": vocab outside 2..2^24 - 1");
         check_processors(repetition_penalty, no_repeat_ngram_size, vocab, fn);
-        OAR_CHECK(off <= n_tokens && (size_t)n_rows <= n_tokens - off, OAR_INVALID_INPUT, fn + ": the tokens do not fit n_tokens");
+        OAR_CHECK(view_fits(off, (uint64_t)n_rows, n_tokens), OAR_INVALID_INPUT, fn + ": the tokens do not fit n_tokens");
         std::vector<const int32_t*> ids;
         std::vector<int32_t> hlen;
         k::LmStep st{};
@@ -1087,8 +1002,7 @@ oar_status oar_k_lm_select(const float* logits, int32_t n_rows, int32_t vocab, c
             cap = std::max(cap, (int)H);
         }
         st.nrows = st.nhead = n_rows;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+        require_device();
         const int ld = k::lm_select_ld(vocab), words = k::lm_select_words(vocab);
         std::vector<int32_t> hist;
         std::vector<uint32_t> seen;

@@ -1127,8 +1127,7 @@ std::vector<host::Contour> Detector::trace_device_mask(const uint8_t* d_mask, in
 void Detector::postprocess_host(const float* pred, int H, int W, uint32_t src_w, uint32_t src_h, float thresh, float box_thresh,
                                 float unclip, uint32_t max_candidates, DetBoxes& out, int score_mode, int use_dilation, int box_type) {
     // Stand-alone DB post-processing on a host probability map (parity hook for a7..a12): same kernels, tiny batch.
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
+    require_device();
     const size_t hw = (size_t)H * W;
     DevBuf dpred, dmask, dmask2, dboxes, dscores, dpts;
     dpred.reserve(hw * 4); dmask.reserve(hw);

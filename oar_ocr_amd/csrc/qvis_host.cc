@@ -2,9 +2,9 @@
 // gate / up, packs the matrices in the implicit-GEMM kernel's fragment order, uploads them, and drives one call as a fixed chain of launches over the packed
 // patches of all its images.  C ABI: oar_qvis_create / encode / cost / check / destroy, oar_qvis_window_plan, and the direct entries of qvis_misc.hip.
 // The Linears are k::conv_igemm as 1x1 layers, the LayerNorms k::layernorm, the attention k::vis_attention with one of two (segment, tile) table pairs --
-// windows or images -- and the rest qvis_misc.hip.
+// windows or images -- and the rest qvis_misc.hip.  The entry guard, the device check, the tensor table, the allocations and the direct entries' device
+// copies come from host_entry.h; the stream a tower owns and the table pairs (HostTables / AttnTables) from vis_common.h.
 #include <cmath>
-#include <mutex>
 
 #include "qvis.h"
 #include "qvis_plan.h"
@@ -28,13 +28,6 @@ struct BlockW {
 };
 struct BlockT { const oar_lm_tensor *n1g, *n1b, *n2g, *n2b, *qw, *qb, *pw, *pb, *aw, *ab, *bw, *bb, *dw, *db; };
 
-struct AttnTables {
-    k::VisSeg* segs = nullptr;
-    k::VisTile* tiles = nullptr;
-    int n_tiles = 0;
-    double bytes = 0.0, flops = 0.0;
-};
-
 int per_block(const oar_qvis_cfg& c) { return c.kind == OAR_QVIS_QWEN2 && c.act != OAR_QVIS_QUICK_GELU ? 7 : 8; }
 
 bool is_full(const oar_qvis_cfg& c, const std::vector<int32_t>& fullatt, int layer) {
@@ -47,9 +40,6 @@ bool is_full(const oar_qvis_cfg& c, const std::vector<int32_t>& fullatt, int lay
 struct oar_qvis : VisDevice {
     oar_qvis_cfg cfg{};
     std::vector<int32_t> fullatt;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::mutex mu;
     std::vector<BlockW> blocks;
     Lin patch, m0, m2;
     const float *lng = nullptr, *lnb = nullptr;
@@ -59,30 +49,11 @@ struct oar_qvis : VisDevice {
     AttnTables win, img;
     int max_segs = 0, max_tiles = 0;
     std::vector<float> inv_freq;
-    ~oar_qvis() {
-        if (stream) {
-            Profiler::get().drop_events();
-            (void)hipStreamDestroy(stream);
-        }
-    }
 };
 
 namespace {
 
-// the two table pairs of a call, on the host: lens -> segs, tiles and what one launch over them costs
-struct HostTables {
-    std::vector<k::VisSeg> segs;
-    std::vector<k::VisTile> tiles;
-    double bytes = 0.0, flops = 0.0;
-    void build(const std::vector<int32_t>& lens, int heads, int dh) {
-        segs.resize(lens.size());
-        tiles.resize((size_t)k::vis_attention_tile_count(lens.data(), (int)lens.size(), heads));
-        k::vis_attention_tables(lens.data(), (int)lens.size(), heads, segs.data(), tiles.data());
-        k::vis_attention_cost(lens.data(), (int)lens.size(), heads, dh, &bytes, &flops);
-    }
-};
-
-struct CallPlan {
+struct CallPlan {   // img, win: the two table pairs of a call, on the host
     int T = 0;
     std::vector<int32_t> img_lens;
     qvis::Plan plan;   // QWEN2_5 only
@@ -141,9 +112,7 @@ oar_status oar_qvis_create(const oar_qvis_cfg* cfg, const oar_lm_tensor* tensors
         const bool q25 = c.kind == OAR_QVIS_QWEN2_5;
         std::vector<int32_t> fullatt;
         if (q25) fullatt.assign(c.fullatt_block_indexes, c.fullatt_block_indexes + c.n_fullatt);
-        Table T{"oar_qvis_create"};
-        for (int32_t i = 0; i < n_tensors; ++i)
-            if (tensors[i].name) T.by_name[tensors[i].name] = &tensors[i];
+        const Table T("oar_qvis_create", tensors, n_tensors);
         const int D = c.embed, L = c.layers, F = c.intermediate, Kp = c.channels * c.temporal_patch * c.patch * c.patch, m2 = c.merge * c.merge, OH = c.out_hidden, dh = D / c.heads;
         // every tensor is looked up and checked before the device is touched
         const oar_lm_tensor& pw = T.need("patch_embed.proj.weight", D, Kp);
@@ -172,10 +141,7 @@ oar_status oar_qvis_create(const oar_qvis_cfg* cfg, const oar_lm_tensor* tensors
         const oar_lm_tensor& m2w = T.need("merger.mlp.2.weight", OH, (int64_t)m2 * D);
         const oar_lm_tensor& m2b = T.need("merger.mlp.2.bias", OH, -1);
 
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
-        OAR_CHECK(device_id >= 0 && device_id < ndev, OAR_DEVICE, "oar_qvis_create: no such device");
-        OAR_HIP(hipSetDevice(device_id));
+        open_device(device_id, "oar_qvis_create: no such device");
         std::unique_ptr<oar_qvis> M(new oar_qvis());
         M->fullatt = fullatt;
         c.fullatt_block_indexes = nullptr;   // (the caller's array ends with the call: the copy above is what the model reads)
@@ -216,11 +182,8 @@ oar_status oar_qvis_create(const oar_qvis_cfg* cfg, const oar_lm_tensor* tensors
         // a window holds at least one merge unit, so a call has at most max_tokens / merge^2 window segments; each segment ends with at most one partial tile
         M->max_segs = (int)MU + c.max_images;
         M->max_tiles = c.heads * (int)((MT + k::kFlashQueries - 1) / k::kFlashQueries + (size_t)M->max_segs);
-        for (AttnTables* t : {&M->img, &M->win}) {
-            if (t == &M->win && !q25) continue;
-            t->segs = M->raw<k::VisSeg>((size_t)M->max_segs);
-            t->tiles = M->raw<k::VisTile>((size_t)M->max_tiles);
-        }
+        M->img.alloc(*M, M->max_segs, M->max_tiles);
+        if (q25) M->win.alloc(*M, M->max_segs, M->max_tiles);
         M->inv_freq = qvis::inv_freq_of(dh, c.rope_theta);
         *out = M.release();
     });
@@ -271,14 +234,9 @@ oar_status oar_qvis_encode(oar_qvis* vis, const oar_qvis_request* req) {
         OAR_HIP(hipMemcpyAsync(vis->pix, req->pixel_values, (size_t)T * Kp * 4, hipMemcpyHostToDevice, s));
         OAR_HIP(hipMemcpyAsync(vis->cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, s));
         OAR_HIP(hipMemcpyAsync(vis->sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, s));
-        auto put = [&](AttnTables& dst, const HostTables& src) {
-            OAR_HIP(hipMemcpyAsync(dst.segs, src.segs.data(), src.segs.size() * sizeof(k::VisSeg), hipMemcpyHostToDevice, s));
-            OAR_HIP(hipMemcpyAsync(dst.tiles, src.tiles.data(), src.tiles.size() * sizeof(k::VisTile), hipMemcpyHostToDevice, s));
-            dst.n_tiles = (int)src.tiles.size(); dst.bytes = src.bytes; dst.flops = src.flops;
-        };
-        put(vis->img, p.img);
+        vis->img.put(p.img, s);
         if (q25) {
-            put(vis->win, p.win);
+            vis->win.put(p.win, s);
             OAR_HIP(hipMemcpyAsync(vis->widx, p.plan.window_index.data(), (size_t)U * 4, hipMemcpyHostToDevice, s));
             OAR_HIP(hipMemcpyAsync(vis->ridx, p.plan.reverse_index.data(), (size_t)U * 4, hipMemcpyHostToDevice, s));
         }
@@ -339,28 +297,16 @@ oar_status oar_qvis_encode(oar_qvis* vis, const oar_qvis_request* req) {
 }
 
 // ------------------------------------------------------------------------------------------------ qvis_misc.hip on host arrays
-namespace {
-
-bool view_fits(size_t off, uint64_t count, size_t total) { return off <= total && count <= total - off; }
-
-void need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
-}
-
-}  // namespace
-
 oar_status oar_k_qvis_rmsnorm(const float* x, const float* g, int64_t rows, int32_t d, float eps, float* o_io, size_t o_floats, size_t o_off) {
     return guard([&] {
         OAR_CHECK(x && g && o_io, OAR_INVALID_INPUT, "oar_k_qvis_rmsnorm: null buffer");
         OAR_CHECK(rows >= 1 && rows < (1 << 24) && d >= 4 && d % 4 == 0 && d < (1 << 20) && eps >= 0.0f, OAR_INVALID_INPUT, "oar_k_qvis_rmsnorm: rows outside 1..2^24, d no multiple of 4 or negative eps");
         OAR_CHECK((o_off & 3) == 0 && view_fits(o_off, (uint64_t)rows * d, o_floats), OAR_INVALID_INPUT, "oar_k_qvis_rmsnorm: o_off is no multiple of 4 floats or the output does not fit o_floats");
-        need_device();
-        DevMem dx, dg, dout;
-        dx.upload(x, (size_t)rows * d * 4); dg.upload(g, (size_t)d * 4); dout.upload(o_io, o_floats * 4);
-        k::qvis_rmsnorm(nullptr, static_cast<const float*>(dx.p), static_cast<const float*>(dg.p), static_cast<float*>(dout.p) + o_off, rows, d, eps);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        require_device();
+        DirectCall dc;
+        const float *dx = dc.in(x, (size_t)rows * d * 4), *dg = dc.in(g, (size_t)d * 4);
+        k::qvis_rmsnorm(nullptr, dx, dg, dc.io(o_io, o_floats) + o_off, rows, d, eps);
+        dc.finish();
     });
 }
 
@@ -372,7 +318,7 @@ oar_status oar_k_qvis_act(const float* in, size_t in_floats, int64_t rows, int32
         const uint64_t width = (uint64_t)f * (gated ? 2 : 1);
         OAR_CHECK(view_fits(0, (uint64_t)rows * width, in_floats), OAR_INVALID_INPUT, "oar_k_qvis_act: in_floats is below rows x f (x 2 when gated)");
         OAR_CHECK((o_off & 3) == 0 && view_fits(o_off, (uint64_t)rows * f, o_floats), OAR_INVALID_INPUT, "oar_k_qvis_act: o_off is no multiple of 4 floats or the output does not fit o_floats");
-        need_device();
+        require_device();
         DevMem din, dout;
         din.upload(in, in_floats * 4); dout.upload(o_io, o_floats * 4);
         float* o = static_cast<float*>(dout.p) + o_off;
@@ -393,11 +339,11 @@ oar_status oar_k_qvis_row_gather(const float* in, int64_t n_in_rows, int32_t row
                   "oar_k_qvis_row_gather: row counts outside 1..2^24 or row_floats no multiple of 4");
         for (int64_t r = 0; r < n_rows; ++r) OAR_CHECK(idx[r] >= 0 && idx[r] < n_in_rows, OAR_INVALID_INPUT, "oar_k_qvis_row_gather: an index outside the input rows");
         OAR_CHECK((o_off & 3) == 0 && view_fits(o_off, (uint64_t)n_rows * row_floats, o_floats), OAR_INVALID_INPUT, "oar_k_qvis_row_gather: o_off is no multiple of 4 floats or the output does not fit o_floats");
-        need_device();
-        DevMem din, didx, dout;
-        din.upload(in, (size_t)n_in_rows * row_floats * 4); didx.upload(idx, (size_t)n_rows * 4); dout.upload(o_io, o_floats * 4);
-        k::qvis_row_gather(nullptr, static_cast<const float*>(din.p), static_cast<const int32_t*>(didx.p), static_cast<float*>(dout.p) + o_off, n_rows, n_in_rows, row_floats);
-        OAR_HIP(hipGetLastError());
-        OAR_HIP(hipMemcpy(o_io, dout.p, o_floats * 4, hipMemcpyDeviceToHost));
+        require_device();
+        DirectCall dc;
+        const float* din = dc.in(in, (size_t)n_in_rows * row_floats * 4);
+        const int32_t* didx = dc.in(idx, (size_t)n_rows * 4);
+        k::qvis_row_gather(nullptr, din, didx, dc.io(o_io, o_floats) + o_off, n_rows, n_in_rows, row_floats);
+        dc.finish();
     });
 }

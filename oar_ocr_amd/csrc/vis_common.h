@@ -1,73 +1,15 @@
-// vis_common.h -- what the hosts of the vision towers share (vis_host.cc: PaddleOCR-VL; qvis_host.cc: Qwen2-VL / Qwen2.5-VL):
-// the error guard of a C entry, the device allocations a model owns, the checkpoint's tensor table, bf16 widening, and a Linear as a 1x1 implicit GEMM with
-// its weights packed once in the kernel's fragment order.
+// vis_common.h -- what is specific to the hosts of the vision towers (vis_host.cc: PaddleOCR-VL; qvis_host.cc: Qwen2-VL / Qwen2.5-VL)
+// on top of host_entry.h: a Linear as a 1x1 implicit GEMM with its weights packed once in the kernel's fragment order, the device, stream and allocations one
+// tower owns, and the (segment, tile) tables of k::vis_attention -- built from segment lengths on the host, kept in the model's buffers on the device.
 #pragma once
-#include <algorithm>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <string>
-#include <vector>
+#include <mutex>
 
-#include "common.h"
 #include "engine.h"
+#include "host_entry.h"
 #include "kernels.h"
 
 namespace oar {
 namespace vishost {
-
-template <typename F>
-oar_status guard(F&& f) {
-    try {
-        f();
-        return OAR_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        set_last_error("host allocation failed");
-        return OAR_OOM;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OAR_INTERNAL;
-    } catch (...) {
-        set_last_error("unknown error");
-        return OAR_INTERNAL;
-    }
-}
-
-struct DevMem {   // one allocation, freed with the model
-    void* p = nullptr;
-    ~DevMem() { if (p) { (void)hipFree(p); (void)hipGetLastError(); } }
-    void alloc(size_t bytes) { OAR_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
-    void upload(const void* src, size_t bytes) { alloc(bytes); OAR_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)); }
-};
-
-struct Table {
-    std::string who;   // the entry the messages name
-    std::map<std::string, const oar_lm_tensor*> by_name;
-    const oar_lm_tensor& need(const std::string& name, int64_t d0, int64_t d1) const {   // [d0] (d1 < 0) or [d0, d1]
-        auto it = by_name.find(name);
-        OAR_CHECK(it != by_name.end(), OAR_INVALID_INPUT, who + ": tensor '" + name + "' is missing");
-        const oar_lm_tensor& t = *it->second;
-        OAR_CHECK(t.data != nullptr, OAR_INVALID_INPUT, who + ": tensor '" + name + "' has no data");
-        OAR_CHECK(t.dtype == OAR_LM_F32 || t.dtype == OAR_LM_BF16, OAR_INVALID_INPUT, who + ": tensor '" + name + "' is neither f32 nor bf16");
-        const bool ok = d1 < 0 ? (t.rank == 1 && t.dims[0] == d0) : (t.rank == 2 && t.dims[0] == d0 && t.dims[1] == d1);
-        OAR_CHECK(ok, OAR_INVALID_INPUT, who + ": tensor '" + name + "' has the wrong shape");
-        return t;
-    }
-};
-
-inline std::vector<float> widen(const oar_lm_tensor& t, size_t n) {
-    std::vector<float> v(n);
-    if (t.dtype == OAR_LM_F32) std::memcpy(v.data(), t.data, n * 4);
-    else
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t u = (uint32_t) static_cast<const uint16_t*>(t.data)[i] << 16;
-            std::memcpy(&v[i], &u, 4);
-        }
-    return v;
-}
 
 struct Lin {   // y [M][N] = act(x [M][K] W^T + b) (+ residual)
     const float *w = nullptr, *b = nullptr;
@@ -84,9 +26,18 @@ inline void run_linear(hipStream_t s, const Lin& l, const float* x, float* y, in
     k::conv_igemm(s, p, prof_class);
 }
 
-struct VisDevice {   // the allocations of one model
+struct VisDevice {   // the device, the stream and the allocations of one model
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
     std::vector<std::unique_ptr<DevMem>> mem;
     double weight_bytes = 0;
+    ~VisDevice() {
+        if (stream) {
+            Profiler::get().drop_events();
+            (void)hipStreamDestroy(stream);
+        }
+    }
     const float* up(const std::vector<float>& v) {
         mem.emplace_back(new DevMem());
         mem.back()->upload(v.data(), v.size() * 4);
@@ -109,6 +60,37 @@ struct VisDevice {   // the allocations of one model
         l.w = up(igemm_to_fragments(l.fmt, w, N, K));
         l.b = up(b);
         return l;
+    }
+};
+
+// lens -> the segments and query tiles of one k::vis_attention launch over them, and what that launch costs
+struct HostTables {
+    std::vector<k::VisSeg> segs;
+    std::vector<k::VisTile> tiles;
+    double bytes = 0.0, flops = 0.0;
+    void build(const int32_t* lens, int n, int heads, int dh) {
+        segs.resize((size_t)n);
+        tiles.resize((size_t)k::vis_attention_tile_count(lens, n, heads));
+        k::vis_attention_tables(lens, n, heads, segs.data(), tiles.data());
+        k::vis_attention_cost(lens, n, heads, dh, &bytes, &flops);
+    }
+    void build(const std::vector<int32_t>& lens, int heads, int dh) { build(lens.data(), (int)lens.size(), heads, dh); }
+};
+
+// the device half: a model's buffers for one table pair and the pair a call put there
+struct AttnTables {
+    k::VisSeg* segs = nullptr;
+    k::VisTile* tiles = nullptr;
+    int n_tiles = 0;
+    double bytes = 0.0, flops = 0.0;
+    void alloc(VisDevice& dev, int max_segs, int max_tiles) {
+        segs = dev.raw<k::VisSeg>((size_t)max_segs);
+        tiles = dev.raw<k::VisTile>((size_t)max_tiles);
+    }
+    void put(const HostTables& src, hipStream_t s) {   // (pageable sources: the caller synchronises before src goes)
+        OAR_HIP(hipMemcpyAsync(segs, src.segs.data(), src.segs.size() * sizeof(k::VisSeg), hipMemcpyHostToDevice, s));
+        OAR_HIP(hipMemcpyAsync(tiles, src.tiles.data(), src.tiles.size() * sizeof(k::VisTile), hipMemcpyHostToDevice, s));
+        n_tiles = (int)src.tiles.size(); bytes = src.bytes; flops = src.flops;
     }
 };
 

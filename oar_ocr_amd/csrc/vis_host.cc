@@ -1,12 +1,11 @@
 // vis_host.cc -- host side of the PaddleOCR-VL vision encoder and projector: checks a checkpoint's tensor table, stacks q / k / v, packs the
 // matrices in the implicit-GEMM kernel's fragment order, uploads them, and drives one call as a fixed chain of launches over the packed patches of all its
 // images.  C ABI: oar_vis_create / oar_vis_encode / oar_vis_cost / oar_vis_destroy.  The Linears are k::conv_igemm as 1x1 layers (bias, GELU and residual in
-// the epilogue), the LayerNorms k::layernorm, the attention k::vis_attention (vis_attention.hip), the rest vis_misc.hip.
+// the epilogue), the LayerNorms k::layernorm, the attention k::vis_attention (vis_attention.hip), the rest vis_misc.hip.  The entry guard, the device check,
+// the tensor table and the allocations come from host_entry.h; the stream a tower owns and its attention tables from vis_common.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -54,29 +53,28 @@ k::VisGrids check_grids(const oar_vis_cfg& c, int32_t n, const int32_t* grids, c
     return g;
 }
 
+// the attention tables of a call: one segment per image
+HostTables grid_tables(const k::VisGrids& g, int heads, int dh) {
+    std::vector<int32_t> lens((size_t)g.n);
+    for (int i = 0; i < g.n; ++i) lens[(size_t)i] = g.h[i] * g.w[i];
+    HostTables t;
+    t.build(lens, heads, dh);
+    return t;
+}
+
 }  // namespace
 
 struct oar_vis : VisDevice {
     oar_vis_cfg cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::mutex mu;
     std::vector<LayerW> layers;
     Lin patch, p1, p2;
     const float *pos_table = nullptr, *postg = nullptr, *postb = nullptr, *preg = nullptr, *preb = nullptr;
     // per-call buffers, sized for max_tokens at create
     float *pix = nullptr, *pos = nullptr, *x = nullptr, *x2 = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *h = nullptr, *merged = nullptr, *ph = nullptr, *emb = nullptr;
     float *cos = nullptr, *sin = nullptr;
-    k::VisSeg* segs = nullptr;
-    k::VisTile* tiles = nullptr;
+    AttnTables att_tab;
     int max_tiles = 0;
     std::vector<float> inv_freq;   // [dh / 4], f32
-    ~oar_vis() {
-        if (stream) {
-            Profiler::get().drop_events();
-            (void)hipStreamDestroy(stream);
-        }
-    }
 };
 
 oar_status oar_vis_create(const oar_vis_cfg* cfg, const oar_lm_tensor* tensors, int32_t n_tensors, int32_t device_id, oar_vis** out) {
@@ -85,9 +83,7 @@ oar_status oar_vis_create(const oar_vis_cfg* cfg, const oar_lm_tensor* tensors, 
         *out = nullptr;
         const oar_vis_cfg c = *cfg;
         check_cfg(c);
-        Table T{"oar_vis_create"};
-        for (int32_t i = 0; i < n_tensors; ++i)
-            if (tensors[i].name) T.by_name[tensors[i].name] = &tensors[i];
+        const Table T("oar_vis_create", tensors, n_tensors);
         const int D = c.hidden, L = c.layers, F = c.intermediate, Kp = c.channels * c.patch * c.patch, G = c.pos_grid, m2 = c.merge * c.merge, TH = c.text_hidden, dh = D / c.heads;
         // every tensor is looked up and checked before the device is touched
         const std::string vm = "visual.vision_model.";
@@ -121,10 +117,7 @@ oar_status oar_vis_create(const oar_vis_cfg* cfg, const oar_lm_tensor* tensors, 
         const oar_lm_tensor& l2w = T.need("mlp_AR.linear_2.weight", TH, (int64_t)m2 * D);
         const oar_lm_tensor& l2b = T.need("mlp_AR.linear_2.bias", TH, -1);
 
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) fail(OAR_DEVICE, "no HIP device visible: libOarMi355x has no CPU fallback");
-        OAR_CHECK(device_id >= 0 && device_id < ndev, OAR_DEVICE, "oar_vis_create: no such device");
-        OAR_HIP(hipSetDevice(device_id));
+        open_device(device_id, "oar_vis_create: no such device");
         std::unique_ptr<oar_vis> M(new oar_vis());
         M->cfg = c; M->device = device_id;
         OAR_HIP(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
@@ -155,8 +148,7 @@ oar_status oar_vis_create(const oar_vis_cfg* cfg, const oar_lm_tensor* tensors, 
         M->merged = M->raw<float>(MT * D); M->ph = M->raw<float>(MT * D); M->emb = M->raw<float>((MT / m2 + 1) * TH);
         M->cos = M->raw<float>(MT * (dh / 2)); M->sin = M->raw<float>(MT * (dh / 2));
         M->max_tiles = c.heads * (int)((MT + k::kFlashQueries - 1) / k::kFlashQueries + c.max_images);
-        M->segs = M->raw<k::VisSeg>((size_t)k::kVisMaxImages);
-        M->tiles = M->raw<k::VisTile>((size_t)M->max_tiles);
+        M->att_tab.alloc(*M, k::kVisMaxImages, M->max_tiles);
         M->inv_freq.resize((size_t)dh / 4);
         for (int j = 0; j < dh / 4; ++j) M->inv_freq[(size_t)j] = (float)(1.0 / std::pow((double)c.rope_theta, 2.0 * j / (dh / 2)));
         *out = M.release();
@@ -175,10 +167,8 @@ oar_status oar_vis_cost(const oar_vis* vis, int32_t n_images, const int32_t* gri
         const oar_vis_cfg& c = vis->cfg;
         const k::VisGrids g = check_grids(c, n_images, grids_hw, "oar_vis_cost");
         const double T = g.start[g.n], D = c.hidden, F = c.intermediate, Kp = (double)c.channels * c.patch * c.patch, m2 = (double)c.merge * c.merge, TH = c.text_hidden, L = c.layers;
-        std::vector<int32_t> lens((size_t)g.n);
-        for (int i = 0; i < g.n; ++i) lens[(size_t)i] = g.h[i] * g.w[i];
-        double ab = 0.0, af = 0.0;
-        k::vis_attention_cost(lens.data(), g.n, c.heads, c.hidden / c.heads, &ab, &af);
+        const HostTables ht = grid_tables(g, c.heads, c.hidden / c.heads);
+        const double ab = ht.bytes, af = ht.flops;
         const double macs = T * (Kp * D + L * (4.0 * D * D + 2.0 * D * F)) + (T / m2) * (m2 * D * m2 * D + m2 * D * TH);
         // rows read and written per launch: embedding (pix, pos twice, x), per layer (LN 2, qkv 4, out 3, LN 2, fc1 1 + F/D, the tanh GELU 2 F/D, fc2 F/D + 2), post LN 2, projector (LN 2, gather 2, l1 2, l2 1 + TH/(m2 D))
         const double acts = 4.0 * T * (Kp + 3.0 * D + L * (14.0 * D + (c.act == OAR_VIS_GELU_ERF ? 2.0 : 4.0) * F) + 2.0 * D + 6.0 * D + D + TH / m2);
@@ -197,9 +187,7 @@ oar_status oar_vis_encode(oar_vis* vis, const oar_vis_request* req) {
         const int T = g.start[g.n], D = c.hidden, F = c.intermediate, Kp = c.channels * c.patch * c.patch, m2 = c.merge * c.merge, TH = c.text_hidden, dh = D / c.heads, h2 = dh / 2, q4 = dh / 4;
         // rotary tables on the host, in f32 like the reference: position x frequency, then cosf / sinf
         std::vector<float> cs((size_t)T * h2), sn((size_t)T * h2);
-        std::vector<int32_t> lens((size_t)g.n);
         for (int i = 0; i < g.n; ++i) {
-            lens[(size_t)i] = g.h[i] * g.w[i];
             for (int idx = 0; idx < g.h[i] * g.w[i]; ++idx) {
                 const float row = (float)(idx / g.w[i]), col = (float)(idx % g.w[i]);
                 float* cr = cs.data() + (size_t)(g.start[i] + idx) * h2;
@@ -210,13 +198,8 @@ oar_status oar_vis_encode(oar_vis* vis, const oar_vis_request* req) {
                 }
             }
         }
-        const int n_tiles = (int)k::vis_attention_tile_count(lens.data(), g.n, c.heads);
-        OAR_CHECK(n_tiles <= vis->max_tiles, OAR_INTERNAL, "oar_vis_encode: more query tiles than the table holds");
-        std::vector<k::VisSeg> segs((size_t)g.n);
-        std::vector<k::VisTile> tiles((size_t)n_tiles);
-        k::vis_attention_tables(lens.data(), g.n, c.heads, segs.data(), tiles.data());
-        double ab = 0.0, af = 0.0;
-        k::vis_attention_cost(lens.data(), g.n, c.heads, dh, &ab, &af);
+        const HostTables ht = grid_tables(g, c.heads, dh);
+        OAR_CHECK((int)ht.tiles.size() <= vis->max_tiles, OAR_INTERNAL, "oar_vis_encode: more query tiles than the table holds");
 
         std::lock_guard<std::mutex> lk(vis->mu);
         OAR_HIP(hipSetDevice(vis->device));
@@ -224,20 +207,20 @@ oar_status oar_vis_encode(oar_vis* vis, const oar_vis_request* req) {
         OAR_HIP(hipMemcpyAsync(vis->pix, req->pixel_values, (size_t)T * Kp * 4, hipMemcpyHostToDevice, s));
         OAR_HIP(hipMemcpyAsync(vis->cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, s));
         OAR_HIP(hipMemcpyAsync(vis->sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, s));
-        OAR_HIP(hipMemcpyAsync(vis->segs, segs.data(), segs.size() * sizeof(k::VisSeg), hipMemcpyHostToDevice, s));
-        OAR_HIP(hipMemcpyAsync(vis->tiles, tiles.data(), tiles.size() * sizeof(k::VisTile), hipMemcpyHostToDevice, s));
+        AttnTables& at = vis->att_tab;
+        at.put(ht, s);
         OAR_HIP(hipStreamSynchronize(s));   // (pageable sources that end with this call)
         const int act = c.act == OAR_VIS_GELU_ERF ? k::ACT_GELU_ERF : k::ACT_GELU_TANH;
         // embedding: the resampled position table is the residual of the patch Linear
         k::vis_pos_embed(s, vis->pos_table, vis->pos, g, c.pos_grid, D);
         run_linear(s, vis->patch, vis->pix, vis->x, T, k::ACT_NONE, vis->pos);
         k::VisAttnP ap{};
-        ap.qkv = vis->qkv; ap.cos = vis->cos; ap.sin = vis->sin; ap.o = vis->att; ap.segs = vis->segs; ap.tiles = vis->tiles;
-        ap.n_tiles = n_tiles; ap.nh = c.heads; ap.dh = dh; ap.ld = 3 * D; ap.scale = (float)std::pow((double)dh, -0.5);
+        ap.qkv = vis->qkv; ap.cos = vis->cos; ap.sin = vis->sin; ap.o = vis->att; ap.segs = at.segs; ap.tiles = at.tiles;
+        ap.n_tiles = at.n_tiles; ap.nh = c.heads; ap.dh = dh; ap.ld = 3 * D; ap.scale = (float)std::pow((double)dh, -0.5);
         for (const LayerW& W : vis->layers) {
             k::layernorm(s, vis->x, W.ln1g, W.ln1b, vis->xn, T, D, c.ln_eps, "vis_layernorm");
             run_linear(s, W.qkv, vis->xn, vis->qkv, T, k::ACT_NONE, nullptr);
-            k::vis_attention(s, ap, ab, af);
+            k::vis_attention(s, ap, at.bytes, at.flops);
             run_linear(s, W.out, vis->att, vis->x2, T, k::ACT_NONE, vis->x);
             k::layernorm(s, vis->x2, W.ln2g, W.ln2b, vis->xn, T, D, c.ln_eps, "vis_layernorm");
             // (the implicit-GEMM epilogue has the erf GELU but not the tanh form, which only the element-wise kernel knows: one more launch per layer)

@@ -227,63 +227,51 @@ def _as_table_entry(name: str, t):
     raise api.OCRError(api.OAR_INVALID_INPUT, f"tensor {name}: dtype {a.dtype} is neither a float type nor uint16 (bf16 bits)")
 
 
-@dataclass
-class LMOutput:
-    tokens: np.ndarray            # [n_seq, max_new_tokens] int32 (or [max_new_tokens] for a single sequence): eos from a sequence's first eos on
-    counts: np.ndarray            # [n_seq] tokens up to and including the first eos
-    logits: Optional[np.ndarray]  # [n_seq, max_new_tokens, vocab] float32 when asked for
+def _tensor_table(tensors: dict, take, rename=None, reshape=None):
+    """The LmTensor array of the tensors whose checkpoint name take(name) accepts -> (array, its length, the arrays it points into, to be kept alive until the
+    library has copied them).  rename(name): the name the library looks up; reshape(name, array): the array as the library expects it, under that name (it may
+    refuse the tensor by raising).  A tensor of a rank above 4 has no place in the struct and is left out."""
+    keep, table = [], []
+    for name, t in tensors.items():
+        if not take(name):
+            continue
+        a, code = _as_table_entry(name, t)
+        if rename is not None:
+            name = rename(name)
+        if reshape is not None:
+            a = reshape(name, a)
+        if a.ndim > 4:
+            continue
+        e = LmTensor()
+        e.name, e.dtype, e.rank, e.data = name.encode(), code, a.ndim, a.ctypes.data
+        for i, v in enumerate(a.shape):
+            e.dims[i] = v
+        keep.append(a)
+        table.append(e)
+    return (LmTensor * max(len(table), 1))(*table), len(table), keep
 
 
-class CausalLM:
-    def __init__(self, cfg: CausalLMConfig, handle):
-        self.cfg, self._h = cfg, handle
-        self.generation_defaults: dict = {}   # from_dir: what the checkpoint's generation_config.json says (not applied by itself)
+def _read_checkpoint(path, names=None) -> Dict[str, np.ndarray]:
+    """Every *.safetensors file of a checkpoint directory as one name -> array dict; `names`: a predicate that selects tensors."""
+    path = Path(path)
+    files = sorted(path.glob("*.safetensors"))
+    if not files:
+        raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
+    tensors = {}
+    for f in files:
+        tensors.update(read_safetensors(f, names=names))
+    return tensors
 
-    @classmethod
-    def from_state_dict(cls, cfg: CausalLMConfig, tensors: dict, prefix: str = "", device_id: int = 0) -> "CausalLM":
-        """tensors: checkpoint name -> float array, uint16 array (bf16 bits) or torch tensor.  `prefix` is cut from the front of every name that has it
-        (a checkpoint that nests the text model, e.g. "language_model.")."""
-        keep, table = [], []
-        for name, t in tensors.items():
-            if prefix:
-                if not name.startswith(prefix):
-                    continue
-                name = name[len(prefix):]
-            if not (name.startswith("model.") or name.startswith("lm_head.")):
-                continue
-            a, code = _as_table_entry(name, t)
-            if a.ndim > 4:
-                continue
-            e = LmTensor()
-            e.name, e.dtype, e.rank, e.data = name.encode(), code, a.ndim, a.ctypes.data
-            for i, v in enumerate(a.shape):
-                e.dims[i] = v
-            keep.append(a)
-            table.append(e)
-        arr = (LmTensor * max(len(table), 1))(*table)
-        h = C.c_void_p()
-        api._check(_lib().oar_lm_create(C.byref(cfg.to_c()), arr, len(table), device_id, C.byref(h)))
-        return cls(cfg, h)
 
-    @classmethod
-    def from_dir(cls, path, prefix: str = "", device_id: int = 0, **cfg_overrides) -> "CausalLM":
-        """config.json + every *.safetensors of a checkpoint directory."""
-        path = Path(path)
-        cfg = CausalLMConfig.from_hf_json(json.loads((path / "config.json").read_text()), **cfg_overrides)
-        files = sorted(path.glob("*.safetensors"))
-        if not files:
-            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
-        want = lambda n: n.startswith(prefix + "model.") or n.startswith(prefix + "lm_head.")   # noqa: E731
-        tensors = {}
-        for f in files:
-            tensors.update(read_safetensors(f, names=want))
-        lm = cls.from_state_dict(cfg, tensors, prefix=prefix, device_id=device_id)
-        lm.generation_defaults = read_generation_defaults(path)
-        return lm
+class _Handle:
+    """An owned handle of the library: destroy(handle) runs once, from close, the end of a `with` block or the collector."""
+
+    def __init__(self, handle, destroy):
+        self._h, self._destroy = handle, destroy
 
     def close(self):
         if self._h:
-            _lib().oar_lm_destroy(self._h)
+            self._destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -297,6 +285,41 @@ class CausalLM:
 
     def __exit__(self, *a):
         self.close()
+
+
+@dataclass
+class LMOutput:
+    tokens: np.ndarray            # [n_seq, max_new_tokens] int32 (or [max_new_tokens] for a single sequence): eos from a sequence's first eos on
+    counts: np.ndarray            # [n_seq] tokens up to and including the first eos
+    logits: Optional[np.ndarray]  # [n_seq, max_new_tokens, vocab] float32 when asked for
+
+
+class CausalLM(_Handle):
+    def __init__(self, cfg: CausalLMConfig, handle):
+        super().__init__(handle, lambda h: _lib().oar_lm_destroy(h))
+        self.cfg = cfg
+        self.generation_defaults: dict = {}   # from_dir: what the checkpoint's generation_config.json says (not applied by itself)
+
+    @classmethod
+    def from_state_dict(cls, cfg: CausalLMConfig, tensors: dict, prefix: str = "", device_id: int = 0) -> "CausalLM":
+        """tensors: checkpoint name -> float array, uint16 array (bf16 bits) or torch tensor.  `prefix` is cut from the front of every name that has it
+        (a checkpoint that nests the text model, e.g. "language_model.")."""
+        if prefix:
+            tensors = {name[len(prefix):]: t for name, t in tensors.items() if name.startswith(prefix)}
+        arr, n, keep = _tensor_table(tensors, lambda name: name.startswith("model.") or name.startswith("lm_head."))
+        h = C.c_void_p()
+        api._check(_lib().oar_lm_create(C.byref(cfg.to_c()), arr, n, device_id, C.byref(h)))
+        return cls(cfg, h)
+
+    @classmethod
+    def from_dir(cls, path, prefix: str = "", device_id: int = 0, **cfg_overrides) -> "CausalLM":
+        """config.json + every *.safetensors of a checkpoint directory."""
+        path = Path(path)
+        cfg = CausalLMConfig.from_hf_json(json.loads((path / "config.json").read_text()), **cfg_overrides)
+        tensors = _read_checkpoint(path, names=lambda n: n.startswith(prefix + "model.") or n.startswith(prefix + "lm_head."))
+        lm = cls.from_state_dict(cfg, tensors, prefix=prefix, device_id=device_id)
+        lm.generation_defaults = read_generation_defaults(path)
+        return lm
 
     def cost(self, n_rows: int, cache_len: int):
         """(flops, bytes, launches) of one step of n_rows rows at cache_len cached positions."""
@@ -661,29 +684,60 @@ def rope_index(input_ids, grids, image_token_id: int, vision_start_token_id: int
     return np.ascontiguousarray(np.asarray(pos, np.int32).reshape(-1, 3).T), cur + 1 - len(ids)
 
 
-class VisionEncoder:
+class _Encoder(_Handle):
+    """cost and encode of a vision tower.  A subclass gives _fns() -> the library's (cost, encode) functions, _Request, its request struct, _widths() -> the
+    floats of (a patch, an embedding row, a feature row), and _grids_ptr(g) -> what the library gets for the grids."""
+    _Request = None
+
+    def _grids_ptr(self, g):
+        return g.ctypes.data
+
+    def cost(self, grids):
+        """(flops, bytes, launches) of one call over these grids."""
+        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+        f, b, n = C.c_double(), C.c_double(), C.c_int32()
+        api._check(self._fns()[0](self._h, g.shape[0], self._grids_ptr(g), C.byref(f), C.byref(b), C.byref(n)))
+        return f.value, b.value, n.value
+
+    def encode(self, pixel_values, grids, return_features: bool = False):
+        """pixel_values [sum h w, patch width], grids [n, 2] -> embeds [sum h w / merge^2, output width] (and features [sum h w, tower width] when asked for);
+        all images run in ONE call, packed back to back, and do not see each other.  The class says what order the rows are in."""
+        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
+        px = np.ascontiguousarray(pixel_values, np.float32)
+        T = int((g[:, 0].astype(np.int64) * g[:, 1]).sum()) if g.size else 0
+        kp, out_width, feat_width = self._widths()
+        if px.size != T * kp:
+            raise api.OCRError(api.OAR_INVALID_INPUT, f"encode: pixel_values hold {px.size} floats, the grids need {T} x {kp}")
+        m2 = self.cfg.spatial_merge_size ** 2
+        emb = np.empty((max(T // m2, 0), out_width), np.float32)
+        feat = np.empty((T, feat_width), np.float32) if return_features else None
+        req = self._Request()
+        req.n_images, req.grids, req.pixel_values, req.embeds = g.shape[0], self._grids_ptr(g), px.ctypes.data, emb.ctypes.data
+        req.features = feat.ctypes.data if return_features else None
+        api._check(self._fns()[1](self._h, C.byref(req)))
+        return (emb, feat) if return_features else emb
+
+
+class VisionEncoder(_Encoder):
+    """PaddleOCR-VL's encoder and projector: pixel_values [sum h w, 3 p p] in raster order -> embeds [sum h w / merge^2, text_hidden], features [sum h w, hidden]."""
+    _Request = VisRequest
+
     def __init__(self, cfg: VisionConfig, handle):
-        self.cfg, self._h = cfg, handle
+        super().__init__(handle, lambda h: _vis_lib().oar_vis_destroy(h))
+        self.cfg = cfg
+
+    def _fns(self):
+        return _vis_lib().oar_vis_cost, _vis_lib().oar_vis_encode
+
+    def _widths(self):
+        return self.cfg.num_channels * self.cfg.patch_size ** 2, self.cfg.text_hidden, self.cfg.hidden_size
 
     @classmethod
     def from_state_dict(cls, cfg: VisionConfig, tensors: dict, device_id: int = 0) -> "VisionEncoder":
         """tensors: checkpoint name -> float array, uint16 array (bf16 bits) or torch tensor; the `visual.` and `mlp_AR.` names are taken."""
-        keep, table = [], []
-        for name, t in tensors.items():
-            if not (name.startswith("visual.") or name.startswith("mlp_AR.")):
-                continue
-            a, code = _as_table_entry(name, t)
-            if a.ndim > 4:
-                continue
-            e = LmTensor()
-            e.name, e.dtype, e.rank, e.data = name.encode(), code, a.ndim, a.ctypes.data
-            for i, v in enumerate(a.shape):
-                e.dims[i] = v
-            keep.append(a)
-            table.append(e)
-        arr = (LmTensor * max(len(table), 1))(*table)
+        arr, n, keep = _tensor_table(tensors, lambda name: name.startswith("visual.") or name.startswith("mlp_AR."))
         h = C.c_void_p()
-        api._check(_vis_lib().oar_vis_create(C.byref(cfg.to_c()), arr, len(table), device_id, C.byref(h)))
+        api._check(_vis_lib().oar_vis_create(C.byref(cfg.to_c()), arr, n, device_id, C.byref(h)))
         return cls(cfg, h)
 
     @classmethod
@@ -692,55 +746,7 @@ class VisionEncoder:
         d = json.loads((path / "config.json").read_text())
         text_hidden = int((d.get("text_config") or {}).get("hidden_size", d.get("hidden_size")))
         cfg = VisionConfig.from_hf_json(d["vision_config"], text_hidden=text_hidden, **cfg_overrides)
-        files = sorted(path.glob("*.safetensors"))
-        if not files:
-            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
-        tensors = {}
-        for f in files:
-            tensors.update(read_safetensors(f, names=lambda n: n.startswith("visual.") or n.startswith("mlp_AR.")))
-        return cls.from_state_dict(cfg, tensors, device_id=device_id)
-
-    def close(self):
-        if self._h:
-            _vis_lib().oar_vis_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def cost(self, grids):
-        """(flops, bytes, launches) of one call over these grids."""
-        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
-        f, b, n = C.c_double(), C.c_double(), C.c_int32()
-        api._check(_vis_lib().oar_vis_cost(self._h, g.shape[0], g.ctypes.data, C.byref(f), C.byref(b), C.byref(n)))
-        return f.value, b.value, n.value
-
-    def encode(self, pixel_values, grids, return_features: bool = False):
-        """pixel_values [sum h w, 3 p p], grids [n, 2] -> embeds [sum h w / merge^2, text_hidden] (and features [sum h w, hidden] when asked for); all
-        images run in ONE call, packed back to back."""
-        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
-        px = np.ascontiguousarray(pixel_values, np.float32)
-        T = int((g[:, 0].astype(np.int64) * g[:, 1]).sum()) if g.size else 0
-        kp = self.cfg.num_channels * self.cfg.patch_size ** 2
-        if px.size != T * kp:
-            raise api.OCRError(api.OAR_INVALID_INPUT, f"encode: pixel_values hold {px.size} floats, the grids need {T} x {kp}")
-        m2 = self.cfg.spatial_merge_size ** 2
-        emb = np.empty((max(T // m2, 0), self.cfg.text_hidden), np.float32)
-        feat = np.empty((T, self.cfg.hidden_size), np.float32) if return_features else None
-        req = VisRequest()
-        req.n_images, req.grids, req.pixel_values, req.embeds = g.shape[0], g.ctypes.data, px.ctypes.data, emb.ctypes.data
-        req.features = feat.ctypes.data if return_features else None
-        api._check(_vis_lib().oar_vis_encode(self._h, C.byref(req)))
-        return (emb, feat) if return_features else emb
+        return cls.from_state_dict(cfg, _read_checkpoint(path, names=lambda n: n.startswith("visual.") or n.startswith("mlp_AR.")), device_id=device_id)
 
 
 def _widen_rows(table: np.ndarray, ids) -> np.ndarray:
@@ -785,37 +791,19 @@ def _generate_from_patches(model, px, grids, prefix_ids, suffix_ids, processors:
     return model.lm.generate(inputs_embeds=seqs, position_ids=pos, history_ids=hist if processors else None, **gen)
 
 
-class PaddleOCRVL:
-    """Vision encoder + projector + text decoder: images and token-id prompts in, generated token ids out."""
+class _ImagesToTokens:
+    """A vision tower in front of a text decoder: images and token-id prompts in, generated token ids out.  A subclass gives from_state_dict and
+    _preprocess(images) -> (pixel_values, grids)."""
 
-    def __init__(self, vision: VisionEncoder, lm: CausalLM, embed_table: np.ndarray, preproc: ImageProcessorConfig, image_token_id: int, vision_start_token_id: int):
+    def __init__(self, vision, lm: CausalLM, embed_table: np.ndarray, preproc: ImageProcessorConfig, image_token_id: int, vision_start_token_id: int):
         self.vision, self.lm, self.embed_table, self.preproc = vision, lm, embed_table, preproc
         self.image_token_id, self.vision_start_token_id = int(image_token_id), int(vision_start_token_id)
         self.generation_defaults: dict = {}   # from_dir: the checkpoint's generation_config.json (not applied by itself)
 
     @classmethod
-    def from_state_dict(cls, cfg_json: dict, preproc_json: dict, tensors: dict, device_id: int = 0, lm_overrides: Optional[dict] = None,
-                        vision_overrides: Optional[dict] = None) -> "PaddleOCRVL":
-        lm_cfg = CausalLMConfig.from_hf_json(cfg_json, **(lm_overrides or {}))
-        vis_cfg = VisionConfig.from_hf_json(cfg_json["vision_config"], text_hidden=lm_cfg.hidden_size, **(vision_overrides or {}))
-        table, _ = _as_table_entry("model.embed_tokens.weight", tensors["model.embed_tokens.weight"])
-        vision = VisionEncoder.from_state_dict(vis_cfg, tensors, device_id=device_id)
-        try:
-            lm = CausalLM.from_state_dict(lm_cfg, tensors, device_id=device_id)
-        except Exception:
-            vision.close()
-            raise
-        return cls(vision, lm, table, ImageProcessorConfig.from_json(preproc_json), cfg_json["image_token_id"], cfg_json["vision_start_token_id"])
-
-    @classmethod
-    def from_dir(cls, path, device_id: int = 0, **kw) -> "PaddleOCRVL":
+    def from_dir(cls, path, device_id: int = 0, **kw):
         path = Path(path)
-        files = sorted(path.glob("*.safetensors"))
-        if not files:
-            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
-        tensors = {}
-        for f in files:
-            tensors.update(read_safetensors(f))
+        tensors = _read_checkpoint(path)
         m = cls.from_state_dict(json.loads((path / "config.json").read_text()), json.loads((path / "preprocessor_config.json").read_text()), tensors, device_id=device_id, **kw)
         m.generation_defaults = read_generation_defaults(path)
         m.lm.generation_defaults = dict(m.generation_defaults)
@@ -843,10 +831,31 @@ class PaddleOCRVL:
         processors = repetition_penalty != 1.0 or no_repeat_ngram_size != 0
         if schedule == "refill" and (repetition_penalty != 1.0 or no_repeat_ngram_size > 1):
             raise api.OCRError(api.OAR_UNSUPPORTED_OP, "generate_tokens: schedule 'refill' does not run the logits processors")
-        px, grids = preprocess_images(images, self.preproc)
+        px, grids = self._preprocess(images)
         return _generate_from_patches(self, px, grids, prefix_ids, suffix_ids, processors, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
                                       forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
                                       stop_at_eos=stop_at_eos, schedule=schedule, slots=slots, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+
+
+class PaddleOCRVL(_ImagesToTokens):
+    """Vision encoder + projector + text decoder: images and token-id prompts in, generated token ids out."""
+
+    @classmethod
+    def from_state_dict(cls, cfg_json: dict, preproc_json: dict, tensors: dict, device_id: int = 0, lm_overrides: Optional[dict] = None,
+                        vision_overrides: Optional[dict] = None) -> "PaddleOCRVL":
+        lm_cfg = CausalLMConfig.from_hf_json(cfg_json, **(lm_overrides or {}))
+        vis_cfg = VisionConfig.from_hf_json(cfg_json["vision_config"], text_hidden=lm_cfg.hidden_size, **(vision_overrides or {}))
+        table, _ = _as_table_entry("model.embed_tokens.weight", tensors["model.embed_tokens.weight"])
+        vision = VisionEncoder.from_state_dict(vis_cfg, tensors, device_id=device_id)
+        try:
+            lm = CausalLM.from_state_dict(lm_cfg, tensors, device_id=device_id)
+        except Exception:
+            vision.close()
+            raise
+        return cls(vision, lm, table, ImageProcessorConfig.from_json(preproc_json), cfg_json["image_token_id"], cfg_json["vision_start_token_id"])
+
+    def _preprocess(self, images):
+        return preprocess_images(images, self.preproc)
 
 
 # ================================================================================== the Qwen2-VL and Qwen2.5-VL vision towers (DESIGN 4.51)
@@ -1002,33 +1011,37 @@ def k_qvis_row_gather(x, idx, o_io, o_off):
     return o_io
 
 
-class QwenVisionEncoder:
+class QwenVisionEncoder(_Encoder):
+    """A Qwen2-VL or Qwen2.5-VL tower: pixel_values [sum h w, channels temporal p p] in merge-grouped order (preprocess_images_qwen) -> embeds
+    [sum h w / merge^2, out_hidden] in raster order of the merged grids, features [sum h w, embed] (the last block's output in the caller's order)."""
+    _Request = QvisRequest
+
     def __init__(self, cfg: QwenVisionConfig, handle):
-        self.cfg, self._h = cfg, handle
+        super().__init__(handle, lambda h: _qvis_lib().oar_qvis_destroy(h))
+        self.cfg = cfg
+
+    def _fns(self):
+        return _qvis_lib().oar_qvis_cost, _qvis_lib().oar_qvis_encode
+
+    def _widths(self):
+        return self.cfg.patch_dim, self.cfg.out_hidden_size, self.cfg.embed_dim
+
+    def _grids_ptr(self, g):   # (no grids: a null pointer, which the library refuses by name)
+        return g.ctypes.data if g.size else None
 
     @classmethod
     def from_state_dict(cls, cfg: QwenVisionConfig, tensors: dict, prefix: str = "visual.", device_id: int = 0) -> "QwenVisionEncoder":
         """tensors: checkpoint name -> float array, uint16 array (bf16 bits) or torch tensor; the names under `prefix` are taken.  A 5-D patch weight
         [embed, channels, temporal, patch, patch] is taken as the [embed, channels temporal patch^2] matrix it is."""
-        keep, table = [], []
-        for name, t in tensors.items():
-            if not name.startswith(prefix):
-                continue
-            a, code = _as_table_entry(name, t)
-            name = name[len(prefix):]
+        def reshape(name, a):
             if name == "patch_embed.proj.weight" and a.ndim > 2:
                 a = a.reshape(a.shape[0], -1)
             if a.ndim > 4:
                 raise api.OCRError(api.OAR_INVALID_INPUT, f"tensor {prefix}{name} has rank {a.ndim}: the tower has no tensor of a rank above 2 but the patch weight")
-            e = LmTensor()
-            e.name, e.dtype, e.rank, e.data = name.encode(), code, a.ndim, a.ctypes.data
-            for i, v in enumerate(a.shape):
-                e.dims[i] = v
-            keep.append(a)
-            table.append(e)
-        arr = (LmTensor * max(len(table), 1))(*table)
+            return a
+        arr, n, keep = _tensor_table(tensors, lambda name: name.startswith(prefix), rename=lambda name: name[len(prefix):], reshape=reshape)
         h = C.c_void_p()
-        api._check(_qvis_lib().oar_qvis_create(C.byref(cfg.to_c(keep)), arr, len(table), device_id, C.byref(h)))
+        api._check(_qvis_lib().oar_qvis_create(C.byref(cfg.to_c(keep)), arr, n, device_id, C.byref(h)))
         return cls(cfg, h)
 
     @classmethod
@@ -1037,55 +1050,7 @@ class QwenVisionEncoder:
         d = json.loads((path / "config.json").read_text())
         text_hidden = int((d.get("text_config") or {}).get("hidden_size", d.get("hidden_size")))
         cfg = QwenVisionConfig.from_hf_json(d["vision_config"], text_hidden=text_hidden, **cfg_overrides)
-        files = sorted(path.glob("*.safetensors"))
-        if not files:
-            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
-        tensors = {}
-        for f in files:
-            tensors.update(read_safetensors(f, names=lambda n: n.startswith(prefix)))
-        return cls.from_state_dict(cfg, tensors, prefix=prefix, device_id=device_id)
-
-    def close(self):
-        if self._h:
-            _qvis_lib().oar_qvis_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def cost(self, grids):
-        """(flops, bytes, launches) of one call over these grids."""
-        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
-        f, b, n = C.c_double(), C.c_double(), C.c_int32()
-        api._check(_qvis_lib().oar_qvis_cost(self._h, g.shape[0], g.ctypes.data if g.size else None, C.byref(f), C.byref(b), C.byref(n)))
-        return f.value, b.value, n.value
-
-    def encode(self, pixel_values, grids, return_features: bool = False):
-        """pixel_values [sum h w, channels temporal p p] in merge-grouped order (preprocess_images_qwen), grids [n, 2] -> embeds [sum h w / merge^2, out_hidden]
-        in raster order of the merged grids (and features [sum h w, embed], the last block's output in the caller's order, when asked for); all images run
-        in ONE call, packed back to back, and do not see each other."""
-        g = np.ascontiguousarray(grids, np.int32).reshape(-1, 2)
-        px = np.ascontiguousarray(pixel_values, np.float32)
-        T = int((g[:, 0].astype(np.int64) * g[:, 1]).sum()) if g.size else 0
-        if px.size != T * self.cfg.patch_dim:
-            raise api.OCRError(api.OAR_INVALID_INPUT, f"encode: pixel_values hold {px.size} floats, the grids need {T} x {self.cfg.patch_dim}")
-        m2 = self.cfg.spatial_merge_size ** 2
-        emb = np.empty((max(T // m2, 0), self.cfg.out_hidden_size), np.float32)
-        feat = np.empty((T, self.cfg.embed_dim), np.float32) if return_features else None
-        req = QvisRequest()
-        req.n_images, req.grids, req.pixel_values, req.embeds = g.shape[0], g.ctypes.data if g.size else None, px.ctypes.data, emb.ctypes.data
-        req.features = feat.ctypes.data if return_features else None
-        api._check(_qvis_lib().oar_qvis_encode(self._h, C.byref(req)))
-        return (emb, feat) if return_features else emb
+        return cls.from_state_dict(cfg, _read_checkpoint(path, names=lambda n: n.startswith(prefix)), prefix=prefix, device_id=device_id)
 
 
 def patchify_merge_grouped(img_f32: np.ndarray, patch: int, merge: int, temporal: int) -> np.ndarray:
@@ -1139,15 +1104,10 @@ def preprocess_images_qwen(images, cfg: ImageProcessorConfig, temporal_patch_siz
     return np.concatenate(rows), np.asarray(grids, np.int32).reshape(-1, 2)
 
 
-class QwenVL:
+class QwenVL(_ImagesToTokens):
     """A Qwen2-VL (MinerU2.5) or Qwen2.5-VL (NaviDC-OCR) vision tower + the Qwen2 text decoder: images and token-id prompts in, generated token ids out.
     generation_defaults: what the checkpoint's generation_config.json says; nothing applies it.  (The reference implementation drives MinerU2.5 with
     no_repeat_ngram_size = 100 when generation_config.json is silent about it: pass it to generate_tokens to decode as it does.)"""
-
-    def __init__(self, vision: QwenVisionEncoder, lm: CausalLM, embed_table: np.ndarray, preproc: ImageProcessorConfig, image_token_id: int, vision_start_token_id: int):
-        self.vision, self.lm, self.embed_table, self.preproc = vision, lm, embed_table, preproc
-        self.image_token_id, self.vision_start_token_id = int(image_token_id), int(vision_start_token_id)
-        self.generation_defaults: dict = {}
 
     @classmethod
     def from_state_dict(cls, cfg_json: dict, preproc_json: dict, tensors: dict, device_id: int = 0, lm_overrides: Optional[dict] = None,
@@ -1172,40 +1132,5 @@ class QwenVL:
             raise
         return cls(vision, lm, table, preproc, cfg_json["image_token_id"], cfg_json["vision_start_token_id"])
 
-    @classmethod
-    def from_dir(cls, path, device_id: int = 0, **kw) -> "QwenVL":
-        path = Path(path)
-        files = sorted(path.glob("*.safetensors"))
-        if not files:
-            raise api.OCRError(api.OAR_MODEL_LOAD, f"{path}: no *.safetensors file")
-        tensors = {}
-        for f in files:
-            tensors.update(read_safetensors(f))
-        m = cls.from_state_dict(json.loads((path / "config.json").read_text()), json.loads((path / "preprocessor_config.json").read_text()), tensors, device_id=device_id, **kw)
-        m.generation_defaults = read_generation_defaults(path)
-        m.lm.generation_defaults = dict(m.generation_defaults)
-        return m
-
-    def close(self):
-        self.vision.close()
-        self.lm.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def generate_tokens(self, images, prefix_ids, suffix_ids, max_new_tokens: int = 16, eos_token_id: Optional[int] = None, return_logits: bool = False, forced_tokens=None,
-                        prefill: str = "rows", prefill_chunk: Optional[int] = None, decode_attention: str = "serial", split_keys: Optional[int] = None,
-                        stop_at_eos: bool = False, schedule: str = "groups", slots: Optional[int] = None, repetition_penalty: float = 1.0,
-                        no_repeat_ngram_size: int = 0) -> LMOutput:
-        """PaddleOCRVL.generate_tokens' arguments and meaning, with this model's preprocessing (preprocess_images_qwen) and tower."""
-        _check_mode_names(prefill, decode_attention)
-        processors = repetition_penalty != 1.0 or no_repeat_ngram_size != 0
-        if schedule == "refill" and (repetition_penalty != 1.0 or no_repeat_ngram_size > 1):
-            raise api.OCRError(api.OAR_UNSUPPORTED_OP, "generate_tokens: schedule 'refill' does not run the logits processors")
-        px, grids = preprocess_images_qwen(images, self.preproc, self.vision.cfg.temporal_patch_size)
-        return _generate_from_patches(self, px, grids, prefix_ids, suffix_ids, processors, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, return_logits=return_logits,
-                                      forced_tokens=forced_tokens, prefill=prefill, prefill_chunk=prefill_chunk, decode_attention=decode_attention, split_keys=split_keys,
-                                      stop_at_eos=stop_at_eos, schedule=schedule, slots=slots, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+    def _preprocess(self, images):
+        return preprocess_images_qwen(images, self.preproc, self.vision.cfg.temporal_patch_size)
