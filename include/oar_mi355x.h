@@ -549,6 +549,26 @@ oar_status oar_k_resize_triangle(const uint8_t* rgb, uint32_t w, uint32_t h, uin
 oar_status oar_k_threshold(const float* pred, size_t n, float thresh, uint8_t* mask);
 /* processors/db_mask.rs:11 (imageproc dilate, LInf, k = 1) on one height x width mask */
 oar_status oar_k_dilate(const uint8_t* mask, uint32_t height, uint32_t width, uint8_t* out);
+/* The u8 front kernels and the detector's finish kernels, each called the way its predictor calls it (tests/test_gpu_front_kernels.py).
+ * oar_k_stem_u8: an engine built from the ONNX bytes runs its first convolution on u8 images (the fused RGB stem) and the rest of the graph; outs as
+ * oar_engine_run.  table == 0: n <= 32 images of h x wt go in by value, tap = (float)byte[src_channels[c]] * alpha[c] + beta[c].  table != 0: images of
+ * height h and their own widths[i] <= wt behind a device table, normalised as oar_k_rec_preprocess and zero padded to wt (alpha, beta, src_channels unused).
+ * OAR_UNSUPPORTED_OP: the graph does not begin with a group-1 convolution of 3 input channels and kh kw 3 <= 128. */
+oar_status oar_k_stem_u8(const uint8_t* onnx, size_t onnx_len, const uint8_t* const* rgb, const uint32_t* widths, uint32_t n, uint32_t h, uint32_t wt,
+                         const int32_t src_channels[3], const float alpha[3], const float beta[3], int32_t table, oar_tensor* outs, int32_t max_out, int32_t* n_out);
+/* the resize half of oar_k_rec_preprocess_flip: crop i -> img_h rows of resized_widths[i] RGB pixels, the images at 64-byte rounded offsets of `pool`, which
+ * is filled with `sentinel` first.  pool == NULL: only tensor_width, resized_widths and pool_bytes are written. */
+oar_status oar_k_rec_resize_u8(const uint8_t* const* rgb, const uint32_t* widths, const uint32_t* heights, const uint8_t* flips, uint32_t n, uint32_t img_h, uint32_t img_w,
+                               uint32_t max_img_w, uint8_t sentinel, uint32_t* tensor_width, int32_t* resized_widths, uint8_t* pool, size_t pool_cap, size_t* pool_bytes);
+/* oar_k_normalize on n_pages <= 32 pages of `plane` pixels in one launch; page i begins offsets[i] bytes into the device copy of `pool` (any alignment) */
+oar_status oar_k_normalize_pages(const uint8_t* pool, size_t pool_bytes, const uint64_t* offsets, uint32_t n_pages, uint64_t plane, const int32_t src_channels[3],
+                                 const float alpha[3], const float beta[3], int32_t hwc_layout, float* out);
+/* the detector's finish in one launch: net_out [n][channels][height][width] -> probs [n][height][width] = channel 0, bits [n][height][ceil(width / 8)] with
+ * bit x & 7 of byte x >> 3 = probs > thresh.  float_offset (0..3): both device bases begin that many floats off their 16-byte alignment. */
+oar_status oar_k_db_keep_and_pack(const float* net_out, uint32_t n, uint32_t channels, uint32_t height, uint32_t width, float thresh, uint32_t float_offset, float* probs,
+                                  uint8_t* bits);
+/* n masks of height x width bytes -> bits as above (a non-zero byte sets its bit); byte_offset (0..7): the device mask begins that many bytes off its alignment */
+oar_status oar_k_pack_mask_bits(const uint8_t* mask, uint32_t n, uint32_t height, uint32_t width, uint32_t byte_offset, uint8_t* bits);
 /* processors/db_score.rs:139-181 (and db_bitmap.rs:49): scanline mean over polygons of any size; polygon i has
  * counts[i] (x, y) points, stored back to back in pts_xy */
 oar_status oar_k_poly_scores(const float* pred, uint32_t height, uint32_t width, const float* pts_xy, const uint32_t* counts,

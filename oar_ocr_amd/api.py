@@ -159,6 +159,7 @@ EXPORTS = [
     "oar_lm_generate_ex", "oar_lm_logits_check", "oar_k_lm_select",
     "oar_vis_create", "oar_vis_destroy", "oar_vis_encode", "oar_vis_cost",
     "oar_qvis_create", "oar_qvis_destroy", "oar_qvis_encode", "oar_qvis_cost", "oar_qvis_check", "oar_qvis_window_plan", "oar_k_qvis_rmsnorm", "oar_k_qvis_act", "oar_k_qvis_row_gather",
+    "oar_k_stem_u8", "oar_k_rec_resize_u8", "oar_k_normalize_pages", "oar_k_db_keep_and_pack", "oar_k_pack_mask_bits",
 ]
 
 
@@ -234,6 +235,12 @@ def lib():
     L.oar_k_rec_preprocess_flip.argtypes = [u8pp, u32p, u32p, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p]
     L.oar_k_resize_triangle.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.oar_k_threshold.argtypes = [vp, C.c_size_t, C.c_float, vp]
+    L.oar_k_stem_u8.argtypes = [vp, C.c_size_t, u8pp, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), f32p, f32p, C.c_int32, C.POINTER(Tensor), C.c_int32,
+                                C.POINTER(C.c_int32)]
+    L.oar_k_rec_resize_u8.argtypes = [u8pp, u32p, u32p, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, u32p, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.oar_k_normalize_pages.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_int32), f32p, f32p, C.c_int32, vp]
+    L.oar_k_db_keep_and_pack.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]
+    L.oar_k_pack_mask_bits.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.oar_k_ctc_argmax.argtypes = [vp, C.c_size_t, C.c_size_t, vp, vp]
     L.oar_k_box_scores.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
     L.oar_k_unclip.argtypes = [vp, C.c_uint32, C.c_float, vp, vp, C.c_uint32]
@@ -1657,6 +1664,83 @@ def k_threshold(pred, thresh):
     out = np.empty(pred.shape, np.uint8)
     _check(lib().oar_k_threshold(_p(pred), pred.size, thresh, _p(out)))
     return out
+
+
+def k_stem_u8(model: bytes, images, src=(0, 1, 2), alpha=(1.0, 1.0, 1.0), beta=(0.0, 0.0, 0.0), table=False, wt=None):
+    """Engine::run_stem of an engine built from `model` on u8 [h, w, 3] images -> the graph's first output, as OrtInfer.infer gives it.  Page form: at most
+    32 images of one size go in by value and a tap is (float)byte[src[c]] * alpha[c] + beta[c].  table=True: images of one height and their own widths sit
+    behind a device table, are normalised as k_rec_preprocess does and zero padded to wt, by default the widest (src, alpha and beta are not used)."""
+    imgs, ptrs, ws, _ = _img_arrays(images)
+    h = imgs[0].shape[0] if imgs else 0
+    if any(im.shape[0] != h for im in imgs):
+        raise OCRError(OAR_INVALID_INPUT, "k_stem_u8: the images differ in height")
+    wt = max((im.shape[1] for im in imgs), default=0) if wt is None else wt
+    n = len(imgs)
+    a, b = np.ascontiguousarray(alpha, np.float32), np.ascontiguousarray(beta, np.float32)
+    buf = (C.c_char * max(len(model), 1)).from_buffer_copy(model or b"\0")
+    outs = (Tensor * 16)()
+    cnt = C.c_int32(0)
+    _check(lib().oar_k_stem_u8(C.cast(buf, C.c_void_p), len(model), ptrs, ws, n, h, wt, (C.c_int32 * 3)(*src), a.ctypes.data_as(C.POINTER(C.c_float)),
+                               b.ctypes.data_as(C.POINTER(C.c_float)), int(bool(table)), outs, 16, C.byref(cnt)))
+    return OrtInfer._collect(outs, cnt.value)[0][1]
+
+
+def k_rec_resize_u8(crops, flips=None, img_h=48, img_w=320, max_img_w=3200, sentinel=0xA5):
+    """pp::rec_resize_u8 behind Recognizer::pack_u8's tables -> ([img_h, rw_i, 3] u8 images, Wt, the raw pool: image i begins at the sum of the 64-byte
+    rounded sizes before it, every other byte still holds `sentinel`)"""
+    imgs, ptrs, ws, hs = _img_arrays(crops)
+    fl = None if flips is None else np.ascontiguousarray(np.asarray(flips, bool).astype(np.uint8))
+    tw, need = C.c_uint32(0), C.c_size_t(0)
+    rws = np.zeros(max(len(imgs), 1), np.int32)
+    args = (ptrs, ws, hs, None if fl is None else _p(fl), len(imgs), img_h, img_w, max_img_w, sentinel, C.byref(tw), _p(rws))
+    _check(lib().oar_k_rec_resize_u8(*args, None, 0, C.byref(need)))
+    pool = np.empty(need.value, np.uint8)
+    _check(lib().oar_k_rec_resize_u8(*args, _p(pool), pool.size, C.byref(need)))
+    out, off = [], 0
+    for rw in rws[:len(imgs)]:
+        size = img_h * int(rw) * 3
+        out.append(pool[off:off + size].reshape(img_h, int(rw), 3).copy())
+        off += (size + 63) & ~63
+    return out, tw.value, pool
+
+
+def k_normalize_pages(pages, alpha, beta, src=(0, 1, 2), layout="chw", byte_offsets=None):
+    """pp::normalize_pages on equally sized u8 [h, w, 3] pages, page i at byte_offsets[i] of one device allocation (default: back to back) -> [n, 3, h, w]
+    or [n, h, w, 3]"""
+    pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
+    n = len(pages)
+    h, w = pages[0].shape[:2] if n else (0, 0)
+    size = h * w * 3
+    offs = np.asarray([i * size for i in range(n)] if byte_offsets is None else list(byte_offsets), np.uint64)
+    if len(offs) != n or any(p.shape != (h, w, 3) for p in pages):
+        raise OCRError(OAR_INVALID_INPUT, "k_normalize_pages: pages of one size and one offset per page")
+    pool = np.zeros(int(offs.max(initial=0)) + size, np.uint8)
+    for o, p in zip(offs, pages):
+        pool[int(o):int(o) + size] = p.reshape(-1)
+    out = np.empty((n, 3, h, w) if layout == "chw" else (n, h, w, 3), np.float32)
+    a, b = np.ascontiguousarray(alpha, np.float32), np.ascontiguousarray(beta, np.float32)
+    _check(lib().oar_k_normalize_pages(_p(pool), pool.size, _p(offs), n, h * w, (C.c_int32 * 3)(*src), a.ctypes.data_as(C.POINTER(C.c_float)),
+                                       b.ctypes.data_as(C.POINTER(C.c_float)), 0 if layout == "chw" else 1, _p(out)))
+    return out
+
+
+def k_db_keep_and_pack(net_out, thresh, float_offset=0):
+    """pp::db_keep_and_pack on net_out [n, C, H, W] -> (probs [n, H, W] f32, bits [n, H, ceil(W / 8)] u8); float_offset: both device bases begin that many
+    floats off their 16-byte alignment"""
+    net_out = np.ascontiguousarray(net_out, np.float32)
+    n, c, h, w = net_out.shape
+    probs, bits = np.empty((n, h, w), np.float32), np.empty((n, h, (w + 7) // 8), np.uint8)
+    _check(lib().oar_k_db_keep_and_pack(_p(net_out), n, c, h, w, thresh, float_offset, _p(probs), _p(bits)))
+    return probs, bits
+
+
+def k_pack_mask_bits(mask, byte_offset=0):
+    """pp::pack_mask_bits on mask [n, H, W] u8 -> bits [n, H, ceil(W / 8)]; byte_offset: the device mask begins that many bytes off its alignment"""
+    mask = np.ascontiguousarray(mask, np.uint8)
+    n, h, w = mask.shape
+    bits = np.empty((n, h, (w + 7) // 8), np.uint8)
+    _check(lib().oar_k_pack_mask_bits(_p(mask), n, h, w, byte_offset, _p(bits)))
+    return bits
 
 
 def k_dilate(mask):

@@ -1091,6 +1091,134 @@ oar_status oar_k_dilate(const uint8_t* mask, uint32_t height, uint32_t width, ui
     });
 }
 
+// ---- the u8 front kernels and the detector's finish kernels, each called the way its predictor calls it
+oar_status oar_k_stem_u8(const uint8_t* onnx, size_t onnx_len, const uint8_t* const* rgb, const uint32_t* widths, uint32_t n, uint32_t h, uint32_t wt,
+                         const int32_t src_channels[3], const float alpha[3], const float beta[3], int32_t table, oar_tensor* outs, int32_t max_out, int32_t* n_out) {
+    return guard([&] {
+        OAR_CHECK(onnx && onnx_len && rgb && widths && src_channels && alpha && beta && outs && max_out > 0 && n_out, OAR_INVALID_INPUT, "oar_k_stem_u8: bad arguments");
+        OAR_CHECK(n >= 1 && h >= 1 && wt >= 1, OAR_INVALID_INPUT, "oar_k_stem_u8: no image, or an empty one");
+        OAR_CHECK(table ? n <= 65535 : n <= 32, OAR_INVALID_INPUT, table ? "oar_k_stem_u8: at most 65535 images behind a table" : "oar_k_stem_u8: at most 32 pages go in by value");
+        for (uint32_t i = 0; i < n; ++i) {
+            OAR_CHECK(rgb[i] && widths[i] >= 1, OAR_INVALID_INPUT, "oar_k_stem_u8: image " + std::to_string(i) + " is null or empty");
+            OAR_CHECK(widths[i] <= wt, OAR_INVALID_INPUT, "oar_k_stem_u8: image " + std::to_string(i) + " is wider than the tensor");
+            OAR_CHECK(table || widths[i] == wt, OAR_INVALID_INPUT, "oar_k_stem_u8: pages by value are all of the tensor's width");
+        }
+        for (int c = 0; c < 3; ++c) OAR_CHECK(src_channels[c] >= 0 && src_channels[c] <= 2, OAR_INVALID_INPUT, "oar_k_stem_u8: a source channel outside 0..2");
+        require_device();
+        Engine E(onnx, onnx_len, 0, nullptr);
+        OAR_CHECK(E.stem_fusable(), OAR_UNSUPPORTED_OP, "oar_k_stem_u8: the graph does not begin with a fusable RGB stem");
+        std::lock_guard<std::mutex> lk(E.mutex());
+        DirectCall dc;
+        k::StemU8 st{};
+        for (int c = 0; c < 3; ++c) { st.src[c] = src_channels[c]; st.alpha[c] = alpha[c]; st.beta[c] = beta[c]; }
+        if (table) {   // one pool, the images at 64-byte rounded offsets behind a StemImg table (Recognizer::pack_u8's layout)
+            std::vector<size_t> offs(n);
+            size_t total = 0;
+            for (uint32_t i = 0; i < n; ++i) { offs[i] = total; total += ((size_t)h * widths[i] * 3 + 63) & ~(size_t)63; }
+            std::vector<uint8_t> pool(total, 0xA5);
+            for (uint32_t i = 0; i < n; ++i) std::memcpy(pool.data() + offs[i], rgb[i], (size_t)h * widths[i] * 3);
+            const uint8_t* dpool = dc.in(pool.data(), total);
+            std::vector<k::StemImg> tab(n);
+            for (uint32_t i = 0; i < n; ++i) { tab[i].ptr = dpool + offs[i]; tab[i].w = (int32_t)widths[i]; tab[i].pad = 0; }
+            st.dev = dc.in(tab.data(), n * sizeof(k::StemImg));
+        } else {
+            for (uint32_t i = 0; i < n; ++i) st.pages[i] = dc.in(rgb[i], (size_t)h * wt * 3);
+        }
+        const Plan& p = E.run_stem(st, {(int64_t)n, 3, (int64_t)h, (int64_t)wt});
+        fetch_outputs(E, p, outs, max_out, n_out);
+        if (Profiler::get().enabled) Profiler::get().flush();
+    });
+}
+
+oar_status oar_k_rec_resize_u8(const uint8_t* const* rgb, const uint32_t* widths, const uint32_t* heights, const uint8_t* flips, uint32_t n, uint32_t img_h, uint32_t img_w,
+                               uint32_t max_img_w, uint8_t sentinel, uint32_t* tensor_width, int32_t* resized_widths, uint8_t* pool, size_t pool_cap, size_t* pool_bytes) {
+    return guard([&] {
+        OAR_CHECK(rgb && widths && heights && tensor_width && resized_widths && pool_bytes && n >= 1 && img_h >= 1, OAR_INVALID_INPUT, "oar_k_rec_resize_u8: bad arguments");
+        for (uint32_t i = 0; i < n; ++i) OAR_CHECK(rgb[i] && widths[i] >= 1 && heights[i] >= 1, OAR_INVALID_INPUT, "oar_k_rec_resize_u8: crop " + std::to_string(i) + " is null or empty");
+        std::vector<uint32_t> ws(widths, widths + n), hs(heights, heights + n);
+        std::vector<int32_t> rws;
+        *tensor_width = (uint32_t)host::rec_tensor_width(ws, hs, (int)img_h, (int)img_w, (int)max_img_w, rws);
+        size_t total = 0, stage = 0;
+        int max_rw = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            resized_widths[i] = rws[i];
+            max_rw = std::max(max_rw, (int)rws[i]);
+            total += ((size_t)img_h * rws[i] * 3 + 63) & ~(size_t)63;
+            stage += ((size_t)ws[i] * hs[i] * 3 + 63) & ~(size_t)63;
+        }
+        *pool_bytes = total;
+        if (!pool) return;   // the size query
+        OAR_CHECK(pool_cap >= total, OAR_INVALID_INPUT, "oar_k_rec_resize_u8: the pool is too small");
+        require_device();
+        DirectCall dc;
+        std::vector<uint8_t> src(stage, 0);
+        std::vector<size_t> soff(n);
+        for (size_t i = 0, off = 0; i < n; ++i) {
+            soff[i] = off;
+            std::memcpy(src.data() + off, rgb[i], (size_t)ws[i] * hs[i] * 3);
+            off += ((size_t)ws[i] * hs[i] * 3 + 63) & ~(size_t)63;
+        }
+        const uint8_t* dsrc = dc.in(src.data(), stage);
+        std::memset(pool, sentinel, total);
+        uint8_t* dpool = dc.io(pool, total);
+        std::vector<pp::CropDesc> descs(n);
+        std::vector<pp::ResizedImg> imgs(n);
+        for (size_t i = 0, roff = 0; i < n; ++i) {
+            descs[i].src = dsrc + soff[i]; descs[i].w = (int)ws[i]; descs[i].h = (int)hs[i]; descs[i].rw = rws[i]; descs[i].flip = flips && flips[i] ? 1 : 0;
+            imgs[i].ptr = dpool + roff; imgs[i].w = rws[i]; imgs[i].pad = 0;
+            roff += ((size_t)img_h * rws[i] * 3 + 63) & ~(size_t)63;
+        }
+        pp::rec_resize_u8(nullptr, dc.in(descs.data(), n * sizeof(pp::CropDesc)), dc.in(imgs.data(), n * sizeof(pp::ResizedImg)), (int)n, (int)img_h, max_rw);
+        dc.finish();
+    });
+}
+
+oar_status oar_k_normalize_pages(const uint8_t* pool, size_t pool_bytes, const uint64_t* offsets, uint32_t n_pages, uint64_t plane, const int32_t src_channels[3],
+                                 const float alpha[3], const float beta[3], int32_t hwc_layout, float* out) {
+    return guard([&] {
+        OAR_CHECK(pool && offsets && src_channels && alpha && beta && out && n_pages >= 1 && plane >= 1 && plane < ((uint64_t)1 << 31), OAR_INVALID_INPUT, "oar_k_normalize_pages: bad arguments");
+        OAR_CHECK(n_pages <= 32, OAR_INVALID_INPUT, "oar_k_normalize_pages: at most 32 pages per launch");
+        for (uint32_t i = 0; i < n_pages; ++i)
+            OAR_CHECK(view_fits((size_t)offsets[i], plane * 3, pool_bytes), OAR_INVALID_INPUT, "oar_k_normalize_pages: page " + std::to_string(i) + " does not fit the pool");
+        for (int c = 0; c < 3; ++c) OAR_CHECK(src_channels[c] >= 0 && src_channels[c] <= 2, OAR_INVALID_INPUT, "oar_k_normalize_pages: a source channel outside 0..2");
+        require_device();
+        DirectCall dc;
+        const uint8_t* dpool = dc.in(pool, pool_bytes);
+        const uint8_t* pages[32];
+        for (uint32_t i = 0; i < n_pages; ++i) pages[i] = dpool + offsets[i];
+        int src[3] = {src_channels[0], src_channels[1], src_channels[2]};
+        pp::normalize_pages(nullptr, pages, (int)n_pages, dc.out(out, (size_t)n_pages * plane * 12), (int64_t)plane, src, alpha, beta, hwc_layout ? 1 : 0);
+        dc.finish();
+    });
+}
+
+oar_status oar_k_db_keep_and_pack(const float* net_out, uint32_t n, uint32_t channels, uint32_t height, uint32_t width, float thresh, uint32_t float_offset, float* probs,
+                                  uint8_t* bits) {
+    return guard([&] {
+        OAR_CHECK(net_out && probs && bits && n && channels && height && width, OAR_INVALID_INPUT, "oar_k_db_keep_and_pack: bad arguments");
+        OAR_CHECK(float_offset <= 3, OAR_INVALID_INPUT, "oar_k_db_keep_and_pack: float_offset is 0..3");
+        require_device();
+        const size_t plane = (size_t)height * width, row_bytes = (width + 7) / 8;
+        DirectCall dc;
+        const float* din = dc.in(net_out, (size_t)n * channels * plane * 4, float_offset * 4);
+        float* dprobs = dc.out(probs, (size_t)n * plane * 4, 0, float_offset * 4);
+        pp::db_keep_and_pack(nullptr, din, (int64_t)channels * plane, dprobs, dc.out(bits, (size_t)n * height * row_bytes), (int)n, (int)height, (int)width, thresh);
+        dc.finish();
+    });
+}
+
+oar_status oar_k_pack_mask_bits(const uint8_t* mask, uint32_t n, uint32_t height, uint32_t width, uint32_t byte_offset, uint8_t* bits) {
+    return guard([&] {
+        OAR_CHECK(mask && bits && n && height && width, OAR_INVALID_INPUT, "oar_k_pack_mask_bits: bad arguments");
+        OAR_CHECK(byte_offset <= 7, OAR_INVALID_INPUT, "oar_k_pack_mask_bits: byte_offset is 0..7");
+        require_device();
+        DirectCall dc;
+        const uint8_t* din = dc.in(mask, (size_t)n * height * width, byte_offset);
+        pp::pack_mask_bits(nullptr, din, dc.out(bits, (size_t)n * height * ((width + 7) / 8)), (int)n, (int)height, (int)width);
+        dc.finish();
+    });
+}
+
 oar_status oar_k_poly_scores(const float* pred, uint32_t height, uint32_t width, const float* pts_xy, const uint32_t* counts, uint32_t n_polys,
                              float* scores) {
     return guard([&] {

@@ -90,10 +90,12 @@ class DirectCall {
 
 public:
     template <class T>
-    const T* in(const T* host, size_t bytes) {   // uploaded now; null in, null out
+    const T* in(const T* host, size_t bytes, size_t lead = 0) {   // uploaded now; null in, null out.  lead: the copy begins that many bytes into its allocation (a base off its alignment)
         if (!host) return nullptr;
-        fresh().upload(host, bytes);
-        return static_cast<const T*>(mem_.back()->p);
+        fresh().alloc(bytes + lead);
+        char* at = static_cast<char*>(mem_.back()->p) + lead;
+        OAR_HIP(hipMemcpy(at, host, bytes, hipMemcpyHostToDevice));
+        return reinterpret_cast<const T*>(at);
     }
     template <class T>
     T* io(T* host, size_t count) {   // uploaded now, downloaded by finish()
@@ -102,10 +104,11 @@ public:
         return static_cast<T*>(mem_.back()->p);
     }
     template <class T>
-    T* out(T* host, size_t bytes, size_t alloc_bytes = 0) {   // not uploaded; its first `bytes` are downloaded by finish()
-        fresh().alloc(std::max(bytes, alloc_bytes));
-        back_.push_back({host, mem_.back()->p, bytes});
-        return static_cast<T*>(mem_.back()->p);
+    T* out(T* host, size_t bytes, size_t alloc_bytes = 0, size_t lead = 0) {   // not uploaded; `bytes` from `lead` on are downloaded by finish()
+        fresh().alloc(std::max(bytes, alloc_bytes) + lead);
+        char* at = static_cast<char*>(mem_.back()->p) + lead;
+        back_.push_back({host, at, bytes});
+        return reinterpret_cast<T*>(at);
     }
     template <class T = void>
     T* scratch(size_t bytes, int fill = -1) {   // neither way; fill: a byte value (0xFF shows a word read before it was written as NaN); no bytes, no buffer

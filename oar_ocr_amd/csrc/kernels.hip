@@ -403,11 +403,19 @@ void conv_smallcin_u8(hipStream_t s, const ConvP& p, const StemU8& st) {
     if (per_image == 0 || p.N == 0) return;
     OAR_CHECK(p.groups == 1 && p.Cin == 3 && p.kh * p.kw * 3 <= 128 && (st.dev ? p.N <= 65535 : p.N <= 32), OAR_INTERNAL, "conv_smallcin_u8: not an RGB stem");
     const double total = (double)p.N * per_image * p.Cout;
-    ProfScope ps(s, "conv_smallcin", 3.0 * (double)p.N * p.H * p.W + 4.0 * total, 2.0 * total * p.kh * p.kw * 3);
     const dim3 grid(grid_for(per_image, 256, 256L * 4), (p.Cout + 15) / 16, p.N);
     const bool k3 = p.kh == 3 && p.kw == 3;
     static const bool sw_off = [] { const char* e = getenv("OAR_STEM_SW"); return e && e[0] == '0'; }();
     const bool sw = k3 && p.Cout % 16 == 0 && !sw_off;   // (Cout % 16: every group is full and its 64 weight bytes are dword aligned)
+    char pname[96];
+    const char* cls = "conv_smallcin";
+    if (Profiler::get().detail) {   // with the instantiation that runs (restated in synth/front_cases.py)
+        const int len = snprintf(pname, sizeof pname, "conv_smallcin_u8 px=%ld n=%d Cout=%d k%dx%d s%dx%d %s %s %s", per_image, p.N, p.Cout, p.kh, p.kw, p.sh, p.sw,
+                                 st.dev ? "table" : "pages", k3 ? "k3" : "gen", sw ? "sw" : "lds");
+        OAR_CHECK(len > 0 && len < (int)sizeof pname, OAR_INTERNAL, "conv_smallcin_u8: the detail name does not fit its buffer");
+        cls = pname;
+    }
+    ProfScope ps(s, cls, 3.0 * (double)p.N * p.H * p.W + 4.0 * total, 2.0 * total * p.kh * p.kw * 3);
     if (st.dev) {
         if (sw) hipLaunchKernelGGL((conv_smallcin_u8_kernel<true, true, true>), grid, dim3(256), 0, s, p, st);
         else if (k3) hipLaunchKernelGGL((conv_smallcin_u8_kernel<true, true, false>), grid, dim3(256), 0, s, p, st);

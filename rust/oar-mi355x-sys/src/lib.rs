@@ -572,6 +572,13 @@ unsafe extern "C" {
     pub fn oar_k_resize_triangle(rgb: *const u8, w: u32, h: u32, nw: u32, nh: u32, out: *mut u8) -> oar_status;
     pub fn oar_k_threshold(pred: *const f32, n: usize, thresh: f32, mask: *mut u8) -> oar_status;
     pub fn oar_k_dilate(mask: *const u8, height: u32, width: u32, out: *mut u8) -> oar_status;
+    /// fixed-length arrays: src_channels: [i32; 3], alpha: [f32; 3], beta: [f32; 3]
+    pub fn oar_k_stem_u8(onnx: *const u8, onnx_len: usize, rgb: *const *const u8, widths: *const u32, n: u32, h: u32, wt: u32, src_channels: *const i32, alpha: *const f32, beta: *const f32, table: i32, outs: *mut oar_tensor, max_out: i32, n_out: *mut i32) -> oar_status;
+    pub fn oar_k_rec_resize_u8(rgb: *const *const u8, widths: *const u32, heights: *const u32, flips: *const u8, n: u32, img_h: u32, img_w: u32, max_img_w: u32, sentinel: u8, tensor_width: *mut u32, resized_widths: *mut i32, pool: *mut u8, pool_cap: usize, pool_bytes: *mut usize) -> oar_status;
+    /// fixed-length arrays: src_channels: [i32; 3], alpha: [f32; 3], beta: [f32; 3]
+    pub fn oar_k_normalize_pages(pool: *const u8, pool_bytes: usize, offsets: *const u64, n_pages: u32, plane: u64, src_channels: *const i32, alpha: *const f32, beta: *const f32, hwc_layout: i32, out: *mut f32) -> oar_status;
+    pub fn oar_k_db_keep_and_pack(net_out: *const f32, n: u32, channels: u32, height: u32, width: u32, thresh: f32, float_offset: u32, probs: *mut f32, bits: *mut u8) -> oar_status;
+    pub fn oar_k_pack_mask_bits(mask: *const u8, n: u32, height: u32, width: u32, byte_offset: u32, bits: *mut u8) -> oar_status;
     pub fn oar_k_poly_scores(pred: *const f32, height: u32, width: u32, pts_xy: *const f32, counts: *const u32, n_polys: u32, scores: *mut f32) -> oar_status;
     pub fn oar_k_contours(mask: *const u8, width: u32, height: u32, max_contours: u32, n_contours: *mut i32, offsets: *mut i64, pts_xy: *mut i32, types: *mut i32, cap_points: i64) -> oar_status;
     pub fn oar_k_ctc_argmax(probs: *const f32, rows: usize, vocab: usize, idx: *mut i64, prob: *mut f32) -> oar_status;

@@ -7,7 +7,7 @@ and the "no HIP device visible" text, and it is not made where a GPU is present.
 GPU refuses with the entry's own "no such device".
 
 The fixture is what `python tests/test_host_entries_cpu.py` writes: it was recorded before the host entries were moved onto their shared layer
-(csrc/host_entry.h) and is replayed unchanged."""
+(csrc/host_entry.h) and is replayed unchanged; the rows of the five image entries of DESIGN 4.53 were added with those entries."""
 import ctypes as C
 import json
 import sys
@@ -40,6 +40,11 @@ def _lens(*v):
 
 _lens.keep = []
 SEG_33_5, SEG_EMPTY, GRID_2x3, GRID_BAD, ROWS_OUT, IDX_OUT = _lens(33, 5), _lens(33, 0), _lens(2, 3), _lens(0, 3), _lens(5, 0), _lens(0, 9)
+# the image entries of DESIGN 4.53: 64 images of 4 x 4 (all the same bytes), their widths, channel orders, two page offsets, room for the outputs
+PU8, W4, W0 = (C.c_void_p * 64)(*[_u8.ctypes.data] * 64), (C.c_uint32 * 64)(*[4] * 64), (C.c_uint32 * 64)()
+SRC_012, SRC_BAD = (C.c_int32 * 3)(0, 1, 2), (C.c_int32 * 3)(0, 3, 2)
+_offs, _out64, _cnt, _tensors = np.asarray([0, 49], np.uint64), (C.c_size_t * 2)(), (C.c_int32 * 2)(), (api.Tensor * 16)()
+OFF_PAGES, FP, N_OUT, TENSORS = _offs.ctypes.data, _f.ctypes.data_as(C.POINTER(C.c_float)), C.cast(_cnt, C.POINTER(C.c_int32)), C.cast(_tensors, C.POINTER(api.Tensor))
 
 # entry -> (parameter names, a valid call, [(label, overrides)]); a string value names a buffer of SYM, anything else goes to ctypes as it is
 DIRECT = {
@@ -133,6 +138,33 @@ DIRECT = {
     "oar_k_rotate_crop": ("rgb w h box out cap out_w out_h".split(), dict(rgb="U8", w=4, h=4, box=_f.ctypes.data_as(C.POINTER(C.c_float)), out="U8", cap=4096,
                                                                        out_w=C.cast(_out32, C.POINTER(C.c_uint32)), out_h=C.cast(_out32, C.POINTER(C.c_uint32))),
                           [("null rgb", dict(rgb="NULL")), ("zero width", dict(w=0))]),
+    # the u8 front kernels and the detector's finish kernels.  The stem's model bytes are not looked at before the device is: any bytes do here
+    "oar_k_stem_u8": (
+        "onnx onnx_len rgb widths n h wt src_channels alpha beta table outs max_out n_out".split(),
+        dict(onnx="U8", onnx_len=64, rgb=PU8, widths=W4, n=2, h=4, wt=4, src_channels=SRC_012, alpha=FP, beta=FP, table=0, outs=TENSORS, max_out=16, n_out=N_OUT),
+        [("null onnx", dict(onnx="NULL")), ("null outs", dict(outs="NULL")), ("no image", dict(n=0)), ("33 pages by value", dict(n=33)), ("wider than the tensor", dict(table=1, wt=3)),
+         ("a page of another width", dict(wt=5)), ("source channel", dict(src_channels=SRC_BAD)), ("null before count", dict(rgb="NULL", n=33)),
+         ("count before width", dict(n=33, wt=3)), ("width before channel", dict(table=1, wt=3, src_channels=SRC_BAD))]),
+    "oar_k_rec_resize_u8": (
+        "rgb widths heights flips n img_h img_w max_img_w sentinel tensor_width resized_widths pool pool_cap pool_bytes".split(),
+        dict(rgb=PU8, widths=W4, heights=W4, flips="NULL", n=2, img_h=8, img_w=32, max_img_w=64, sentinel=0xA5, tensor_width=C.cast(_out32, C.POINTER(C.c_uint32)), resized_widths="I",
+             pool="U8", pool_cap=4096, pool_bytes=C.cast(_out64, C.POINTER(C.c_size_t))),
+        [("null rgb", dict(rgb="NULL")), ("null pool_bytes", dict(pool_bytes=None)), ("no crop", dict(n=0)), ("empty crop", dict(widths=W0)), ("pool too small", dict(pool_cap=64)),
+         ("crop before pool", dict(widths=W0, pool_cap=64))]),
+    "oar_k_normalize_pages": (
+        "pool pool_bytes offsets n_pages plane src_channels alpha beta hwc_layout out".split(),
+        dict(pool="U8", pool_bytes=4096, offsets=OFF_PAGES, n_pages=2, plane=16, src_channels=SRC_012, alpha=FP, beta=FP, hwc_layout=0, out="F"),
+        [("null pool", dict(pool="NULL")), ("null out", dict(out="NULL")), ("no page", dict(n_pages=0)), ("33 pages", dict(n_pages=33)), ("page does not fit", dict(pool_bytes=96)),
+         ("source channel", dict(src_channels=SRC_BAD)), ("count before fit", dict(n_pages=33, pool_bytes=1)), ("fit before channel", dict(pool_bytes=96, src_channels=SRC_BAD))]),
+    "oar_k_db_keep_and_pack": (
+        "net_out n channels height width thresh float_offset probs bits".split(),
+        dict(net_out="F", n=2, channels=2, height=3, width=9, thresh=0.3, float_offset=1, probs="F", bits="U8"),
+        [("null net_out", dict(net_out="NULL")), ("null bits", dict(bits="NULL")), ("zero width", dict(width=0)), ("float_offset", dict(float_offset=4)),
+         ("null before offset", dict(probs="NULL", float_offset=4))]),
+    "oar_k_pack_mask_bits": (
+        "mask n height width byte_offset bits".split(),
+        dict(mask="U8", n=2, height=3, width=9, byte_offset=3, bits="U8"),
+        [("null mask", dict(mask="NULL")), ("zero height", dict(height=0)), ("byte_offset", dict(byte_offset=8)), ("null before offset", dict(bits="NULL", byte_offset=8))]),
 }
 
 
